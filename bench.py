@@ -14,17 +14,28 @@ upwind with the van Albada limiter (kappa = 1/3), as a WALL-BOUNDED 2x2x2 brick
 (round 4: viscous wall below the four lower blocks, one symmetry plane,
 farfield elsewhere, 1-to-1 interfaces inside), stepped as the reference's WHOLE
 blocketteRes (blockette.F90:199-283): derived values, turbulence + mean-flow
-boundary conditions, whalo2, core with storeWall.  Other configurations are
-reported under "extra" at N=1 (the fully periodic brick of rounds 1-3, 4b matrix
+boundary conditions, whalo2, core with storeWall.
+
+A plain run sets up, warms up (W steps), times exactly K steps, writes the
+outputs of the last step when --dump-outputs DIR is given, and prints the result
+line.  --full adds everything else: per-kernel phase times and the roofline
+figures built on them, the CPU baselines, and the other configurations reported
+under "extra" at N=1 (the fully periodic brick of rounds 1-3, 4b matrix
 dissipation, config 5 GMRES proxy, config 3 D-ADI iteration, config 2 Euler JST
 + 3-level W multigrid cycle, small blocks).
 
+--dump-outputs DIR: what the timed step hands its caller, from the last timed
+evaluation, as float64 .npy files (at most 64 MB in all): a fixed, seeded sample
+of the owned cells' residual dw of every block, the residual norms of every
+block over all its owned cells, and viscSubface%tau / %q of every viscous
+subface.  The inputs are seeded, so two builds can be compared file by file.
+
 metric  : Mcells*residual-evals/s  (BASELINE.json)
 roofline: HBM-bound; algorithmic bytes/cell/eval from SURVEY.md §8(d)
-          (Euler 175 B, RANS-SA 255 B).  Per-kernel durations are measured live
+          (Euler 175 B, RANS-SA 255 B).  Per-kernel durations (--full) are measured live
           with HIP events on the library's own stream (tuning "phase_events").
 cpu_baseline: the reference's own Fortran (oracle/_ref, "reference") timed on
-          the host cores of this box on a bounded sample (rank 0, N=1 only).
+          the host cores of this box on a bounded sample (rank 0, N=1, --full only).
 """
 import argparse
 import json
@@ -421,6 +432,7 @@ class Job:
         self.wvec = []
         self.nsubfaces = self.nwallfaces = 0
         self._keep = []
+        self.walls = []           # (block, owned face-cell shape of every viscous subface): what --dump-outputs downloads
         for g in self.topo[0].blocks_of(rank):
             if self.bc:
                 # wall-bounded brick: the block sits at its place in the brick (wall distance measured from the brick's floor), only
@@ -444,6 +456,7 @@ class Job:
                 eng.register(b_, nn=lid[g], level=l + 1)
             if faces:
                 eng.bc_register(faces, nvisc, nn=lid[g], level=1)
+                self.walls.append((lid[g], [owned_face_shape(f, blk) for f in faces[:nvisc]]))
                 self._keep.append(faces)          # BCData arrays: the library keeps device copies, the host arrays stay valid anyway
                 self.nsubfaces += len(faces)
                 self.nwallfaces += sum((f["icEnd"] - f["icBeg"] - 1) * (f["jcEnd"] - f["jcBeg"] - 1) for f in faces[:nvisc])
@@ -493,16 +506,19 @@ class Job:
 
 def timed(eng, fn, steps, barrier, min_seconds=1.0, max_reps=2000, agree=None):
     """Time `steps` calls of fn, repeated until the region lasts >= min_seconds (the driver's busy sampler needs that);
+    min_seconds <= 0: exactly `steps` calls, no probe and no repeats (the headline step count is --steps).
     returns (seconds per step, repeats, event ms per step)."""
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        fn()
-    barrier()
-    probe = time.perf_counter() - t0
-    if agree is not None:
-        probe = agree(probe)      # every rank must repeat the same number of times: each step holds a halo exchange
-    reps = int(min(max_reps, max(1, -(-min_seconds // max(probe, 1e-6)))))
+    reps = 1
+    if min_seconds > 0:
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        barrier()
+        probe = time.perf_counter() - t0
+        if agree is not None:
+            probe = agree(probe)      # every rank must repeat the same number of times: each step holds a halo exchange
+        reps = int(min(max_reps, max(1, -(-min_seconds // max(probe, 1e-6)))))
     barrier()
     t0 = time.perf_counter()
     eng.event_record(0)
@@ -513,6 +529,69 @@ def timed(eng, fn, steps, barrier, min_seconds=1.0, max_reps=2000, agree=None):
     barrier()
     dt = time.perf_counter() - t0
     return dt / (reps * steps), reps, eng.event_elapsed_ms(0, 1) / (reps * steps)
+
+
+def owned_face_shape(f, blk):
+    """(n1, n2) owned face cells of subface f: the range adflow_gpu_download_wall_stress copies (bc_owned_range, internal.h)"""
+    amax = blk.jl if f["faceID"] <= 2 else blk.il
+    bmax = blk.kl if f["faceID"] <= 4 else blk.jl
+    return (max(0, min(f["icEnd"], amax) - max(f["icBeg"], 2) + 1), max(0, min(f["jcEnd"], bmax) - max(f["jcBeg"], 2) + 1))
+
+
+DUMP_BYTES = 60_000_000     # --dump-outputs: the arrays of all ranks together (under 64 MB with the .npy headers)
+DUMP_SEED = 20261016
+
+
+def seeded_rows(x, nmax, seed):
+    """x (rows, n) whole when it has at most nmax rows, else a fixed seeded sample of nmax rows in their original order"""
+    import numpy as np
+    if x.shape[0] <= nmax:
+        return x
+    idx = np.sort(np.random.default_rng(seed).choice(x.shape[0], nmax, replace=False))
+    return x[idx]
+
+
+def dump_outputs(job, eng, out_dir, rank, world):
+    """--dump-outputs: what the step hands its caller after the LAST timed evaluation (nothing runs on the device in between),
+    as float64 .npy files in out_dir (suffix _rank<r> when N > 1):
+      residual_sample (blocks, cells, nw): dw of the owned cells, i fastest; a fixed seeded sample of cells per block when the whole
+                      mesh exceeds the budget
+      residual_norms  (blocks, 2, nw): L2 norm and max |dw| over ALL owned cells of every block
+      wall_tau (faces, 6), wall_q (faces, 3): viscSubface%tau / %q of every viscous subface, owned face cells in the order of the
+                      blocks and subfaces (storeWall of the wall-bounded workload; sampled the same way beyond a quarter of the budget)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    budget = DUMP_BYTES // world
+    nw = job.prm.nw
+    files = {}
+    taus, qs = [], []
+    for nn, shapes in job.walls:
+        for mm, shape in enumerate(shapes, start=1):
+            if shape[0] * shape[1] == 0:
+                continue
+            tau, q = eng.wall_stress(shape, mm, nn=nn)
+            taus.append(tau.reshape(-1, 6, order="F"))
+            qs.append(q.reshape(-1, 3, order="F"))
+    if taus:
+        nmax = budget // 4 // (9 * 8)
+        files["wall_tau"] = seeded_rows(np.concatenate(taus), nmax, DUMP_SEED)
+        files["wall_q"] = seeded_rows(np.concatenate(qs), nmax, DUMP_SEED)
+    keys = sorted(k for k in eng.blocks if k[1] == 1)
+    left = budget - sum(v.nbytes for v in files.values()) - len(keys) * 2 * nw * 8
+    per_block = max(1, min(left // (len(keys) * nw * 8), min(eng.blocks[k].ncells for k in keys)))
+    samples, norms = [], []
+    for nn, level, sps in keys:
+        blk = eng.blocks[(nn, level, sps)]
+        eng.download_residual(nn, level, sps)
+        dw = blk.owned("dw")[..., :nw].reshape(-1, nw, order="F")
+        norms.append(np.stack([np.sqrt((dw * dw).sum(axis=0)), np.abs(dw).max(axis=0)]))
+        samples.append(seeded_rows(dw, per_block, DUMP_SEED + nn))
+    files["residual_sample"] = np.stack(samples)
+    files["residual_norms"] = np.stack(norms)
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    log(f"outputs of the last step written to {out_dir}: " + ", ".join(f"{k} {v.shape}" for k, v in files.items()))
 
 
 def phase_times(eng, fn, n=10, names=PHASES):
@@ -547,7 +626,14 @@ def main():
     ap.add_argument("--force-extras", action="store_true", help="run the extras although --tuning is given (A/B runs of a tuning key)")
     ap.add_argument("--no-mg", action="store_true", help="skip the config-2 multigrid cycle measurement")
     ap.add_argument("--only-extras", default="", help="comma list out of 4b,matvec,pc,config3,periodic,config2,config1,shard,drdw,small (drdw8, drdw_jst, pc_jst on request only): time only these extras (kernel traces)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the timed K steps until the region lasts this long")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline also the per-kernel phase times and the roofline figures built on them, the CPU "
+                         "baselines and the other configurations under 'extra' (N=1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--min-seconds", type=float, default=1.0,
+                    help="--full extras: repeat their timed steps until the region lasts this long (the headline times exactly "
+                         "--steps steps)")
     ap.add_argument("--tuning", action="append", default=[], help="key=value knobs of adflow_gpu_set_tuning")
     ap.add_argument("--separate-halo", action="store_true",
                     help="whalo2 and the blocketteRes core as two calls (rounds 1-2) instead of one call with the exchange inside")
@@ -609,14 +695,16 @@ def main():
         dist.all_reduce(t_, op=dist.ReduceOp.MAX)
         return float(t_.item())
 
-    extras_on = (world == 1 and not a.no_extras and a.workload == DEFAULT_WORKLOAD and (not a.tuning or a.force_extras))
+    extras_on = (a.full and world == 1 and not a.no_extras and a.workload == DEFAULT_WORKLOAD and (not a.tuning or a.force_extras))
     job = Job(a, a.workload, eng, rank, world, keep_w=extras_on)
     wl, prm = job.wl, job.prm
     eng.set_async(True)
     for _ in range(a.warmup):
         job.step()
-    sec_step, reps, ev_ms = timed(eng, job.step, a.steps, barrier, a.min_seconds, agree=agree)
+    sec_step, reps, ev_ms = timed(eng, job.step, a.steps, barrier, 0.0, agree=agree)
     log(f"timed loop done: {sec_step * 1e3:.3f} ms/step ({reps} x {a.steps} steps)")
+    if a.dump_outputs:
+        dump_outputs(job, eng, a.dump_outputs, rank, world)
     if world > 1:
         t = torch.tensor([sec_step], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -658,7 +746,7 @@ def main():
         comm_info["ok"] = all(v is not False for v in comm_info["checks"].values())
     comm_ok = (world == 1) or (comm_info is not None and comm_info["ok"] and job.do_halo)
 
-    # ---- per-kernel durations of one evaluation, live HIP events on the library's stream
+    # ---- per-kernel durations of one evaluation, live HIP events on the library's stream (--full: evaluations of their own)
     eng.set_async(False)
     # NS / RANS over the tile table: the fused gradient + viscous march runs in front of the inviscid march (api.hip enqueue_flow_fluxes)
     gf_on = wl["equations"] >= 2
@@ -667,11 +755,13 @@ def main():
         if gf_on:
             return PHASES_GF_FIRST if first else PHASES_GF
         return PHASES
-    ph = phase_times(eng, job.step, names=phase_names(True))
-    log("phases (ms): " + ", ".join(f"{k} {v:.3f}" for k, v in ph.items()))
-    # every phase between the step's events is part of the evaluation (the front part = derived values, boundary conditions, whalo2)
-    kern = {("closures + BCs + whalo2" if k == "closures+bc" else k): v for k, v in ph.items() if k != "(mark)"}
-    dom = max(kern, key=kern.get)
+    kern, dom = {}, None
+    if a.full:
+        ph = phase_times(eng, job.step, names=phase_names(True))
+        log("phases (ms): " + ", ".join(f"{k} {v:.3f}" for k, v in ph.items()))
+        # every phase between the step's events is part of the evaluation (the front part = derived values, boundary conditions, whalo2)
+        kern = {("closures + BCs + whalo2" if k == "closures+bc" else k): v for k, v in ph.items() if k != "(mark)"}
+        dom = max(kern, key=kern.get)
 
     extra = {}
     only = set(x for x in a.only_extras.split(",") if x)
@@ -852,9 +942,10 @@ def main():
                          # also runs (round-4 verdict, weak 4: `frac` is the contract's 255 B figure)
                          "frac_with_derived_values": (wl["bytes_per_cell"] + wl.get("bytes_front", 0.0)) * job.cells_local / (ev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                          "frac_core_bytes_only": wl["bytes_per_cell"] * job.cells_local / (ev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "eval_ms": ev_ms, "kernels_ms": kern, "kernels_ms_sum_serial": eval_ms,
-                         "dominant_kernel": dom, "dominant_kernel_ms": kern[dom], "dominant_kernel_traffic": dom_traffic,
-                         "dominant_kernel_share": kern[dom] / eval_ms,
+                         # per-kernel figures: --full only (phase times are evaluations of their own)
+                         "eval_ms": ev_ms, "kernels_ms": kern or None, "kernels_ms_sum_serial": eval_ms if kern else None,
+                         "dominant_kernel": dom, "dominant_kernel_ms": kern[dom] if kern else None, "dominant_kernel_traffic": dom_traffic,
+                         "dominant_kernel_share": kern[dom] / eval_ms if kern else None,
                          # context, not the priced peak: the streaming-copy ceiling measured on this pool and the fraction of it the
                          # evaluation reaches for the bytes the counters say it actually moves
                          "streaming_copy_gbs": stream_gbs,
@@ -862,9 +953,10 @@ def main():
                                                   "thread, 1 GiB arrays)" if "copy16u8_1gib_gbs" in cal else "MI355X_MICROARCH.md (float4 copy)",
                          "infinity_cache_copy_gbs": cal.get("copy16u8_32mib_gbs"),
                          # the second bound: FP64 VALU issue (SURVEY section 8(d) asks for it beside GB/s)
-                         "fp64_issue": fp64_issue_roofline(eng, ev_ms, kern, gf=gf_on, spaceDiscr=wl["spaceDiscr"]) if wl["equations"] == 3 else None,
+                         "fp64_issue": fp64_issue_roofline(eng, ev_ms, kern, gf=gf_on, spaceDiscr=wl["spaceDiscr"])
+                         if a.full and wl["equations"] == 3 else None,
                          "traffic_gbs": ((traffic or {}).get("traffic_bytes_per_eval") or 0.0) / (ev_ms * 1e-3) / 1e9 or None},
-            "whole_eval": {"event_ms_per_step": ev_ms, "overlap_gain_ms": eval_ms - ev_ms,
+            "whole_eval": {"event_ms_per_step": ev_ms, "overlap_gain_ms": eval_ms - ev_ms if kern else None,
                            "hbm_frac": alg_bytes / (ev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                            "traffic_over_algorithmic": ((traffic or {}).get("traffic_bytes_per_eval") or 0.0) / alg_bytes or None},
         }
@@ -1064,7 +1156,7 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         out["extra"] = extra or None
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             log("cpu baseline (reference Fortran on the host cores) ...")
             out["cpu_baseline"] = cpu_baseline(wl["equations"], wl["spaceDiscr"])
             log("cpu baseline done")

@@ -6,8 +6,8 @@ if [ -z "$NOTESTS" ]; then timeout 1500 python -m pytest ${TESTS:-tests} -m gpu 
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
 tools/pmc_calib.bin bw2 | tee $O/${TAG}_calibration.json
 cp $O/${TAG}_calibration.json profiles/calibration.json
-timeout 1200 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log; tail -c 1500 $O/${TAG}_bench.log; cut -c1-400 $O/${TAG}_bench.json
-B="python bench.py --no-extras --no-cpu-baseline --steps 10 --warmup 2 --min-seconds 0.2"
+timeout 1200 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log; tail -c 1500 $O/${TAG}_bench.log; cut -c1-400 $O/${TAG}_bench.json
+B="python bench.py --full --no-extras --no-cpu-baseline --steps 10 --warmup 2 --min-seconds 0.2"
 timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof -o t -- $B > $O/${TAG}_prof.log 2>&1
 python tools/rocpd_summary.py $O/prof/t_results.db $O/${TAG}_kernel_trace.md "($TAG, git ${GIT}: $B)" | head -12
 BP="$B --tuning overlap=0"
