@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "flow_plan.h"
 
 extern int g_march_kch, g_viscous_tiled, g_inviscid_march, g_roe_march, g_sa_march;
 int g_test_fault = 0;        // tuning "test_fault" (tests only): bit 0 = the hipGraph capture of a multigrid cycle reports failure, bit 1 = the
@@ -991,7 +992,7 @@ int adflow_gpu_initres(int level, int varStart, int varEnd)
     return sync_and_check();
 }
 
-static int enqueue_flow_fluxes(int level, const KParams& kp, bool viscApprox, bool needGrad);
+static int enqueue_flow_fluxes(int level, const KParams& kp, const struct FlowPlan& P, bool needGrad);
 static int source_terms_enqueue(int withBlank);
 
 // residual (residuals.F90:1028) = residual_block of every block; blockResCore (blockette.F90:755) is the same sum of
@@ -1002,48 +1003,65 @@ static int wall_stress_enqueue(int level, const KParams& kp, bool formGrad);
 // and heat flux of the viscous subfaces (storeWallTensor, fluxes.F90:2586-2592)
 static bool has_wall_subfaces(int level);
 
-// needGradHbm: the caller wants the nodal gradients in the block arrays (updateIntermed copy-out, blockette.F90:706-750)
-// the scheme of the preconditioner matrix that k_pc_march serves: first-order upwind (lumpedDiss, or the user's first-order limiter) on
-// the fine level, no matrix-free vector, no multigrid forcing
-static bool pc_march_scheme(const KParams& kp)
-{
-    const int lim = kp.lumpedDiss ? ADFLOW_LIM_FIRST_ORDER : kp.limiter;
-    return g_pc_fused && kp.spaceDiscr == ADFLOW_UPWIND && kp.fineGrid && lim == ADFLOW_LIM_FIRST_ORDER && !kp.rvec && !kp.coarseInit &&
-           roe_march_takes(kp);
-}
-// ... and the conditions under which enqueue_flow_residual reaches it (thin-layer viscous flux, blocks at rest, the marching kernels on)
-static bool pc_march_applies(int level, const KParams& kp, bool viscApprox)
+// blocks at rest: no grid velocities, no rotational source (only the generic kernels carry them)
+static bool level_at_rest(int level)
 {
     bool anyMoving = false;
     for_level(level, [&](Block* b) { anyMoving = anyMoving || b->v.sFace || b->v.moving; return 0; });
-    return viscApprox && viscous_is_tiled() >= 2 && kp.viscous && fabs(kp.rFil) >= 1.e-10 && !kp.fwMode && inviscid_march_enabled() &&
-           !anyMoving && pc_march_scheme(kp);
-}
-// the exact viscous residual on the upwind scheme ends in k_roe_march<.., ADDV, RV> when a matrix-free vector is the target
-// (enqueue_flow_residual: viscFirst): that kernel can write all six entries of a cell (KParams::rvecTurbFromDw)
-static bool roe_rv_completes(int level, const KParams& kp, bool viscApprox)
-{
-    bool anyMoving = false;
-    for_level(level, [&](Block* b) { anyMoving = anyMoving || b->v.sFace || b->v.moving; return 0; });
-    return kp.rvec && kp.viscous && fabs(kp.rFil) >= 1.e-10 && !viscApprox && viscous_is_tiled() >= 2 && !kp.fwMode && inviscid_march_enabled() &&
-           !kp.dissApprox && !kp.lumpedDiss && !anyMoving && roe_march_takes(kp);
-}
-static bool ad_pc_march_applies(const KParams& kp, bool viscApprox)
-{
-    return viscApprox && viscous_is_tiled() >= 2 && kp.viscous && fabs(kp.rFil) >= 1.e-10 && pc_march_scheme(kp);
+    return !anyMoving;
 }
 
+// dI / dJ / dK (and the cell centres) derived from x, once per geometry
+static void block_face_vectors(Block* b)
+{
+    if (b->face_vectors_valid) return;
+    launch_face_vectors(b->v, g_stream);
+    b->face_vectors_valid = true;
+}
+static int ensure_face_vectors(int level)
+{
+    return for_level(level, [&](Block* b) { block_face_vectors(b); return 0; });
+}
+
+// the KParams of the evaluation block_res_enqueue(level, flags) runs (the Jacobian assembly plans with the same)
+static KParams res_kparams(int level, unsigned flags)
+{
+    KParams kp = make_kparams(level, 1.0, 0);
+    kp.onlyRadii = !(flags & ADFLOW_RES_UPDATE_INTERMED);
+    kp.coarseInit = 0;
+    if (level == 1 && g_rvec_target) { kp.rvec = g_rvec_target; kp.rvecTurbScale = g_opts.turbResScale; }
+    kp.dissApprox = (flags & ADFLOW_RES_DISS_APPROX) ? 1 : 0;
+    if (kp.dissApprox && (flags & ADFLOW_RES_UPWIND_FIRST_ORDER)) kp.lumpedDiss = 1;   // blockette.F90:643
+    return kp;
+}
+
+// what plan_flow (flow_plan.h) reads, gathered in one place; resFlags: which parts the evaluation forms (ADFLOW_RES_FLOW / _TURB)
+static FlowFacts flow_facts(int level, const KParams& kp, bool viscApprox, bool needGradHbm, bool dual = false,
+                            unsigned resFlags = ADFLOW_RES_FLOW)
+{
+    FlowFacts f = {};
+    f.spaceDiscr = kp.spaceDiscr; f.viscous = kp.viscous; f.fineGrid = kp.fineGrid; f.fwMode = kp.fwMode; f.dissApprox = kp.dissApprox;
+    f.lumpedDiss = kp.lumpedDiss; f.limiter = kp.limiter; f.coarseInit = kp.coarseInit; f.onlyRadii = kp.onlyRadii;
+    f.doScaling = kp.doScaling; f.rvec = kp.rvec != nullptr; f.rFil = kp.rFil; f.adis = kp.adis;
+    f.viscApprox = viscApprox; f.needGradHbm = needGradHbm; f.dual = dual;
+    f.wantFlow = (resFlags & ADFLOW_RES_FLOW) != 0; f.wantTurb = (resFlags & ADFLOW_RES_TURB) != 0;
+    f.atRest = level_at_rest(level);
+    f.rans = g_opts.equations == ADFLOW_RANS;
+    f.eulerMarch = g_use_march; f.inviscidMarch = g_inviscid_march; f.roeMarch = g_roe_march; f.viscousTiled = g_viscous_tiled;
+    f.saMarch = g_sa_march; f.pcFused = g_pc_fused; f.rvecJoint = g_rvec_joint; f.jacSnap = g_jac_snap;
+    return f;
+}
+
+// needGradHbm: the caller wants the nodal gradients in the block arrays (updateIntermed copy-out, blockette.F90:706-750)
 static int enqueue_flow_residual(int level, const KParams& kp, bool viscApprox = false, bool lowSpeed = true, bool stage0 = true,
                                  bool needGradHbm = false)
 {
     const bool wallStress = stage0 && !viscApprox && kp.viscous && level == g_opts.groundLevel && fabs(kp.rFil) >= 1.e-10 &&
                             has_wall_subfaces(level);
-    // the wall stress reads the gradients of the node planes ON the wall faces only: when the flux kernel keeps its gradients in
-    // LDS (k_visc_gf) those few nodes are formed again by the wall-stress launch instead of every node of the level being stored
-    const bool gradOnChip = viscous_is_tiled() >= 2 && !needGradHbm;
-    if (enqueue_flow_fluxes(level, kp, viscApprox, needGradHbm)) return 1;
+    const FlowPlan P = plan_flow(flow_facts(level, kp, viscApprox, needGradHbm));
+    if (enqueue_flow_fluxes(level, kp, P, needGradHbm)) return 1;
     if (wallStress)
-        if (wall_stress_enqueue(level, kp, gradOnChip)) return 1;
+        if (wall_stress_enqueue(level, kp, P.wallGradOnChip)) return 1;
     // sourceTerms() of the call sites of `residual` (smoothers.F90:74,409, multiGrid.F90:52,887,949): fine level only
     if (lowSpeed && level == 1 && source_terms_enqueue(1)) return 1;
     if (lowSpeed && g_opts.lowSpeedPreconditioner) {
@@ -1054,29 +1072,17 @@ static int enqueue_flow_residual(int level, const KParams& kp, bool viscApprox =
     return 0;
 }
 
-static int enqueue_flow_fluxes(int level, const KParams& kp, bool viscApprox, bool needGrad)
+// the mean-flow fluxes the plan names, in its order (phase marks: 4 .. 5 = nodal gradients + viscous fluxes, 5 .. 6 = inviscid fluxes
+// when they follow; bench.py labels them so)
+static int enqueue_flow_fluxes(int level, const KParams& kp, const FlowPlan& P, bool needGrad)
 {
-    bool anyMoving = false;     // grid velocities / rotational source: the generic kernels carry them
-    for_level(level, [&](Block* b) { anyMoving = anyMoving || b->v.sFace || b->v.moving; return 0; });
-    if (g_use_march && !kp.viscous && kp.spaceDiscr == ADFLOW_DISS_SCALAR && kp.fineGrid && !kp.dissApprox && !anyMoving) {
-        // Euler + scalar JST: one k-marching launch over every block of the level
-        int rc = for_level(level, [&](Block* b) {
-            if (!b->geom_uploaded) return fail("geometry of a level-%d block has not been uploaded", level);
-            return 0;
-        });
-        if (rc) return rc;
-        if (ensure_tiles(level)) return 1;
-        launch_euler_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kp, g_stream);
-        return 0;
-    }
     if (kp.spaceDiscr != ADFLOW_DISS_SCALAR && kp.spaceDiscr != ADFLOW_DISS_MATRIX && kp.spaceDiscr != ADFLOW_UPWIND)
         return fail("spaceDiscr=%d not supported (1 scalar, 2 matrix, 9 upwind)", kp.spaceDiscr);
-    const bool wantSensor = kp.viscous && kp.spaceDiscr == ADFLOW_DISS_SCALAR && fabs(kp.rFil) >= 1.e-10 && !kp.dissApprox;
     int nStale = 0, nBlk = 0;
     int rc = for_level(level, [&](Block* b) {
         if (!b->geom_uploaded) return fail("geometry of a level-%d block has not been uploaded", level);
         ++nBlk;
-        if (wantSensor && !b->ss_valid) ++nStale;
+        if (P.needSensor && !b->ss_valid) ++nStale;
         return 0;
     });
     if (rc) return rc;
@@ -1093,93 +1099,52 @@ static int enqueue_flow_fluxes(int level, const KParams& kp, bool viscApprox, bo
             return 0;
         });
     }
-    // inviscid part: one launch for every block of the level (blocks are independent given their halos)
     LevelTab t;
     if (level_tab(level, &t)) return 1;
-    // exact viscous fluxes of blocks at rest: nodal gradients + face fluxes as ONE marching kernel (k_visc_gf)
-    const bool viscMarch = kp.viscous && fabs(kp.rFil) >= 1.e-10 && !viscApprox && viscous_is_tiled() >= 2;
-    // viscous march first, inviscid march last: the inviscid kernel (Roe: bound by FP64 issue) adds the viscous sums it finds in
-    // dw(2:5) instead of the viscous kernel reading dw back.  Any inviscid kernel over the tile table can take that role (Roe,
-    // matrix dissipation, scalar JST of NS / RANS); not with the persistent fw of the Runge-Kutta stages.
-    // (scalar JST: the marching form reads its sensor from b.ss -- the entropy sensor of NS / RANS, or the frozen sensor of the
-    //  approximate residual, which Euler has too)
-    const bool scalarViscM = (inviscid_march_enabled() >= 2 && kp.spaceDiscr == ADFLOW_DISS_SCALAR && (kp.viscous || kp.dissApprox) &&
-                              kp.fineGrid);
-    // the approximate residual of the preconditioner matrix: the lumped scalar / matrix dissipation has a marching form on the fine
-    // level (k_inviscid_march<.., APX>, round 6); the upwind scheme changes through its limiter only
-    const bool approxOk = !kp.dissApprox || kp.spaceDiscr == ADFLOW_UPWIND || (kp.fineGrid && g_pc_fused && !kp.fwMode);
-    const bool tileInviscid = inviscid_march_enabled() && (kp.spaceDiscr != ADFLOW_DISS_SCALAR || scalarViscM) && approxOk && !anyMoving;
-    const bool viscFirst = viscMarch && !kp.fwMode && tileInviscid && !kp.dissApprox && !kp.lumpedDiss;
-    // the same order for the thin-layer viscous march of the preconditioner assembly (no gradients)
-    const bool approxFirst = viscApprox && viscous_is_tiled() >= 2 && kp.viscous && fabs(kp.rFil) >= 1.e-10 && !kp.fwMode &&
-                             tileInviscid;
-    // scalar JST with the entropy sensor (NS / RANS, fine level) also has a marching form, but it is bound by memory like
-    // the gather form (1.06 vs 1.10 ms on 8 x 128x128x96): only with tuning inviscid_march = 2
-    if (viscFirst || approxFirst) {
-        // enqueued behind the viscous march below
-    } else if (tileInviscid) {
-        // (the approximate residual changes the Roe scheme only through the limiter: inviscidUpwindFlux is called either way)
-        // matrix dissipation / Roe upwind: k-marching kernel over the level's tile table (every face once in k and i)
-        if (ensure_tiles(level)) return 1;
-        // second-order Roe upwind on the fine level: the per-cell reconstruction kernel; everything else (matrix, first order)
-        // stays with the per-face kernel
-        if (!launch_roe_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kp, g_stream))
-            launch_inviscid_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kp, g_stream);
-    } else {
-        launch_inviscid_level(t.tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
-    }
-    if (!viscFirst && !approxFirst) phase_mark(4);
-    if (!(kp.viscous && fabs(kp.rFil) >= 1.e-10)) return 0;
-    const bool batched = !viscApprox && viscMarch;
-    // thin-layer viscous flux of the preconditioner assembly: marching form over the tile table (blocks at rest, 4-row tiles)
-    const bool approxMarch = viscApprox && viscous_is_tiled() >= 2 && !anyMoving;
-    rc = for_level(level, [&](Block* b) {
-        if (!b->face_vectors_valid) {
-            launch_face_vectors(b->v, g_stream);
-            b->face_vectors_valid = true;
+    if ((P.needGfTiles && ensure_gf_tiles(level)) || (P.needTiles && ensure_tiles(level))) return 1;
+    KParams kv = kp;
+    kv.viscFirst = P.viscFirst ? 1 : 0;
+    auto inviscid = [&]() -> int {
+        switch (P.inviscid) {
+        case InviscidK::EulerMarch: launch_euler_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream); return 0;
+        case InviscidK::RoeMarch: return launch_roe_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream);
+        case InviscidK::FaceMarch: return launch_inviscid_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream);
+        case InviscidK::PcMarch: launch_pc_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_march_kch, g_stream); return 0;
+        case InviscidK::LevelGather: launch_inviscid_level(t.tab, t.n, t.nx, t.ny, t.nz, kv, g_stream); return 0;
+        case InviscidK::None: break;
         }
-        if (viscApprox && !approxMarch) launch_viscous_approx(b->v, kp, g_stream);   // viscousFluxApprox instead of gradients + viscousFlux
-        else if (!viscApprox && !batched) launch_viscous(b->v, kp, g_stream);
         return 0;
-    });
-    if (rc) return rc;
-    if (approxMarch) {
-        if (ensure_tiles(level)) return 1;
-        if (approxFirst && pc_march_scheme(kp)) {
-            // first-order upwind + thin-layer viscous flux: both are functions of the two cells of a face -- one march, dw written once
-            phase_mark(4);
-            launch_pc_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kp, g_march_kch, g_stream);
-            phase_mark(5);
-        } else if (approxFirst) {
-            KParams kv = kp;
-            kv.viscFirst = 1;
-            phase_mark(4);
-            launch_visc_march_approx(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream);
-            phase_mark(5);
-            if (!launch_roe_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream))
-                launch_inviscid_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream);
-        } else
-            launch_visc_march_approx(g_tab[level], g_tiles[level].first, g_tiles[level].second, kp, g_stream);
-    }
-    if (batched) {
-        // gradients and face fluxes in one kernel: the gradients stay in LDS (and go to HBM only when a caller reads them)
-        // (phase marks: 4 .. 5 = nodal gradients + viscous fluxes, 5 .. 6 = inviscid fluxes when they follow; bench.py labels them so)
-        if (ensure_gf_tiles(level)) return 1;
-        if (viscFirst) {
-            KParams kv = kp;
-            kv.viscFirst = 1;
-            if (ensure_tiles(level)) return 1;
-            phase_mark(4);
-            launch_visc_gf(g_tab[level], g_gf_tiles[level].first, g_gf_tiles[level].second, kv, needGrad, g_stream);
-            phase_mark(5);
-            if (!launch_roe_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream))
-                launch_inviscid_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream);
-            return 0;
+    };
+    auto viscous = [&]() -> int {
+        switch (P.viscous) {
+        case ViscousK::GfMarch: launch_visc_gf(g_tab[level], g_gf_tiles[level].first, g_gf_tiles[level].second, kv, needGrad, g_stream); return 0;
+        case ViscousK::ThinLayerMarch: launch_visc_march_approx(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream); return 0;
+        case ViscousK::GatherExact: return for_level(level, [&](Block* b) { block_face_vectors(b); launch_viscous(b->v, kv, g_stream); return 0; });
+        case ViscousK::GatherApprox: return for_level(level, [&](Block* b) { block_face_vectors(b); launch_viscous_approx(b->v, kv, g_stream); return 0; });
+        case ViscousK::None: break;
         }
+        return 0;
+    };
+    if (P.inviscid == InviscidK::EulerMarch) return inviscid();          // (no viscous part, one phase)
+    if (P.inviscid == InviscidK::PcMarch) {
+        if (ensure_face_vectors(level)) return 1;
+        phase_mark(4);
+        if (inviscid()) return 1;
         phase_mark(5);
-        launch_visc_gf(g_tab[level], g_gf_tiles[level].first, g_gf_tiles[level].second, kp, needGrad, g_stream);
+        return 0;
     }
-    return 0;
+    if (P.viscFirst) {
+        if (ensure_face_vectors(level)) return 1;
+        phase_mark(4);
+        if (viscous()) return 1;
+        phase_mark(5);
+        return inviscid();
+    }
+    if (inviscid()) return 1;
+    phase_mark(4);
+    if (P.needFaceVectors && ensure_face_vectors(level)) return 1;
+    if (P.viscous == ViscousK::GfMarch) phase_mark(5);
+    return viscous();
 }
 
 int adflow_gpu_residual(int level, int rkStage)
@@ -1211,7 +1176,7 @@ static int early_pressure_exchange_enqueue(int level);
 static int halo_exchange_close(int level, int varStart, int varEnd, int commPressure, int nLayers);
 static int comm_exchange_begin(CommPattern* cp, BlkView* tab, unsigned mask, int nvar, bool* remoteOut);
 static int comm_exchange_end(CommPattern* cp, BlkView* tab, unsigned mask, bool remote);
-static int block_res_split_enqueue(int level, unsigned flags, const KParams& kp0, int lStart, int lEnd, int* taken,
+static int block_res_split_enqueue(int level, unsigned flags, const KParams& kp, const FlowPlan& P, int lStart, int lEnd, int* taken,
                                    const std::function<int()>& frontBCs);
 
 // whalo2 + blocketteRes core with the exchange -- and, round 4, the boundary conditions in front of it -- HIDDEN behind the tiles that
@@ -1225,21 +1190,20 @@ static int block_res_split_enqueue(int level, unsigned flags, const KParams& kp0
 // Taken for the default flags of blocketteRes on NS / RANS with the marching kernels, blocks at rest, when the pattern has messages
 // (tuning "split_eval" = 1, the default), always (2: tests), never (0).  On the north-star mesh
 // 16 % of the tiles are interior.
-static int block_res_split_enqueue(int level, unsigned flags, const KParams& kp0, int lStart, int lEnd, int* taken,
+static int block_res_split_enqueue(int level, unsigned flags, const KParams& kp, const FlowPlan& P, int lStart, int lEnd, int* taken,
                                    const std::function<int()>& frontBCs)
 {
     *taken = 0;
-    if (!g_split_eval || !g_overlap || g_phase_base > 0 || kp0.rvec) return 0;
+    if (!g_split_eval || !g_overlap || g_phase_base > 0 || kp.rvec) return 0;
     const unsigned need = ADFLOW_RES_FLOW | ADFLOW_RES_HALO;
     if ((flags & need) != need || (flags & (ADFLOW_RES_DISS_APPROX | ADFLOW_RES_VISC_APPROX | ADFLOW_RES_UPDATE_INTERMED))) return 0;
-    KParams kp = kp0;
-    if (!kp.viscous || fabs(kp.rFil) < 1.e-10 || viscous_is_tiled() < 2 || !inviscid_march_enabled() || !kp.fineGrid) return 0;
-    if (kp.spaceDiscr == ADFLOW_DISS_SCALAR) return 0;         // (needs the time-step pass in front: not split)
-    const bool rans = (flags & ADFLOW_RES_TURB) && g_opts.equations == ADFLOW_RANS;
-    if (rans && !g_sa_march) return 0;
-    bool moving = false, wall = has_wall_subfaces(level) && level == g_opts.groundLevel;
-    for_level(level, [&](Block* b) { moving = moving || b->v.sFace || b->v.moving; return 0; });
-    if (moving || !g_act.empty()) return 0;
+    // the evaluation the split is written for: fused viscous march in front of an inviscid march over the tile table, SA as a march, no
+    // time-step pass in front (scalar JST: not split), fine level
+    if (P.viscous != ViscousK::GfMarch || !P.viscFirst || (P.inviscid != InviscidK::RoeMarch && P.inviscid != InviscidK::FaceMarch) ||
+        P.turb == TurbK::LevelGather || P.needTimeStep || !kp.fineGrid) return 0;
+    const bool rans = P.turb == TurbK::SaMarch;
+    const bool wall = has_wall_subfaces(level) && level == g_opts.groundLevel;
+    if (!g_act.empty()) return 0;
     CommPattern* cp;
     if (build_comm(level, 2, &cp)) return 1;
     const bool messages = !cp->sends.empty() || !cp->recvs.empty();
@@ -1255,10 +1219,7 @@ static int block_res_split_enqueue(int level, unsigned flags, const KParams& kp0
     int rc = for_level(level, [&](Block* b) {
         if (!b->geom_uploaded) return fail("geometry of a level-%d block has not been uploaded", level);
         if (rans && b->v.nw < 6) return fail("RANS/SA needs nw = 6 (block has %d)", b->v.nw);
-        if (!b->face_vectors_valid) {
-            launch_face_vectors(b->v, g_stream);
-            b->face_vectors_valid = true;
-        }
+        block_face_vectors(b);
         return 0;
     });
     if (rc) return rc;
@@ -1290,8 +1251,9 @@ static int block_res_split_enqueue(int level, unsigned flags, const KParams& kp0
         HIPCHK(hipEventRecord(g_evB, g_streamB));
         launch_visc_gf(g_tab[level], g_gf_tiles_bnd[level].first, g_gf_tiles_bnd[level].second, kv, false, g_stream);
         HIPCHK(hipStreamWaitEvent(g_stream, g_evB1, 0));               // the interior viscous sums are in dw(2:5)
-        if (!launch_roe_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream))
-            launch_inviscid_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream);
+        if (P.inviscid == InviscidK::RoeMarch ? launch_roe_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream)
+                                              : launch_inviscid_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream))
+            return 1;
         HIPCHK(hipStreamWaitEvent(g_stream, g_evB, 0));                // join
         forked = false;
         return 0;
@@ -1309,13 +1271,9 @@ static int block_res_enqueue(int level, unsigned flags)
 {
     if (need_ready()) return 1;
     phase_mark(0);
-    KParams kp = make_kparams(level, 1.0, 0);
-    kp.onlyRadii = !(flags & ADFLOW_RES_UPDATE_INTERMED);
-    kp.coarseInit = 0;
-    if (level == 1 && g_rvec_target) { kp.rvec = g_rvec_target; kp.rvecTurbScale = g_opts.turbResScale; }
-    kp.dissApprox = (flags & ADFLOW_RES_DISS_APPROX) ? 1 : 0;
-    if (kp.dissApprox && (flags & ADFLOW_RES_UPWIND_FIRST_ORDER)) kp.lumpedDiss = 1;   // blockette.F90:643
+    KParams kp = res_kparams(level, flags);
     const bool viscApprox = (flags & ADFLOW_RES_VISC_APPROX) != 0;
+    const FlowPlan P = plan_flow(flow_facts(level, kp, viscApprox, (flags & ADFLOW_RES_UPDATE_INTERMED) != 0, false, flags));
     int rc = 0;
     bool etotInClosures = false;
     if (flags & ADFLOW_RES_CLOSURES) {
@@ -1359,7 +1317,7 @@ static int block_res_enqueue(int level, unsigned flags)
             int taken = 0;
             const int flagLevelWas = g_etot_flag_level;
             if (etotInClosures) g_etot_flag_level = level;
-            rc = block_res_split_enqueue(level, flags, kp, lStart, lEnd, &taken, frontBCs);
+            rc = block_res_split_enqueue(level, flags, kp, P, lStart, lEnd, &taken, frontBCs);
             if (!rc && !taken) {
                 rc = frontBCs();
                 if (!rc) rc = halo_exchange_enqueue(level, lStart, lEnd, 1, 1, 2);
@@ -1370,46 +1328,25 @@ static int block_res_enqueue(int level, unsigned flags)
         } else if (frontBCs()) return 1;
     }
     phase_mark(1);
-    // timeStep_block(onlyRadii): with matrix dissipation / Roe upwind nothing in the residual reads the spectral radii, and
-    // without updateIntermed the reference's default path (blocketteResCore, blockette.F90:299-753) keeps them in the
-    // blockette's private arrays: they are not an output of the evaluation.  Only scalar JST needs them (and the entropy
-    // sensor the same kernel leaves in ss).
-    // Euler + scalar JST: the marching kernel forms the radii itself when nothing else needs them (no updateIntermed: neither the
-    // radii nor dtl are outputs, blockette.F90:660-750)
-    bool anyMovingR = false;
-    for_level(level, [&](Block* b) { anyMovingR = anyMovingR || b->v.sFace || b->v.moving; return 0; });
-    const bool radiiInMarch = kp.onlyRadii && (flags & ADFLOW_RES_FLOW) && g_use_march && !kp.viscous &&
-                              kp.spaceDiscr == ADFLOW_DISS_SCALAR && kp.fineGrid && !kp.dissApprox && !anyMovingR && fabs(kp.rFil) >= 1.e-10 &&
-                              euler_march_radii_capable(kp);
-    kp.radiiInMarch = radiiInMarch ? 1 : 0;
-    if (!radiiInMarch && !(kp.onlyRadii && kp.spaceDiscr != ADFLOW_DISS_SCALAR)) {
+    kp.radiiInMarch = P.radiiInMarch ? 1 : 0;
+    if (P.needTimeStep) {
         rc = time_step_level(level, kp);
         if (rc) return rc;
     }
     phase_mark(2);
-    // blockResCore order: SA residual first, then the mean-flow fluxes (blockette.F90:806-851)
-    if ((flags & ADFLOW_RES_TURB) && g_opts.equations == ADFLOW_RANS) {
-        bool moving = false;
+    if (P.turb != TurbK::None) {
         rc = for_level(level, [&](Block* b) {
             if (b->v.nw < 6) return fail("RANS/SA needs nw = 6 (block has %d)", b->v.nw);
-            moving = moving || b->v.sFace || b->v.moving;
             return 0;
         });
         if (rc) return rc;
-        {
-            LevelTab t;
-            if (level_tab(level, &t)) return 1;
-            // (on a side queue beside the mean-flow kernels -- the default of rounds 2-3 -- the march gains nothing since every march fills
-            // the device: 2.26 against 2.21 ms, round 4)
-            hipStream_t ss = g_stream;
-            if (g_sa_march && !moving) {
-                if (ensure_sa_tiles(level)) return 1;
-                // the matrix-free vector: the Roe march that follows in the same queue writes the turbulence entry with its own five
-                // (tuning "rvec_joint"; every block holds six variables here: checked above)
-                if (kp.rvec && g_rvec_joint && (flags & ADFLOW_RES_FLOW) && roe_rv_completes(level, kp, viscApprox)) kp.rvecTurbFromDw = 1;
-                launch_sa_march(t.tab, g_sa_tiles[level].first, g_sa_tiles[level].second, kp, ss, false);
-            } else launch_sa_residual_level(t.tab, t.n, t.nx, t.ny, t.nz, kp, ss);
-        }
+        LevelTab t;
+        if (level_tab(level, &t)) return 1;
+        if (P.turb == TurbK::SaMarch) {
+            if (ensure_sa_tiles(level)) return 1;
+            if (P.roeWritesTurbRvec) kp.rvecTurbFromDw = 1;
+            launch_sa_march(t.tab, g_sa_tiles[level].first, g_sa_tiles[level].second, kp, g_stream, false);
+        } else launch_sa_residual_level(t.tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
     }
     phase_mark(3);
     if (flags & ADFLOW_RES_FLOW) {
@@ -1651,10 +1588,7 @@ static int ad_prepare(int level)
     std::vector<long> sig = {level, viscous ? 1 : 0, maxnn};
     int rc = for_level(level, [&](Block* b) {
         if (!b->geom_uploaded) return fail("geometry of a level-%d block has not been uploaded", level);
-        if (viscous && !b->face_vectors_valid) {
-            launch_face_vectors(b->v, g_stream);
-            b->face_vectors_valid = true;
-        }
+        if (viscous) block_face_vectors(b);
         const BlkView& p = b->v;
         sig.push_back((long)(uintptr_t)b); sig.push_back(p.nbox); sig.push_back(p.nw);
         sig.push_back((p.d2wall ? 1 : 0) | (p.dI ? 2 : 0) | (p.bmt[0] ? 4 : 0));
@@ -1708,22 +1642,13 @@ static KParams ad_kparams(int level, unsigned resFlags)
     kp.dissApprox = (resFlags & ADFLOW_RES_DISS_APPROX) ? 1 : 0;
     return kp;
 }
-// closuresDone: the seed launch of the caller formed pressure and viscosities already (k_seed_closures)
-// the schemes the dual per-face march takes in the exact linearisation (as the plain evaluation chooses, api.hip residual_enqueue:
-// scalar JST only with the entropy sensor of NS / RANS on the fine level -- Euler + scalar JST has its own pipelined kernel, which has
-// no dual form)
-static bool ad_inviscid_march_takes(const KParams& kp)
-{
-    if (!inviscid_march_enabled() || kp.fwMode) return false;
-    if (kp.dissApprox && !kp.fineGrid) return false;
-    if (kp.spaceDiscr == ADFLOW_DISS_SCALAR) return inviscid_march_enabled() >= 2 && (kp.viscous || kp.dissApprox) && kp.fineGrid;
-    return kp.spaceDiscr == ADFLOW_DISS_MATRIX;       // (upwind: k_roe_march on dual numbers, or the gather kernel)
-}
+static bool ad_visc_approx(unsigned resFlags, bool viscPC) { return (resFlags & ADFLOW_RES_VISC_APPROX) != 0 && !viscPC; }
 
+// closuresDone: the seed launch of the caller formed pressure and viscosities already (k_seed_closures)
 static int ad_block_res_state_enqueue(int level, unsigned resFlags, bool turbBC, bool viscPC, bool closuresDone = false)
 {
     KParams kp = ad_kparams(level, resFlags);
-    const bool viscApprox = (resFlags & ADFLOW_RES_VISC_APPROX) != 0 && !viscPC;
+    const FlowPlan P = plan_flow(flow_facts(level, kp, ad_visc_approx(resFlags, viscPC), false, true, resFlags));
     LevelTab t;
     if (level_tab(level, &t)) return 1;
     int rc = 0;
@@ -1733,106 +1658,49 @@ static int ad_block_res_state_enqueue(int level, unsigned resFlags, bool turbBC,
     });
     if (rc) return rc;
     if (ad_apply_bc_enqueue(level, kp, turbBC)) return 1;
-    // timeStep_block_d: only the scalar dissipation reads the spectral radii; the NS / RANS kernel also leaves the entropy sensor
-    // in ss -- not under dissApprox, where ss keeps the frozen sensor of referenceShockSensor (value part, derivative 0)
-    if ((resFlags & ADFLOW_RES_FLOW) && kp.spaceDiscr == ADFLOW_DISS_SCALAR)
-        ad_launch_time_step_level(g_ad_tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
-    if ((resFlags & ADFLOW_RES_TURB) && g_opts.equations == ADFLOW_RANS) {
-        // the marching form on dual numbers (kernels_sa_march.hip; blocks at rest: moving blocks were refused by the caller)
-        if (g_sa_march && g_pc_fused) {
-            if (ensure_sa_tiles(level)) return 1;
-            ad_launch_sa_march(g_ad_tab, g_sa_tiles[level].first, g_sa_tiles[level].second, kp, g_stream);
-        } else
-            ad_launch_sa_residual_level(g_ad_tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
+    // timeStep_block_d: the NS / RANS kernel also leaves the entropy sensor in ss -- not under dissApprox, where ss keeps the frozen
+    // sensor of referenceShockSensor (value part, derivative 0)
+    if (P.needTimeStep) ad_launch_time_step_level(g_ad_tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
+    switch (P.turb) {
+    case TurbK::SaMarch:      // the marching form on dual numbers (kernels_sa_march.hip)
+        if (ensure_sa_tiles(level)) return 1;
+        ad_launch_sa_march(g_ad_tab, g_sa_tiles[level].first, g_sa_tiles[level].second, kp, g_stream);
+        break;
+    case TurbK::LevelGather: ad_launch_sa_residual_level(g_ad_tab, t.n, t.nx, t.ny, t.nz, kp, g_stream); break;
+    case TurbK::None: break;
     }
-    if ((resFlags & ADFLOW_RES_FLOW) && ad_pc_march_applies(kp, viscApprox)) {
-        // the preconditioner matrix on the upwind scheme: the dual form of the one-march residual (kernels_pc_march.hip) instead of the
-        // gather kernels (blocks at rest: moving blocks were refused by the caller)
-        rc = for_level(level, [&](Block* b) {
-            if (!b->face_vectors_valid) {
-                launch_face_vectors(b->v, g_stream);
-                b->face_vectors_valid = true;
-            }
-            return 0;
-        });
-        if (rc || ensure_tiles(level)) return 1;
-        ad_launch_pc_march(g_ad_tab, g_tiles[level].first, g_tiles[level].second, kp, g_march_kch, g_stream);
-    } else if (resFlags & ADFLOW_RES_FLOW) {
-        // the Roe upwind scheme of the exact linearisation (second order, the user's limiter): the marching kernel on dual numbers
-        // (kernels_roe_march.hip compiled a second time, round 6) instead of the cell-gather kernel -- 3.25 instead of 6 face
-        // evaluations and 3.5 instead of 12 reconstructions per cell; it leaves dw + fw in dw for the viscous kernel that follows
-        // ... and the full viscous flux as the fused gradient + flux march on dual numbers (k_visc_gf compiled a second time: the metric
-        // sums and face geometry stay plain, the ring holds dual gradients -- 160 KB of LDS, one workgroup per CU) instead of the dual
-        // gather pair k_nodal_gradients + k_viscous (1.01 ms per pass and 1.3 M cells): in front of the Roe march, which adds its sums
-        // (viscFirst), or behind the gather inviscid kernel of the other schemes, completing dw itself
-        const bool viscous = kp.viscous && fabs(kp.rFil) >= 1.e-10;
-        const bool gfDual = viscous && !viscApprox && g_pc_fused && viscous_is_tiled() >= 2 && kp.fineGrid;
-        if (gfDual) {
-            rc = for_level(level, [&](Block* b) {
-                if (!b->face_vectors_valid) {
-                    launch_face_vectors(b->v, g_stream);
-                    b->face_vectors_valid = true;
-                }
-                return 0;
-            });
-            if (rc || ensure_gf_tiles(level)) return 1;
+    // the mean flow on dual numbers: the marching kernels compiled a second time (kernels_ad.hip) in the order of the plain evaluation
+    // -- the Roe march of the exact linearisation (3.25 instead of 6 face evaluations and 3.5 instead of 12 reconstructions per cell),
+    // the per-face march of scalar JST / matrix dissipation (four face evaluations per cell instead of the gather kernel's six), the
+    // one-march residual of the preconditioner matrix, k_visc_gf (instead of the dual gather pair k_nodal_gradients + k_viscous: 1.01 ms
+    // per pass and 1.3 M cells) -- or the gather kernels behind them
+    if (P.needFaceVectors && ensure_face_vectors(level)) return 1;
+    if ((P.needGfTiles && ensure_gf_tiles(level)) || (P.needTiles && ensure_tiles(level))) return 1;
+    KParams kv = kp;
+    kv.viscFirst = P.viscFirst ? 1 : 0;
+    auto inviscid = [&]() -> int {
+        switch (P.inviscid) {
+        case InviscidK::PcMarch: ad_launch_pc_march(g_ad_tab, g_tiles[level].first, g_tiles[level].second, kv, g_march_kch, g_stream); return 0;
+        case InviscidK::RoeMarch: return ad_launch_roe_march(g_ad_tab, g_tiles[level].first, g_tiles[level].second, kv, g_stream);
+        case InviscidK::FaceMarch: return ad_launch_inviscid_march(g_ad_tab, g_tiles[level].first, g_tiles[level].second, kv, g_stream);
+        case InviscidK::LevelGather: ad_launch_inviscid_level(g_ad_tab, t.n, t.nx, t.ny, t.nz, kv, g_stream); return 0;
+        case InviscidK::None: return 0;
+        case InviscidK::EulerMarch: break;
         }
-        bool marched = false;
-        if (g_pc_fused && roe_march_takes(kp)) {
-            if (ensure_tiles(level)) return 1;
-            KParams kr = kp;
-            if (gfDual) {
-                kr.viscFirst = 1;
-                ad_launch_visc_gf(g_ad_tab, g_gf_tiles[level].first, g_gf_tiles[level].second, kr, g_stream);
-            }
-            marched = ad_launch_roe_march(g_ad_tab, g_tiles[level].first, g_tiles[level].second, kr, g_stream);
-            if (marched && gfDual) return 0;
+        return fail("forward mode: the plan names a kernel without a dual form (internal error)");
+    };
+    auto viscous = [&]() -> int {
+        switch (P.viscous) {
+        case ViscousK::GfMarch: ad_launch_visc_gf(g_ad_tab, g_gf_tiles[level].first, g_gf_tiles[level].second, kv, g_stream); return 0;
+        case ViscousK::ThinLayerMarch: ad_launch_visc_march_approx(g_ad_tab, g_tiles[level].first, g_tiles[level].second, kv, g_stream); return 0;
+        case ViscousK::GatherExact: return for_level(level, [&](Block* b) { ad_launch_viscous(g_ad[b].v, kv, g_stream); return 0; });
+        case ViscousK::GatherApprox: return for_level(level, [&](Block* b) { ad_launch_viscous_approx(g_ad[b].v, kv, g_stream); return 0; });
+        case ViscousK::None: break;
         }
-        if (!marched && g_pc_fused && ad_inviscid_march_takes(kp)) {
-            // scalar JST with the entropy sensor, matrix dissipation: the per-face march on dual numbers
-            // (kernels_inviscid_march.hip compiled a second time) -- four face evaluations per cell instead of the gather kernel's six;
-            // behind the viscous march it adds the sums it finds in dw(2:5), as in the plain evaluation
-            if (ensure_tiles(level)) return 1;
-            KParams ki = kp;
-            // the thin-layer viscous flux of the preconditioner matrix marches in front of it as well (k_visc_approx_march on dual
-            // numbers), as in the plain approximate residual
-            const bool vaDual = viscous && viscApprox && viscous_is_tiled() >= 2 && kp.fineGrid;
-            if (vaDual) {
-                rc = for_level(level, [&](Block* b) {
-                    if (!b->face_vectors_valid) {
-                        launch_face_vectors(b->v, g_stream);
-                        b->face_vectors_valid = true;
-                    }
-                    return 0;
-                });
-                if (rc) return rc;
-            }
-            if (gfDual) {
-                ki.viscFirst = 1;
-                ad_launch_visc_gf(g_ad_tab, g_gf_tiles[level].first, g_gf_tiles[level].second, ki, g_stream);
-            } else if (vaDual) {
-                ki.viscFirst = 1;
-                ad_launch_visc_march_approx(g_ad_tab, g_tiles[level].first, g_tiles[level].second, ki, g_stream);
-            }
-            ad_launch_inviscid_march(g_ad_tab, g_tiles[level].first, g_tiles[level].second, ki, g_stream);
-            if (gfDual || vaDual) return 0;
-            marched = true;
-        }
-        if (!marched) ad_launch_inviscid_level(g_ad_tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
-        if (gfDual) {
-            ad_launch_visc_gf(g_ad_tab, g_gf_tiles[level].first, g_gf_tiles[level].second, kp, g_stream);
-            return 0;
-        }
-        if (kp.viscous && fabs(kp.rFil) >= 1.e-10) {
-            rc = for_level(level, [&](Block* b) {
-                if (viscApprox) ad_launch_viscous_approx(g_ad[b].v, kp, g_stream);
-                else ad_launch_viscous(g_ad[b].v, kp, g_stream);
-                return 0;
-            });
-            if (rc) return rc;
-        }
-    }
-    return 0;
+        return 0;
+    };
+    if (P.viscFirst) return viscous() || inviscid();
+    return inviscid() || viscous();
 }
 
 // the device table of the snapshot request: per block slot of the level its snapshot array and its scaled reference residual
@@ -1868,9 +1736,7 @@ int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
     if (!useAD && !(delta > 0.0)) return fail("fd_jacobian: delta must be positive");     // forward mode has no step size
     if (useAD) {
         // forward-mode seeds instead of perturbations (adjointUtils.F90:227-409): gather kernels on dual numbers, blocks at rest
-        bool moving = false;
-        for_level(level, [&](Block* b) { moving = moving || b->v.sFace || b->v.moving; return 0; });
-        if (moving) return fail("fd_jacobian(useAD): moving blocks are not linearised (grid velocities)");
+        if (!level_at_rest(level)) return fail("fd_jacobian(useAD): moving blocks are not linearised (grid velocities)");
         if (!g_act.empty()) return fail("fd_jacobian(useAD): actuator regions are not linearised");
         if (g_bc_callback) return fail("fd_jacobian(useAD): a host boundary-condition hook cannot be linearised");
         if (g_turb_bc_callback && g_opts.equations == ADFLOW_RANS && !(flags & ADFLOW_JAC_FROZEN_TURB))
@@ -1960,12 +1826,11 @@ int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
         // included), block_res_state_d, the derivative of the scaled residual is the column of every stencil block
         if (!rc) rc = ad_prepare(level);
         // the marching kernels of the preconditioner matrix write the snapshot of a pass themselves (KParams::snapTab)
+        const bool viscPC = (flags & ADFLOW_JAC_VISC_PC) != 0;
         bool snapInMarch = false;
         if (!rc) {
-            const KParams kq = ad_kparams(level, resFlags);
-            const bool viscApproxA = (resFlags & ADFLOW_RES_VISC_APPROX) != 0 && !(flags & ADFLOW_JAC_VISC_PC);
-            snapInMarch = g_jac_snap && (!(resFlags & ADFLOW_RES_FLOW) || ad_pc_march_applies(kq, viscApproxA)) &&
-                          (!(resFlags & ADFLOW_RES_TURB) || (g_sa_march && g_pc_fused));
+            const FlowPlan P = plan_flow(flow_facts(level, ad_kparams(level, resFlags), ad_visc_approx(resFlags, viscPC), false, true, resFlags));
+            snapInMarch = (!(resFlags & ADFLOW_RES_FLOW) || P.flowSnapInMarch) && (!(resFlags & ADFLOW_RES_TURB) || P.turbSnapInMarch);
             if (snapInMarch) rc = snap_request_begin(level, J);
         }
         for (int l = J.lStart; l < J.lStart + J.nState && !rc; ++l) {
@@ -2013,16 +1878,15 @@ int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
     const double deltaInv = 1.0 / delta;
     // the reference loops colours outside and state variables inside; every (colour, variable) evaluation is independent, so the
     // loops are exchanged here: the nColour evaluations of one variable are kept (dense) and scattered into the blocks together
-    const KParams kpc = make_kparams(level, 1.0, 0);
+    // (the state-perturbation kernel reads only options of kpc that no flag of the evaluation changes)
+    const KParams kpc = res_kparams(level, resFlags);
     // the marching kernels of the preconditioner matrix write the snapshot of an evaluation themselves (KParams::snapTab): not with
-    // actuator regions (their sources are added to dw behind the core)
+    // actuator regions (their sources are added to dw behind the core).  The plan is that of the KParams and flags every coloured
+    // evaluation below builds again (block_res_enqueue)
     bool snapInMarch = false;
     if (!rc) {
-        bool moving = false;
-        for_level(level, [&](Block* b) { moving = moving || b->v.sFace || b->v.moving; return 0; });
-        snapInMarch = g_jac_snap && g_act.empty() &&
-                      (!(resFlags & ADFLOW_RES_FLOW) || pc_march_applies(level, kpc, (resFlags & ADFLOW_RES_VISC_APPROX) != 0)) &&
-                      (!(resFlags & ADFLOW_RES_TURB) || (g_sa_march && !moving));
+        const FlowPlan P = plan_flow(flow_facts(level, kpc, (resFlags & ADFLOW_RES_VISC_APPROX) != 0, false, false, resFlags));
+        snapInMarch = g_act.empty() && (!(resFlags & ADFLOW_RES_FLOW) || P.flowSnapInMarch) && (!(resFlags & ADFLOW_RES_TURB) || P.turbSnapInMarch);
         if (snapInMarch) rc = snap_request_begin(level, J);
     }
     for (int l = J.lStart; l < J.lStart + J.nState && !rc; ++l) {
@@ -2230,6 +2094,7 @@ int res_averaging_level(int level, const KParams& kp, double scaleDtl)
 
 // workgroups of a marching kernel resident at a time: two per CU (256 VGPRs, <= 80 KB of LDS each)
 void adf_note_rvec(int bits) { g_rvec_done |= bits; }
+int adf_fail(const char* what) { return fail("%s", what); }
 void adf_note_snap(int bits) { g_snap_done |= bits; }
 
 int adf_round_size()
@@ -2891,9 +2756,8 @@ static int apply_bc_enqueue(int level, int secondHalo)
         return fail("eulerWallBCTreatment=%d: bcEulerWall has no quadratic extrapolation (1 constant, 2 linear, 4 normal momentum)",
                     g_opts.eulerWallBCTreatment);
     if (pl->anyEulerWall && g_opts.eulerWallBCTreatment == ADFLOW_WALLBC_NORMAL_MOMENTUM && kp.fineGrid) {
-        bool moving = false;
-        for_level(level, [&](Block* b) { moving = moving || b->v.sFace || b->v.moving; return 0; });
-        if (moving) return fail("eulerWallBCTreatment = normal momentum on moving blocks needs the cell-centre grid velocity (not mirrored)");
+        if (!level_at_rest(level))
+            return fail("eulerWallBCTreatment = normal momentum on moving blocks needs the cell-centre grid velocity (not mirrored)");
     }
     LevelTab t;
     if (level_tab(level, &t)) return 1;
@@ -3843,9 +3707,7 @@ int adflow_gpu_sa_solve(int level)
         if (turb_bc_treatment_enqueue(level, kp)) return 1;
         LevelTab t;
         if (level_tab(level, &t)) return 1;
-        bool movingS = false;
-        for_level(level, [&](Block* b) { movingS = movingS || b->v.sFace || b->v.moving; return 0; });
-        const bool marchRes = (g_sa_march == 1 && !movingS);
+        const bool marchRes = (g_sa_march == 1 && level_at_rest(level));
         if (marchRes) {
             if (ensure_sa_tiles(level)) return 1;
             launch_sa_march(t.tab, g_sa_tiles[level].first, g_sa_tiles[level].second, kp, g_stream, true);

@@ -399,9 +399,10 @@ void launch_viscous(const BlkView& b, const KParams& kp, hipStream_t s);
 int viscous_is_tiled();
 void launch_sa_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s, bool solve);
 void launch_visc_march_approx(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
-bool euler_march_radii_capable(const KParams& kp);
+bool euler_march_radii_capable(int fwMode, int doScaling, double adis);
 void launch_visc_gf(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, bool storeGrad, hipStream_t s);
 void adf_note_snap(int bits);   // api.hip: a launcher reports that its kernel wrote the flow (1) / turbulence (2) snapshot entries (KParams::snapTab)
+int adf_fail(const char* what); // api.hip: a launcher reports an internal error (the text of the failed call); returns 1
 void adf_note_rvec(int bits);   // api.hip: a launcher reports that its kernel wrote the flow (1) / turbulence (2) part of kp.rvec
 int adf_round_size();          // api.hip: workgroups of a marching kernel resident at a time (2 x CUs)
 void adf_phase_mark(int i);    // api.hip: optional HIP event between the phases of blocketteRes
@@ -432,12 +433,12 @@ void launch_periodic(const BlkView* tab, const int* blk, const long* off, int n,
 void launch_halo_pack(const BlkView* tab, const int* blk, const long* off, int n, unsigned mask, double* buf, hipStream_t s);
 void launch_halo_unpack(const BlkView* tab, const int* blk, const long* off, int n, unsigned mask, const double* buf,
                         hipStream_t s);
-void launch_inviscid_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
+int launch_inviscid_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
 int inviscid_march_enabled();
-bool launch_roe_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
+int launch_roe_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
 // kernels_pc_march.hip: first-order Roe + thin-layer viscous flux in one march (the mean-flow residual of the preconditioner matrix)
 void launch_pc_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, int kch, hipStream_t s);
-bool roe_march_takes(const KParams& kp);
+bool roe_march_takes(int limiter);   // kernels_roe_march.hip: called by plan_flow (flow_plan.h) only
 void launch_euler_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
 void euler_march_tiles(const BlkView& b, int* ntx, int* nty, int* ntz);
 void launch_restrict_level(const BlkView* ctab, const BlkView* ftab, int nslots, int nx, int ny, int nz, const KParams& kp, hipStream_t s);
@@ -497,7 +498,7 @@ void ad_launch_seed_closures(const BlkView& real, const BlkView& adv, int l, int
 void ad_launch_pc_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, int kch, hipStream_t s);
 void ad_launch_sa_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
 void ad_launch_visc_gf(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
-bool ad_launch_roe_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
-void ad_launch_inviscid_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
+int ad_launch_roe_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
+int ad_launch_inviscid_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
 void ad_launch_selftest_math(int which, const double* x, const double* a, long n, double* y, double* dy, hipStream_t s);
 void ad_launch_visc_march_approx(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);

@@ -283,7 +283,7 @@ void ad_launch_visc_gf(const BlkView* tab, const int4* tiles, int ntiles, const 
 {
     adj::launch_visc_gf(ADV(tab), tiles, ntiles, kp, false, s);
 }
-bool ad_launch_roe_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s)
+int ad_launch_roe_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s)
 {
     return adj::launch_roe_march(ADV(tab), tiles, ntiles, kp, s);
 }
@@ -291,8 +291,8 @@ void ad_launch_visc_march_approx(const BlkView* tab, const int4* tiles, int ntil
 {
     adj::launch_visc_march_approx(ADV(tab), tiles, ntiles, kp, s);
 }
-void ad_launch_inviscid_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s)
+int ad_launch_inviscid_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s)
 {
-    adj::launch_inviscid_march(ADV(tab), tiles, ntiles, kp, s);
+    return adj::launch_inviscid_march(ADV(tab), tiles, ntiles, kp, s);
 }
 #undef ADV

@@ -528,10 +528,10 @@ void launch_euler_march(const BlkView* tab, const int4* tiles, int ntiles, const
 }
 
 // true when launch_euler_march would run the form of the kernel that can compute the radii itself
-bool euler_march_radii_capable(const KParams& kp)
+bool euler_march_radii_capable(int fwMode, int doScaling, double adis)
 {
     // fast_powa is built for moderate exponents (2^(adis log2 r) must stay far from the ends of the exponent range)
-    return !kp.fwMode && (!kp.doScaling || (kp.adis > 0.0 && kp.adis <= 2.0));
+    return !fwMode && (!doScaling || (adis > 0.0 && adis <= 2.0));
 }
 
 // tile decomposition of one block for the table built by the host

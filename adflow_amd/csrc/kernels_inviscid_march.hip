@@ -322,16 +322,19 @@ extern int g_march_kch;
 #endif
 
 // matrix dissipation / Roe upwind over the tile table of the level (the table of the Euler marching kernel)
-void launch_inviscid_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s)
+int launch_inviscid_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s)
 {
-    if (ntiles <= 0) return;
+#ifdef ADF_AD_BUILD
+    // (forward mode: the upwind scheme is k_roe_march's or the gather kernel's)
+    if (kp.spaceDiscr == ADFLOW_UPWIND) return adf_fail("the dual per-face march has no upwind form (internal error)");
+#endif
+    if (ntiles <= 0) return 0;
     if (kp.spaceDiscr == ADFLOW_DISS_MATRIX) launch_im<ADFLOW_DISS_MATRIX>(tab, tiles, ntiles, kp, ::g_march_kch, s);
 #ifndef ADF_AD_BUILD
     else if (kp.spaceDiscr == ADFLOW_UPWIND) launch_im<ADFLOW_UPWIND>(tab, tiles, ntiles, kp, ::g_march_kch, s);
-#else
-    else if (kp.spaceDiscr == ADFLOW_UPWIND) return;      // (forward mode: the upwind scheme is k_roe_march's or the gather kernel's)
 #endif
-    else launch_im<ADFLOW_DISS_SCALAR>(tab, tiles, ntiles, kp, ::g_march_kch, s);     // NS / RANS on the fine level only (caller)
+    else launch_im<ADFLOW_DISS_SCALAR>(tab, tiles, ntiles, kp, ::g_march_kch, s);     // NS / RANS on the fine level only (plan_flow)
+    return 0;
 }
 
 #ifndef ADF_AD_BUILD

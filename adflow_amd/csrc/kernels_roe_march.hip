@@ -489,24 +489,25 @@ static void launch_rm(const BlkView* tab, const int4* tiles, int ntiles, const K
 #endif
 }
 
-bool roe_march_takes(const KParams& kp)
+#ifndef ADF_AD_BUILD
+// the limiters the switch below has kernels for: plan_flow (flow_plan.h), its only caller, names the Roe march for these alone
+bool roe_march_takes(int limiter)
 {
-    if (!::g_roe_march || kp.spaceDiscr != ADFLOW_UPWIND || !kp.fineGrid) return false;
-    const int lim = kp.lumpedDiss ? ADFLOW_LIM_FIRST_ORDER : kp.limiter;
-    return lim == ADFLOW_LIM_FIRST_ORDER || lim == ADFLOW_LIM_NONE || lim == ADFLOW_LIM_VANALBADA || lim == ADFLOW_LIM_MINMOD;
+    return limiter == ADFLOW_LIM_FIRST_ORDER || limiter == ADFLOW_LIM_NONE || limiter == ADFLOW_LIM_VANALBADA || limiter == ADFLOW_LIM_MINMOD;
 }
+#endif
 
-// true when the launch was taken: second-order Roe upwind on the fine level of blocks at rest
-bool launch_roe_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s)
+// Roe upwind on the fine level of blocks at rest; 0, or the error of a launch the plan should not have named
+int launch_roe_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s)
 {
+    if (kp.spaceDiscr != ADFLOW_UPWIND || !kp.fineGrid) return adf_fail("launch_roe_march: not the upwind scheme on the fine level (internal error)");
+    if (ntiles <= 0) return 0;
     // (the approximate residual changes the Roe scheme only through the limiter: lumpedDiss = first order)
-    if (!::g_roe_march || kp.spaceDiscr != ADFLOW_UPWIND || !kp.fineGrid) return false;
-    if (ntiles <= 0) return true;
     switch (kp.lumpedDiss ? ADFLOW_LIM_FIRST_ORDER : kp.limiter) {
-    case ADFLOW_LIM_FIRST_ORDER: launch_rm<ADFLOW_LIM_FIRST_ORDER>(tab, tiles, ntiles, kp, s); return true;
-    case ADFLOW_LIM_NONE: launch_rm<ADFLOW_LIM_NONE>(tab, tiles, ntiles, kp, s); return true;
-    case ADFLOW_LIM_VANALBADA: launch_rm<ADFLOW_LIM_VANALBADA>(tab, tiles, ntiles, kp, s); return true;
-    case ADFLOW_LIM_MINMOD: launch_rm<ADFLOW_LIM_MINMOD>(tab, tiles, ntiles, kp, s); return true;
-    default: return false;
+    case ADFLOW_LIM_FIRST_ORDER: launch_rm<ADFLOW_LIM_FIRST_ORDER>(tab, tiles, ntiles, kp, s); return 0;
+    case ADFLOW_LIM_NONE: launch_rm<ADFLOW_LIM_NONE>(tab, tiles, ntiles, kp, s); return 0;
+    case ADFLOW_LIM_VANALBADA: launch_rm<ADFLOW_LIM_VANALBADA>(tab, tiles, ntiles, kp, s); return 0;
+    case ADFLOW_LIM_MINMOD: launch_rm<ADFLOW_LIM_MINMOD>(tab, tiles, ntiles, kp, s); return 0;
+    default: return adf_fail("launch_roe_march: no kernel for this limiter (internal error: roe_march_takes lists the same ones)");
     }
 }

@@ -87,13 +87,13 @@ inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { std::memmove(d, s, n); return hipSuccess; }
 
 namespace hostsim {
-void launch(dim3 grid, dim3 block, const std::function<void()>& body);
+void launch(const char* kernel, dim3 grid, dim3 block, const std::function<void()>& body);
 void syncthreads();
 double shfl_exchange(double v, int srcLaneInBlock);   // block-convergent
 }  // namespace hostsim
 
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    hostsim::launch((grid), (block), [&]() { kernel(__VA_ARGS__); })
+    hostsim::launch(#kernel, (grid), (block), [&]() { kernel(__VA_ARGS__); })
 
 inline void __syncthreads() { hostsim::syncthreads(); }
 inline double atomicAdd(double* p, double v) {

@@ -2,9 +2,13 @@
 // (see hip/hip_runtime.h in this directory).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 
 thread_local uint3_ threadIdx, blockIdx;
 thread_local dim3 blockDim, gridDim;
@@ -151,8 +155,20 @@ double shfl_exchange(double v, int src)
     return out;
 }
 
-void launch(dim3 grid, dim3 block, const std::function<void()>& body)
+// launch trace (tests/test_dispatch_plan.py): off by default; one line per launch -- the kernel as SPELLED at the launch site (template
+// arguments and parentheses included: the recorded tables depend on that spelling), grid, block.  Not synchronised: launches come from
+// the one host thread that drives the library.
+static bool g_trace_on = false;
+static std::string g_trace;
+
+void launch(const char* kernel, dim3 grid, dim3 block, const std::function<void()>& body)
 {
+    if (g_trace_on) {
+        char dims[96];
+        std::snprintf(dims, sizeof dims, " %u,%u,%u %u,%u,%u\n", grid.x, grid.y, grid.z, block.x, block.y, block.z);
+        g_trace += kernel;
+        g_trace += dims;
+    }
     const int nthreads = (int)(block.x * block.y * block.z);
     const long nblocks = (long)grid.x * grid.y * grid.z;
 #pragma omp parallel
@@ -200,3 +216,21 @@ void launch(dim3 grid, dim3 block, const std::function<void()>& body)
 }
 
 }  // namespace hostsim
+
+// on != 0: start (or clear) the launch trace; 0: stop and drop it
+extern "C" void hostsim_trace_start(int on)
+{
+    hostsim::g_trace_on = on != 0;
+    hostsim::g_trace.clear();
+}
+// copies the trace (text, NUL-terminated, at most cap bytes) and returns the size a full copy needs: a caller whose cap is smaller got a
+// truncated copy (ask with cap = 0 first)
+extern "C" long hostsim_trace_read(char* buf, long cap)
+{
+    if (buf && cap > 0) {
+        const size_t n = std::min((size_t)cap - 1, hostsim::g_trace.size());
+        std::memcpy(buf, hostsim::g_trace.data(), n);
+        buf[n] = 0;
+    }
+    return (long)hostsim::g_trace.size() + 1;
+}
