@@ -116,6 +116,10 @@ struct CommPattern {
     };
     std::vector<Periodic> periodic;
     bool built = false;
+    // the exchange in reverse (adflow_gpu_jacobian_mult, transposed): donor-sorted accumulation lists, [0] the same-process pairs,
+    // [1 + i] the message that comes back over send list i; built at the first transposed product
+    std::vector<JmAccList> acc;
+    bool accBuilt = false;
 };
 
 struct ActRegion {       // one actuator region (actuatorRegionData.F90); the cell list addresses level-1 blocks
@@ -162,9 +166,22 @@ void free_list(CommList& l)
     l = CommList();
 }
 
+void free_acc_list(JmAccList& a)
+{
+    if (a.tBlk) (void)hipFree(a.tBlk);
+    if (a.tOff) (void)hipFree(a.tOff);
+    if (a.seg) (void)hipFree(a.seg);
+    if (a.sBlk) (void)hipFree(a.sBlk);
+    if (a.sOff) (void)hipFree(a.sOff);
+    a = JmAccList();
+}
+
 // device lists of a pattern: rebuilt from the host copies at the next exchange
 void drop_comm_lists(CommPattern& cp)
 {
+    for (auto& a : cp.acc) free_acc_list(a);
+    cp.acc.clear();
+    cp.accBuilt = false;
     free_list(cp.local);
     for (auto& l : cp.sends) free_list(l);
     for (auto& l : cp.recvs) free_list(l);
@@ -590,6 +607,9 @@ int adflow_gpu_block_register(int nn, int level, int sps, const adflow_block_des
 static void bc_plan_drop(int level);
 static void bc_plan_drop_all();
 static void ad_cache_drop();      // the cached dual arrays of the forward-mode assembly refer to the blocks
+static int64_t jm_release();      // ... and so do the scratch arrays of the matrix products (adflow_gpu_jacobian_mult)
+static bool g_jac_valid = false; // adflow_gpu_fd_jacobian left a matrix on the blocks of level g_jac_level
+static int g_jac_level = 0;
 
 int adflow_gpu_block_release(int nn, int level, int sps)
 {
@@ -598,6 +618,7 @@ int adflow_gpu_block_release(int nn, int level, int sps)
     if (g_stream) (void)hipStreamSynchronize(g_stream);
     bc_plan_drop(level);
     ad_cache_drop();
+    (void)jm_release();
     for (void* p : it->second->allocs) (void)hipFree(p);
     if (it->second->jac_raw) (void)hipFree(it->second->jac_raw);
     if (it->second->snap_raw) (void)hipFree(it->second->snap_raw);
@@ -613,6 +634,7 @@ int adflow_gpu_release_all(void)
     if (g_stream) (void)hipStreamSynchronize(g_stream);
     bc_plan_drop_all();
     ad_cache_drop();
+    (void)jm_release();
     for (auto& kv : g_blocks) {
         for (void* p : kv.second->allocs) (void)hipFree(p);
         if (kv.second->jac_raw) (void)hipFree(kv.second->jac_raw);
@@ -621,6 +643,7 @@ int adflow_gpu_release_all(void)
         delete kv.second;
     }
     g_blocks.clear();
+    g_jac_valid = false;          // the stencil blocks went with the blocks
     {
         std::vector<int> levels;
         for (auto& kv : g_tab) levels.push_back(kv.first);
@@ -1438,7 +1461,6 @@ int adflow_gpu_block_res(int level, unsigned flags)
 
 // ---- coloured finite-difference Jacobian (adjointUtils::setupStateResidualMatrix, useAD = F; adjointUtils.F90:7-715) ----------
 static JacSpec g_jac;                 // stencil / colouring / state range of the last assembly
-static bool g_jac_valid = false;
 
 static void jac_spec(unsigned flags, bool viscous, bool rans, JacSpec* J)
 {
@@ -1861,6 +1883,7 @@ int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
         restore();
         if (rc) return rc;
         g_jac = J;
+        g_jac_level = level;
         g_jac_valid = true;
         return 0;
     }
@@ -1931,6 +1954,7 @@ int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
     restore();
     if (rc) return rc;
     g_jac = J;
+    g_jac_level = level;
     g_jac_valid = true;
     return sync_and_check();
 }
@@ -1939,7 +1963,8 @@ int adflow_gpu_release_workspace(int64_t* bytes)
 {
     if (need_ready()) return 1;
     if (g_stream) HIPCHK(hipStreamSynchronize(g_stream));
-    if (bytes) *bytes = (int64_t)g_ad_slab_bytes;
+    const int64_t jm = jm_release();
+    if (bytes) *bytes = (int64_t)g_ad_slab_bytes + jm;
     ad_drop();
     return 0;
 }
@@ -3685,6 +3710,283 @@ int adflow_gpu_nk_residual(const double* wVec, double* rVec, long n)
     HIPCHK(hipMemcpyAsync(g_vec_dev, wVec, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
     if (nk_residual_enqueue(g_vec_dev, g_vec_dev)) return 1;
     HIPCHK(hipMemcpyAsync(rVec, g_vec_dev, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+// ---- products with the assembled matrix (kernels_jacmult.hip): y = J x, y = J^T x on PETSc-layout device vectors ----------------
+// MatMult on the matrices of setupStateResidualMatrix: solveAdjoint's GMRES on dRdwT (adjointAPI.F90:661-863, :741, :806).
+namespace {
+struct JmWork {
+    int level = 0, nState = 0, nslots = 0, nx = 0, ny = 0, nz = 0;
+    long ndof = 0;                     // nState x owned cells of the level
+    long zeroGen = -1;                 // g_state_gen at which the halos of xs were last cleared
+    size_t bytes = 0;
+    std::vector<long> sig;             // what the work space was laid out for
+    std::vector<void*> raw;            // one allocation per block: xs, ys (nState components each)
+    std::vector<JmBlk> h;              // host copy of the table, indexed by nn
+    JmBlk* tab = nullptr;
+    BlkView *tabX = nullptr, *tabY = nullptr;    // the level's block table with w -> xs / ys: the halo kernels on a foreign array
+};
+JmWork g_jm;
+}  // namespace
+
+static int64_t jm_release()
+{
+    const int64_t n = (int64_t)g_jm.bytes;
+    for (void* p : g_jm.raw) (void)hipFree(p);
+    if (g_jm.tab) (void)hipFree(g_jm.tab);
+    if (g_jm.tabX) (void)hipFree(g_jm.tabX);
+    if (g_jm.tabY) (void)hipFree(g_jm.tabY);
+    g_jm = JmWork();
+    return n;
+}
+
+// scratch arrays and tables of the product on `level` (kept between calls; laid out again when blocks or matrix changed)
+static int jm_prepare(int level)
+{
+    const int nS = g_jac.nState;
+    std::vector<long> sig = {level, nS};
+    int maxnn = 0;
+    int rc = for_level(level, [&](Block* b) {
+        if (!b->jac || b->jac_ncomp != g_jac.nStencil * nS * nS)
+            return fail("jacobian_mult: a block of level %d has no assembled blocks (registered after the assembly?)", level);
+        if ((double)b->v.nbox * nS * nS * 8.0 >= 4294967296.0)
+            return fail("jacobian_mult: block of %ld box cells: nState^2 planes exceed the 4 GiB the kernels address from one base", b->v.nbox);
+        return 0;
+    });
+    if (rc) return rc;
+    for (auto& kv : g_blocks)
+        if (std::get<0>(kv.first) == level) {
+            sig.push_back(std::get<2>(kv.first)); sig.push_back((long)(intptr_t)kv.second); sig.push_back((long)(intptr_t)kv.second->jac);
+            sig.push_back(kv.second->v.nbox);
+            maxnn = std::max(maxnn, std::get<2>(kv.first));
+        }
+    if (g_jm.tab && sig == g_jm.sig) return 0;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    (void)jm_release();
+    g_jm.level = level; g_jm.nState = nS; g_jm.nslots = maxnn;
+    g_jm.h.assign(maxnn + 1, JmBlk());
+    memset(g_jm.h.data(), 0, sizeof(JmBlk) * g_jm.h.size());
+    std::vector<BlkView> hx(maxnn + 1), hy(maxnn + 1);
+    memset(hx.data(), 0, sizeof(BlkView) * hx.size());
+    memset(hy.data(), 0, sizeof(BlkView) * hy.size());
+    for (auto& kv : g_blocks) {
+        if (std::get<0>(kv.first) != level) continue;
+        Block* b = kv.second;
+        const BlkView& v = b->v;
+        const size_t bytes = (size_t)v.nbox * 2 * nS * sizeof(double) + 256;
+        void* raw = nullptr;
+        HIPCHK(hipMalloc(&raw, bytes));
+        g_jm.raw.push_back(raw);
+        g_jm.bytes += bytes;
+        HIPCHK(hipMemsetAsync(raw, 0, bytes, g_stream));
+        JmBlk& q = g_jm.h[std::get<2>(kv.first)];
+        q.nx = v.nx; q.ny = v.ny; q.nz = v.nz; q.il = v.il; q.jl = v.jl; q.kl = v.kl; q.ib = v.ib; q.jb = v.jb; q.kb = v.kb;
+        q.ldi = v.ldi; q.ldk = v.ldk; q.nbox = v.nbox;
+        q.jac = b->jac;
+        q.xs = (double*)raw + ADF_PAD0;
+        q.ys = q.xs + (size_t)v.nbox * nS;
+        hx[std::get<2>(kv.first)] = v; hx[std::get<2>(kv.first)].w = q.xs;
+        hy[std::get<2>(kv.first)] = v; hy[std::get<2>(kv.first)].w = q.ys;
+        g_jm.nx = std::max(g_jm.nx, v.nx); g_jm.ny = std::max(g_jm.ny, v.ny); g_jm.nz = std::max(g_jm.nz, v.nz);
+    }
+    long off = 0;                     // PETSc vector order: block nn ascending (NKSolvers.F90:1240-1253), nState entries per cell
+    for (auto& q : g_jm.h) { q.vecOff = off; off += (long)q.nx * q.ny * q.nz * nS; }
+    g_jm.ndof = off;
+    HIPCHK(hipMalloc((void**)&g_jm.tab, sizeof(JmBlk) * g_jm.h.size()));
+    HIPCHK(hipMalloc((void**)&g_jm.tabX, sizeof(BlkView) * hx.size()));
+    HIPCHK(hipMalloc((void**)&g_jm.tabY, sizeof(BlkView) * hy.size()));
+    HIPCHK(hipMemcpy(g_jm.tab, g_jm.h.data(), sizeof(JmBlk) * g_jm.h.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(g_jm.tabX, hx.data(), sizeof(BlkView) * hx.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(g_jm.tabY, hy.data(), sizeof(BlkView) * hy.size(), hipMemcpyHostToDevice));
+    g_jm.sig = sig;
+    g_jm.zeroGen = g_state_gen;
+    return 0;
+}
+
+// one reverse exchange as a donor-sorted list: targets (tb, to) with sources (sb, so), or with the position in the message
+static int jm_acc_build(JmAccList& a, const int* d_tBlk, const long* d_tOff, const int* d_sBlk, const long* d_sOff, int n)
+{
+    a = JmAccList();
+    if (n <= 0) return 0;
+    std::vector<int> tb(n), sb(n);
+    std::vector<long> to(n), so(n);
+    HIPCHK(hipMemcpy(tb.data(), d_tBlk, sizeof(int) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(to.data(), d_tOff, sizeof(long) * n, hipMemcpyDeviceToHost));
+    if (d_sBlk) {
+        HIPCHK(hipMemcpy(sb.data(), d_sBlk, sizeof(int) * n, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(so.data(), d_sOff, sizeof(long) * n, hipMemcpyDeviceToHost));
+    } else
+        for (int t = 0; t < n; ++t) { sb[t] = t; so[t] = 0; }
+    std::vector<int> perm(n);
+    for (int t = 0; t < n; ++t) perm[t] = t;
+    std::sort(perm.begin(), perm.end(), [&](int p, int q) {
+        if (tb[p] != tb[q]) return tb[p] < tb[q];
+        if (to[p] != to[q]) return to[p] < to[q];
+        if (sb[p] != sb[q]) return sb[p] < sb[q];
+        return so[p] < so[q];
+    });
+    std::vector<int> utb, seg, ssb(n);
+    std::vector<long> uto, sso(n);
+    for (int e = 0; e < n; ++e) {
+        const int t = perm[e];
+        if (e == 0 || tb[t] != utb.back() || to[t] != uto.back()) { utb.push_back(tb[t]); uto.push_back(to[t]); seg.push_back(e); }
+        ssb[e] = sb[t]; sso[e] = so[t];
+    }
+    seg.push_back(n);
+    a.nu = (int)utb.size(); a.nsrc = n;
+    HIPCHK(hipMalloc((void**)&a.tBlk, sizeof(int) * a.nu));
+    HIPCHK(hipMalloc((void**)&a.tOff, sizeof(long) * a.nu));
+    HIPCHK(hipMalloc((void**)&a.seg, sizeof(int) * (a.nu + 1)));
+    HIPCHK(hipMalloc((void**)&a.sBlk, sizeof(int) * n));
+    HIPCHK(hipMemcpy(a.tBlk, utb.data(), sizeof(int) * a.nu, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(a.tOff, uto.data(), sizeof(long) * a.nu, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(a.seg, seg.data(), sizeof(int) * (a.nu + 1), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(a.sBlk, ssb.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+    if (d_sBlk) {
+        HIPCHK(hipMalloc((void**)&a.sOff, sizeof(long) * n));
+        HIPCHK(hipMemcpy(a.sOff, sso.data(), sizeof(long) * n, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+static int jm_acc_lists(CommPattern* cp)
+{
+    if (cp->accBuilt) return 0;
+    for (auto& a : cp->acc) free_acc_list(a);
+    cp->acc.assign(1 + cp->sends.size(), JmAccList());
+    if (jm_acc_build(cp->acc[0], cp->local.blkA, cp->local.offA, cp->local.blkB, cp->local.offB, cp->local.n)) return 1;
+    for (size_t i = 0; i < cp->sends.size(); ++i)
+        if (jm_acc_build(cp->acc[1 + i], cp->sends[i].blkA, cp->sends[i].offA, nullptr, nullptr, cp->sends[i].n)) return 1;
+    cp->accBuilt = true;
+    return 0;
+}
+
+// the registered 2-layer cell pattern of the level, or NULL when there is none (then no halo has a donor).  A rotational
+// periodicity would have to turn the velocity entries of the halos (forward: rotMatrix, reverse: its transpose): refused
+static int jm_pattern(int level, CommPattern** out)
+{
+    *out = nullptr;
+    if (!g_comm.count(std::make_pair(level, 2))) return 0;
+    if (build_comm(level, 2, out)) return 1;
+    if (g_jac.lStart == 0 && g_jac.nState >= 5)
+        for (auto& pd : (*out)->periodic) {
+            bool identity = true;
+            for (int q = 0; q < 9; ++q)
+                if (pd.rotMatrix[q] != ((q % 4 == 0) ? 1.0 : 0.0)) identity = false;
+            if (!identity && !pd.h_block.empty())
+                return fail("jacobian_mult: rotational periodicity is not supported by the product (a registered periodic transformation of "
+                            "level %d rotates the velocities of its halos)", level);
+        }
+    return 0;
+}
+
+static int jm_mult_enqueue(int level, int transpose, const double* d_x, double* d_y)
+{
+    if (jm_prepare(level)) return 1;
+    CommPattern* cp;
+    if (jm_pattern(level, &cp)) return 1;
+    const int nS = g_jm.nState;
+    const unsigned mask = (1u << nS) - 1u;
+    JmStencil S;
+    S.n = g_jac.nStencil;
+    for (int s = 0; s < S.n; ++s)
+        for (int d = 0; d < 3; ++d) {
+            S.d[s][d] = g_jac.st[s][d];
+            if (S.d[s][d] < -2 || S.d[s][d] > 2) return fail("jacobian_mult: stencil offset beyond the two halo layers");
+        }
+    if (g_jm.zeroGen != g_state_gen) {
+        // patterns may have changed: a halo that lost its donor must read as zero again
+        for (auto& q : g_jm.h)
+            if (q.xs) HIPCHK(hipMemsetAsync(q.xs - ADF_PAD0, 0, ((size_t)q.nbox * nS + ADF_PAD0) * sizeof(double), g_stream));
+        g_jm.zeroGen = g_state_gen;
+    }
+    launch_jm_scatter(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, d_x, g_stream);
+    if (!transpose) {
+        if (cp) {
+            bool remote = false;
+            if (comm_exchange_begin(cp, g_jm.tabX, mask, nS, &remote)) return 1;
+#ifndef ADFLOW_NO_RCCL
+            if (remote && g_overlap) HIPCHK(hipStreamWaitEvent(g_stream, g_evComm, 0));
+#endif
+            for (auto& l : cp->recvs) launch_halo_unpack(g_jm.tabX, l.blkA, l.offA, l.n, mask, l.buf, g_stream);
+        }
+        launch_jac_mult(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, S, d_y, g_stream);
+        return 0;
+    }
+    launch_jac_mult_t(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, S, g_stream);
+    if (cp) {
+        if (jm_acc_lists(cp)) return 1;
+        // the messages of the forward exchange the other way: the halos of the receive lists go back to the ranks they came from
+        for (auto& l : cp->recvs) launch_halo_pack(g_jm.tabY, l.blkA, l.offA, l.n, mask, l.buf, g_stream);
+        const bool remote = !cp->sends.empty() || !cp->recvs.empty();
+        if (remote) {
+#ifndef ADFLOW_NO_RCCL
+            if (!g_nccl) return fail("jacobian_mult needs other ranks but adflow_gpu_comm_init was not called");
+            hipStream_t sx = g_overlap ? g_streamX : g_stream;
+            if (g_overlap) {
+                HIPCHK(hipEventRecord(g_evPack, g_stream));
+                HIPCHK(hipStreamWaitEvent(g_streamX, g_evPack, 0));
+            }
+            NCCLCHK(ncclGroupStart());
+            for (auto& l : cp->recvs)
+                if (l.n > 0) NCCLCHK(ncclSend(l.buf, (size_t)nS * l.n, ncclDouble, l.peer, g_nccl, sx));
+            for (auto& l : cp->sends)
+                if (l.n > 0) NCCLCHK(ncclRecv(l.buf, (size_t)nS * l.n, ncclDouble, l.peer, g_nccl, sx));
+            NCCLCHK(ncclGroupEnd());
+            if (g_overlap) HIPCHK(hipEventRecord(g_evComm, g_streamX));
+#else
+            return fail("built without RCCL: the product across ranks needs it");
+#endif
+        }
+        // same-process pairs while the messages are in flight, then the messages in the order of the send lists: every donor is
+        // updated by one lane per list, the lists one after the other
+        launch_jac_halo_accumulate(g_jm.tab, cp->acc[0], nS, nullptr, 0, g_stream);
+#ifndef ADFLOW_NO_RCCL
+        if (remote && g_overlap) HIPCHK(hipStreamWaitEvent(g_stream, g_evComm, 0));
+#endif
+        for (size_t i = 0; i < cp->sends.size(); ++i)
+            launch_jac_halo_accumulate(g_jm.tab, cp->acc[1 + i], nS, cp->sends[i].buf, cp->sends[i].n, g_stream);
+    }
+    launch_jm_gather(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, d_y, g_stream);
+    return 0;
+}
+
+static int jm_check(int level, const double* x, const double* y, long n)
+{
+    if (need_ready()) return 1;
+    if (!g_jac_valid) return fail("jacobian_mult: no assembled Jacobian (call adflow_gpu_fd_jacobian first)");
+    if (level != g_jac_level) return fail("jacobian_mult: level %d is not the level of the assembly (%d)", level, g_jac_level);
+    if (!x || !y) return fail("jacobian_mult: %s is NULL", !x ? "x" : "y");
+    if (x == y) return fail("jacobian_mult: x and y are the same vector (the product is not done in place)");
+    long cells = 0;
+    int rc = for_level(level, [&](Block* b) {
+        if (!b->jac) return fail("jacobian_mult: a block of level %d has no assembled blocks (registered after the assembly?)", level);
+        cells += (long)b->v.nx * b->v.ny * b->v.nz;
+        return 0;
+    });
+    if (rc) return rc;
+    if (n != cells * g_jac.nState)
+        return fail("jacobian_mult: n=%ld but the matrix of level %d has %ld rows (nState = %d x %ld owned cells)", n, level,
+                    cells * g_jac.nState, g_jac.nState, cells);
+    return 0;
+}
+
+int adflow_gpu_jacobian_mult_dev(int level, int transpose, const double* d_x, double* d_y, long n)
+{
+    if (jm_check(level, d_x, d_y, n)) return 1;
+    if (jm_mult_enqueue(level, transpose, d_x, d_y)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_jacobian_mult(int level, int transpose, const double* x, double* y, long n)
+{
+    if (jm_check(level, x, y, n)) return 1;
+    if (vec_reserve((size_t)2 * n)) return 1;
+    HIPCHK(hipMemcpyAsync(g_vec_dev, x, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    if (jm_mult_enqueue(level, transpose, g_vec_dev, g_vec_dev + n)) return 1;
+    HIPCHK(hipMemcpyAsync(y, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
 }

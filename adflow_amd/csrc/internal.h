@@ -368,6 +368,29 @@ void launch_closures_halo(const BlkView& b, const KParams& kp, hipStream_t s);
 void launch_fd_extract(const BlkView& b, double* dwref, double* jac, int l, int col, const JacSpec& J, double deltaInv, double turbResScale,
                        hipStream_t s);
 
+// products with the assembled matrix (kernels_jacmult.hip): one block of the level as the product kernels see it.  xs / ys: the
+// halo'd scratch arrays of nState components (box layout of the block); jac: the stencil blocks of the assembly
+struct JmBlk {
+    int nx, ny, nz, il, jl, kl, ib, jb, kb, ldi, ldk, pad;
+    long nbox;
+    long vecOff;          // first entry of the block in the vectors of the product: nState (not nw) entries per owned cell
+    const double* jac;
+    double *xs, *ys;
+};
+struct JmStencil { int n; int d[33][3]; };
+// one reverse exchange as a donor-sorted list: target t (an owned cell) receives the sources seg[t] .. seg[t+1]-1 in list order
+struct JmAccList {
+    int nu = 0, nsrc = 0;
+    int* tBlk = nullptr; long* tOff = nullptr; int* seg = nullptr;
+    int* sBlk = nullptr;      // block slot of the source halo cell, or its position in the message
+    long* sOff = nullptr;     // offset of the source halo cell (NULL: the sources are message entries)
+};
+void launch_jm_scatter(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const double* x, hipStream_t s);
+void launch_jm_gather(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, double* y, hipStream_t s);
+void launch_jac_mult(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, double* y, hipStream_t s);
+void launch_jac_mult_t(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, hipStream_t s);
+void launch_jac_halo_accumulate(const JmBlk* tab, const JmAccList& a, int nState, const double* buf, int nbuf, hipStream_t s);
+
 // The level-batched launches fold (block slot, plane) into gridDim.z, which HIP limits to 65535: a launcher whose level has more
 // slots than fit calls itself on consecutive slot ranges (the kernels index the table relative to the pointer they get).
 extern int g_max_grid_z;          // 65535; tuning "max_grid_z" lowers it for the tests

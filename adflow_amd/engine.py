@@ -124,7 +124,8 @@ class Engine:
         self._chk(self.lib.adflow_gpu_fd_jacobian(level, flags, float(delta)))
 
     def releaseWorkspace(self) -> int:
-        """gives the dual-number slab a forward-mode assembly keeps between calls back to the device; returns the bytes released"""
+        """gives the dual-number slab a forward-mode assembly keeps between calls, and the scratch arrays of jacobianMult, back to the
+        device; returns the bytes released"""
         n = ctypes.c_int64(0)
         self._chk(self.lib.adflow_gpu_release_workspace(ctypes.byref(n)))
         return int(n.value)
@@ -162,6 +163,18 @@ class Engine:
         out = np.zeros((ns, ns, st.shape[0], blk.nx, blk.ny, blk.nz), order="F")
         self._chk(self.lib.adflow_gpu_download_jacobian_rows(nn, level, sps, out.ctypes.data))
         return out
+
+    def jacobianMult(self, x, level=1, transpose=False):
+        """y = J x, or J^T x with transpose, for the matrix setupStateResidualMatrix left on the device (MatMult on dRdw / dRdwT,
+        adjointAPI.F90:741): x and y in the PETSc layout with nState variables per owned cell of the level"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.zeros_like(x)
+        self._chk(self.lib.adflow_gpu_jacobian_mult(level, int(bool(transpose)), x.ctypes.data, y.ctypes.data, x.size))
+        return y
+
+    def jacobianMultDev(self, d_x: int, d_y: int, n: int, level=1, transpose=False):
+        """the same on device pointers (the addresses of two device vectors of n doubles, e.g. torch.Tensor.data_ptr())"""
+        self._chk(self.lib.adflow_gpu_jacobian_mult_dev(level, int(bool(transpose)), ctypes.c_void_p(d_x), ctypes.c_void_p(d_y), int(n)))
 
     def blocketteRes(self, level=1, updateIntermed=True, flowRes=True, turbRes=True, dissApprox=False, viscApprox=False,
                      useBlockettes=False, halo=False, closures=False):

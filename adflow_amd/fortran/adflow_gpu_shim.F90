@@ -315,6 +315,21 @@ module adflowGpuShim
             integer(c_int), value :: nn, level, sps
             type(c_ptr), value :: rows
         end function
+        ! y = J x / J^T x with the assembled blocks (MatMult on dRdw / dRdwT, adjointAPI.F90:741): host vectors, and DEVICE
+        ! pointers (VecHIPGetArrayRead / VecHIPGetArrayWrite) for the _dev form
+        integer(c_int) function adflow_gpu_jacobian_mult(level, transpose, x, y, n) bind(C, name="adflow_gpu_jacobian_mult")
+            import :: c_int, c_long, c_double
+            integer(c_int), value :: level, transpose
+            real(c_double), intent(in) :: x(*)
+            real(c_double), intent(out) :: y(*)
+            integer(c_long), value :: n
+        end function
+        integer(c_int) function adflow_gpu_jacobian_mult_dev(level, transpose, x, y, n) bind(C, name="adflow_gpu_jacobian_mult_dev")
+            import :: c_int, c_ptr, c_long
+            integer(c_int), value :: level, transpose
+            type(c_ptr), value :: x, y
+            integer(c_long), value :: n
+        end function
         integer(c_int) function adflow_gpu_reference_shock_sensor(level) bind(C, name="adflow_gpu_reference_shock_sensor")
             import :: c_int
             integer(c_int), value :: level
@@ -697,5 +712,19 @@ contains
         call gpuCheck(adflow_gpu_update_wall_distances(int(level, c_int), c_loc(xSurf), int(size(xSurf), c_int64_t)), &
                       "gpuUpdateWallDistances")
     end subroutine gpuUpdateWallDistances
+
+    ! the body of a MatShell's MATOP_MULT (transposed = .false.) / MATOP_MULT_TRANSPOSE (.true.) in place of MatMult on the
+    ! assembled dRdw / dRdwT (adjointAPI.F90:741, :806; dRdwMatMult :1050, dRdwTMatMult :1007): xDev, yDev are the device arrays
+    ! of the two PETSc vectors (VECHIP), n their local size = nState x owned cells of the level
+    subroutine gpuJacobianMult(level, transposed, xDev, yDev, n)
+        integer(kind=intType), intent(in) :: level
+        logical, intent(in) :: transposed
+        type(c_ptr), intent(in) :: xDev, yDev
+        integer(kind=intType), intent(in) :: n
+        integer(c_int) :: tr
+        tr = 0_c_int
+        if (transposed) tr = 1_c_int
+        call gpuCheck(adflow_gpu_jacobian_mult_dev(int(level, c_int), tr, xDev, yDev, int(n, c_long)), "gpuJacobianMult")
+    end subroutine gpuJacobianMult
 
 end module adflowGpuShim

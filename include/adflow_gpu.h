@@ -435,7 +435,7 @@ int adflow_gpu_abi_sizes2(int* bc_subface_bytes, int* comm_pattern_bytes);
 enum { ADFLOW_JAC_PC = 1u, ADFLOW_JAC_FROZEN_TURB = 2u, ADFLOW_JAC_TURB_ONLY = 4u, ADFLOW_JAC_VISC_PC = 8u, ADFLOW_JAC_USE_AD = 16u };
 int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta);
 /* Hands back the work space an assembly keeps between calls -- the slab of dual arrays of ADFLOW_JAC_USE_AD (about 640 B per box cell:
- * 8.4 GB on the 8 x 160x128x64 mesh) -- to the device allocator: what the host calls when the matrix is assembled and the memory is
+ * 8.4 GB on the 8 x 160x128x64 mesh) -- and the scratch arrays of adflow_gpu_jacobian_mult to the device allocator: what the host calls when the matrix is assembled and the memory is
  * wanted elsewhere (PETSc objects, further multigrid levels).  *bytes (may be NULL): what was released.  The next forward-mode
  * assembly lays the slab out again.  Mirrors nothing in the reference, whose Tapenade derivative arrays live in flowDomsd for the
  * whole run (adjointUtils.F90:87-99 allocDerivativeValues). */
@@ -458,6 +458,22 @@ int adflow_gpu_download_jacobian(int nn, int level, int sps, double* blocks);
  * blocks blk(ll, l) of a row cell are contiguous and the cells follow in the order of the PETSc rows of the block (i fastest).
  * Transposed on the device, copied in slabs of k planes */
 int adflow_gpu_download_jacobian_rows(int nn, int level, int sps, double* rows);
+/* y = J x (transpose = 0) or y = J^T x (transpose != 0) with the matrix of the last successful adflow_gpu_fd_jacobian, across the
+ * blocks of `level` (the level of the assembly): MatMult on dRdw / dRdwT, the operation solveAdjoint's GMRES is made of
+ * (adjointAPI.F90:661-863, MatMult :741 / :806; dRdwTMatMult :1007, dRdwMatMult :1050) -- the blocks never leave the device.
+ * Vectors: the layout of adflow_gpu_set_w_vec / _get_r_vec (block, k, j, i, variable fastest) with nState (not nw) variables per
+ * owned cell, n = nState x owned cells of the level; host pointers, or device pointers for the _dev form (PETSc VECHIP).
+ *   transpose = 0: y(row) = sum_s B_s(row) x(row - d_s)          transpose != 0: y(col) = sum_s B_s(col + d_s)^T x(col + d_s)
+ * with B_s(row) the block of stencil entry s as adflow_gpu_jacobian_info documents it.  A column on a halo cell is the owned cell
+ * that halo has as donor in the 2-layer cell pattern of adflow_gpu_comm_register(level, 2, ...) (same process or another rank);
+ * a halo without a donor is no column (the insertion loop of the reference, adjointUtils.F90:560-700: globalCell >= 0).  The
+ * transposed product adds every halo's contribution to its donor through a donor-sorted list: the result does not depend on
+ * the execution order.  Periodic translations need nothing; a registered ROTATIONAL periodicity is an error when the matrix
+ * covers the mean-flow variables.  State, residual and matrix are not touched; x and y must differ.  Scratch arrays of
+ * 2 x nState doubles per box cell are kept between calls and released by adflow_gpu_release_workspace (which counts them in
+ * *bytes) and with the blocks.  Honours adflow_gpu_set_async (the _dev form). */
+int adflow_gpu_jacobian_mult(int level, int transpose, const double* x, double* y, long n);
+int adflow_gpu_jacobian_mult_dev(int level, int transpose, const double* d_x, double* d_y, long n);
 
 #ifdef __cplusplus
 }

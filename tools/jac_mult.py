@@ -1,0 +1,76 @@
+#!/usr/bin/env python
+"""The products with the assembled matrix alone (adflow_gpu_jacobian_mult_dev: y = J x, y = J^T x on device vectors), timed with HIP
+events: the RANS Roe preconditioner matrix (7-point, forward-mode assembly) on one 160 x 128 x 64 wall-bounded block and the exact
+dR/dw (33-point) on a 96 x 64 x 48 block.  Prints ms per product, the bytes of the byte floor (nStencil nState^2 x 8 B per owned
+cell: one pass over the matrix), TB/s and the fraction of the measured copy ceiling (profiles/r06_fin6_calibration.json).
+usage: jac_mult.py [n]   (n timed products of each kind, default 20)"""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from adflow_amd import capi  # noqa: E402
+from adflow_amd.engine import Engine  # noqa: E402
+from adflow_amd.params import FlowParams, RANSEquations, upwind, vanAlbeda  # noqa: E402
+from adflow_amd.synth import make_block, make_bocos  # noqa: E402
+from adflow_amd.topology import CommPattern  # noqa: E402
+
+WALL = {1: -6, 2: -6, 3: -1, 4: -1, 5: -3, 6: -6}
+
+
+def case(eng, torch, dims, usePC, n_it, ceiling):
+    prm = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda).replace(currentLevel=1, groundLevel=1)
+    blk = make_block(*dims, prm, seed=7, stretch_k=2.0)
+    faces, nvisc = make_bocos(blk, prm, WALL, seed=8)
+    eng.release_all()
+    eng.set_options(prm)
+    eng.register(blk)
+    eng.bc_register(faces, nvisc)
+    for L in (1, 2):
+        eng.comm_register(1, L, CommPattern())
+    eng.applyAllBC(1, True)
+    eng.setupStateResidualMatrix(1, usePC, useAD=True)
+    ns, st = eng.jacobianInfo()
+    cells = blk.nx * blk.ny * blk.nz
+    n = ns * cells
+    floor = st.shape[0] * ns * ns * 8 * cells
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 0.5
+    y = torch.empty_like(x)
+    torch.cuda.synchronize()
+    eng.set_async(True)
+    try:
+        for tr in (False, True):
+            for _ in range(3):
+                eng.jacobianMultDev(x.data_ptr(), y.data_ptr(), n, 1, tr)
+            eng.event_record(1)
+            for _ in range(n_it):
+                eng.jacobianMultDev(x.data_ptr(), y.data_ptr(), n, 1, tr)
+            eng.event_record(2)
+            eng.sync()
+            ms = eng.event_elapsed_ms(1, 2) / n_it
+            tbs = floor / (ms * 1e-3) / 1e12
+            print(json.dumps({"matrix": "PC 7-point" if usePC else "dRdw 33-point", "dims": list(dims), "nState": ns, "nStencil": int(st.shape[0]),
+                              "product": "J^T x" if tr else "J x", "ms": round(ms, 4), "floor_bytes": floor, "TB_per_s": round(tbs, 3),
+                              "of_copy_ceiling": round(tbs / ceiling, 3), "checksum": float(y.abs().sum().item())}), flush=True)
+    finally:
+        eng.set_async(False)
+    eng.releaseWorkspace()
+
+
+def main():
+    import torch
+    n_it = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+    with open(os.path.join(ROOT, "profiles", "r06_fin6_calibration.json")) as f:
+        ceiling = json.load(f)["copy16u8_1gib_gbs"] / 1e3
+    eng = Engine(0)
+    case(eng, torch, (160, 128, 64), True, n_it, ceiling)
+    case(eng, torch, (96, 64, 48), False, n_it, ceiling)
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
