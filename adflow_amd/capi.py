@@ -154,6 +154,8 @@ EXPORTS = [
     "adflow_gpu_wall_distance_register", "adflow_gpu_update_wall_distances",
     "adflow_gpu_fd_jacobian", "adflow_gpu_release_workspace", "adflow_gpu_selftest_math", "adflow_gpu_jacobian_info", "adflow_gpu_download_jacobian", "adflow_gpu_download_jacobian_rows",
     "adflow_gpu_jacobian_mult", "adflow_gpu_jacobian_mult_dev",
+    "adflow_gpu_pc_setup", "adflow_gpu_pc_info", "adflow_gpu_pc_apply", "adflow_gpu_pc_apply_dev", "adflow_gpu_pc_release",
+    "adflow_gpu_gmres_solve", "adflow_gpu_gmres_solve_dev",
     "adflow_gpu_event_record", "adflow_gpu_event_elapsed_ms", "adflow_gpu_sync", "adflow_gpu_set_async",
     "adflow_gpu_abi_sizes", "adflow_gpu_set_tuning", "adflow_gpu_march_stats",
 ]
@@ -210,6 +212,14 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     lib.adflow_gpu_download_jacobian_rows.argtypes = [c_int, c_int, c_int, c_void_p]
     lib.adflow_gpu_jacobian_mult.argtypes = [c_int, c_int, c_void_p, c_void_p, ctypes.c_long]
     lib.adflow_gpu_jacobian_mult_dev.argtypes = [c_int, c_int, c_void_p, c_void_p, ctypes.c_long]
+    lib.adflow_gpu_pc_setup.argtypes = [c_int]
+    lib.adflow_gpu_pc_info.argtypes = [POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), POINTER(ctypes.c_int64)]
+    lib.adflow_gpu_pc_apply.argtypes = [c_int, c_int, c_void_p, c_void_p, ctypes.c_long]
+    lib.adflow_gpu_pc_apply_dev.argtypes = [c_int, c_int, c_void_p, c_void_p, ctypes.c_long]
+    lib.adflow_gpu_pc_release.argtypes = [POINTER(ctypes.c_int64)]
+    for f in (lib.adflow_gpu_gmres_solve, lib.adflow_gpu_gmres_solve_dev):
+        f.argtypes = [c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_double, c_double, c_int,
+                      POINTER(c_int), POINTER(c_double), POINTER(c_double)]
     lib.adflow_gpu_set_tuning.argtypes = [c_char_p, c_int]
     lib.adflow_gpu_abi_sizes.argtypes = [POINTER(c_int), POINTER(c_int)]
     lib.adflow_gpu_rk_smooth.argtypes = [c_int]

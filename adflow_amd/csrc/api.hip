@@ -608,6 +608,7 @@ static void bc_plan_drop(int level);
 static void bc_plan_drop_all();
 static void ad_cache_drop();      // the cached dual arrays of the forward-mode assembly refer to the blocks
 static int64_t jm_release();      // ... and so do the scratch arrays of the matrix products (adflow_gpu_jacobian_mult)
+static int64_t pc_release();      // ... and the block ILU(0) factor (adflow_gpu_pc_setup)
 static bool g_jac_valid = false; // adflow_gpu_fd_jacobian left a matrix on the blocks of level g_jac_level
 static int g_jac_level = 0;
 
@@ -619,6 +620,7 @@ int adflow_gpu_block_release(int nn, int level, int sps)
     bc_plan_drop(level);
     ad_cache_drop();
     (void)jm_release();
+    (void)pc_release();
     for (void* p : it->second->allocs) (void)hipFree(p);
     if (it->second->jac_raw) (void)hipFree(it->second->jac_raw);
     if (it->second->snap_raw) (void)hipFree(it->second->snap_raw);
@@ -635,6 +637,7 @@ int adflow_gpu_release_all(void)
     bc_plan_drop_all();
     ad_cache_drop();
     (void)jm_release();
+    (void)pc_release();
     for (auto& kv : g_blocks) {
         for (void* p : kv.second->allocs) (void)hipFree(p);
         if (kv.second->jac_raw) (void)hipFree(kv.second->jac_raw);
@@ -3987,6 +3990,375 @@ int adflow_gpu_jacobian_mult(int level, int transpose, const double* x, double* 
     HIPCHK(hipMemcpyAsync(g_vec_dev, x, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
     if (jm_mult_enqueue(level, transpose, g_vec_dev, g_vec_dev + n)) return 1;
     HIPCHK(hipMemcpyAsync(y, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+// ---- block ILU(0) of the 7-point preconditioner matrix and right-preconditioned GMRES (kernels_pc.hip) --------------------------
+// The PCApply and the KSPSolve of setupStandardKSP (adjointUtils.F90:1374-1562) in the configuration PCBJACOBI / ILU(0) / natural
+// ordering, one subdomain per block; see the header for what is out of scope.
+namespace {
+struct PcFactor {
+    bool valid = false;
+    int level = 0, nState = 0, nPlanes = 0;
+    long ncell = 0;
+    size_t bytes = 0;
+    std::vector<void*> raw;
+    std::vector<int> planeStart;      // first position of every hyperplane in the order of the factor, and the end
+    PcTab tab;
+};
+PcFactor g_pc;
+struct DevBuf {                       // a device allocation that lives as long as one call
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+}  // namespace
+
+static int64_t pc_release()
+{
+    const int64_t n = (int64_t)g_pc.bytes;
+    for (void* p : g_pc.raw) (void)hipFree(p);
+    g_pc = PcFactor();
+    return n;
+}
+
+static int pc_alloc(void** p, size_t bytes)
+{
+    *p = nullptr;
+    HIPCHK(hipMalloc(p, bytes));
+    g_pc.raw.push_back(*p);
+    g_pc.bytes += bytes;
+    return 0;
+}
+
+static int pc_setup_build(int level)
+{
+    const int nS = g_jac.nState;
+    int sten[7];
+    for (int q = 0; q < 7; ++q) sten[q] = -1;
+    for (int s = 0; s < g_jac.nStencil; ++s) {
+        const int* d = g_jac.st[s];               // the column of entry s is the row cell - d
+        const int nz = (d[0] != 0) + (d[1] != 0) + (d[2] != 0);
+        if (nz == 0) sten[6] = s;
+        for (int a = 0; a < 3; ++a)
+            if (nz == 1 && d[a] == 1) sten[a] = s;
+            else if (nz == 1 && d[a] == -1) sten[3 + a] = s;
+    }
+    for (int q = 0; q < 7; ++q)
+        if (sten[q] < 0) return fail("pc_setup: the assembled stencil lacks one of the seven points");
+    std::map<int, Block*> byNN;
+    for (auto& kv : g_blocks)
+        if (std::get<0>(kv.first) == level) byNN[std::get<2>(kv.first)] = kv.second;
+    if (byNN.empty()) return fail("no block registered on level %d", level);
+    std::vector<JmBlk> hb;
+    std::vector<int> nnOf;
+    long N = 0;
+    int nPlanes = 0;
+    for (auto& kv : byNN) {
+        Block* b = kv.second;
+        const BlkView& v = b->v;
+        if (!b->jac || b->jac_ncomp != 7 * nS * nS)
+            return fail("pc_setup: a block of level %d has no assembled blocks (registered after the assembly?)", level);
+        if ((double)v.nbox * nS * nS * 8.0 >= 4294967296.0)
+            return fail("pc_setup: block of %ld box cells: nState^2 planes exceed the 4 GiB the kernels address from one base", v.nbox);
+        JmBlk q;
+        memset(&q, 0, sizeof q);
+        q.nx = v.nx; q.ny = v.ny; q.nz = v.nz; q.il = v.il; q.jl = v.jl; q.kl = v.kl; q.ib = v.ib; q.jb = v.jb; q.kb = v.kb;
+        q.ldi = v.ldi; q.ldk = v.ldk; q.nbox = v.nbox;
+        q.jac = b->jac;
+        q.vecOff = N;                             // here: the first CELL of the block in the PETSc layout
+        hb.push_back(q);
+        nnOf.push_back(kv.first);
+        N += (long)v.nx * v.ny * v.nz;
+        nPlanes = std::max(nPlanes, v.nx + v.ny + v.nz - 2);
+    }
+    if ((double)N * nS * 8.0 >= 4294967296.0)
+        return fail("pc_setup: %ld cells on level %d: a vector of the factor exceeds the 4 GiB the kernels address from one base", N, level);
+    // the hyperplane order: (i + j + k, block, k, j, i)
+    std::vector<int> start(nPlanes + 1, 0);
+    for (auto& q : hb)
+        for (int k = 0; k < q.nz; ++k)
+            for (int j = 0; j < q.ny; ++j)
+                for (int i = 0; i < q.nx; ++i) start[i + j + k + 1]++;
+    for (int p = 0; p < nPlanes; ++p) start[p + 1] += start[p];
+    std::vector<int> cur(start.begin(), start.end() - 1), pos(N), nbr(6 * N), vec(N), cblk(N), cbox(N);
+    for (size_t s = 0; s < hb.size(); ++s) {
+        const JmBlk& q = hb[s];
+        long nat = q.vecOff;
+        for (int k = 0; k < q.nz; ++k)
+            for (int j = 0; j < q.ny; ++j)
+                for (int i = 0; i < q.nx; ++i, ++nat) {
+                    const int at = cur[i + j + k]++;
+                    pos[nat] = at;
+                    vec[at] = (int)nat;
+                    cblk[at] = (int)s;
+                    cbox[at] = (i + 2) + (j + 2) * q.ldi + (k + 2) * q.ldk;
+                }
+    }
+    for (size_t s = 0; s < hb.size(); ++s) {
+        const JmBlk& q = hb[s];
+        long nat = q.vecOff;
+        const long sj = q.nx, sk = (long)q.nx * q.ny;
+        for (int k = 0; k < q.nz; ++k)
+            for (int j = 0; j < q.ny; ++j)
+                for (int i = 0; i < q.nx; ++i, ++nat) {
+                    const long at = pos[nat];
+                    nbr[0 * N + at] = i > 0 ? pos[nat - 1] : -1;
+                    nbr[1 * N + at] = j > 0 ? pos[nat - sj] : -1;
+                    nbr[2 * N + at] = k > 0 ? pos[nat - sk] : -1;
+                    nbr[3 * N + at] = i < q.nx - 1 ? pos[nat + 1] : -1;
+                    nbr[4 * N + at] = j < q.ny - 1 ? pos[nat + sj] : -1;
+                    nbr[5 * N + at] = k < q.nz - 1 ? pos[nat + sk] : -1;
+                }
+    }
+    PcTab& T = g_pc.tab;
+    memset(&T, 0, sizeof T);
+    T.ncell = N;
+    for (int q = 0; q < 7; ++q) T.sten[q] = sten[q];
+    void *dn, *dv, *db, *dc, *dt, *df;
+    if (pc_alloc((void**)&T.fac, (size_t)N * 7 * nS * nS * sizeof(double))) return 1;
+    if (pc_alloc((void**)&T.ws, (size_t)N * nS * sizeof(double))) return 1;
+    if (pc_alloc(&dn, sizeof(int) * 6 * N) || pc_alloc(&dv, sizeof(int) * N) || pc_alloc(&db, sizeof(int) * N) ||
+        pc_alloc(&dc, sizeof(int) * N) || pc_alloc(&dt, sizeof(JmBlk) * hb.size()) || pc_alloc(&df, sizeof(int)))
+        return 1;
+    HIPCHK(hipMemcpy(dn, nbr.data(), sizeof(int) * 6 * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dv, vec.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db, cblk.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dc, cbox.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dt, hb.data(), sizeof(JmBlk) * hb.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(df, 0, sizeof(int), g_stream));
+    T.nbr = (const int*)dn; T.vec = (const int*)dv; T.cblk = (const int*)db; T.cbox = (const int*)dc;
+    T.blk = (const JmBlk*)dt; T.flag = (int*)df;
+    if (launch_pc_factor(T, nS, start, g_stream)) return 1;
+    int flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, df, sizeof(int), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    HIPCHK(hipGetLastError());
+    if (flag) {
+        const int at = flag - 1, s = cblk[at];
+        const long loc = vec[at] - hb[s].vecOff;
+        return fail("pc_setup: the pivot block of cell (%d,%d,%d) of block %d is singular or not finite (ILU(0) in natural order, "
+                    "level %d); no factor is kept", (int)(loc % hb[s].nx) + 2, (int)(loc / hb[s].nx % hb[s].ny) + 2,
+                    (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2, nnOf[s], level);
+    }
+    g_pc.level = level; g_pc.nState = nS; g_pc.nPlanes = nPlanes; g_pc.ncell = N;
+    g_pc.planeStart = start;
+    g_pc.valid = true;
+    return 0;
+}
+
+int adflow_gpu_pc_setup(int level)
+{
+    if (need_ready()) return 1;
+    if (!g_jac_valid) return fail("pc_setup: no assembled Jacobian (call adflow_gpu_fd_jacobian with ADFLOW_JAC_PC first)");
+    if (level != g_jac_level) return fail("pc_setup: level %d is not the level of the assembly (%d)", level, g_jac_level);
+    if (g_jac.nStencil != 7)
+        return fail("pc_setup: the assembled matrix has a %d-point stencil; the block ILU(0) takes the 7-point preconditioner matrix "
+                    "(ADFLOW_JAC_PC without ADFLOW_JAC_VISC_PC)", g_jac.nStencil);
+    HIPCHK(hipStreamSynchronize(g_stream));
+    (void)pc_release();
+    if (pc_setup_build(level)) {
+        if (g_stream) (void)hipStreamSynchronize(g_stream);
+        (void)pc_release();
+        return 1;
+    }
+    return 0;
+}
+
+int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes)
+{
+    if (!g_pc.valid) return fail("pc_info: no factor (call adflow_gpu_pc_setup first)");
+    if (nState) *nState = g_pc.nState;
+    if (nPlanes) *nPlanes = g_pc.nPlanes;
+    if (bytes) *bytes = (int64_t)g_pc.bytes;
+    return 0;
+}
+
+int adflow_gpu_pc_release(int64_t* bytes)
+{
+    if (g_stream) HIPCHK(hipStreamSynchronize(g_stream));
+    const int64_t n = pc_release();
+    if (bytes) *bytes = n;
+    return 0;
+}
+
+static int pc_check(const char* who, int level, const double* r, const double* z, long n, bool rows = true)
+{
+    if (need_ready()) return 1;
+    if (!g_pc.valid) return fail("%s: no factor (call adflow_gpu_pc_setup first)", who);
+    if (level != g_pc.level) return fail("%s: level %d is not the level of the factor (%d)", who, level, g_pc.level);
+    if (!r || !z) return fail("%s: %s is NULL", who, !r ? "the right-hand side" : "the result");
+    if (r == z) return fail("%s: right-hand side and result are the same vector (not done in place)", who);
+    if (rows && n != g_pc.ncell * g_pc.nState)
+        return fail("%s: n=%ld but the factor of level %d has %ld rows (nState = %d x %ld owned cells)", who, n, level,
+                    g_pc.ncell * g_pc.nState, g_pc.nState, g_pc.ncell);
+    return 0;
+}
+
+int adflow_gpu_pc_apply_dev(int level, int transpose, const double* d_r, double* d_z, long n)
+{
+    if (pc_check("pc_apply", level, d_r, d_z, n)) return 1;
+    if (launch_pc_apply(g_pc.tab, g_pc.nState, transpose, g_pc.planeStart, d_r, d_z, g_stream)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, long n)
+{
+    if (pc_check("pc_apply", level, r, z, n)) return 1;
+    if (vec_reserve((size_t)2 * n)) return 1;
+    HIPCHK(hipMemcpyAsync(g_vec_dev, r, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    if (launch_pc_apply(g_pc.tab, g_pc.nState, transpose, g_pc.planeStart, g_vec_dev, g_vec_dev + n, g_stream)) return 1;
+    HIPCHK(hipMemcpyAsync(z, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+// GMRES(restart) on  A M^-1 u = b, x = M^-1 u  (transpose: A^T M^-T), A = adflow_gpu_jacobian_mult with the matrix on the device,
+// M = the factor.  Basis, dots and updates on the device (one launch per basis vector of a modified Gram-Schmidt step, one
+// download of the new Hessenberg column per step); Hessenberg matrix and Givens rotations on the host.
+static int gm_solve(int level, int transpose, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol, double atol,
+                    int useGuess, int* its, double* rnorm0, double* rnorm)
+{
+    const int m = std::max(1, std::min(restart, std::max(maxIts, 1)));
+    DevBuf buf;
+    const size_t nv = (size_t)(m + 3) * n, nred = 2 * 256 + (size_t)m + 2;
+    HIPCHK(hipMalloc(&buf.p, (nv + nred) * sizeof(double)));
+    double* V = (double*)buf.p;
+    double *zt = V + (size_t)(m + 1) * n, *tv = zt + n, *P[2] = {tv + n, tv + n + 256}, *dH = tv + n + 512;
+    std::vector<double> H(m + 2);
+    hipStream_t s = g_stream;
+    auto norm = [&](const double* a, double* out) -> int {
+        launch_gm_mgs(const_cast<double*>(a), nullptr, nullptr, nullptr, P[0], nullptr, n, s);
+        launch_gm_sum(P[0], n, dH, s);
+        HIPCHK(hipMemcpyAsync(H.data(), dH, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        *out = sqrt(std::max(H[0], 0.0));
+        if (!(H[0] == H[0])) *out = H[0];            // NaN stays NaN
+        return 0;
+    };
+    auto residual = [&](double* r, bool zeroX) -> int {          // r = b - A x
+        if (zeroX) {
+            HIPCHK(hipMemcpyAsync(r, d_b, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+            return 0;
+        }
+        if (jm_mult_enqueue(level, transpose, d_x, r)) return 1;
+        launch_gm_axpby(r, 1.0, d_b, -1.0, n, s);
+        return 0;
+    };
+    double bnorm = 0.0, beta = 0.0, res = 0.0;
+    if (norm(d_b, &bnorm)) return 1;
+    if (!(bnorm == bnorm)) return fail("gmres_solve: the right-hand side is not finite");
+    const double tol = std::max(rtol * bnorm, atol);
+    if (!useGuess) HIPCHK(hipMemsetAsync(d_x, 0, sizeof(double) * n, s));
+    int total = 0;
+    bool first = true, zeroX = !useGuess;
+    std::vector<std::vector<double>> R(m);
+    std::vector<double> cs(m), sn(m), g(m + 1), y(m);
+    for (;;) {
+        if (residual(V, zeroX)) return 1;
+        if (norm(V, &beta)) return 1;
+        if (!(beta == beta)) return fail("gmres_solve: the residual is not finite after %d iterations", total);
+        if (first) { if (rnorm0) *rnorm0 = beta; first = false; }
+        res = beta;
+        if (beta <= tol || total >= maxIts) break;
+        launch_gm_axpby(V, 1.0 / beta, V, 0.0, n, s);
+        g.assign(m + 1, 0.0);
+        g[0] = beta;
+        int k = 0;
+        bool stop = false;
+        for (int j = 0; j < m && !stop; ++j) {
+            double* w = V + (size_t)(j + 1) * n;
+            if (launch_pc_apply(g_pc.tab, g_pc.nState, transpose, g_pc.planeStart, V + (size_t)j * n, zt, s)) return 1;
+            if (jm_mult_enqueue(level, transpose, zt, w)) return 1;
+            launch_gm_mgs(w, nullptr, nullptr, V, P[0], nullptr, n, s);
+            for (int i = 1; i <= j; ++i)
+                launch_gm_mgs(w, V + (size_t)(i - 1) * n, P[(i - 1) & 1], V + (size_t)i * n, P[i & 1], dH + (i - 1), n, s);
+            launch_gm_mgs(w, V + (size_t)j * n, P[j & 1], nullptr, P[(j + 1) & 1], dH + j, n, s);
+            launch_gm_sum(P[(j + 1) & 1], n, dH + j + 1, s);
+            HIPCHK(hipMemcpyAsync(H.data(), dH, sizeof(double) * (j + 2), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            const double hn = sqrt(std::max(H[j + 1], 0.0));
+            if (!(H[j + 1] == H[j + 1])) return fail("gmres_solve: the Krylov vector of iteration %d is not finite", total + 1);
+            std::vector<double>& c = R[j];
+            c.assign(H.begin(), H.begin() + j + 1);
+            for (int i = 0; i < j; ++i) {
+                const double a = c[i], b = c[i + 1];
+                c[i] = cs[i] * a + sn[i] * b;
+                c[i + 1] = -sn[i] * a + cs[i] * b;
+            }
+            const double d = hypot(c[j], hn);
+            cs[j] = d > 0.0 ? c[j] / d : 1.0;
+            sn[j] = d > 0.0 ? hn / d : 0.0;
+            c[j] = d;
+            g[j + 1] = -sn[j] * g[j];
+            g[j] = cs[j] * g[j];
+            res = fabs(g[j + 1]);
+            ++total;
+            k = j + 1;
+            if (hn > 0.0) launch_gm_axpby(w, 1.0 / hn, w, 0.0, n, s);
+            stop = res <= tol || total >= maxIts || !(hn > 0.0);
+        }
+        for (int i = k - 1; i >= 0; --i) {
+            double t = g[i];
+            for (int q = i + 1; q < k; ++q) t -= R[q][i] * y[q];
+            y[i] = R[i][i] != 0.0 ? t / R[i][i] : 0.0;
+        }
+        for (int i = 0; i < k; ++i) launch_gm_axpby(tv, y[i], V + (size_t)i * n, i == 0 ? 0.0 : 1.0, n, s);
+        if (k > 0) {
+            if (launch_pc_apply(g_pc.tab, g_pc.nState, transpose, g_pc.planeStart, tv, zt, s)) return 1;
+            launch_gm_axpby(d_x, 1.0, zt, 1.0, n, s);
+            zeroX = false;
+        }
+        if (stop) {
+            // converged on the recurrence (or out of iterations): the reported norm is the true residual
+            if (residual(V, false)) return 1;
+            if (norm(V, &res)) return 1;
+            break;
+        }
+    }
+    if (its) *its = total;
+    if (rnorm) *rnorm = res;
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int gm_check(int level, const double* b, const double* x, long n, int restart, int maxIts, double rtol, double atol)
+{
+    if (need_ready()) return 1;
+#ifndef ADFLOW_NO_RCCL
+    if (g_nranks > 1)
+        return fail("gmres_solve: %d ranks in the communicator; the dot products of the solver are not reduced across ranks (use the "
+                    "host's KSP with adflow_gpu_jacobian_mult_dev and adflow_gpu_pc_apply_dev)", g_nranks);
+#endif
+    if (!g_jac_valid) return fail("gmres_solve: no assembled Jacobian (call adflow_gpu_fd_jacobian first)");
+    if (pc_check("gmres_solve", level, b, x, n, false)) return 1;
+    if (g_jac.nState != g_pc.nState)
+        return fail("gmres_solve: the factor was set up for nState = %d, the assembled matrix has nState = %d", g_pc.nState, g_jac.nState);
+    if (jm_check(level, b, x, n)) return 1;
+    if (n != g_pc.ncell * g_pc.nState) return fail("gmres_solve: n=%ld but the factor has %ld rows", n, g_pc.ncell * g_pc.nState);
+    if (restart < 1 || maxIts < 0) return fail("gmres_solve: restart = %d, maxIts = %d", restart, maxIts);
+    if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail("gmres_solve: rtol = %g, atol = %g", rtol, atol);
+    return 0;
+}
+
+int adflow_gpu_gmres_solve_dev(int level, int transpose, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol,
+                               double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
+{
+    if (gm_check(level, d_b, d_x, n, restart, maxIts, rtol, atol)) return 1;
+    return gm_solve(level, transpose, d_b, d_x, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm);
+}
+
+int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x, long n, int restart, int maxIts, double rtol,
+                           double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
+{
+    if (gm_check(level, b, x, n, restart, maxIts, rtol, atol)) return 1;
+    DevBuf buf;
+    HIPCHK(hipMalloc(&buf.p, sizeof(double) * 2 * n));
+    double *d_b = (double*)buf.p, *d_x = d_b + n;
+    HIPCHK(hipMemcpyAsync(d_b, b, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    if (useGuess) HIPCHK(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    if (gm_solve(level, transpose, d_b, d_x, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm)) return 1;
+    HIPCHK(hipMemcpyAsync(x, d_x, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
 }

@@ -391,6 +391,31 @@ void launch_jac_mult(const JmBlk* tab, int nslots, int maxnx, int maxny, int max
 void launch_jac_mult_t(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, hipStream_t s);
 void launch_jac_halo_accumulate(const JmBlk* tab, const JmAccList& a, int nState, const double* buf, int nbuf, hipStream_t s);
 
+// block ILU(0) of the 7-point matrix (kernels_pc.hip): the factor of a level as its kernels see it.  Position q of the hyperplane
+// order (hyperplane, block, k, j, i) holds fac[q + ((s nState + l) nState + ll) ncell], s = 0..2 L of the lower neighbour along
+// i, j, k, 3..5 U of the upper neighbour, 6 the inverted pivot block
+#include <vector>
+struct PcTab {
+    long ncell;           // owned cells of the level
+    double* fac;
+    double* ws;           // nState components in hyperplane order: the vector between and during the two sweeps
+    const int* nbr;       // nbr[e ncell + q]: position of neighbour e (0..2 lower, 3..5 upper), -1 outside the block
+    const int* vec;       // the cell's number in the PETSc layout (block, k, j, i)
+    const int* cblk;      // setup only: slot of the cell's block in blk[] and its box index
+    const int* cbox;
+    const JmBlk* blk;
+    int* flag;            // != 0: 1 + position of a cell whose pivot block is singular or not finite
+    int sten[7];          // stencil entries of the assembly: the columns c - e_i, c - e_j, c - e_k, c + e_i, c + e_j, c + e_k, c
+};
+int launch_pc_factor(const PcTab& T, int nState, const std::vector<int>& planeStart, hipStream_t s);
+int launch_pc_apply(const PcTab& T, int nState, int transpose, const std::vector<int>& planeStart, const double* r, double* z,
+                    hipStream_t s);
+// the vectors of GMRES: one step of modified Gram-Schmidt per launch (partial sums in, partial sums out), see kernels_pc.hip
+int gm_groups(long n);
+void launch_gm_mgs(double* w, const double* v, const double* hp, const double* u, double* out, double* hOut, long n, hipStream_t s);
+void launch_gm_sum(const double* hp, long n, double* hOut, hipStream_t s);
+void launch_gm_axpby(double* y, double a, const double* x, double b, long n, hipStream_t s);
+
 // The level-batched launches fold (block slot, plane) into gridDim.z, which HIP limits to 65535: a launcher whose level has more
 // slots than fit calls itself on consecutive slot ranges (the kernels index the table relative to the pointer they get).
 extern int g_max_grid_z;          // 65535; tuning "max_grid_z" lowers it for the tests

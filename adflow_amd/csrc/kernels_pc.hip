@@ -1,0 +1,348 @@
+// Block ILU(0) of the assembled 7-point preconditioner matrix, factored and applied on the device, and the vector kernels of the
+// right-preconditioned GMRES that uses it (adflow_gpu_pc_setup / _pc_apply / _gmres_solve, api.hip).
+//
+// Reference semantics: the PCApply of setupStandardKSP (adjointUtils.F90:1374-1562) in the configuration PCBJACOBI (= PCASM with
+// overlap 0), one subdomain per structured block, sub-preconditioner ILU with 0 levels in the natural ordering (k, j, i with i
+// fastest) on BAIJ blocks of size nState.  A column on a halo cell, with or without a donor, is not part of a subdomain.
+// Out of scope: ILU(k > 0) and the RCM ordering (the reference's defaults), ASM overlap and couplings across blocks, the
+// pseudo-time diagonal term of ANK, GMRES across ranks, a matrix-free operator inside the solver.
+//
+// Arithmetic: eliminating row c of a 7-point stencil in natural order with the rows c - e_i, c - e_j, c - e_k creates no entry
+// inside the pattern but on the diagonal, so
+//   D_c = A_cc - sum_lower A_{c,n} D_n^-1 A_{n,c},    L_{c,n} = A_{c,n} D_n^-1,    U_{c,n} = A_{c,n},    M = L (D + U)
+// and D_c needs the cells of the hyperplane i + j + k - 1 only: setup, forward and backward sweep run hyperplane by hyperplane,
+// one plain launch per hyperplane that covers every block of the level, in stream order.  M^T = (D + U)^T L^T has the diagonal
+// blocks D_c^T: the same factor serves M^-1 r and M^-T r.
+//
+// Storage (owned by the factor): the cells of the level sorted by (hyperplane, block, k, j, i); position q of that order holds
+//   fac[q + ((s nState + l) nState + ll) N]   s = 0..2: L of the lower neighbour along i, j, k; 3..5: U of the upper neighbour;
+//                                             6: D^-1;  (ll, l) = (row, column) of the block as in jac[]
+// so the lanes of a wave stream every component plane coalesced (in the box layout the cells of a hyperplane are ldi - 1 apart).
+// nbr[e N + q]: position of neighbour e (0..2 lower, 3..5 upper) or -1 outside the block; vec[q]: the cell's number in the PETSc
+// layout.  Only the neighbour values of the vector are gathered (ws, hyperplane order, component-major); the transposed sweeps
+// read the blocks at the neighbours' positions, which are monotone in q along a hyperplane.
+#include "internal.h"
+
+#define PC_T 64           // one wave per workgroup: a hyperplane of a few thousand cells still spreads over the CUs
+
+#define PCE(a, r, c) a[(c) * NS + (r)]
+
+// a <- a^-1 by LU with partial pivoting on [a | 1] and back substitution, in registers (every index is a compile-time constant;
+// a row exchange is a conditional swap).  Returns false when a pivot is zero or not finite.
+template <int NS>
+__device__ __forceinline__ bool pc_invert(double (&a)[NS * NS])
+{
+    double b[NS * NS];
+#pragma unroll
+    for (int e = 0; e < NS * NS; ++e) b[e] = (e % (NS + 1) == 0) ? 1.0 : 0.0;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+#pragma unroll
+        for (int r = k + 1; r < NS; ++r) {
+            const bool sw = fabs(PCE(a, r, k)) > fabs(PCE(a, k, k));
+#pragma unroll
+            for (int c = k; c < NS; ++c) {
+                const double t = PCE(a, k, c), u = PCE(a, r, c);
+                PCE(a, k, c) = sw ? u : t;
+                PCE(a, r, c) = sw ? t : u;
+            }
+#pragma unroll
+            for (int c = 0; c < NS; ++c) {
+                const double t = PCE(b, k, c), u = PCE(b, r, c);
+                PCE(b, k, c) = sw ? u : t;
+                PCE(b, r, c) = sw ? t : u;
+            }
+        }
+        const double piv = PCE(a, k, k);
+        ok = ok && (fabs(piv) > 0.0) && (fabs(piv) <= 1.7976931348623157e308);
+#pragma unroll
+        for (int r = k + 1; r < NS; ++r) {
+            const double f = PCE(a, r, k) / piv;
+#pragma unroll
+            for (int c = k + 1; c < NS; ++c) PCE(a, r, c) -= f * PCE(a, k, c);
+#pragma unroll
+            for (int c = 0; c < NS; ++c) PCE(b, r, c) -= f * PCE(b, k, c);
+        }
+    }
+#pragma unroll
+    for (int k = NS - 1; k >= 0; --k) {
+        const double piv = PCE(a, k, k);
+#pragma unroll
+        for (int c = 0; c < NS; ++c) {
+            double t = PCE(b, k, c);
+#pragma unroll
+            for (int m = k + 1; m < NS; ++m) t -= PCE(a, k, m) * PCE(b, m, c);
+            PCE(b, k, c) = t / piv;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < NS * NS; ++e) a[e] = b[e];
+    return ok;
+}
+
+// one hyperplane of the factorisation: lanes q0 .. q0 + cnt - 1.  The rows of the lower neighbours are complete (earlier launches)
+template <int NS>
+__global__ __launch_bounds__(PC_T) void k_pc_factor(PcTab T, int q0, int cnt)
+{
+    const int t = blockIdx.x * PC_T + threadIdx.x;
+    if (t >= cnt) return;
+    const unsigned q = (unsigned)(q0 + t), q8 = q * 8u;
+    const long N = T.ncell;
+    const JmBlk b = T.blk[T.cblk[q]];
+    const unsigned c8 = (unsigned)T.cbox[q] * 8u, nb8 = (unsigned)b.nbox * 8u;
+    GPTR(double) F = (GPTR(double))T.fac;
+    double D[NS * NS];
+    {
+        GPTR(const double) A = (GPTR(const double))(b.jac + (long)T.sten[6] * (NS * NS) * b.nbox);
+#pragma unroll
+        for (int e = 0; e < NS * NS; ++e) D[e] = ldg(A, c8 + e * nb8);
+    }
+    for (int s = 0; s < 3; ++s) {
+        const int n = T.nbr[(long)s * N + q];
+        GPTR(double) Fs = F + (long)s * (NS * NS) * N;
+        if (n < 0) {
+#pragma unroll
+            for (int e = 0; e < NS * NS; ++e) stg(Fs + e * N, q8, 0.0);
+            continue;
+        }
+        const unsigned n8 = (unsigned)n * 8u;
+        GPTR(const double) A = (GPTR(const double))(b.jac + (long)T.sten[s] * (NS * NS) * b.nbox);
+        double X[NS * NS], L[NS * NS];
+        {
+            GPTR(const double) Fd = F + (long)6 * (NS * NS) * N;
+#pragma unroll
+            for (int e = 0; e < NS * NS; ++e) X[e] = ldg(Fd + e * N, n8);           // D_n^-1
+        }
+#pragma unroll
+        for (int e = 0; e < NS * NS; ++e) L[e] = 0.0;
+#pragma unroll
+        for (int m = 0; m < NS; ++m)
+#pragma unroll
+            for (int r = 0; r < NS; ++r) {
+                const double arm = ldg(A, c8 + (unsigned)(m * NS + r) * nb8);        // A_{c,n}(r, m)
+#pragma unroll
+                for (int l = 0; l < NS; ++l) PCE(L, r, l) += arm * PCE(X, m, l);
+            }
+#pragma unroll
+        for (int e = 0; e < NS * NS; ++e) stg(Fs + e * N, q8, L[e]);
+        {
+            GPTR(const double) Fu = F + (long)(3 + s) * (NS * NS) * N;
+#pragma unroll
+            for (int e = 0; e < NS * NS; ++e) X[e] = ldg(Fu + e * N, n8);           // U_{n,c} = A_{n, n + e_s}
+        }
+#pragma unroll
+        for (int m = 0; m < NS; ++m)
+#pragma unroll
+            for (int l = 0; l < NS; ++l)
+#pragma unroll
+                for (int r = 0; r < NS; ++r) PCE(D, r, l) -= PCE(L, r, m) * PCE(X, m, l);
+    }
+    for (int s = 3; s < 6; ++s) {
+        const bool in = T.nbr[(long)s * N + q] >= 0;
+        GPTR(const double) A = (GPTR(const double))(b.jac + (long)T.sten[s] * (NS * NS) * b.nbox);
+        GPTR(double) Fs = F + (long)s * (NS * NS) * N;
+#pragma unroll
+        for (int e = 0; e < NS * NS; ++e) stg(Fs + e * N, q8, in ? ldg(A, c8 + e * nb8) : 0.0);
+    }
+    if (!pc_invert<NS>(D)) T.flag[0] = (int)q + 1;      // any of the failing cells: the host names one of them
+    GPTR(double) Fd = F + (long)6 * (NS * NS) * N;
+#pragma unroll
+    for (int e = 0; e < NS * NS; ++e) stg(Fd + e * N, q8, D[e]);
+}
+
+// one hyperplane of a triangular sweep.  BACK = 0: ascending hyperplanes, lower neighbours, input r; BACK = 1: descending, upper
+// neighbours, input ws, output also to z.
+//   TR = 0:  forward  y_c = r_c - sum L_{c,n} y_n            backward  z_c = D_c^-1 (y_c - sum U_{c,n} z_n)      (blocks of c)
+//   TR = 1:  forward  y_c = D_c^-T (r_c - sum U_{n,c}^T y_n)  backward  z_c = y_c - sum L_{n,c}^T z_n             (blocks of n)
+template <int NS, int TR, int BACK>
+__global__ __launch_bounds__(PC_T) void k_pc_sweep(PcTab T, int q0, int cnt, const double* __restrict__ r, double* __restrict__ z)
+{
+    const int t = blockIdx.x * PC_T + threadIdx.x;
+    if (t >= cnt) return;
+    const unsigned q = (unsigned)(q0 + t), q8 = q * 8u;
+    const long N = T.ncell;
+    const unsigned N8 = (unsigned)N * 8u;
+    GPTR(const double) F = (GPTR(const double))T.fac;
+    GPTR(double) W = (GPTR(double))T.ws;
+    const long m = (long)T.vec[q] * NS;
+    double acc[NS];
+    if (BACK) {
+#pragma unroll
+        for (int l = 0; l < NS; ++l) acc[l] = ldg(W, q8 + l * N8);
+    } else {
+#pragma unroll
+        for (int l = 0; l < NS; ++l) acc[l] = r[m + l];
+    }
+    // the blocks of the sweep: TR = 0 the cell's own L (forward) / U (backward); TR = 1 the neighbour's U (forward) / L (backward)
+    const int slot0 = (TR != BACK) ? 3 : 0;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const int n = T.nbr[(long)((BACK ? 3 : 0) + s) * N + q];
+        if (n < 0) continue;
+        const unsigned n8 = (unsigned)n * 8u, at = TR ? n8 : q8;
+        GPTR(const double) Fs = F + (long)(slot0 + s) * (NS * NS) * N;
+        double xv[NS], bv[NS * NS];
+#pragma unroll
+        for (int l = 0; l < NS; ++l) xv[l] = ldg(W, n8 + l * N8);
+#pragma unroll
+        for (int e = 0; e < NS * NS; ++e) bv[e] = ldg(Fs + e * N, at);
+        if (TR) {
+#pragma unroll
+            for (int l = 0; l < NS; ++l)
+#pragma unroll
+                for (int ll = 0; ll < NS; ++ll) acc[l] -= PCE(bv, ll, l) * xv[ll];
+        } else {
+#pragma unroll
+            for (int l = 0; l < NS; ++l)
+#pragma unroll
+                for (int ll = 0; ll < NS; ++ll) acc[ll] -= PCE(bv, ll, l) * xv[l];
+        }
+    }
+    if (TR != BACK) {
+        GPTR(const double) Fd = F + (long)6 * (NS * NS) * N;
+        double bv[NS * NS], o[NS];
+#pragma unroll
+        for (int e = 0; e < NS * NS; ++e) bv[e] = ldg(Fd + e * N, q8);
+#pragma unroll
+        for (int l = 0; l < NS; ++l) o[l] = 0.0;
+        if (TR) {
+#pragma unroll
+            for (int l = 0; l < NS; ++l)
+#pragma unroll
+                for (int ll = 0; ll < NS; ++ll) o[l] += PCE(bv, ll, l) * acc[ll];
+        } else {
+#pragma unroll
+            for (int l = 0; l < NS; ++l)
+#pragma unroll
+                for (int ll = 0; ll < NS; ++ll) o[ll] += PCE(bv, ll, l) * acc[l];
+        }
+#pragma unroll
+        for (int l = 0; l < NS; ++l) acc[l] = o[l];
+    }
+#pragma unroll
+    for (int l = 0; l < NS; ++l) stg(W, q8 + l * N8, acc[l]);
+    if (BACK) {
+#pragma unroll
+        for (int l = 0; l < NS; ++l) z[m + l] = acc[l];
+    }
+}
+
+#define PC_DISPATCH(nState, ...)                                                       \
+    switch (nState) {                                                                  \
+    case 1: { constexpr int NS_ = 1; __VA_ARGS__; } break;                             \
+    case 5: { constexpr int NS_ = 5; __VA_ARGS__; } break;                             \
+    case 6: { constexpr int NS_ = 6; __VA_ARGS__; } break;                             \
+    default: return adf_fail("pc: no kernel for this nState");                         \
+    }
+
+int launch_pc_factor(const PcTab& T, int nState, const std::vector<int>& planeStart, hipStream_t s)
+{
+    for (size_t p = 0; p + 1 < planeStart.size(); ++p) {
+        const int q0 = planeStart[p], cnt = planeStart[p + 1] - q0;
+        if (cnt <= 0) continue;
+        PC_DISPATCH(nState, hipLaunchKernelGGL((k_pc_factor<NS_>), dim3((cnt + PC_T - 1) / PC_T), dim3(PC_T), 0, s, T, q0, cnt))
+    }
+    return 0;
+}
+
+template <int NS, int TR>
+static void pc_apply_planes(const PcTab& T, const std::vector<int>& planeStart, const double* r, double* z, hipStream_t s)
+{
+    const int np = (int)planeStart.size() - 1;
+    for (int p = 0; p < np; ++p) {
+        const int q0 = planeStart[p], cnt = planeStart[p + 1] - q0;
+        if (cnt > 0) hipLaunchKernelGGL((k_pc_sweep<NS, TR, 0>), dim3((cnt + PC_T - 1) / PC_T), dim3(PC_T), 0, s, T, q0, cnt, r, z);
+    }
+    for (int p = np - 1; p >= 0; --p) {
+        const int q0 = planeStart[p], cnt = planeStart[p + 1] - q0;
+        if (cnt > 0) hipLaunchKernelGGL((k_pc_sweep<NS, TR, 1>), dim3((cnt + PC_T - 1) / PC_T), dim3(PC_T), 0, s, T, q0, cnt, r, z);
+    }
+}
+
+int launch_pc_apply(const PcTab& T, int nState, int transpose, const std::vector<int>& planeStart, const double* r, double* z,
+                    hipStream_t s)
+{
+    if (transpose) { PC_DISPATCH(nState, pc_apply_planes<NS_, 1>(T, planeStart, r, z, s)) }
+    else { PC_DISPATCH(nState, pc_apply_planes<NS_, 0>(T, planeStart, r, z, s)) }
+    return 0;
+}
+
+// ---- the vectors of GMRES: everything stays on the device, one download of a column of the Hessenberg matrix per step -----------
+#define GM_T 256          // threads of a workgroup = the largest number of workgroups (partial sums) of a reduction
+
+__device__ __forceinline__ double gm_block_sum(double v, double* red)
+{
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int s = GM_T / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    const double out = red[0];
+    __syncthreads();
+    return out;
+}
+
+// One step of modified Gram-Schmidt per launch: h = sum of the partial sums hp[] the launch before left (every workgroup adds them
+// in the same order; workgroup 0 stores h to *hOut), w -= h v, and the partial sums of <w, u> (u == NULL: <w, w>) go to out[].
+// v == NULL: no update, only the dot product.  The dot with basis vector i + 1 needs the update with vector i: MGS allows no wider
+// batch than this chain, which costs one launch per basis vector and no trip to the host.
+__global__ __launch_bounds__(GM_T) void k_gm_mgs(double* w, const double* v, const double* hp, const double* u, double* out,
+                                                 double* hOut, long n)
+{
+    __shared__ double red[GM_T];
+    const int tid = threadIdx.x;
+    double h = 0.0;
+    if (v) {
+        h = gm_block_sum(tid < (int)gridDim.x ? hp[tid] : 0.0, red);
+        if (blockIdx.x == 0 && tid == 0) *hOut = h;
+    }
+    double sum = 0.0;
+    for (long i = (long)blockIdx.x * GM_T + tid; i < n; i += (long)gridDim.x * GM_T) {
+        double wi = w[i];
+        if (v) {
+            wi -= h * v[i];
+            w[i] = wi;
+        }
+        sum += wi * (u ? u[i] : wi);
+    }
+    sum = gm_block_sum(sum, red);
+    if (tid == 0) out[blockIdx.x] = sum;
+}
+
+// the last partial sums of a chain
+__global__ __launch_bounds__(GM_T) void k_gm_sum(const double* hp, int np, double* hOut)
+{
+    __shared__ double red[GM_T];
+    const double h = gm_block_sum((int)threadIdx.x < np ? hp[threadIdx.x] : 0.0, red);
+    if (threadIdx.x == 0) *hOut = h;
+}
+
+// y = a x + b y (b == 0: y is not read)
+__global__ __launch_bounds__(GM_T) void k_gm_axpby(double* y, double a, const double* x, double b, long n)
+{
+    const long i = (long)blockIdx.x * GM_T + threadIdx.x;
+    if (i >= n) return;
+    y[i] = (b == 0.0) ? a * x[i] : a * x[i] + b * y[i];
+}
+
+int gm_groups(long n)
+{
+    const long g = (n + 4L * GM_T - 1) / (4L * GM_T);
+    return (int)(g < 1 ? 1 : g > GM_T ? GM_T : g);
+}
+void launch_gm_mgs(double* w, const double* v, const double* hp, const double* u, double* out, double* hOut, long n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_gm_mgs, dim3(gm_groups(n)), dim3(GM_T), 0, s, w, v, hp, u, out, hOut, n);
+}
+void launch_gm_sum(const double* hp, long n, double* hOut, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_gm_sum, dim3(1), dim3(GM_T), 0, s, hp, gm_groups(n), hOut);
+}
+void launch_gm_axpby(double* y, double a, const double* x, double b, long n, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_gm_axpby, dim3((unsigned)((n + GM_T - 1) / GM_T)), dim3(GM_T), 0, s, y, a, x, b, n);
+}

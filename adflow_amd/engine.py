@@ -176,6 +176,54 @@ class Engine:
         """the same on device pointers (the addresses of two device vectors of n doubles, e.g. torch.Tensor.data_ptr())"""
         self._chk(self.lib.adflow_gpu_jacobian_mult_dev(level, int(bool(transpose)), ctypes.c_void_p(d_x), ctypes.c_void_p(d_y), int(n)))
 
+    def pcSetup(self, level=1):
+        """block ILU(0) of the 7-point preconditioner matrix of the last setupStateResidualMatrix, one subdomain per block (the PC
+        of setupStandardKSP, adjointUtils.F90:1374-1562, as PCBJACOBI / ILU(0) / natural ordering); kept until pcRelease"""
+        self._chk(self.lib.adflow_gpu_pc_setup(level))
+
+    def pcInfo(self):
+        """(nState, number of hyperplanes, bytes held) of the factor"""
+        ns, npl, nb = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        self._chk(self.lib.adflow_gpu_pc_info(ctypes.byref(ns), ctypes.byref(npl), ctypes.byref(nb)))
+        return int(ns.value), int(npl.value), int(nb.value)
+
+    def pcApply(self, r, level=1, transpose=False):
+        """z = M^-1 r, or M^-T r with transpose, for the factor of pcSetup; vectors as for jacobianMult"""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        z = np.zeros_like(r)
+        self._chk(self.lib.adflow_gpu_pc_apply(level, int(bool(transpose)), r.ctypes.data, z.ctypes.data, r.size))
+        return z
+
+    def pcApplyDev(self, d_r: int, d_z: int, n: int, level=1, transpose=False):
+        """the same on device pointers (e.g. torch.Tensor.data_ptr())"""
+        self._chk(self.lib.adflow_gpu_pc_apply_dev(level, int(bool(transpose)), ctypes.c_void_p(d_r), ctypes.c_void_p(d_z), int(n)))
+
+    def pcRelease(self) -> int:
+        """frees the factor; returns the bytes released (0 when there was none)"""
+        n = ctypes.c_int64(0)
+        self._chk(self.lib.adflow_gpu_pc_release(ctypes.byref(n)))
+        return int(n.value)
+
+    def gmresSolve(self, b, level=1, transpose=False, restart=50, maxIts=200, rtol=1e-8, atol=0.0, x0=None):
+        """right-preconditioned GMRES(restart) on the matrix assembled last with the factor of pcSetup (KSPSolve of solveAdjoint,
+        adjointAPI.F90:661-863); returns (x, iterations, initial residual norm, true residual norm of x)"""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        x = np.zeros_like(b) if x0 is None else np.array(x0, dtype=np.float64, order="C", copy=True)
+        its, r0, rn = ctypes.c_int(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        self._chk(self.lib.adflow_gpu_gmres_solve(level, int(bool(transpose)), b.ctypes.data, x.ctypes.data, b.size, int(restart),
+                                                  int(maxIts), float(rtol), float(atol), int(x0 is not None), ctypes.byref(its),
+                                                  ctypes.byref(r0), ctypes.byref(rn)))
+        return x, int(its.value), float(r0.value), float(rn.value)
+
+    def gmresSolveDev(self, d_b: int, d_x: int, n: int, level=1, transpose=False, restart=50, maxIts=200, rtol=1e-8, atol=0.0,
+                      useGuess=False):
+        """the same on device pointers; returns (iterations, initial residual norm, true residual norm)"""
+        its, r0, rn = ctypes.c_int(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        self._chk(self.lib.adflow_gpu_gmres_solve_dev(level, int(bool(transpose)), ctypes.c_void_p(d_b), ctypes.c_void_p(d_x), int(n),
+                                                      int(restart), int(maxIts), float(rtol), float(atol), int(bool(useGuess)),
+                                                      ctypes.byref(its), ctypes.byref(r0), ctypes.byref(rn)))
+        return int(its.value), float(r0.value), float(rn.value)
+
     def blocketteRes(self, level=1, updateIntermed=True, flowRes=True, turbRes=True, dissApprox=False, viscApprox=False,
                      useBlockettes=False, halo=False, closures=False):
         """halo: also the part of blocketteRes in front of the core -- boundary conditions and whalo2 (ADFLOW_RES_HALO);

@@ -330,6 +330,58 @@ module adflowGpuShim
             type(c_ptr), value :: x, y
             integer(c_long), value :: n
         end function
+        ! block ILU(0) of the 7-point preconditioner matrix, one subdomain per block (the PC of setupStandardKSP,
+        ! adjointUtils.F90:1374-1562, as PCBJACOBI / ILU(0) / natural ordering): setup after the PC matrix is assembled, then
+        ! z = M^-1 r / M^-T r on host vectors or on DEVICE pointers (the body of a PCSHELL on VECHIP)
+        integer(c_int) function adflow_gpu_pc_setup(level) bind(C, name="adflow_gpu_pc_setup")
+            import :: c_int
+            integer(c_int), value :: level
+        end function
+        integer(c_int) function adflow_gpu_pc_info(nState, nPlanes, bytes) bind(C, name="adflow_gpu_pc_info")
+            import :: c_int, c_int32_t, c_int64_t
+            integer(c_int32_t), intent(out) :: nState, nPlanes
+            integer(c_int64_t), intent(out) :: bytes
+        end function
+        integer(c_int) function adflow_gpu_pc_apply(level, transpose, r, z, n) bind(C, name="adflow_gpu_pc_apply")
+            import :: c_int, c_long, c_double
+            integer(c_int), value :: level, transpose
+            real(c_double), intent(in) :: r(*)
+            real(c_double), intent(out) :: z(*)
+            integer(c_long), value :: n
+        end function
+        integer(c_int) function adflow_gpu_pc_apply_dev(level, transpose, r, z, n) bind(C, name="adflow_gpu_pc_apply_dev")
+            import :: c_int, c_ptr, c_long
+            integer(c_int), value :: level, transpose
+            type(c_ptr), value :: r, z
+            integer(c_long), value :: n
+        end function
+        integer(c_int) function adflow_gpu_pc_release(bytes) bind(C, name="adflow_gpu_pc_release")
+            import :: c_int, c_int64_t
+            integer(c_int64_t), intent(out) :: bytes
+        end function
+        ! right-preconditioned GMRES(restart) with that factor on the matrix assembled last (KSPSolve of solveAdjoint,
+        ! adjointAPI.F90:661-863); one rank only
+        integer(c_int) function adflow_gpu_gmres_solve(level, transpose, b, x, n, restart, maxIts, rtol, atol, useGuess, its, &
+                                                       rnorm0, rnorm) bind(C, name="adflow_gpu_gmres_solve")
+            import :: c_int, c_long, c_double
+            integer(c_int), value :: level, transpose, restart, maxIts, useGuess
+            real(c_double), intent(in) :: b(*)
+            real(c_double), intent(inout) :: x(*)
+            integer(c_long), value :: n
+            real(c_double), value :: rtol, atol
+            integer(c_int), intent(out) :: its
+            real(c_double), intent(out) :: rnorm0, rnorm
+        end function
+        integer(c_int) function adflow_gpu_gmres_solve_dev(level, transpose, b, x, n, restart, maxIts, rtol, atol, useGuess, its, &
+                                                           rnorm0, rnorm) bind(C, name="adflow_gpu_gmres_solve_dev")
+            import :: c_int, c_ptr, c_long, c_double
+            integer(c_int), value :: level, transpose, restart, maxIts, useGuess
+            type(c_ptr), value :: b, x
+            integer(c_long), value :: n
+            real(c_double), value :: rtol, atol
+            integer(c_int), intent(out) :: its
+            real(c_double), intent(out) :: rnorm0, rnorm
+        end function
         integer(c_int) function adflow_gpu_reference_shock_sensor(level) bind(C, name="adflow_gpu_reference_shock_sensor")
             import :: c_int
             integer(c_int), value :: level
@@ -726,5 +778,25 @@ contains
         if (transposed) tr = 1_c_int
         call gpuCheck(adflow_gpu_jacobian_mult_dev(int(level, c_int), tr, xDev, yDev, int(n, c_long)), "gpuJacobianMult")
     end subroutine gpuJacobianMult
+
+    ! after the preconditioner matrix is assembled (setupStateResidualMatrix with usePC = .true.): factor it on the device, in
+    ! place of PCSetUp on the assembled usePC matrix (adjointUtils.F90:1374-1562)
+    subroutine gpuPCSetup(level)
+        integer(kind=intType), intent(in) :: level
+        call gpuCheck(adflow_gpu_pc_setup(int(level, c_int)), "gpuPCSetup")
+    end subroutine gpuPCSetup
+
+    ! the body of a PCSHELL's apply (transposed = .false.) / applyTranspose (.true.): rDev, zDev are the device arrays of the two
+    ! PETSc vectors (VECHIP), n their local size
+    subroutine gpuPCApply(level, transposed, rDev, zDev, n)
+        integer(kind=intType), intent(in) :: level
+        logical, intent(in) :: transposed
+        type(c_ptr), intent(in) :: rDev, zDev
+        integer(kind=intType), intent(in) :: n
+        integer(c_int) :: tr
+        tr = 0_c_int
+        if (transposed) tr = 1_c_int
+        call gpuCheck(adflow_gpu_pc_apply_dev(int(level, c_int), tr, rDev, zDev, int(n, c_long)), "gpuPCApply")
+    end subroutine gpuPCApply
 
 end module adflowGpuShim

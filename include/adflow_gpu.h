@@ -474,6 +474,49 @@ int adflow_gpu_download_jacobian_rows(int nn, int level, int sps, double* rows);
  * *bytes) and with the blocks.  Honours adflow_gpu_set_async (the _dev form). */
 int adflow_gpu_jacobian_mult(int level, int transpose, const double* x, double* y, long n);
 int adflow_gpu_jacobian_mult_dev(int level, int transpose, const double* d_x, double* d_y, long n);
+/* Block ILU(0) of the assembled 7-point preconditioner matrix, factored and applied on the device: the PCApply of the KSP that
+ * setupStandardKSP builds (adjointUtils.F90:1374-1562) in the configuration PCBJACOBI (PCASM with overlap 0), one subdomain per
+ * structured block, sub-preconditioner ILU with 0 levels of fill and the natural ordering (k, j, i with i fastest: the rows of
+ * adflow_gpu_set_w_vec) on BAIJ blocks of size nState.  A column on a halo cell, with or without a donor, is not part of a
+ * subdomain: the preconditioner is local to the rank whatever the number of ranks.
+ *   D_c = A_cc - sum_lower A_{c,n} D_n^-1 A_{n,c},   L_{c,n} = A_{c,n} D_n^-1,   U_{c,n} = A_{c,n},   M = L (D + U)
+ * over the neighbours n = c - e_i, c - e_j, c - e_k inside the block; M^T has the pivot blocks D_c^T, so one setup serves
+ * z = M^-1 r (transpose = 0) and z = M^-T r (transpose != 0).  Setup and both triangular sweeps run hyperplane i + j + k by
+ * hyperplane, one launch per hyperplane over every block of the level (2 x nPlanes launches per application).
+ * adflow_gpu_pc_setup factors the matrix of the last adflow_gpu_fd_jacobian on `level`; it is an error unless that matrix has the
+ * 7-point stencil (ADFLOW_JAC_PC without ADFLOW_JAC_VISC_PC), or when a pivot block is singular or not finite (the message names
+ * block and cell; no factor is kept).  The factor owns its data -- six off-diagonal blocks and D^-1 per owned cell, 7 nState^2 x
+ * 8 B, in hyperplane order, plus index tables of 36 B per cell and one vector -- and survives later assemblies: the adjoint
+ * assembles the preconditioner matrix, calls adflow_gpu_pc_setup, then assembles the exact matrix.  It is released by
+ * adflow_gpu_pc_release (*bytes, may be NULL: what was released, 0 without a factor), adflow_gpu_block_release and
+ * adflow_gpu_release_all; adflow_gpu_release_workspace does not touch it.  adflow_gpu_pc_info: nState and the number of
+ * hyperplanes of the factor and the bytes it holds; an error without a factor.
+ * Vectors as for adflow_gpu_jacobian_mult (n = nState x owned cells of the level); host pointers, or device pointers for the _dev
+ * form, which honours adflow_gpu_set_async.  r and z must differ.  State, residual and matrix are not touched.
+ * Out of scope: ILU(k > 0) and the RCM ordering (the reference's defaults), ASM overlap and couplings across blocks, the
+ * pseudo-time diagonal term of ANK. */
+int adflow_gpu_pc_setup(int level);
+int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes);
+int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, long n);
+int adflow_gpu_pc_apply_dev(int level, int transpose, const double* d_r, double* d_z, long n);
+int adflow_gpu_pc_release(int64_t* bytes);
+/* Restarted GMRES with the factor as RIGHT preconditioner, the KSPSolve of solveAdjoint (adjointAPI.F90:661-863) with the settings
+ * of setupStandardKSP (adjointUtils.F90:1374-1562: KSPGMRES, PC_RIGHT, modified Gram-Schmidt):  A M^-1 u = b, x = M^-1 u, with
+ * A = adflow_gpu_jacobian_mult on the matrix assembled last (7-, 13-, 27- or 33-point) and M = the factor of adflow_gpu_pc_setup,
+ * both transposed when transpose != 0 (the adjoint: assemble the preconditioner matrix, adflow_gpu_pc_setup, assemble the exact
+ * matrix, solve with transpose = 1).  Basis vectors, dot products and updates stay on the device; the Hessenberg matrix and the
+ * Givens rotations are kept on the host, one download of a column per iteration.  The iteration stops when the residual of the
+ * recurrence is <= max(rtol ||b||, atol), or after maxIts iterations (not an error); restart = size of the Krylov space.
+ * useGuess != 0: x holds the initial guess (else it is ignored and the solve starts from 0).  *its: iterations done; *rnorm0: the
+ * initial residual norm; *rnorm: the TRUE residual ||b - A x|| of the returned x, computed once at the end (each may be NULL).
+ * Errors: no matrix or no factor, nState of factor and matrix differ, wrong level or n, b == x, and more than one rank in the
+ * communicator of adflow_gpu_comm_init -- the dot products are not reduced across ranks (out of scope, as is a matrix-free
+ * operator): such a host keeps its KSP and calls the two _dev operators.  Work space of restart + 4 vectors is allocated for the
+ * call.  State, residual, matrix and factor are not touched. */
+int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x, long n, int restart, int maxIts, double rtol,
+                           double atol, int useGuess, int* its, double* rnorm0, double* rnorm);
+int adflow_gpu_gmres_solve_dev(int level, int transpose, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol,
+                               double atol, int useGuess, int* its, double* rnorm0, double* rnorm);
 
 #ifdef __cplusplus
 }
