@@ -135,6 +135,7 @@ BC_CALLBACK = ctypes.CFUNCTYPE(None, c_int, c_int)
 
 JAC_PC, JAC_FROZEN_TURB, JAC_TURB_ONLY, JAC_VISC_PC, JAC_USE_AD = 1, 2, 4, 8, 16     # include/adflow_gpu.h
 RES_UPDATE_INTERMED, RES_FLOW, RES_TURB, RES_CLOSURES, RES_HALO = 1, 2, 4, 8, 16
+RES_DISS_APPROX, RES_VISC_APPROX, RES_UPWIND_FIRST_ORDER, ANK_COUPLED = 32, 64, 128, 256
 
 EXPORTS = [
     "adflow_gpu_init", "adflow_gpu_finalize", "adflow_gpu_last_error", "adflow_gpu_device_name",
@@ -156,6 +157,10 @@ EXPORTS = [
     "adflow_gpu_jacobian_mult", "adflow_gpu_jacobian_mult_dev",
     "adflow_gpu_pc_setup", "adflow_gpu_pc_info", "adflow_gpu_pc_apply", "adflow_gpu_pc_apply_dev", "adflow_gpu_pc_release",
     "adflow_gpu_gmres_solve", "adflow_gpu_gmres_solve_dev",
+    "adflow_gpu_ank_set_w", "adflow_gpu_ank_set_w_dev", "adflow_gpu_ank_get_r", "adflow_gpu_ank_get_r_dev", "adflow_gpu_ank_time_step",
+    "adflow_gpu_ank_download_time_step", "adflow_gpu_ank_pc_setup", "adflow_gpu_ank_set_base", "adflow_gpu_ank_set_base_dev",
+    "adflow_gpu_ank_mult", "adflow_gpu_ank_mult_dev", "adflow_gpu_ank_last_h", "adflow_gpu_ank_solve", "adflow_gpu_ank_solve_dev",
+    "adflow_gpu_ank_physicality_check", "adflow_gpu_ank_physicality_check_dev", "adflow_gpu_ank_release",
     "adflow_gpu_event_record", "adflow_gpu_event_elapsed_ms", "adflow_gpu_sync", "adflow_gpu_set_async",
     "adflow_gpu_abi_sizes", "adflow_gpu_set_tuning", "adflow_gpu_march_stats",
 ]
@@ -220,6 +225,21 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     for f in (lib.adflow_gpu_gmres_solve, lib.adflow_gpu_gmres_solve_dev):
         f.argtypes = [c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_double, c_double, c_int,
                       POINTER(c_int), POINTER(c_double), POINTER(c_double)]
+    for f in (lib.adflow_gpu_ank_set_w, lib.adflow_gpu_ank_set_w_dev, lib.adflow_gpu_ank_get_r, lib.adflow_gpu_ank_get_r_dev,
+              lib.adflow_gpu_ank_set_base, lib.adflow_gpu_ank_set_base_dev):
+        f.argtypes = [c_void_p, ctypes.c_long, c_uint]
+    lib.adflow_gpu_ank_time_step.argtypes = [c_int, c_double, c_double, c_uint]
+    lib.adflow_gpu_ank_download_time_step.argtypes = [c_int, c_void_p]
+    lib.adflow_gpu_ank_pc_setup.argtypes = [c_int]
+    lib.adflow_gpu_ank_mult.argtypes = [c_void_p, c_void_p, ctypes.c_long]
+    lib.adflow_gpu_ank_mult_dev.argtypes = [c_void_p, c_void_p, ctypes.c_long]
+    lib.adflow_gpu_ank_last_h.argtypes = [POINTER(c_double)]
+    for f in (lib.adflow_gpu_ank_solve, lib.adflow_gpu_ank_solve_dev):
+        f.argtypes = [c_int, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_double, c_double, POINTER(c_int), POINTER(c_double),
+                      POINTER(c_double)]
+    for f in (lib.adflow_gpu_ank_physicality_check, lib.adflow_gpu_ank_physicality_check_dev):
+        f.argtypes = [c_void_p, c_void_p, ctypes.c_long, c_uint, c_double, c_double, c_double, c_double, POINTER(c_double)]
+    lib.adflow_gpu_ank_release.argtypes = [POINTER(ctypes.c_int64)]
     lib.adflow_gpu_set_tuning.argtypes = [c_char_p, c_int]
     lib.adflow_gpu_abi_sizes.argtypes = [POINTER(c_int), POINTER(c_int)]
     lib.adflow_gpu_rk_smooth.argtypes = [c_int]

@@ -609,6 +609,7 @@ static void bc_plan_drop_all();
 static void ad_cache_drop();      // the cached dual arrays of the forward-mode assembly refer to the blocks
 static int64_t jm_release();      // ... and so do the scratch arrays of the matrix products (adflow_gpu_jacobian_mult)
 static int64_t pc_release();      // ... and the block ILU(0) factor (adflow_gpu_pc_setup)
+static int64_t ank_release();     // ... and the pseudo-time term, base vectors and sums of the ANK operator (adflow_gpu_ank_*)
 static bool g_jac_valid = false; // adflow_gpu_fd_jacobian left a matrix on the blocks of level g_jac_level
 static int g_jac_level = 0;
 
@@ -621,6 +622,7 @@ int adflow_gpu_block_release(int nn, int level, int sps)
     ad_cache_drop();
     (void)jm_release();
     (void)pc_release();
+    (void)ank_release();
     for (void* p : it->second->allocs) (void)hipFree(p);
     if (it->second->jac_raw) (void)hipFree(it->second->jac_raw);
     if (it->second->snap_raw) (void)hipFree(it->second->snap_raw);
@@ -638,6 +640,7 @@ int adflow_gpu_release_all(void)
     ad_cache_drop();
     (void)jm_release();
     (void)pc_release();
+    (void)ank_release();
     for (auto& kv : g_blocks) {
         for (void* p : kv.second->allocs) (void)hipFree(p);
         if (kv.second->jac_raw) (void)hipFree(kv.second->jac_raw);
@@ -4031,7 +4034,8 @@ static int pc_alloc(void** p, size_t bytes)
     return 0;
 }
 
-static int pc_setup_build(int level)
+// shift != NULL: the pseudo-time term of ANK (tsm of kernels_ank.hip) is added to the diagonal blocks as the factorisation reads them
+static int pc_setup_build(int level, const double* shift = nullptr, double turbDiag = 0.0)
 {
     const int nS = g_jac.nState;
     int sten[7];
@@ -4129,7 +4133,10 @@ static int pc_setup_build(int level)
     HIPCHK(hipMemsetAsync(df, 0, sizeof(int), g_stream));
     T.nbr = (const int*)dn; T.vec = (const int*)dv; T.cblk = (const int*)db; T.cbox = (const int*)dc;
     T.blk = (const JmBlk*)dt; T.flag = (int*)df;
-    if (launch_pc_factor(T, nS, start, g_stream)) return 1;
+    T.tsm = shift; T.turbDiag = turbDiag;
+    const int rcf = launch_pc_factor(T, nS, start, g_stream);
+    T.tsm = nullptr;                              // the sweeps do not read it, and it may be released before the factor
+    if (rcf) return 1;
     int flag = 0;
     HIPCHK(hipMemcpyAsync(&flag, df, sizeof(int), hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
@@ -4216,8 +4223,10 @@ int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, lo
 // GMRES(restart) on  A M^-1 u = b, x = M^-1 u  (transpose: A^T M^-T), A = adflow_gpu_jacobian_mult with the matrix on the device,
 // M = the factor.  Basis, dots and updates on the device (one launch per basis vector of a modified Gram-Schmidt step, one
 // download of the new Hessenberg column per step); Hessenberg matrix and Givens rotations on the host.
-static int gm_solve(int level, int transpose, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol, double atol,
-                    int useGuess, int* its, double* rnorm0, double* rnorm)
+// op(v, y) enqueues y = A v: jm_mult_enqueue on the assembled matrix, or the matrix-free operator of ANK (ank_mult_enqueue).
+typedef std::function<int(const double*, double*)> GmOperator;
+static int gm_solve(const char* who, const GmOperator& op, int transpose, const double* d_b, double* d_x, long n, int restart, int maxIts,
+                    double rtol, double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
 {
     const int m = std::max(1, std::min(restart, std::max(maxIts, 1)));
     DevBuf buf;
@@ -4241,13 +4250,13 @@ static int gm_solve(int level, int transpose, const double* d_b, double* d_x, lo
             HIPCHK(hipMemcpyAsync(r, d_b, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
             return 0;
         }
-        if (jm_mult_enqueue(level, transpose, d_x, r)) return 1;
+        if (op(d_x, r)) return 1;
         launch_gm_axpby(r, 1.0, d_b, -1.0, n, s);
         return 0;
     };
     double bnorm = 0.0, beta = 0.0, res = 0.0;
     if (norm(d_b, &bnorm)) return 1;
-    if (!(bnorm == bnorm)) return fail("gmres_solve: the right-hand side is not finite");
+    if (!(bnorm == bnorm)) return fail("%s: the right-hand side is not finite", who);
     const double tol = std::max(rtol * bnorm, atol);
     if (!useGuess) HIPCHK(hipMemsetAsync(d_x, 0, sizeof(double) * n, s));
     int total = 0;
@@ -4257,7 +4266,7 @@ static int gm_solve(int level, int transpose, const double* d_b, double* d_x, lo
     for (;;) {
         if (residual(V, zeroX)) return 1;
         if (norm(V, &beta)) return 1;
-        if (!(beta == beta)) return fail("gmres_solve: the residual is not finite after %d iterations", total);
+        if (!(beta == beta)) return fail("%s: the residual is not finite after %d iterations", who, total);
         if (first) { if (rnorm0) *rnorm0 = beta; first = false; }
         res = beta;
         if (beta <= tol || total >= maxIts) break;
@@ -4269,7 +4278,7 @@ static int gm_solve(int level, int transpose, const double* d_b, double* d_x, lo
         for (int j = 0; j < m && !stop; ++j) {
             double* w = V + (size_t)(j + 1) * n;
             if (launch_pc_apply(g_pc.tab, g_pc.nState, transpose, g_pc.planeStart, V + (size_t)j * n, zt, s)) return 1;
-            if (jm_mult_enqueue(level, transpose, zt, w)) return 1;
+            if (op(zt, w)) return 1;
             launch_gm_mgs(w, nullptr, nullptr, V, P[0], nullptr, n, s);
             for (int i = 1; i <= j; ++i)
                 launch_gm_mgs(w, V + (size_t)(i - 1) * n, P[(i - 1) & 1], V + (size_t)i * n, P[i & 1], dH + (i - 1), n, s);
@@ -4278,7 +4287,7 @@ static int gm_solve(int level, int transpose, const double* d_b, double* d_x, lo
             HIPCHK(hipMemcpyAsync(H.data(), dH, sizeof(double) * (j + 2), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             const double hn = sqrt(std::max(H[j + 1], 0.0));
-            if (!(H[j + 1] == H[j + 1])) return fail("gmres_solve: the Krylov vector of iteration %d is not finite", total + 1);
+            if (!(H[j + 1] == H[j + 1])) return fail("%s: the Krylov vector of iteration %d is not finite", who, total + 1);
             std::vector<double>& c = R[j];
             c.assign(H.begin(), H.begin() + j + 1);
             for (int i = 0; i < j; ++i) {
@@ -4345,7 +4354,8 @@ int adflow_gpu_gmres_solve_dev(int level, int transpose, const double* d_b, doub
                                double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
 {
     if (gm_check(level, d_b, d_x, n, restart, maxIts, rtol, atol)) return 1;
-    return gm_solve(level, transpose, d_b, d_x, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm);
+    const GmOperator op = [=](const double* v, double* y) { return jm_mult_enqueue(level, transpose, v, y); };
+    return gm_solve("gmres_solve", op, transpose, d_b, d_x, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm);
 }
 
 int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x, long n, int restart, int maxIts, double rtol,
@@ -4357,8 +4367,449 @@ int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x,
     double *d_b = (double*)buf.p, *d_x = d_b + n;
     HIPCHK(hipMemcpyAsync(d_b, b, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
     if (useGuess) HIPCHK(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (gm_solve(level, transpose, d_b, d_x, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm)) return 1;
+    const GmOperator op = [=](const double* v, double* y) { return jm_mult_enqueue(level, transpose, v, y); };
+    if (gm_solve("gmres_solve", op, transpose, d_b, d_x, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm)) return 1;
     HIPCHK(hipMemcpyAsync(x, d_x, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+// ---- the flow update of the approximate Newton-Krylov step (kernels_ank.hip) ----------------------------------------------------
+// ANKStep (NKSolvers.F90:3629-4112) up to the linear solve and the step limiter: setWANK / setRVecANK, computeTimeStepMat for
+// ANK_charTimeStepType = 'None', the ILU(0) of dRdwPre + timeStepMat, the matrix-free operator of FormFunction_mf under MatMFFD,
+// KSPSolve and physicalityCheckANK.  Vectors carry nState = nw (ADFLOW_ANK_COUPLED) or 5 variables per owned level-1 cell.
+namespace {
+struct AnkState {
+    bool haveT = false;                // the pseudo-time term: tsm[q N + m], q = 0 dtInv, 1 rho, 2..4 u, v, w (kernels_ank.hip)
+    int tLevel = 0, tNState = 0;
+    long tCells = 0;
+    double turbDiag = 0.0;
+    double* tsm = nullptr;
+    bool haveBase = false;             // the base of the matrix-free operator: w and r0 = R(w)
+    int nState = 0;
+    unsigned flags = 0;
+    long ncell = 0;
+    double *w0 = nullptr, *r0 = nullptr;
+    double* red = nullptr;             // 3 x 256 partial sums, 256 partial minima, 8 scalars: h, 1/h, the three sums; lambda
+    size_t bytesT = 0, bytesBase = 0, bytesRed = 0;
+};
+AnkState g_ank;
+const size_t ANK_RED = 4 * 256 + 8;
+const unsigned ANK_RES_FLAGS = ADFLOW_RES_DISS_APPROX | ADFLOW_RES_VISC_APPROX | ADFLOW_RES_UPWIND_FIRST_ORDER;
+}  // namespace
+
+static int64_t ank_release()
+{
+    const int64_t n = (int64_t)(g_ank.bytesT + g_ank.bytesBase + g_ank.bytesRed);
+    if (g_ank.tsm) (void)hipFree(g_ank.tsm);
+    if (g_ank.w0) (void)hipFree(g_ank.w0);
+    if (g_ank.red) (void)hipFree(g_ank.red);
+    g_ank = AnkState();
+    return n;
+}
+
+int adflow_gpu_ank_release(int64_t* bytes)
+{
+    if (g_stream) HIPCHK(hipStreamSynchronize(g_stream));
+    const int64_t n = ank_release();
+    if (bytes) *bytes = n;
+    return 0;
+}
+
+static int ank_red()
+{
+    if (g_ank.red) return 0;
+    HIPCHK(hipMalloc((void**)&g_ank.red, ANK_RED * sizeof(double)));
+    HIPCHK(hipMemsetAsync(g_ank.red, 0, ANK_RED * sizeof(double), g_stream));
+    g_ank.bytesRed = ANK_RED * sizeof(double);
+    return 0;
+}
+
+// owned cells and nState of the vectors of `level` for these flags
+static int ank_dims(const char* who, int level, unsigned flags, long* cells, int* nS)
+{
+    if (need_ready()) return 1;
+    if (flags & ~(ADFLOW_ANK_COUPLED | ANK_RES_FLAGS))
+        return fail("%s: flags = %u; accepted are ADFLOW_ANK_COUPLED and ADFLOW_RES_DISS_APPROX / _VISC_APPROX / _UPWIND_FIRST_ORDER", who, flags);
+    long n = 0;
+    int nw = 0;
+    int rc = for_level(level, [&](Block* b) {
+        if (nw && nw != b->v.nw) return fail("%s: the blocks of level %d carry different nw", who, level);
+        nw = b->v.nw;
+        n += (long)b->v.nx * b->v.ny * b->v.nz;
+        return 0;
+    });
+    if (rc) return rc;
+    if (!n) return fail("no block registered on level %d", level);
+    *cells = n;
+    *nS = (flags & ADFLOW_ANK_COUPLED) ? nw : 5;
+    return 0;
+}
+
+static int ank_vec_check(const char* who, const double* a, const double* b, long n, unsigned flags, long* cells, int* nS)
+{
+    if (ank_dims(who, 1, flags, cells, nS)) return 1;
+    if (!a || !b) return fail("%s: a vector is NULL", who);
+    if (n != *cells * *nS)
+        return fail("%s: n=%ld but the level-1 blocks hold %ld entries (nState = %d x %ld owned cells)", who, n, *cells * *nS, *nS, *cells);
+    return 0;
+}
+
+static int ank_set_w_enqueue(const double* d_w, int nS, bool withClosures, const double* d_v = nullptr, const double* hdev = nullptr)
+{
+    LevelTab t;
+    if (level_tab(1, &t)) return 1;
+    if (withClosures) {
+        KParams kp = make_kparams(1, 1.0, 0);
+        if (!g_floor_flag_dev) HIPCHK(hipMalloc((void**)&g_floor_flag_dev, sizeof(int)));
+        HIPCHK(hipMemsetAsync(g_floor_flag_dev, 0, sizeof(int), g_stream));
+        launch_ank_set_w(t.tab, t.n, t.nx, t.ny, t.nz, nS, d_w, d_v, hdev, &kp, g_floor_flag_dev, g_stream);
+    } else
+        launch_ank_set_w(t.tab, t.n, t.nx, t.ny, t.nz, nS, d_w, d_v, hdev, nullptr, nullptr, g_stream);
+    return for_level1_in_order([&](Block* b, long) {
+        b->ss_valid = false;
+        b->etot_consistent = false;
+        return 0;
+    });
+}
+
+// blocketteRes(useDissApprox, useViscApprox, useTurbRes = ANK_coupled, useStoreWall = F) behind a state write that did the closures
+static int ank_res_enqueue(unsigned flags)
+{
+    unsigned f = ADFLOW_RES_HALO | ADFLOW_RES_FLOW | (flags & ANK_RES_FLAGS);
+    if ((flags & ADFLOW_ANK_COUPLED) && g_opts.equations == ADFLOW_RANS) f |= ADFLOW_RES_TURB;
+    g_etot_flag_level = 1;      // the owned energy is computeEtot(p) already wherever p kept its value
+    const int rc = block_res_enqueue(1, f);
+    g_etot_flag_level = 0;
+    return rc;
+}
+
+static int ank_get_r_enqueue(double* d_r, int nS)
+{
+    LevelTab t;
+    if (level_tab(1, &t)) return 1;
+    launch_ank_get_r(t.tab, t.n, t.nx, t.ny, t.nz, nS, d_r, g_opts.turbResScale, g_stream);
+    return 0;
+}
+
+int adflow_gpu_ank_set_w_dev(const double* d_w, long n, unsigned flags)
+{
+    long cells; int nS;
+    if (ank_vec_check("ank_set_w", d_w, d_w, n, flags, &cells, &nS)) return 1;
+    if (ank_set_w_enqueue(d_w, nS, false)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_ank_set_w(const double* w, long n, unsigned flags)
+{
+    long cells; int nS;
+    if (ank_vec_check("ank_set_w", w, w, n, flags, &cells, &nS)) return 1;
+    if (vec_reserve((size_t)n)) return 1;
+    HIPCHK(hipMemcpyAsync(g_vec_dev, w, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    if (ank_set_w_enqueue(g_vec_dev, nS, false)) return 1;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+int adflow_gpu_ank_get_r_dev(double* d_r, long n, unsigned flags)
+{
+    long cells; int nS;
+    if (ank_vec_check("ank_get_r", d_r, d_r, n, flags, &cells, &nS)) return 1;
+    if (ank_get_r_enqueue(d_r, nS)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_ank_get_r(double* r, long n, unsigned flags)
+{
+    long cells; int nS;
+    if (ank_vec_check("ank_get_r", r, r, n, flags, &cells, &nS)) return 1;
+    if (vec_reserve((size_t)n)) return 1;
+    if (ank_get_r_enqueue(g_vec_dev, nS)) return 1;
+    HIPCHK(hipMemcpyAsync(r, g_vec_dev, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+int adflow_gpu_ank_time_step(int level, double cfl, double turbCFLScale, unsigned flags)
+{
+    long cells; int nS;
+    if (ank_dims("ank_time_step", level, flags & ADFLOW_ANK_COUPLED, &cells, &nS)) return 1;
+    if (!(cfl > 0.0)) return fail("ank_time_step: cfl = %g", cfl);
+    if (nS > 5 && !(turbCFLScale > 0.0)) return fail("ank_time_step: turbCFLScale = %g", turbCFLScale);
+    if (g_ank.tsm && g_ank.tCells != cells) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        (void)hipFree(g_ank.tsm);
+        g_ank.tsm = nullptr;
+        g_ank.bytesT = 0;
+    }
+    g_ank.haveT = false;
+    if (!g_ank.tsm) {
+        HIPCHK(hipMalloc((void**)&g_ank.tsm, sizeof(double) * 5 * cells));
+        g_ank.bytesT = sizeof(double) * 5 * cells;
+    }
+    LevelTab t;
+    if (level_tab(level, &t)) return 1;
+    launch_ank_time_step(t.tab, t.n, t.nx, t.ny, t.nz, cfl, g_ank.tsm, cells, g_stream);
+    g_ank.tLevel = level; g_ank.tNState = nS; g_ank.tCells = cells;
+    g_ank.turbDiag = nS > 5 ? g_opts.turbResScale / turbCFLScale : 0.0;
+    g_ank.haveT = true;
+    return sync_and_check();
+}
+
+int adflow_gpu_ank_download_time_step(int nn, double* blocks)
+{
+    if (need_ready()) return 1;
+    if (!g_ank.haveT) return fail("ank_download_time_step: no pseudo-time term (call adflow_gpu_ank_time_step first)");
+    if (!blocks) return fail("ank_download_time_step: blocks is NULL");
+    Block* b = find_block(nn, g_ank.tLevel, 1);
+    if (!b) return fail("block (%d,%d,1) not registered", nn, g_ank.tLevel);
+    long off = 0;
+    for (auto& kv : g_blocks)
+        if (std::get<0>(kv.first) == g_ank.tLevel && std::get<2>(kv.first) < nn) off += (long)kv.second->v.nx * kv.second->v.ny * kv.second->v.nz;
+    const long nc = (long)b->v.nx * b->v.ny * b->v.nz, N = g_ank.tCells;
+    const int nS = g_ank.tNState;
+    std::vector<double> h((size_t)5 * nc);
+    HIPCHK(hipStreamSynchronize(g_stream));
+    for (int q = 0; q < 5; ++q) HIPCHK(hipMemcpy(h.data() + (size_t)q * nc, g_ank.tsm + (size_t)q * N + off, sizeof(double) * nc, hipMemcpyDeviceToHost));
+    memset(blocks, 0, sizeof(double) * nS * nS * nc);
+    for (long c = 0; c < nc; ++c) {
+        double* B = blocks + (size_t)c * nS * nS;      // B[ll + l nS] = T(ll, l)
+        const double dtInv = h[c], rho = h[nc + c];
+        B[0] = dtInv;
+        B[4 + 4 * nS] = dtInv;
+        for (int l = 1; l < 4; ++l) {
+            B[l] = dtInv * h[(size_t)(l + 1) * nc + c];
+            B[l + l * nS] = dtInv * rho;
+        }
+        if (nS > 5) B[5 + 5 * nS] = dtInv * g_ank.turbDiag;
+    }
+    return 0;
+}
+
+int adflow_gpu_ank_pc_setup(int level)
+{
+    if (need_ready()) return 1;
+    if (!g_jac_valid) return fail("ank_pc_setup: no assembled Jacobian (call adflow_gpu_fd_jacobian with ADFLOW_JAC_PC first)");
+    if (level != g_jac_level) return fail("ank_pc_setup: level %d is not the level of the assembly (%d)", level, g_jac_level);
+    if (g_jac.nStencil != 7)
+        return fail("ank_pc_setup: the assembled matrix has a %d-point stencil; the block ILU(0) takes the 7-point preconditioner matrix "
+                    "(ADFLOW_JAC_PC without ADFLOW_JAC_VISC_PC)", g_jac.nStencil);
+    if (!g_ank.haveT) return fail("ank_pc_setup: no pseudo-time term (call adflow_gpu_ank_time_step first)");
+    if (g_ank.tLevel != level) return fail("ank_pc_setup: level %d is not the level of the pseudo-time term (%d)", level, g_ank.tLevel);
+    if (g_ank.tNState != g_jac.nState)
+        return fail("ank_pc_setup: the pseudo-time term was formed for nState = %d, the assembled matrix has nState = %d", g_ank.tNState,
+                    g_jac.nState);
+    HIPCHK(hipStreamSynchronize(g_stream));
+    (void)pc_release();
+    if (pc_setup_build(level, g_ank.tsm, g_ank.turbDiag)) {
+        if (g_stream) (void)hipStreamSynchronize(g_stream);
+        (void)pc_release();
+        return 1;
+    }
+    return 0;
+}
+
+static int ank_set_base_enqueue(const double* d_w, long n, long cells, int nS, unsigned flags)
+{
+    if (ank_red()) return 1;
+    if (g_ank.w0 && (g_ank.ncell != cells || g_ank.nState != nS)) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        (void)hipFree(g_ank.w0);
+        g_ank.w0 = g_ank.r0 = nullptr;
+        g_ank.bytesBase = 0;
+    }
+    g_ank.haveBase = false;
+    if (!g_ank.w0) {
+        HIPCHK(hipMalloc((void**)&g_ank.w0, sizeof(double) * 2 * n));
+        g_ank.r0 = g_ank.w0 + n;
+        g_ank.bytesBase = sizeof(double) * 2 * n;
+    }
+    g_ank.ncell = cells; g_ank.nState = nS; g_ank.flags = flags;
+    HIPCHK(hipMemcpyAsync(g_ank.w0, d_w, sizeof(double) * n, hipMemcpyDeviceToDevice, g_stream));
+    if (ank_set_w_enqueue(g_ank.w0, nS, true)) return 1;
+    if (ank_res_enqueue(flags)) return 1;
+    if (ank_get_r_enqueue(g_ank.r0, nS)) return 1;
+    g_ank.haveBase = true;
+    return 0;
+}
+
+int adflow_gpu_ank_set_base_dev(const double* d_w, long n, unsigned flags)
+{
+    long cells; int nS;
+    if (ank_vec_check("ank_set_base", d_w, d_w, n, flags, &cells, &nS)) return 1;
+    if (ank_set_base_enqueue(d_w, n, cells, nS, flags)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_ank_set_base(const double* w, long n, unsigned flags)
+{
+    long cells; int nS;
+    if (ank_vec_check("ank_set_base", w, w, n, flags, &cells, &nS)) return 1;
+    if (vec_reserve((size_t)n)) return 1;
+    HIPCHK(hipMemcpyAsync(g_vec_dev, w, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    if (ank_set_base_enqueue(g_vec_dev, n, cells, nS, flags)) return 1;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+static int ank_mult_check(const char* who, const double* v, const double* y, long n)
+{
+    if (need_ready()) return 1;
+    if (!g_ank.haveBase) return fail("%s: no base state (call adflow_gpu_ank_set_base first)", who);
+    if (!g_ank.haveT) return fail("%s: no pseudo-time term (call adflow_gpu_ank_time_step first)", who);
+    if (g_ank.tLevel != 1 || g_ank.tNState != g_ank.nState || g_ank.tCells != g_ank.ncell)
+        return fail("%s: the pseudo-time term was formed for nState = %d on level %d, the base state has nState = %d on level 1", who,
+                    g_ank.tNState, g_ank.tLevel, g_ank.nState);
+    if (!v || !y) return fail("%s: a vector is NULL", who);
+    if (v == y) return fail("%s: input and result are the same vector (not done in place)", who);
+    if (n != g_ank.ncell * g_ank.nState)
+        return fail("%s: n=%ld but the base state has %ld rows (nState = %d x %ld owned cells)", who, n, g_ank.ncell * g_ank.nState,
+                    g_ank.nState, g_ank.ncell);
+    return 0;
+}
+
+// y = (R(w + h v) - r0) / h + T v, h = the MATMFFD_DS step, formed and consumed on the device: no host synchronisation
+static int ank_mult_enqueue(const double* d_v, double* d_y)
+{
+    const long n = g_ank.ncell * g_ank.nState;
+    const int nS = g_ank.nState;
+    double *part = g_ank.red, *hdev = g_ank.red + 4 * 256;
+    launch_ank_step(g_ank.w0, d_v, n, 1.490116119384766e-08, 1e-6, part, hdev, g_stream);
+    if (ank_set_w_enqueue(g_ank.w0, nS, true, d_v, hdev)) return 1;
+    if (ank_res_enqueue(g_ank.flags)) return 1;
+    LevelTab t;
+    if (level_tab(1, &t)) return 1;
+    launch_ank_quotient(t.tab, t.n, t.nx, t.ny, t.nz, nS, d_v, g_ank.r0, g_ank.tsm, g_ank.tCells, g_ank.turbDiag, g_opts.turbResScale, hdev,
+                        d_y, g_stream);
+    return 0;
+}
+
+int adflow_gpu_ank_mult_dev(const double* d_v, double* d_y, long n)
+{
+    if (ank_mult_check("ank_mult", d_v, d_y, n)) return 1;
+    if (ank_mult_enqueue(d_v, d_y)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_ank_mult(const double* v, double* y, long n)
+{
+    if (ank_mult_check("ank_mult", v, y, n)) return 1;
+    bool zero = true;                  // v = 0: y = 0 and no residual is evaluated
+    for (long i = 0; i < n && zero; ++i) zero = v[i] == 0.0;
+    if (zero) {
+        memset(y, 0, sizeof(double) * n);
+        HIPCHK(hipMemsetAsync(g_ank.red + 4 * 256, 0, 8 * sizeof(double), g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        return 0;
+    }
+    if (vec_reserve((size_t)2 * n)) return 1;
+    HIPCHK(hipMemcpyAsync(g_vec_dev, v, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    if (ank_mult_enqueue(g_vec_dev, g_vec_dev + n)) return 1;
+    HIPCHK(hipMemcpyAsync(y, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+int adflow_gpu_ank_last_h(double* h)
+{
+    if (need_ready()) return 1;
+    if (!g_ank.haveBase || !h) return fail("ank_last_h: no base state (call adflow_gpu_ank_set_base first)");
+    HIPCHK(hipMemcpyAsync(h, g_ank.red + 4 * 256, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+static int ank_gm_check(int level, const double* b, const double* x, long n, int restart, int maxIts, double rtol, double atol)
+{
+    if (need_ready()) return 1;
+#ifndef ADFLOW_NO_RCCL
+    if (g_nranks > 1)
+        return fail("ank_solve: %d ranks in the communicator; the dot products of the solver are not reduced across ranks (use the "
+                    "host's KSP with adflow_gpu_ank_mult_dev and adflow_gpu_pc_apply_dev)", g_nranks);
+#endif
+    if (level != 1) return fail("ank_solve: level %d; the matrix-free operator acts on level 1", level);
+    if (ank_mult_check("ank_solve", b, x, n)) return 1;
+    if (pc_check("ank_solve", level, b, x, n, false)) return 1;
+    if (g_pc.nState != g_ank.nState || g_pc.ncell != g_ank.ncell)
+        return fail("ank_solve: the factor was set up for nState = %d, the base state has nState = %d", g_pc.nState, g_ank.nState);
+    if (restart < 1 || maxIts < 0) return fail("ank_solve: restart = %d, maxIts = %d", restart, maxIts);
+    if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail("ank_solve: rtol = %g, atol = %g", rtol, atol);
+    return 0;
+}
+
+int adflow_gpu_ank_solve_dev(int level, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol, double atol, int* its,
+                             double* rnorm0, double* rnorm)
+{
+    if (ank_gm_check(level, d_b, d_x, n, restart, maxIts, rtol, atol)) return 1;
+    const GmOperator op = [](const double* v, double* y) { return ank_mult_enqueue(v, y); };
+    if (gm_solve("ank_solve", op, 0, d_b, d_x, n, restart, maxIts, rtol, atol, 0, its, rnorm0, rnorm)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_ank_solve(int level, const double* b, double* x, long n, int restart, int maxIts, double rtol, double atol, int* its,
+                         double* rnorm0, double* rnorm)
+{
+    if (ank_gm_check(level, b, x, n, restart, maxIts, rtol, atol)) return 1;
+    DevBuf buf;
+    HIPCHK(hipMalloc(&buf.p, sizeof(double) * 2 * n));
+    double *d_b = (double*)buf.p, *d_x = d_b + n;
+    HIPCHK(hipMemcpyAsync(d_b, b, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    const GmOperator op = [](const double* v, double* y) { return ank_mult_enqueue(v, y); };
+    if (gm_solve("ank_solve", op, 0, d_b, d_x, n, restart, maxIts, rtol, atol, 0, its, rnorm0, rnorm)) return 1;
+    HIPCHK(hipMemcpyAsync(x, d_x, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+static int ank_phys_check(const double* w, const double* dw, long n, unsigned flags, double stepFactor, double stepMin, const double* lambda,
+                          long* cells, int* nS)
+{
+    if (need_ready()) return 1;
+#ifndef ADFLOW_NO_RCCL
+    if (g_nranks > 1)
+        return fail("ank_physicality_check: %d ranks in the communicator; the minimum is not reduced across ranks (the mpi_allreduce of "
+                    "physicalityCheckANK is the host's)", g_nranks);
+#endif
+    if (flags & ~ADFLOW_ANK_COUPLED) return fail("ank_physicality_check: flags = %u; accepted is ADFLOW_ANK_COUPLED", flags);
+    if (ank_vec_check("ank_physicality_check", w, dw, n, flags, cells, nS)) return 1;
+    if (!lambda) return fail("ank_physicality_check: lambda is NULL");
+    if (w == dw) return fail("ank_physicality_check: state and update are the same vector");
+    (void)stepFactor; (void)stepMin;
+    return 0;
+}
+
+static int ank_phys_enqueue(const double* d_w, double* d_dw, long cells, int nS, double physLSTol, double physLSTolTurb, double stepFactor,
+                            double stepMin, double lambda0)
+{
+    if (ank_red()) return 1;
+    launch_ank_phys(d_w, d_dw, cells, nS, nS > 5 ? 1 : 0, 1.e-25, physLSTol, physLSTolTurb, stepFactor * stepMin, lambda0, g_ank.red + 3 * 256,
+                    g_ank.red + 4 * 256 + 5, g_stream);
+    return 0;
+}
+
+int adflow_gpu_ank_physicality_check_dev(const double* d_w, double* d_dw, long n, unsigned flags, double physLSTol, double physLSTolTurb,
+                                         double stepFactor, double stepMin, double* lambda)
+{
+    long cells; int nS;
+    if (ank_phys_check(d_w, d_dw, n, flags, stepFactor, stepMin, lambda, &cells, &nS)) return 1;
+    if (ank_phys_enqueue(d_w, d_dw, cells, nS, physLSTol, physLSTolTurb, stepFactor, stepMin, *lambda)) return 1;
+    HIPCHK(hipMemcpyAsync(lambda, g_ank.red + 4 * 256 + 5, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));      // lambda goes to the host: synchronous whatever adflow_gpu_set_async says
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int adflow_gpu_ank_physicality_check(const double* w, double* dw, long n, unsigned flags, double physLSTol, double physLSTolTurb,
+                                     double stepFactor, double stepMin, double* lambda)
+{
+    long cells; int nS;
+    if (ank_phys_check(w, dw, n, flags, stepFactor, stepMin, lambda, &cells, &nS)) return 1;
+    if (vec_reserve((size_t)2 * n)) return 1;
+    HIPCHK(hipMemcpyAsync(g_vec_dev, w, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(g_vec_dev + n, dw, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    if (ank_phys_enqueue(g_vec_dev, g_vec_dev + n, cells, nS, physLSTol, physLSTolTurb, stepFactor, stepMin, *lambda)) return 1;
+    if (nS > 5) HIPCHK(hipMemcpyAsync(dw, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(lambda, g_ank.red + 4 * 256 + 5, sizeof(double), hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
 }

@@ -406,6 +406,8 @@ struct PcTab {
     const JmBlk* blk;
     int* flag;            // != 0: 1 + position of a cell whose pivot block is singular or not finite
     int sten[7];          // stencil entries of the assembly: the columns c - e_i, c - e_j, c - e_k, c + e_i, c + e_j, c + e_k, c
+    const double* tsm;    // setup only: the pseudo-time term of ANK added to the diagonal blocks (kernels_ank.hip), NULL = none
+    double turbDiag;      // S(nt1, nt1) = turbResScale / turbCFLScale of the coupled T
 };
 int launch_pc_factor(const PcTab& T, int nState, const std::vector<int>& planeStart, hipStream_t s);
 int launch_pc_apply(const PcTab& T, int nState, int transpose, const std::vector<int>& planeStart, const double* r, double* z,
@@ -415,6 +417,18 @@ int gm_groups(long n);
 void launch_gm_mgs(double* w, const double* v, const double* hp, const double* u, double* out, double* hOut, long n, hipStream_t s);
 void launch_gm_sum(const double* hp, long n, double* hOut, hipStream_t s);
 void launch_gm_axpby(double* y, double a, const double* x, double b, long n, hipStream_t s);
+// approximate Newton-Krylov step (kernels_ank.hip): vectors of nS variables per owned cell; kp != NULL: with the closures of blocketteRes
+struct KParams;
+int ank_groups(long n);
+void launch_ank_set_w(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, int nS, const double* vec, const double* hv,
+                      const double* hdev, const KParams* kp, int* floored, hipStream_t s);
+void launch_ank_get_r(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, int nS, double* vec, double turbScale, hipStream_t s);
+void launch_ank_time_step(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, double cfl, double* tsm, long N, hipStream_t s);
+void launch_ank_quotient(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, int nS, const double* v, const double* r0,
+                         const double* tsm, long N, double turbDiag, double turbScale, const double* hdev, double* y, hipStream_t s);
+void launch_ank_step(const double* w, const double* v, long n, double errRel, double umin, double* part, double* hdev, hipStream_t s);
+void launch_ank_phys(const double* w, double* dw, long ncell, int nS, int turb, double eps, double tol, double tolTurb, double turbThreshold,
+                     double lambda0, double* part, double* out, hipStream_t s);
 
 // The level-batched launches fold (block slot, plane) into gridDim.z, which HIP limits to 65535: a launcher whose level has more
 // slots than fit calls itself on consecutive slot ranges (the kernels index the table relative to the pointer they get).

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "nk_closures.h"
 
 #define NK_BX 64
 #define NK_BY 4
@@ -99,8 +100,6 @@ __global__ __launch_bounds__(NK_BX* NK_BY) void k_get_r_level(const BlkView* __r
 // pass over w, p is saved; a cell whose pressure hit the floor keeps the vector's energy for the exchange and raises *floored, on
 // which the pass behind the exchange then runs as before
 template <bool ETOT = false>
-__device__ __forceinline__ void closures_cell(const BlkView& b, int i, int j, int k, const KParams& kp, int* __restrict__ floored);
-template <bool ETOT = false>
 __device__ __forceinline__ void closures_body(const BlkView& b, int kz, const KParams& kp, int* __restrict__ floored = nullptr)
 {
     const int i = blockIdx.x * NK_BX + threadIdx.x + 2;
@@ -109,42 +108,6 @@ __device__ __forceinline__ void closures_body(const BlkView& b, int kz, const KP
     if (i > b.il || j > b.jl || k > b.kl) return;
     closures_cell<ETOT>(b, i, j, k, kp, floored);
 }
-template <bool ETOT>
-__device__ __forceinline__ void closures_cell(const BlkView& b, int i, int j, int k, const KParams& kp, int* __restrict__ floored)
-{
-    const long c = b.idx(i, j, k);
-    const long nb = b.nbox;
-    const double rho = b.w[c], u = b.w[c + nb], v = b.w[c + 2 * nb], w = b.w[c + 3 * nb];
-    const double gm1 = kp.gammaConstant - 1.0;
-    const double v2 = u * u + v * v + w * w;
-    double p = gm1 * (b.w[c + 4 * nb] - 0.5 * rho * v2);
-    const double pFloor = 1.e-4 * kp.pInfCorr;
-    const bool hitFloor = !(p >= pFloor);
-    p = fmax(p, pFloor);
-    b.p[c] = p;
-    if (ETOT) {
-        if (hitFloor) *floored = 1;
-        else {
-            const double ovgm1 = 1.0 / (kp.gammaConstant - 1.0);
-            b.w[c + 4 * nb] = ovgm1 * p + 0.5 * rho * v2;
-        }
-    }
-    if (kp.viscous) {
-        const double muSuth = kp.muSuthDim / kp.muRef, TSuth = kp.TSuthDim / kp.TRef, SSuth = kp.SSuthDim / kp.TRef;
-        const double T = p / (kp.RGas * rho);
-        const double tt = T / TSuth;
-        const double rlv = muSuth * ((TSuth + SSuth) / (T + SSuth)) * (tt * sqrt(tt));
-        b.rlv[c] = rlv;
-        if (kp.eddyModel && kp.updateEddy) {
-            const double cv13 = kp.sa_cv1 * kp.sa_cv1 * kp.sa_cv1;
-            const double rnuSA = b.w[c + 5 * nb] * rho;
-            const double chi = rnuSA / rlv;
-            const double chi3 = chi * chi * chi;
-            b.rev[c] = chi3 / (chi3 + cv13) * rnuSA;
-        }
-    }
-}
-
 __global__ __launch_bounds__(NK_BX* NK_BY) void k_closures(BlkView b, KParams kp) { closures_body(b, (int)blockIdx.z, kp); }
 
 // setW followed by the closures of blocketteRes in one pass (FormFunction_mf: NKSolvers.F90:437-461 -> blockette.F90:199-203):

@@ -4,8 +4,8 @@
 // Reference semantics: the PCApply of setupStandardKSP (adjointUtils.F90:1374-1562) in the configuration PCBJACOBI (= PCASM with
 // overlap 0), one subdomain per structured block, sub-preconditioner ILU with 0 levels in the natural ordering (k, j, i with i
 // fastest) on BAIJ blocks of size nState.  A column on a halo cell, with or without a donor, is not part of a subdomain.
-// Out of scope: ILU(k > 0) and the RCM ordering (the reference's defaults), ASM overlap and couplings across blocks, the
-// pseudo-time diagonal term of ANK, GMRES across ranks, a matrix-free operator inside the solver.
+// Out of scope: ILU(k > 0) and the RCM ordering (the reference's defaults), ASM overlap and couplings across blocks, GMRES across
+// ranks.  (The pseudo-time diagonal term of ANK and the matrix-free operator: adflow_gpu_ank_pc_setup / _ank_solve, kernels_ank.hip.)
 //
 // Arithmetic: eliminating row c of a 7-point stencil in natural order with the rows c - e_i, c - e_j, c - e_k creates no entry
 // inside the pattern but on the diagonal, so
@@ -97,6 +97,22 @@ __global__ __launch_bounds__(PC_T) void k_pc_factor(PcTab T, int q0, int cnt)
         GPTR(const double) A = (GPTR(const double))(b.jac + (long)T.sten[6] * (NS * NS) * b.nbox);
 #pragma unroll
         for (int e = 0; e < NS * NS; ++e) D[e] = ldg(A, c8 + e * nb8);
+    }
+    if constexpr (NS >= 5) {
+        // adflow_gpu_ank_pc_setup: dRdwPre + timeStepMat (FormJacobianANK, NKSolvers.F90:1996-1998), T = dtInv S formed from the
+        // compact storage of kernels_ank.hip (PETSc cell order)
+        if (T.tsm) {
+            const long m = T.vec[q];
+            const double dtInv = T.tsm[m], rho = T.tsm[N + m];
+            PCE(D, 0, 0) += dtInv;
+            PCE(D, 4, 4) += dtInv;
+#pragma unroll
+            for (int l = 1; l < 4; ++l) {
+                PCE(D, l, 0) += dtInv * T.tsm[(l + 1) * N + m];
+                PCE(D, l, l) += dtInv * rho;
+            }
+            if (NS > 5) PCE(D, NS - 1, NS - 1) += dtInv * T.turbDiag;
+        }
     }
     for (int s = 0; s < 3; ++s) {
         const int n = T.nbr[(long)s * N + q];

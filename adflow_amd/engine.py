@@ -224,6 +224,94 @@ class Engine:
                                                       ctypes.byref(its), ctypes.byref(r0), ctypes.byref(rn)))
         return int(its.value), float(r0.value), float(rn.value)
 
+    # ---- the flow update of ANKStep (NKSolvers.F90:3629-4112); vectors carry nState = nw (coupled) or 5 variables per cell ------
+    @staticmethod
+    def _ankFlags(coupled=False, dissApprox=False, viscApprox=False, useBlockettes=False):
+        return (capi.ANK_COUPLED if coupled else 0) | (capi.RES_DISS_APPROX if dissApprox else 0) \
+            | (capi.RES_VISC_APPROX if viscApprox else 0) | (capi.RES_UPWIND_FIRST_ORDER if useBlockettes else 0)
+
+    def ankNState(self, coupled=False):
+        return next(b.nw for (nn, lv, sps), b in self.blocks.items() if lv == 1) if coupled else 5
+
+    def ankSetW(self, w, coupled=False):
+        """setWANK(wVec, 1, nState): w(1:nState) of the owned cells, no clipping"""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        self._chk(self.lib.adflow_gpu_ank_set_w(w.ctypes.data, w.size, self._ankFlags(coupled)))
+
+    def ankGetR(self, coupled=False):
+        """setRVecANK (decoupled) / setRVec (coupled) of the residual on the device"""
+        n = self.ankNState(coupled) * sum(b.nx * b.ny * b.nz for (nn, lv, sps), b in self.blocks.items() if lv == 1)
+        r = np.zeros(n)
+        self._chk(self.lib.adflow_gpu_ank_get_r(r.ctypes.data, n, self._ankFlags(coupled)))
+        return r
+
+    def ankTimeStep(self, cfl, turbCFLScale=1.0, coupled=False, level=1):
+        """computeTimeStepMat for ANK_charTimeStepType = 'None' from the dtl on the device"""
+        self._chk(self.lib.adflow_gpu_ank_time_step(level, float(cfl), float(turbCFLScale), self._ankFlags(coupled)))
+
+    def ankTimeStepBlocks(self, nn=1, coupled=False, level=1):
+        """the dense blocks of T of block nn, (nState, nState, nx, ny, nz)"""
+        blk = self.blocks[(nn, level, 1)]
+        ns = self.ankNState(coupled)
+        out = np.zeros((ns, ns, blk.nx, blk.ny, blk.nz), order="F")
+        self._chk(self.lib.adflow_gpu_ank_download_time_step(nn, out.ctypes.data))
+        return out
+
+    def ankPcSetup(self, level=1):
+        """ILU(0) of dRdwPre + timeStepMat into the factor slot of pcSetup (FormJacobianANK)"""
+        self._chk(self.lib.adflow_gpu_ank_pc_setup(level))
+
+    def ankSetBase(self, w, coupled=False, dissApprox=False, viscApprox=False, useBlockettes=False):
+        """formFunction_mf(wVec, baseRes) + MatMFFDSetBase: the state from w, r0 = R(w) kept on the device"""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        self._chk(self.lib.adflow_gpu_ank_set_base(w.ctypes.data, w.size, self._ankFlags(coupled, dissApprox, viscApprox, useBlockettes)))
+
+    def ankMult(self, v):
+        """y = (R(w + h v) - r0) / h + T v with the MATMFFD_DS step h; the device state is the perturbed one afterwards"""
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        y = np.zeros_like(v)
+        self._chk(self.lib.adflow_gpu_ank_mult(v.ctypes.data, y.ctypes.data, v.size))
+        return y
+
+    def ankMultDev(self, d_v: int, d_y: int, n: int):
+        self._chk(self.lib.adflow_gpu_ank_mult_dev(ctypes.c_void_p(d_v), ctypes.c_void_p(d_y), int(n)))
+
+    def ankLastH(self) -> float:
+        h = ctypes.c_double(0.0)
+        self._chk(self.lib.adflow_gpu_ank_last_h(ctypes.byref(h)))
+        return float(h.value)
+
+    def ankSolve(self, b, level=1, restart=50, maxIts=200, rtol=1e-8, atol=0.0):
+        """KSPSolve(ANK_KSP, rVec, deltaW): GMRES on ankMult with the factor slot as right preconditioner, from zero; returns
+        (x, iterations, initial residual norm, true residual norm of x)"""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        x = np.zeros_like(b)
+        its, r0, rn = ctypes.c_int(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        self._chk(self.lib.adflow_gpu_ank_solve(level, b.ctypes.data, x.ctypes.data, b.size, int(restart), int(maxIts), float(rtol),
+                                                float(atol), ctypes.byref(its), ctypes.byref(r0), ctypes.byref(rn)))
+        return x, int(its.value), float(r0.value), float(rn.value)
+
+    def ankSolveDev(self, d_b: int, d_x: int, n: int, level=1, restart=50, maxIts=200, rtol=1e-8, atol=0.0):
+        its, r0, rn = ctypes.c_int(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        self._chk(self.lib.adflow_gpu_ank_solve_dev(level, ctypes.c_void_p(d_b), ctypes.c_void_p(d_x), int(n), int(restart), int(maxIts),
+                                                    float(rtol), float(atol), ctypes.byref(its), ctypes.byref(r0), ctypes.byref(rn)))
+        return int(its.value), float(r0.value), float(rn.value)
+
+    def ankPhysicalityCheck(self, w, dw, lambda0=1.0, coupled=False, physLSTol=0.2, physLSTolTurb=0.99, stepFactor=1.0, stepMin=0.01):
+        """physicalityCheckANK: returns (lambda, dw with the clipped turbulence entries)"""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        dw = np.array(dw, dtype=np.float64, order="C", copy=True)
+        lam = ctypes.c_double(float(lambda0))
+        self._chk(self.lib.adflow_gpu_ank_physicality_check(w.ctypes.data, dw.ctypes.data, w.size, self._ankFlags(coupled), float(physLSTol),
+                                                            float(physLSTolTurb), float(stepFactor), float(stepMin), ctypes.byref(lam)))
+        return float(lam.value), dw
+
+    def ankRelease(self) -> int:
+        """frees T, the base vectors and the sums; returns the bytes released"""
+        n = ctypes.c_int64(0)
+        self._chk(self.lib.adflow_gpu_ank_release(ctypes.byref(n)))
+        return int(n.value)
+
     def blocketteRes(self, level=1, updateIntermed=True, flowRes=True, turbRes=True, dissApprox=False, viscApprox=False,
                      useBlockettes=False, halo=False, closures=False):
         """halo: also the part of blocketteRes in front of the core -- boundary conditions and whalo2 (ADFLOW_RES_HALO);

@@ -382,6 +382,118 @@ module adflowGpuShim
             integer(c_int), intent(out) :: its
             real(c_double), intent(out) :: rnorm0, rnorm
         end function
+        ! the flow update of ANKStep (NKSolvers.F90:3629-4112): setWANK / setRVecANK, computeTimeStepMat ('None'), the ILU(0) of
+        ! dRdwPre + timeStepMat, the matrix-free operator of FormFunction_mf under MatMFFD, KSPSolve, physicalityCheckANK.
+        ! flags: ADFLOW_ANK_COUPLED = 256 (nState = nw, else 5) plus the ADFLOW_RES_*_APPROX flags of the residual; one rank only
+        integer(c_int) function adflow_gpu_ank_set_w(w, n, flags) bind(C, name="adflow_gpu_ank_set_w")
+            import :: c_int, c_long, c_double
+            real(c_double), intent(in) :: w(*)
+            integer(c_long), value :: n
+            integer(c_int), value :: flags
+        end function
+        integer(c_int) function adflow_gpu_ank_set_w_dev(w, n, flags) bind(C, name="adflow_gpu_ank_set_w_dev")
+            import :: c_int, c_long, c_ptr
+            type(c_ptr), value :: w
+            integer(c_long), value :: n
+            integer(c_int), value :: flags
+        end function
+        integer(c_int) function adflow_gpu_ank_get_r(r, n, flags) bind(C, name="adflow_gpu_ank_get_r")
+            import :: c_int, c_long, c_double
+            real(c_double), intent(out) :: r(*)
+            integer(c_long), value :: n
+            integer(c_int), value :: flags
+        end function
+        integer(c_int) function adflow_gpu_ank_get_r_dev(r, n, flags) bind(C, name="adflow_gpu_ank_get_r_dev")
+            import :: c_int, c_long, c_ptr
+            type(c_ptr), value :: r
+            integer(c_long), value :: n
+            integer(c_int), value :: flags
+        end function
+        integer(c_int) function adflow_gpu_ank_time_step(level, cfl, turbCFLScale, flags) bind(C, name="adflow_gpu_ank_time_step")
+            import :: c_int, c_double
+            integer(c_int), value :: level, flags
+            real(c_double), value :: cfl, turbCFLScale
+        end function
+        integer(c_int) function adflow_gpu_ank_download_time_step(nn, blocks) bind(C, name="adflow_gpu_ank_download_time_step")
+            import :: c_int, c_double
+            integer(c_int), value :: nn
+            real(c_double), intent(out) :: blocks(*)
+        end function
+        integer(c_int) function adflow_gpu_ank_pc_setup(level) bind(C, name="adflow_gpu_ank_pc_setup")
+            import :: c_int
+            integer(c_int), value :: level
+        end function
+        integer(c_int) function adflow_gpu_ank_set_base(w, n, flags) bind(C, name="adflow_gpu_ank_set_base")
+            import :: c_int, c_long, c_double
+            real(c_double), intent(in) :: w(*)
+            integer(c_long), value :: n
+            integer(c_int), value :: flags
+        end function
+        integer(c_int) function adflow_gpu_ank_set_base_dev(w, n, flags) bind(C, name="adflow_gpu_ank_set_base_dev")
+            import :: c_int, c_long, c_ptr
+            type(c_ptr), value :: w
+            integer(c_long), value :: n
+            integer(c_int), value :: flags
+        end function
+        integer(c_int) function adflow_gpu_ank_mult(v, y, n) bind(C, name="adflow_gpu_ank_mult")
+            import :: c_int, c_long, c_double
+            real(c_double), intent(in) :: v(*)
+            real(c_double), intent(out) :: y(*)
+            integer(c_long), value :: n
+        end function
+        integer(c_int) function adflow_gpu_ank_mult_dev(v, y, n) bind(C, name="adflow_gpu_ank_mult_dev")
+            import :: c_int, c_long, c_ptr
+            type(c_ptr), value :: v, y
+            integer(c_long), value :: n
+        end function
+        integer(c_int) function adflow_gpu_ank_last_h(h) bind(C, name="adflow_gpu_ank_last_h")
+            import :: c_int, c_double
+            real(c_double), intent(out) :: h
+        end function
+        integer(c_int) function adflow_gpu_ank_solve(level, b, x, n, restart, maxIts, rtol, atol, its, rnorm0, rnorm) &
+            bind(C, name="adflow_gpu_ank_solve")
+            import :: c_int, c_long, c_double
+            integer(c_int), value :: level, restart, maxIts
+            real(c_double), intent(in) :: b(*)
+            real(c_double), intent(out) :: x(*)
+            integer(c_long), value :: n
+            real(c_double), value :: rtol, atol
+            integer(c_int), intent(out) :: its
+            real(c_double), intent(out) :: rnorm0, rnorm
+        end function
+        integer(c_int) function adflow_gpu_ank_solve_dev(level, b, x, n, restart, maxIts, rtol, atol, its, rnorm0, rnorm) &
+            bind(C, name="adflow_gpu_ank_solve_dev")
+            import :: c_int, c_ptr, c_long, c_double
+            integer(c_int), value :: level, restart, maxIts
+            type(c_ptr), value :: b, x
+            integer(c_long), value :: n
+            real(c_double), value :: rtol, atol
+            integer(c_int), intent(out) :: its
+            real(c_double), intent(out) :: rnorm0, rnorm
+        end function
+        integer(c_int) function adflow_gpu_ank_physicality_check(w, dw, n, flags, physLSTol, physLSTolTurb, stepFactor, stepMin, &
+                                                                 lambda) bind(C, name="adflow_gpu_ank_physicality_check")
+            import :: c_int, c_long, c_double
+            real(c_double), intent(in) :: w(*)
+            real(c_double), intent(inout) :: dw(*)
+            integer(c_long), value :: n
+            integer(c_int), value :: flags
+            real(c_double), value :: physLSTol, physLSTolTurb, stepFactor, stepMin
+            real(c_double), intent(inout) :: lambda
+        end function
+        integer(c_int) function adflow_gpu_ank_physicality_check_dev(w, dw, n, flags, physLSTol, physLSTolTurb, stepFactor, &
+                                                                     stepMin, lambda) bind(C, name="adflow_gpu_ank_physicality_check_dev")
+            import :: c_int, c_long, c_ptr, c_double
+            type(c_ptr), value :: w, dw
+            integer(c_long), value :: n
+            integer(c_int), value :: flags
+            real(c_double), value :: physLSTol, physLSTolTurb, stepFactor, stepMin
+            real(c_double), intent(inout) :: lambda
+        end function
+        integer(c_int) function adflow_gpu_ank_release(bytes) bind(C, name="adflow_gpu_ank_release")
+            import :: c_int, c_int64_t
+            integer(c_int64_t), intent(out) :: bytes
+        end function
         integer(c_int) function adflow_gpu_reference_shock_sensor(level) bind(C, name="adflow_gpu_reference_shock_sensor")
             import :: c_int
             integer(c_int), value :: level

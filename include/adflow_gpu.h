@@ -493,8 +493,8 @@ int adflow_gpu_jacobian_mult_dev(int level, int transpose, const double* d_x, do
  * hyperplanes of the factor and the bytes it holds; an error without a factor.
  * Vectors as for adflow_gpu_jacobian_mult (n = nState x owned cells of the level); host pointers, or device pointers for the _dev
  * form, which honours adflow_gpu_set_async.  r and z must differ.  State, residual and matrix are not touched.
- * Out of scope: ILU(k > 0) and the RCM ordering (the reference's defaults), ASM overlap and couplings across blocks, the
- * pseudo-time diagonal term of ANK. */
+ * Out of scope: ILU(k > 0) and the RCM ordering (the reference's defaults), ASM overlap and couplings across blocks.  (The
+ * pseudo-time diagonal term of ANK: adflow_gpu_ank_pc_setup below, into the same factor slot.) */
 int adflow_gpu_pc_setup(int level);
 int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes);
 int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, long n);
@@ -510,13 +510,90 @@ int adflow_gpu_pc_release(int64_t* bytes);
  * useGuess != 0: x holds the initial guess (else it is ignored and the solve starts from 0).  *its: iterations done; *rnorm0: the
  * initial residual norm; *rnorm: the TRUE residual ||b - A x|| of the returned x, computed once at the end (each may be NULL).
  * Errors: no matrix or no factor, nState of factor and matrix differ, wrong level or n, b == x, and more than one rank in the
- * communicator of adflow_gpu_comm_init -- the dot products are not reduced across ranks (out of scope, as is a matrix-free
- * operator): such a host keeps its KSP and calls the two _dev operators.  Work space of restart + 4 vectors is allocated for the
- * call.  State, residual, matrix and factor are not touched. */
+ * communicator of adflow_gpu_comm_init -- the dot products are not reduced across ranks (out of scope): such a host keeps its KSP
+ * and calls the two _dev operators.  (The same solver on a matrix-free operator: adflow_gpu_ank_solve below.)  Work space of
+ * restart + 4 vectors is allocated for the call.  State, residual, matrix and factor are not touched. */
 int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x, long n, int restart, int maxIts, double rtol,
                            double atol, int useGuess, int* its, double* rnorm0, double* rnorm);
 int adflow_gpu_gmres_solve_dev(int level, int transpose, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol,
                                double atol, int useGuess, int* its, double* rnorm0, double* rnorm);
+
+/* ---- the flow update of the approximate Newton-Krylov step, NKSolver::ANKStep (src/NKSolver/NKSolvers.F90:3629-4112) --------------
+ * Everything acts on the level-1 blocks of the process.  Vectors: the layout of adflow_gpu_set_w_vec (block, k, j, i, variable
+ * fastest) with nState variables per owned cell, n = nState x owned cells: nState = nw with ADFLOW_ANK_COUPLED, else 5 -- the flow
+ * variables only, turbulence frozen, the reference's default ANK_coupled = .False. .  Host pointers, or device pointers for the _dev
+ * forms, which honour adflow_gpu_set_async.
+ *   adflow_gpu_ank_set_w   setWANK(wVec, 1, nState) (:2975-3011): w(i,j,k,1:nState) of the owned cells and nothing else.  Unlike setW
+ *                          it does not clip the turbulence variable; nuTilde of a RANS block stays as it is without
+ *                          ADFLOW_ANK_COUPLED.  Invalidates what adflow_gpu_set_w_vec invalidates.
+ *   adflow_gpu_ank_get_r   setRVecANK (:2895-2933): dw / volRef of the flow variables, no turbResScale; with ADFLOW_ANK_COUPLED
+ *                          setRVec (:1262-1329).
+ *   adflow_gpu_ank_time_step   computeTimeStepMat / computeTimeStepBlock (:2041-2329) for ANK_charTimeStepType = 'None' (the default):
+ *                          per owned cell of `level`  T = dtInv S,  dtInv = 1 / (cfl dtl volRef),  S = the state-to-conservative block
+ *                          (ones on rho and rhoE, S(ivx..ivz, iRho) = u, v, w, S(ivx..ivz, ivx..ivz) = rho on the diagonal; with
+ *                          ADFLOW_ANK_COUPLED also S(nt1, nt1) = turbResScale / turbCFLScale).  dtl is read as it stands on the device:
+ *                          the caller refreshes it with adflow_gpu_time_step or ADFLOW_RES_UPDATE_INTERMED (see there).  No dense block
+ *                          is stored: dtInv and rho, u, v, w of the state T was formed from (40 B per cell); products with T and the
+ *                          shift of the diagonal are formed on the fly.  adflow_gpu_ank_download_time_step hands out the dense
+ *                          blocks of block nn, (nState, nState, nx, ny, nz) column-major: timeStepMat for a host that wants it.
+ *   adflow_gpu_ank_pc_setup    the ILU(0) of dRdwPre + timeStepMat (FormJacobianANK, :1996-1998): adflow_gpu_pc_setup with T added to
+ *                          the diagonal blocks as the factorisation reads them.  It lands in the same factor slot:
+ *                          adflow_gpu_pc_apply, _pc_info and _pc_release serve it unchanged.  Errors beside those of
+ *                          adflow_gpu_pc_setup: no T, T's nState differs from the matrix's (a coupled T against an
+ *                          ADFLOW_JAC_FROZEN_TURB matrix), T formed on another level.
+ *   adflow_gpu_ank_set_base    formFunction_mf(wVec, baseRes) + MatMFFDSetBase (:3906-3908): sets the state from w (as
+ *                          adflow_gpu_ank_set_w), evaluates the residual and keeps w and r0 = R(w) on the device.  flags:
+ *                          ADFLOW_ANK_COUPLED plus ADFLOW_RES_DISS_APPROX, _VISC_APPROX, _UPWIND_FIRST_ORDER, passed to the residual
+ *                          = blocketteRes(useDissApprox, useViscApprox, useTurbRes = ANK_coupled, useStoreWall = F) (:2500).  The
+ *                          caller freezes the sensor first (adflow_gpu_reference_shock_sensor), as ANKStep:3859 does.
+ *   adflow_gpu_ank_mult    y = (R(w + h v) - r0) / h + T v: what MatMFFD computes from FormFunction_mf (:2468-2538, R(u) + T u), the
+ *                          linear part taken analytically instead of differenced.  h is PETSc's default MATMFFD_DS step:
+ *                          s = w.v, d = |v|_1, q = |v|_2^2; |s| < umin d: s = +-umin d (the sign of s, + for zero);
+ *                          h = errRel s / q, errRel = 1.490116119384766e-08, umin = 1e-6.  h is formed and read on the device and never
+ *                          visits the host (adflow_gpu_ank_last_h downloads it, for tests): an application has no host
+ *                          synchronisation of its own.  v = 0 gives y = 0; the host-pointer form then evaluates no residual, the
+ *                          _dev form cannot know without a synchronisation and evaluates R(w).  v and y must differ.  AFTER A PRODUCT
+ *                          THE DEVICE STATE IS THE PERTURBED ONE w + h v, as in the reference (physicalityCheckANK notes it,
+ *                          :3043-3046): call adflow_gpu_ank_set_w before anything that reads the state.
+ *   adflow_gpu_ank_solve   KSPSolve(ANK_KSP, rVec, deltaW) (:3912): the GMRES of adflow_gpu_gmres_solve with adflow_gpu_ank_mult as
+ *                          operator and the factor slot as right preconditioner; starts from zero, never transposed.  Errors: those
+ *                          of adflow_gpu_gmres_solve (more than one rank included), no base, no T, a factor whose nState differs.
+ *   adflow_gpu_ank_physicality_check   physicalityCheckANK (:3013-3210, real mode; eps = 1e-25 of constants.F90): *lambda comes in as the
+ *                          start value and goes out as the minimum over the cells of |w / (dw + eps)| physLSTol for density and
+ *                          energy.  With ADFLOW_ANK_COUPLED the turbulence rule: the ratio (w / (dw + eps)) physLSTolTurb is signed; a
+ *                          ratio below stepFactor stepMin does not limit the step, and if it is positive dw of that entry is
+ *                          overwritten with w physLSTolTurb.  A NaN gives *lambda = 0.  More than one rank is an error: the
+ *                          mpi_allreduce is the host's.  Synchronous (lambda goes to the host).
+ * The rest of the step is the host's, on its device vectors: rVec = adflow_gpu_ank_get_r of the base state, deltaW from
+ * adflow_gpu_ank_solve, lambda from adflow_gpu_ank_physicality_check, the `lambda < stepMin` rule, VecAXPY(wVec, -lambda, deltaW),
+ * adflow_gpu_ank_set_w(wVec) + residual for the backtracking, the CFL ramp; INTEGRATION.md has the call sites.
+ * Lifetime: T, the base vectors and the sums are released by adflow_gpu_ank_release (*bytes, may be NULL: what was released),
+ * adflow_gpu_block_release and adflow_gpu_release_all; adflow_gpu_release_workspace does not touch them.
+ * Out of scope: approxSA (the library has no such switch: the coupled operator uses the full SA source; the decoupled operator has
+ * no SA residual and is exact in this respect); the turbulence KSP of ANK (FormFunction_mf_turb, physicalityCheckANKTurb); the
+ * Turkel and VLR time-step types; ANK_precondType = 'mg'; more than one rank; ILU(k > 0), RCM and ASM overlap, as above. */
+enum { ADFLOW_ANK_COUPLED = 256u };
+int adflow_gpu_ank_set_w(const double* w, long n, unsigned flags);
+int adflow_gpu_ank_set_w_dev(const double* d_w, long n, unsigned flags);
+int adflow_gpu_ank_get_r(double* r, long n, unsigned flags);
+int adflow_gpu_ank_get_r_dev(double* d_r, long n, unsigned flags);
+int adflow_gpu_ank_time_step(int level, double cfl, double turbCFLScale, unsigned flags);
+int adflow_gpu_ank_download_time_step(int nn, double* blocks);
+int adflow_gpu_ank_pc_setup(int level);
+int adflow_gpu_ank_set_base(const double* w, long n, unsigned flags);
+int adflow_gpu_ank_set_base_dev(const double* d_w, long n, unsigned flags);
+int adflow_gpu_ank_mult(const double* v, double* y, long n);
+int adflow_gpu_ank_mult_dev(const double* d_v, double* d_y, long n);
+int adflow_gpu_ank_last_h(double* h);
+int adflow_gpu_ank_solve(int level, const double* b, double* x, long n, int restart, int maxIts, double rtol, double atol, int* its,
+                         double* rnorm0, double* rnorm);
+int adflow_gpu_ank_solve_dev(int level, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol, double atol, int* its,
+                             double* rnorm0, double* rnorm);
+int adflow_gpu_ank_physicality_check(const double* w, double* dw, long n, unsigned flags, double physLSTol, double physLSTolTurb,
+                                     double stepFactor, double stepMin, double* lambda);
+int adflow_gpu_ank_physicality_check_dev(const double* d_w, double* d_dw, long n, unsigned flags, double physLSTol, double physLSTolTurb,
+                                         double stepFactor, double stepMin, double* lambda);
+int adflow_gpu_ank_release(int64_t* bytes);
 
 #ifdef __cplusplus
 }
