@@ -136,6 +136,7 @@ BC_CALLBACK = ctypes.CFUNCTYPE(None, c_int, c_int)
 JAC_PC, JAC_FROZEN_TURB, JAC_TURB_ONLY, JAC_VISC_PC, JAC_USE_AD = 1, 2, 4, 8, 16     # include/adflow_gpu.h
 RES_UPDATE_INTERMED, RES_FLOW, RES_TURB, RES_CLOSURES, RES_HALO = 1, 2, 4, 8, 16
 RES_DISS_APPROX, RES_VISC_APPROX, RES_UPWIND_FIRST_ORDER, ANK_COUPLED = 32, 64, 128, 256
+ANK_TURB, RES_APPROX_SA, RES_TURB_FIRST_ORDER, JAC_APPROX_SA = 512, 1024, 2048, 32
 
 EXPORTS = [
     "adflow_gpu_init", "adflow_gpu_finalize", "adflow_gpu_last_error", "adflow_gpu_device_name",
@@ -155,12 +156,13 @@ EXPORTS = [
     "adflow_gpu_wall_distance_register", "adflow_gpu_update_wall_distances",
     "adflow_gpu_fd_jacobian", "adflow_gpu_release_workspace", "adflow_gpu_selftest_math", "adflow_gpu_jacobian_info", "adflow_gpu_download_jacobian", "adflow_gpu_download_jacobian_rows",
     "adflow_gpu_jacobian_mult", "adflow_gpu_jacobian_mult_dev",
-    "adflow_gpu_pc_setup", "adflow_gpu_pc_info", "adflow_gpu_pc_apply", "adflow_gpu_pc_apply_dev", "adflow_gpu_pc_release",
+    "adflow_gpu_pc_setup", "adflow_gpu_pc_info", "adflow_gpu_pc_apply", "adflow_gpu_pc_apply_dev", "adflow_gpu_pc_release", "adflow_gpu_pc_select",
     "adflow_gpu_gmres_solve", "adflow_gpu_gmres_solve_dev",
     "adflow_gpu_ank_set_w", "adflow_gpu_ank_set_w_dev", "adflow_gpu_ank_get_r", "adflow_gpu_ank_get_r_dev", "adflow_gpu_ank_time_step",
     "adflow_gpu_ank_download_time_step", "adflow_gpu_ank_pc_setup", "adflow_gpu_ank_set_base", "adflow_gpu_ank_set_base_dev",
     "adflow_gpu_ank_mult", "adflow_gpu_ank_mult_dev", "adflow_gpu_ank_last_h", "adflow_gpu_ank_solve", "adflow_gpu_ank_solve_dev",
     "adflow_gpu_ank_physicality_check", "adflow_gpu_ank_physicality_check_dev", "adflow_gpu_ank_release",
+    "adflow_gpu_ank_download_time_step_turb", "adflow_gpu_ank_unsteady_res", "adflow_gpu_ank_unsteady_res_dev", "adflow_gpu_ank_select_base",
     "adflow_gpu_event_record", "adflow_gpu_event_elapsed_ms", "adflow_gpu_sync", "adflow_gpu_set_async",
     "adflow_gpu_abi_sizes", "adflow_gpu_set_tuning", "adflow_gpu_march_stats",
 ]
@@ -240,6 +242,11 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     for f in (lib.adflow_gpu_ank_physicality_check, lib.adflow_gpu_ank_physicality_check_dev):
         f.argtypes = [c_void_p, c_void_p, ctypes.c_long, c_uint, c_double, c_double, c_double, c_double, POINTER(c_double)]
     lib.adflow_gpu_ank_release.argtypes = [POINTER(ctypes.c_int64)]
+    lib.adflow_gpu_ank_download_time_step_turb.argtypes = [c_int, c_void_p, c_uint]
+    for f in (lib.adflow_gpu_ank_unsteady_res, lib.adflow_gpu_ank_unsteady_res_dev):
+        f.argtypes = [c_void_p, c_double, c_void_p, ctypes.c_long, c_uint, POINTER(c_double)]
+    lib.adflow_gpu_pc_select.argtypes = [c_int]
+    lib.adflow_gpu_ank_select_base.argtypes = [c_uint]
     lib.adflow_gpu_set_tuning.argtypes = [c_char_p, c_int]
     lib.adflow_gpu_abi_sizes.argtypes = [POINTER(c_int), POINTER(c_int)]
     lib.adflow_gpu_rk_smooth.argtypes = [c_int]

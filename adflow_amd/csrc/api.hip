@@ -608,7 +608,7 @@ static void bc_plan_drop(int level);
 static void bc_plan_drop_all();
 static void ad_cache_drop();      // the cached dual arrays of the forward-mode assembly refer to the blocks
 static int64_t jm_release();      // ... and so do the scratch arrays of the matrix products (adflow_gpu_jacobian_mult)
-static int64_t pc_release();      // ... and the block ILU(0) factor (adflow_gpu_pc_setup)
+static int64_t pc_release_all();  // ... and the block ILU(0) factors of both slots (adflow_gpu_pc_setup, adflow_gpu_pc_select)
 static int64_t ank_release();     // ... and the pseudo-time term, base vectors and sums of the ANK operator (adflow_gpu_ank_*)
 static bool g_jac_valid = false; // adflow_gpu_fd_jacobian left a matrix on the blocks of level g_jac_level
 static int g_jac_level = 0;
@@ -621,7 +621,7 @@ int adflow_gpu_block_release(int nn, int level, int sps)
     bc_plan_drop(level);
     ad_cache_drop();
     (void)jm_release();
-    (void)pc_release();
+    (void)pc_release_all();
     (void)ank_release();
     for (void* p : it->second->allocs) (void)hipFree(p);
     if (it->second->jac_raw) (void)hipFree(it->second->jac_raw);
@@ -639,7 +639,7 @@ int adflow_gpu_release_all(void)
     bc_plan_drop_all();
     ad_cache_drop();
     (void)jm_release();
-    (void)pc_release();
+    (void)pc_release_all();
     (void)ank_release();
     for (auto& kv : g_blocks) {
         for (void* p : kv.second->allocs) (void)hipFree(p);
@@ -1061,6 +1061,7 @@ static KParams res_kparams(int level, unsigned flags)
     if (level == 1 && g_rvec_target) { kp.rvec = g_rvec_target; kp.rvecTurbScale = g_opts.turbResScale; }
     kp.dissApprox = (flags & ADFLOW_RES_DISS_APPROX) ? 1 : 0;
     if (kp.dissApprox && (flags & ADFLOW_RES_UPWIND_FIRST_ORDER)) kp.lumpedDiss = 1;   // blockette.F90:643
+    kp.approxSA = (flags & ADFLOW_RES_APPROX_SA) ? 1 : 0;
     return kp;
 }
 
@@ -1296,9 +1297,19 @@ static int block_res_split_enqueue(int level, unsigned flags, const KParams& kp,
     return 0;
 }
 
+namespace {
+// ADFLOW_RES_TURB_FIRST_ORDER: orderTurb = firstOrder for one evaluation (NKSolvers.F90:3411-3412, :3855-3856), restored on every exit
+struct OrderTurbGuard {
+    const int was;
+    explicit OrderTurbGuard(bool firstOrder) : was(g_opts.orderTurb) { if (firstOrder) g_opts.orderTurb = 1; }
+    ~OrderTurbGuard() { g_opts.orderTurb = was; }
+};
+}  // namespace
+
 static int block_res_enqueue(int level, unsigned flags)
 {
     if (need_ready()) return 1;
+    OrderTurbGuard orderGuard((flags & ADFLOW_RES_TURB_FIRST_ORDER) != 0);
     phase_mark(0);
     KParams kp = res_kparams(level, flags);
     const bool viscApprox = (flags & ADFLOW_RES_VISC_APPROX) != 0;
@@ -1668,6 +1679,7 @@ static KParams ad_kparams(int level, unsigned resFlags)
     kp.onlyRadii = 1;
     kp.coarseInit = 0;
     kp.dissApprox = (resFlags & ADFLOW_RES_DISS_APPROX) ? 1 : 0;
+    kp.approxSA = (resFlags & ADFLOW_RES_APPROX_SA) ? 1 : 0;
     return kp;
 }
 static bool ad_visc_approx(unsigned resFlags, bool viscPC) { return (resFlags & ADFLOW_RES_VISC_APPROX) != 0 && !viscPC; }
@@ -1758,7 +1770,7 @@ int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
 {
     if (need_ready()) return 1;
     SnapRequestGuard snapGuard;        // no exit leaves the request standing
-    if (flags & ~(ADFLOW_JAC_PC | ADFLOW_JAC_FROZEN_TURB | ADFLOW_JAC_TURB_ONLY | ADFLOW_JAC_VISC_PC | ADFLOW_JAC_USE_AD))
+    if (flags & ~(ADFLOW_JAC_PC | ADFLOW_JAC_FROZEN_TURB | ADFLOW_JAC_TURB_ONLY | ADFLOW_JAC_VISC_PC | ADFLOW_JAC_USE_AD | ADFLOW_JAC_APPROX_SA))
         return fail("fd_jacobian: unknown flags 0x%x", flags);
     const bool useAD = (flags & ADFLOW_JAC_USE_AD) != 0;
     if (!useAD && !(delta > 0.0)) return fail("fd_jacobian: delta must be positive");     // forward mode has no step size
@@ -1776,7 +1788,7 @@ int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
     if ((flags & ADFLOW_JAC_TURB_ONLY) && !rans) return fail("fd_jacobian: ADFLOW_JAC_TURB_ONLY needs the RANS equations");
     if ((flags & ADFLOW_JAC_TURB_ONLY) && (flags & ADFLOW_JAC_FROZEN_TURB)) return fail("fd_jacobian: TURB_ONLY and FROZEN_TURB exclude each other");
     JacSpec J;
-    jac_spec(flags & ~ADFLOW_JAC_USE_AD, viscous, rans, &J);
+    jac_spec(flags & ~(ADFLOW_JAC_USE_AD | ADFLOW_JAC_APPROX_SA), viscous, rans, &J);
     const int ncomp = J.nStencil * J.nState * J.nState;
     int rc = for_level(level, [&](Block* b) {
         if (!b->wref) {
@@ -1816,6 +1828,7 @@ int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
     if (!(flags & ADFLOW_JAC_TURB_ONLY)) resFlags |= ADFLOW_RES_FLOW;
     const bool turbRes = rans && !(flags & ADFLOW_JAC_FROZEN_TURB);
     if (turbRes) resFlags |= ADFLOW_RES_TURB;
+    if (turbRes && (flags & ADFLOW_JAC_APPROX_SA)) resFlags |= ADFLOW_RES_APPROX_SA;     // FormJacobianANK:1978, FormJacobianANKTurb:2364
     if (flags & ADFLOW_JAC_PC) {
         g_lumped = 1;
         g_opts.acousticScaleFactor = 1.0;
@@ -4010,27 +4023,46 @@ struct PcFactor {
     std::vector<int> planeStart;      // first position of every hyperplane in the order of the factor, and the end
     PcTab tab;
 };
-PcFactor g_pc;
+PcFactor g_pc_slots[2];              // adflow_gpu_pc_select: e.g. the flow factor and the turbulence factor of ANK_jacobianLag
+int g_pc_slot = 0;
+static PcFactor& pc_sel() { return g_pc_slots[g_pc_slot]; }
 struct DevBuf {                       // a device allocation that lives as long as one call
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 }  // namespace
 
+// the selected slot
 static int64_t pc_release()
 {
-    const int64_t n = (int64_t)g_pc.bytes;
-    for (void* p : g_pc.raw) (void)hipFree(p);
-    g_pc = PcFactor();
+    const int64_t n = (int64_t)pc_sel().bytes;
+    for (void* p : pc_sel().raw) (void)hipFree(p);
+    pc_sel() = PcFactor();
     return n;
+}
+
+static int64_t pc_release_all()
+{
+    const int was = g_pc_slot;
+    int64_t n = 0;
+    for (g_pc_slot = 0; g_pc_slot < 2; ++g_pc_slot) n += pc_release();
+    g_pc_slot = was;
+    return n;
+}
+
+int adflow_gpu_pc_select(int slot)
+{
+    if (slot < 0 || slot > 1) return fail("pc_select: slot %d; the library keeps two factors, slot 0 and slot 1", slot);
+    g_pc_slot = slot;
+    return 0;
 }
 
 static int pc_alloc(void** p, size_t bytes)
 {
     *p = nullptr;
     HIPCHK(hipMalloc(p, bytes));
-    g_pc.raw.push_back(*p);
-    g_pc.bytes += bytes;
+    pc_sel().raw.push_back(*p);
+    pc_sel().bytes += bytes;
     return 0;
 }
 
@@ -4115,7 +4147,7 @@ static int pc_setup_build(int level, const double* shift = nullptr, double turbD
                     nbr[5 * N + at] = k < q.nz - 1 ? pos[nat + sk] : -1;
                 }
     }
-    PcTab& T = g_pc.tab;
+    PcTab& T = pc_sel().tab;
     memset(&T, 0, sizeof T);
     T.ncell = N;
     for (int q = 0; q < 7; ++q) T.sten[q] = sten[q];
@@ -4148,9 +4180,9 @@ static int pc_setup_build(int level, const double* shift = nullptr, double turbD
                     "level %d); no factor is kept", (int)(loc % hb[s].nx) + 2, (int)(loc / hb[s].nx % hb[s].ny) + 2,
                     (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2, nnOf[s], level);
     }
-    g_pc.level = level; g_pc.nState = nS; g_pc.nPlanes = nPlanes; g_pc.ncell = N;
-    g_pc.planeStart = start;
-    g_pc.valid = true;
+    pc_sel().level = level; pc_sel().nState = nS; pc_sel().nPlanes = nPlanes; pc_sel().ncell = N;
+    pc_sel().planeStart = start;
+    pc_sel().valid = true;
     return 0;
 }
 
@@ -4174,10 +4206,10 @@ int adflow_gpu_pc_setup(int level)
 
 int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes)
 {
-    if (!g_pc.valid) return fail("pc_info: no factor (call adflow_gpu_pc_setup first)");
-    if (nState) *nState = g_pc.nState;
-    if (nPlanes) *nPlanes = g_pc.nPlanes;
-    if (bytes) *bytes = (int64_t)g_pc.bytes;
+    if (!pc_sel().valid) return fail("pc_info: no factor (call adflow_gpu_pc_setup first)");
+    if (nState) *nState = pc_sel().nState;
+    if (nPlanes) *nPlanes = pc_sel().nPlanes;
+    if (bytes) *bytes = (int64_t)pc_sel().bytes;
     return 0;
 }
 
@@ -4192,20 +4224,20 @@ int adflow_gpu_pc_release(int64_t* bytes)
 static int pc_check(const char* who, int level, const double* r, const double* z, long n, bool rows = true)
 {
     if (need_ready()) return 1;
-    if (!g_pc.valid) return fail("%s: no factor (call adflow_gpu_pc_setup first)", who);
-    if (level != g_pc.level) return fail("%s: level %d is not the level of the factor (%d)", who, level, g_pc.level);
+    if (!pc_sel().valid) return fail("%s: no factor (call adflow_gpu_pc_setup first)", who);
+    if (level != pc_sel().level) return fail("%s: level %d is not the level of the factor (%d)", who, level, pc_sel().level);
     if (!r || !z) return fail("%s: %s is NULL", who, !r ? "the right-hand side" : "the result");
     if (r == z) return fail("%s: right-hand side and result are the same vector (not done in place)", who);
-    if (rows && n != g_pc.ncell * g_pc.nState)
+    if (rows && n != pc_sel().ncell * pc_sel().nState)
         return fail("%s: n=%ld but the factor of level %d has %ld rows (nState = %d x %ld owned cells)", who, n, level,
-                    g_pc.ncell * g_pc.nState, g_pc.nState, g_pc.ncell);
+                    pc_sel().ncell * pc_sel().nState, pc_sel().nState, pc_sel().ncell);
     return 0;
 }
 
 int adflow_gpu_pc_apply_dev(int level, int transpose, const double* d_r, double* d_z, long n)
 {
     if (pc_check("pc_apply", level, d_r, d_z, n)) return 1;
-    if (launch_pc_apply(g_pc.tab, g_pc.nState, transpose, g_pc.planeStart, d_r, d_z, g_stream)) return 1;
+    if (launch_pc_apply(pc_sel().tab, pc_sel().nState, transpose, pc_sel().planeStart, d_r, d_z, g_stream)) return 1;
     return sync_and_check();
 }
 
@@ -4214,7 +4246,7 @@ int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, lo
     if (pc_check("pc_apply", level, r, z, n)) return 1;
     if (vec_reserve((size_t)2 * n)) return 1;
     HIPCHK(hipMemcpyAsync(g_vec_dev, r, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (launch_pc_apply(g_pc.tab, g_pc.nState, transpose, g_pc.planeStart, g_vec_dev, g_vec_dev + n, g_stream)) return 1;
+    if (launch_pc_apply(pc_sel().tab, pc_sel().nState, transpose, pc_sel().planeStart, g_vec_dev, g_vec_dev + n, g_stream)) return 1;
     HIPCHK(hipMemcpyAsync(z, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
@@ -4277,7 +4309,7 @@ static int gm_solve(const char* who, const GmOperator& op, int transpose, const 
         bool stop = false;
         for (int j = 0; j < m && !stop; ++j) {
             double* w = V + (size_t)(j + 1) * n;
-            if (launch_pc_apply(g_pc.tab, g_pc.nState, transpose, g_pc.planeStart, V + (size_t)j * n, zt, s)) return 1;
+            if (launch_pc_apply(pc_sel().tab, pc_sel().nState, transpose, pc_sel().planeStart, V + (size_t)j * n, zt, s)) return 1;
             if (op(zt, w)) return 1;
             launch_gm_mgs(w, nullptr, nullptr, V, P[0], nullptr, n, s);
             for (int i = 1; i <= j; ++i)
@@ -4314,7 +4346,7 @@ static int gm_solve(const char* who, const GmOperator& op, int transpose, const 
         }
         for (int i = 0; i < k; ++i) launch_gm_axpby(tv, y[i], V + (size_t)i * n, i == 0 ? 0.0 : 1.0, n, s);
         if (k > 0) {
-            if (launch_pc_apply(g_pc.tab, g_pc.nState, transpose, g_pc.planeStart, tv, zt, s)) return 1;
+            if (launch_pc_apply(pc_sel().tab, pc_sel().nState, transpose, pc_sel().planeStart, tv, zt, s)) return 1;
             launch_gm_axpby(d_x, 1.0, zt, 1.0, n, s);
             zeroX = false;
         }
@@ -4341,10 +4373,10 @@ static int gm_check(int level, const double* b, const double* x, long n, int res
 #endif
     if (!g_jac_valid) return fail("gmres_solve: no assembled Jacobian (call adflow_gpu_fd_jacobian first)");
     if (pc_check("gmres_solve", level, b, x, n, false)) return 1;
-    if (g_jac.nState != g_pc.nState)
-        return fail("gmres_solve: the factor was set up for nState = %d, the assembled matrix has nState = %d", g_pc.nState, g_jac.nState);
+    if (g_jac.nState != pc_sel().nState)
+        return fail("gmres_solve: the factor was set up for nState = %d, the assembled matrix has nState = %d", pc_sel().nState, g_jac.nState);
     if (jm_check(level, b, x, n)) return 1;
-    if (n != g_pc.ncell * g_pc.nState) return fail("gmres_solve: n=%ld but the factor has %ld rows", n, g_pc.ncell * g_pc.nState);
+    if (n != pc_sel().ncell * pc_sel().nState) return fail("gmres_solve: n=%ld but the factor has %ld rows", n, pc_sel().ncell * pc_sel().nState);
     if (restart < 1 || maxIts < 0) return fail("gmres_solve: restart = %d, maxIts = %d", restart, maxIts);
     if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail("gmres_solve: rtol = %g, atol = %g", rtol, atol);
     return 0;
@@ -4374,13 +4406,15 @@ int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x,
     return 0;
 }
 
-// ---- the flow update of the approximate Newton-Krylov step (kernels_ank.hip) ----------------------------------------------------
+// ---- the approximate Newton-Krylov step (kernels_ank.hip) -------------------------------------------------------------------------
 // ANKStep (NKSolvers.F90:3629-4112) up to the linear solve and the step limiter: setWANK / setRVecANK, computeTimeStepMat for
 // ANK_charTimeStepType = 'None', the ILU(0) of dRdwPre + timeStepMat, the matrix-free operator of FormFunction_mf under MatMFFD,
 // KSPSolve and physicalityCheckANK.  Vectors carry nState = nw (ADFLOW_ANK_COUPLED) or 5 variables per owned level-1 cell.
+// ANKTurbSolveKSP (:3337-3627) the same way with ADFLOW_ANK_TURB: one entry per cell, FormFunction_mf_turb, physicalityCheckANKTurb.
+// The flow kind (nState 5 or nw) and the turbulence kind (nState 1) each keep a T and a base; the flag selects one on every entry.
 namespace {
-struct AnkState {
-    bool haveT = false;                // the pseudo-time term: tsm[q N + m], q = 0 dtInv, 1 rho, 2..4 u, v, w (kernels_ank.hip)
+struct AnkKind {
+    bool haveT = false;                // the pseudo-time term: flow tsm[q N + m], q = 0 dtInv, 1 rho, 2..4 u, v, w; turbulence dtInv only
     int tLevel = 0, tNState = 0;
     long tCells = 0;
     double turbDiag = 0.0;
@@ -4390,20 +4424,36 @@ struct AnkState {
     unsigned flags = 0;
     long ncell = 0;
     double *w0 = nullptr, *r0 = nullptr;
-    double* red = nullptr;             // 3 x 256 partial sums, 256 partial minima, 8 scalars: h, 1/h, the three sums; lambda
-    size_t bytesT = 0, bytesBase = 0, bytesRed = 0;
+    size_t bytesT = 0, bytesBase = 0;
+};
+struct AnkState {
+    AnkKind kind[2];                   // 0 flow, 1 turbulence
+    int last = 0;                      // the kind of the base set last: adflow_gpu_ank_mult / _solve / _last_h act on it
+    double* red = nullptr;             // 3 x 256 partial sums, 256 partial minima, 8 scalars: h, 1/h, the three sums; lambda; the norm
+    double* part = nullptr;            // the partial sums of adflow_gpu_ank_unsteady_res, one per workgroup
+    long partCap = 0;
+    size_t bytesRed = 0, bytesPart = 0;
 };
 AnkState g_ank;
 const size_t ANK_RED = 4 * 256 + 8;
-const unsigned ANK_RES_FLAGS = ADFLOW_RES_DISS_APPROX | ADFLOW_RES_VISC_APPROX | ADFLOW_RES_UPWIND_FIRST_ORDER;
+const unsigned ANK_RES_FLAGS = ADFLOW_RES_DISS_APPROX | ADFLOW_RES_VISC_APPROX | ADFLOW_RES_UPWIND_FIRST_ORDER | ADFLOW_RES_APPROX_SA |
+                               ADFLOW_RES_TURB_FIRST_ORDER;
+const unsigned ANK_KIND_FLAGS = ADFLOW_ANK_COUPLED | ADFLOW_ANK_TURB;
+static bool ank_is_turb(unsigned flags) { return (flags & ADFLOW_ANK_TURB) != 0; }
+static AnkKind& ank_kind(unsigned flags) { return g_ank.kind[ank_is_turb(flags) ? 1 : 0]; }
+static AnkKind& ank_last() { return g_ank.kind[g_ank.last]; }
 }  // namespace
 
 static int64_t ank_release()
 {
-    const int64_t n = (int64_t)(g_ank.bytesT + g_ank.bytesBase + g_ank.bytesRed);
-    if (g_ank.tsm) (void)hipFree(g_ank.tsm);
-    if (g_ank.w0) (void)hipFree(g_ank.w0);
+    int64_t n = (int64_t)(g_ank.bytesRed + g_ank.bytesPart);
+    for (AnkKind& k : g_ank.kind) {
+        n += (int64_t)(k.bytesT + k.bytesBase);
+        if (k.tsm) (void)hipFree(k.tsm);
+        if (k.w0) (void)hipFree(k.w0);
+    }
     if (g_ank.red) (void)hipFree(g_ank.red);
+    if (g_ank.part) (void)hipFree(g_ank.part);
     g_ank = AnkState();
     return n;
 }
@@ -4429,8 +4479,12 @@ static int ank_red()
 static int ank_dims(const char* who, int level, unsigned flags, long* cells, int* nS)
 {
     if (need_ready()) return 1;
-    if (flags & ~(ADFLOW_ANK_COUPLED | ANK_RES_FLAGS))
-        return fail("%s: flags = %u; accepted are ADFLOW_ANK_COUPLED and ADFLOW_RES_DISS_APPROX / _VISC_APPROX / _UPWIND_FIRST_ORDER", who, flags);
+    if (flags & ~(ANK_KIND_FLAGS | ANK_RES_FLAGS))
+        return fail("%s: flags = %u; accepted are ADFLOW_ANK_COUPLED or ADFLOW_ANK_TURB and ADFLOW_RES_DISS_APPROX / _VISC_APPROX / "
+                    "_UPWIND_FIRST_ORDER / _APPROX_SA / _TURB_FIRST_ORDER", who, flags);
+    if ((flags & ANK_KIND_FLAGS) == ANK_KIND_FLAGS)
+        return fail("%s: flags = %u; ADFLOW_ANK_TURB (the turbulence KSP of the decoupled step) excludes ADFLOW_ANK_COUPLED", who, flags);
+    if (ank_is_turb(flags) && g_opts.equations != ADFLOW_RANS) return fail("%s: ADFLOW_ANK_TURB needs the RANS equations", who);
     long n = 0;
     int nw = 0;
     int rc = for_level(level, [&](Block* b) {
@@ -4441,8 +4495,9 @@ static int ank_dims(const char* who, int level, unsigned flags, long* cells, int
     });
     if (rc) return rc;
     if (!n) return fail("no block registered on level %d", level);
+    if (ank_is_turb(flags) && nw < 6) return fail("%s: RANS/SA needs nw = 6 (block has %d)", who, nw);
     *cells = n;
-    *nS = (flags & ADFLOW_ANK_COUPLED) ? nw : 5;
+    *nS = ank_is_turb(flags) ? 1 : (flags & ADFLOW_ANK_COUPLED) ? nw : 5;
     return 0;
 }
 
@@ -4455,10 +4510,18 @@ static int ank_vec_check(const char* who, const double* a, const double* b, long
     return 0;
 }
 
-static int ank_set_w_enqueue(const double* d_w, int nS, bool withClosures, const double* d_v = nullptr, const double* hdev = nullptr)
+// turb: nuTilde only (nS = 1); withClosures then means the eddy viscosity of the cell and nothing else (the flow variables stand)
+static int ank_set_w_enqueue(const double* d_w, int nS, bool withClosures, const double* d_v = nullptr, const double* hdev = nullptr,
+                             bool turb = false)
 {
     LevelTab t;
     if (level_tab(1, &t)) return 1;
+    if (turb) {
+        // no flow variable moves: the sensor and the energy / pressure consistency of the blocks stand as they are
+        KParams kp = make_kparams(1, 1.0, 0);
+        launch_ank_set_w_turb(t.tab, t.n, t.nx, t.ny, t.nz, d_w, d_v, hdev, withClosures ? &kp : nullptr, g_stream);
+        return 0;
+    }
     if (withClosures) {
         KParams kp = make_kparams(1, 1.0, 0);
         if (!g_floor_flag_dev) HIPCHK(hipMalloc((void**)&g_floor_flag_dev, sizeof(int)));
@@ -4473,22 +4536,28 @@ static int ank_set_w_enqueue(const double* d_w, int nS, bool withClosures, const
     });
 }
 
-// blocketteRes(useDissApprox, useViscApprox, useTurbRes = ANK_coupled, useStoreWall = F) behind a state write that did the closures
-static int ank_res_enqueue(unsigned flags)
+// blocketteRes(useDissApprox, useViscApprox, useTurbRes = ANK_coupled, useStoreWall = F) behind a state write that did the closures;
+// ADFLOW_ANK_TURB: blocketteRes(useFlowRes = F, useStoreWall = F) behind a turbulence state write that re-formed the eddy viscosity.
+// closures: the evaluation forms them itself (the state came from adflow_gpu_ank_set_w)
+static int ank_res_enqueue(unsigned flags, bool closures = false)
 {
-    unsigned f = ADFLOW_RES_HALO | ADFLOW_RES_FLOW | (flags & ANK_RES_FLAGS);
+    unsigned f = ADFLOW_RES_HALO | (flags & ANK_RES_FLAGS) | (closures ? ADFLOW_RES_CLOSURES : 0u);
+    if (ank_is_turb(flags)) return block_res_enqueue(1, f | ADFLOW_RES_TURB);
+    f |= ADFLOW_RES_FLOW;
     if ((flags & ADFLOW_ANK_COUPLED) && g_opts.equations == ADFLOW_RANS) f |= ADFLOW_RES_TURB;
+    if (closures) return block_res_enqueue(1, f);
     g_etot_flag_level = 1;      // the owned energy is computeEtot(p) already wherever p kept its value
     const int rc = block_res_enqueue(1, f);
     g_etot_flag_level = 0;
     return rc;
 }
 
-static int ank_get_r_enqueue(double* d_r, int nS)
+static int ank_get_r_enqueue(double* d_r, int nS, bool turb = false)
 {
     LevelTab t;
     if (level_tab(1, &t)) return 1;
-    launch_ank_get_r(t.tab, t.n, t.nx, t.ny, t.nz, nS, d_r, g_opts.turbResScale, g_stream);
+    if (turb) launch_ank_get_r_turb(t.tab, t.n, t.nx, t.ny, t.nz, d_r, g_opts.turbResScale, g_stream);
+    else launch_ank_get_r(t.tab, t.n, t.nx, t.ny, t.nz, nS, d_r, g_opts.turbResScale, g_stream);
     return 0;
 }
 
@@ -4496,7 +4565,7 @@ int adflow_gpu_ank_set_w_dev(const double* d_w, long n, unsigned flags)
 {
     long cells; int nS;
     if (ank_vec_check("ank_set_w", d_w, d_w, n, flags, &cells, &nS)) return 1;
-    if (ank_set_w_enqueue(d_w, nS, false)) return 1;
+    if (ank_set_w_enqueue(d_w, nS, false, nullptr, nullptr, ank_is_turb(flags))) return 1;
     return sync_and_check();
 }
 
@@ -4506,7 +4575,7 @@ int adflow_gpu_ank_set_w(const double* w, long n, unsigned flags)
     if (ank_vec_check("ank_set_w", w, w, n, flags, &cells, &nS)) return 1;
     if (vec_reserve((size_t)n)) return 1;
     HIPCHK(hipMemcpyAsync(g_vec_dev, w, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (ank_set_w_enqueue(g_vec_dev, nS, false)) return 1;
+    if (ank_set_w_enqueue(g_vec_dev, nS, false, nullptr, nullptr, ank_is_turb(flags))) return 1;
     HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
 }
@@ -4515,7 +4584,7 @@ int adflow_gpu_ank_get_r_dev(double* d_r, long n, unsigned flags)
 {
     long cells; int nS;
     if (ank_vec_check("ank_get_r", d_r, d_r, n, flags, &cells, &nS)) return 1;
-    if (ank_get_r_enqueue(d_r, nS)) return 1;
+    if (ank_get_r_enqueue(d_r, nS, ank_is_turb(flags))) return 1;
     return sync_and_check();
 }
 
@@ -4524,7 +4593,7 @@ int adflow_gpu_ank_get_r(double* r, long n, unsigned flags)
     long cells; int nS;
     if (ank_vec_check("ank_get_r", r, r, n, flags, &cells, &nS)) return 1;
     if (vec_reserve((size_t)n)) return 1;
-    if (ank_get_r_enqueue(g_vec_dev, nS)) return 1;
+    if (ank_get_r_enqueue(g_vec_dev, nS, ank_is_turb(flags))) return 1;
     HIPCHK(hipMemcpyAsync(r, g_vec_dev, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
@@ -4533,44 +4602,56 @@ int adflow_gpu_ank_get_r(double* r, long n, unsigned flags)
 int adflow_gpu_ank_time_step(int level, double cfl, double turbCFLScale, unsigned flags)
 {
     long cells; int nS;
-    if (ank_dims("ank_time_step", level, flags & ADFLOW_ANK_COUPLED, &cells, &nS)) return 1;
+    if (ank_dims("ank_time_step", level, flags & ANK_KIND_FLAGS, &cells, &nS)) return 1;
     if (!(cfl > 0.0)) return fail("ank_time_step: cfl = %g", cfl);
-    if (nS > 5 && !(turbCFLScale > 0.0)) return fail("ank_time_step: turbCFLScale = %g", turbCFLScale);
-    if (g_ank.tsm && g_ank.tCells != cells) {
+    const bool turb = ank_is_turb(flags);
+    if ((nS > 5 || turb) && !(turbCFLScale > 0.0)) return fail("ank_time_step: turbCFLScale = %g", turbCFLScale);
+    AnkKind& K = ank_kind(flags);
+    if (K.tsm && K.tCells != cells) {
         HIPCHK(hipStreamSynchronize(g_stream));
-        (void)hipFree(g_ank.tsm);
-        g_ank.tsm = nullptr;
-        g_ank.bytesT = 0;
+        (void)hipFree(K.tsm);
+        K.tsm = nullptr;
+        K.bytesT = 0;
     }
-    g_ank.haveT = false;
-    if (!g_ank.tsm) {
-        HIPCHK(hipMalloc((void**)&g_ank.tsm, sizeof(double) * 5 * cells));
-        g_ank.bytesT = sizeof(double) * 5 * cells;
+    K.haveT = false;
+    const int nq = turb ? 1 : 5;
+    if (!K.tsm) {
+        HIPCHK(hipMalloc((void**)&K.tsm, sizeof(double) * nq * cells));
+        K.bytesT = sizeof(double) * nq * cells;
     }
     LevelTab t;
     if (level_tab(level, &t)) return 1;
-    launch_ank_time_step(t.tab, t.n, t.nx, t.ny, t.nz, cfl, g_ank.tsm, cells, g_stream);
-    g_ank.tLevel = level; g_ank.tNState = nS; g_ank.tCells = cells;
-    g_ank.turbDiag = nS > 5 ? g_opts.turbResScale / turbCFLScale : 0.0;
-    g_ank.haveT = true;
+    if (turb) launch_ank_time_step_turb(t.tab, t.n, t.nx, t.ny, t.nz, cfl, K.tsm, g_stream);
+    else launch_ank_time_step(t.tab, t.n, t.nx, t.ny, t.nz, cfl, K.tsm, cells, g_stream);
+    K.tLevel = level; K.tNState = nS; K.tCells = cells;
+    K.turbDiag = (nS > 5 || turb) ? g_opts.turbResScale / turbCFLScale : 0.0;
+    K.haveT = true;
     return sync_and_check();
 }
 
-int adflow_gpu_ank_download_time_step(int nn, double* blocks)
+static int ank_download_time_step(int nn, double* blocks, unsigned flags)
 {
     if (need_ready()) return 1;
-    if (!g_ank.haveT) return fail("ank_download_time_step: no pseudo-time term (call adflow_gpu_ank_time_step first)");
+    if (flags & ~ADFLOW_ANK_TURB) return fail("ank_download_time_step: flags = %u; accepted is ADFLOW_ANK_TURB", flags);
+    const bool turb = ank_is_turb(flags);
+    const AnkKind& K = ank_kind(flags);
+    if (!K.haveT)
+        return fail("ank_download_time_step: no pseudo-time term%s (call adflow_gpu_ank_time_step first)", turb ? " of the turbulence KSP" : "");
     if (!blocks) return fail("ank_download_time_step: blocks is NULL");
-    Block* b = find_block(nn, g_ank.tLevel, 1);
-    if (!b) return fail("block (%d,%d,1) not registered", nn, g_ank.tLevel);
+    Block* b = find_block(nn, K.tLevel, 1);
+    if (!b) return fail("block (%d,%d,1) not registered", nn, K.tLevel);
     long off = 0;
     for (auto& kv : g_blocks)
-        if (std::get<0>(kv.first) == g_ank.tLevel && std::get<2>(kv.first) < nn) off += (long)kv.second->v.nx * kv.second->v.ny * kv.second->v.nz;
-    const long nc = (long)b->v.nx * b->v.ny * b->v.nz, N = g_ank.tCells;
-    const int nS = g_ank.tNState;
-    std::vector<double> h((size_t)5 * nc);
+        if (std::get<0>(kv.first) == K.tLevel && std::get<2>(kv.first) < nn) off += (long)kv.second->v.nx * kv.second->v.ny * kv.second->v.nz;
+    const long nc = (long)b->v.nx * b->v.ny * b->v.nz, N = K.tCells;
+    const int nS = K.tNState, nq = turb ? 1 : 5;
+    std::vector<double> h((size_t)nq * nc);
     HIPCHK(hipStreamSynchronize(g_stream));
-    for (int q = 0; q < 5; ++q) HIPCHK(hipMemcpy(h.data() + (size_t)q * nc, g_ank.tsm + (size_t)q * N + off, sizeof(double) * nc, hipMemcpyDeviceToHost));
+    for (int q = 0; q < nq; ++q) HIPCHK(hipMemcpy(h.data() + (size_t)q * nc, K.tsm + (size_t)q * N + off, sizeof(double) * nc, hipMemcpyDeviceToHost));
+    if (turb) {
+        for (long c = 0; c < nc; ++c) blocks[c] = h[c] * K.turbDiag;
+        return 0;
+    }
     memset(blocks, 0, sizeof(double) * nS * nS * nc);
     for (long c = 0; c < nc; ++c) {
         double* B = blocks + (size_t)c * nS * nS;      // B[ll + l nS] = T(ll, l)
@@ -4581,10 +4662,13 @@ int adflow_gpu_ank_download_time_step(int nn, double* blocks)
             B[l] = dtInv * h[(size_t)(l + 1) * nc + c];
             B[l + l * nS] = dtInv * rho;
         }
-        if (nS > 5) B[5 + 5 * nS] = dtInv * g_ank.turbDiag;
+        if (nS > 5) B[5 + 5 * nS] = dtInv * K.turbDiag;
     }
     return 0;
 }
+
+int adflow_gpu_ank_download_time_step(int nn, double* blocks) { return ank_download_time_step(nn, blocks, 0u); }
+int adflow_gpu_ank_download_time_step_turb(int nn, double* blocks, unsigned flags) { return ank_download_time_step(nn, blocks, flags); }
 
 int adflow_gpu_ank_pc_setup(int level)
 {
@@ -4594,14 +4678,19 @@ int adflow_gpu_ank_pc_setup(int level)
     if (g_jac.nStencil != 7)
         return fail("ank_pc_setup: the assembled matrix has a %d-point stencil; the block ILU(0) takes the 7-point preconditioner matrix "
                     "(ADFLOW_JAC_PC without ADFLOW_JAC_VISC_PC)", g_jac.nStencil);
-    if (!g_ank.haveT) return fail("ank_pc_setup: no pseudo-time term (call adflow_gpu_ank_time_step first)");
-    if (g_ank.tLevel != level) return fail("ank_pc_setup: level %d is not the level of the pseudo-time term (%d)", level, g_ank.tLevel);
-    if (g_ank.tNState != g_jac.nState)
-        return fail("ank_pc_setup: the pseudo-time term was formed for nState = %d, the assembled matrix has nState = %d", g_ank.tNState,
+    // an ADFLOW_JAC_TURB_ONLY matrix takes the turbulence T (FormJacobianANKTurb), every other the flow T (FormJacobianANK)
+    const bool turb = g_jac.nState == 1;
+    const AnkKind& K = g_ank.kind[turb ? 1 : 0];
+    if (!K.haveT)
+        return fail("ank_pc_setup: no pseudo-time term%s (call adflow_gpu_ank_time_step first)",
+                    turb ? " of the turbulence KSP, which the ADFLOW_JAC_TURB_ONLY matrix takes" : "");
+    if (K.tLevel != level) return fail("ank_pc_setup: level %d is not the level of the pseudo-time term (%d)", level, K.tLevel);
+    if (K.tNState != g_jac.nState)
+        return fail("ank_pc_setup: the pseudo-time term was formed for nState = %d, the assembled matrix has nState = %d", K.tNState,
                     g_jac.nState);
     HIPCHK(hipStreamSynchronize(g_stream));
     (void)pc_release();
-    if (pc_setup_build(level, g_ank.tsm, g_ank.turbDiag)) {
+    if (pc_setup_build(level, K.tsm, K.turbDiag)) {
         if (g_stream) (void)hipStreamSynchronize(g_stream);
         (void)pc_release();
         return 1;
@@ -4612,24 +4701,27 @@ int adflow_gpu_ank_pc_setup(int level)
 static int ank_set_base_enqueue(const double* d_w, long n, long cells, int nS, unsigned flags)
 {
     if (ank_red()) return 1;
-    if (g_ank.w0 && (g_ank.ncell != cells || g_ank.nState != nS)) {
+    AnkKind& K = ank_kind(flags);
+    const bool turb = ank_is_turb(flags);
+    if (K.w0 && (K.ncell != cells || K.nState != nS)) {
         HIPCHK(hipStreamSynchronize(g_stream));
-        (void)hipFree(g_ank.w0);
-        g_ank.w0 = g_ank.r0 = nullptr;
-        g_ank.bytesBase = 0;
+        (void)hipFree(K.w0);
+        K.w0 = K.r0 = nullptr;
+        K.bytesBase = 0;
     }
-    g_ank.haveBase = false;
-    if (!g_ank.w0) {
-        HIPCHK(hipMalloc((void**)&g_ank.w0, sizeof(double) * 2 * n));
-        g_ank.r0 = g_ank.w0 + n;
-        g_ank.bytesBase = sizeof(double) * 2 * n;
+    K.haveBase = false;
+    if (!K.w0) {
+        HIPCHK(hipMalloc((void**)&K.w0, sizeof(double) * 2 * n));
+        K.r0 = K.w0 + n;
+        K.bytesBase = sizeof(double) * 2 * n;
     }
-    g_ank.ncell = cells; g_ank.nState = nS; g_ank.flags = flags;
-    HIPCHK(hipMemcpyAsync(g_ank.w0, d_w, sizeof(double) * n, hipMemcpyDeviceToDevice, g_stream));
-    if (ank_set_w_enqueue(g_ank.w0, nS, true)) return 1;
+    K.ncell = cells; K.nState = nS; K.flags = flags;
+    g_ank.last = turb ? 1 : 0;
+    HIPCHK(hipMemcpyAsync(K.w0, d_w, sizeof(double) * n, hipMemcpyDeviceToDevice, g_stream));
+    if (ank_set_w_enqueue(K.w0, nS, true, nullptr, nullptr, turb)) return 1;
     if (ank_res_enqueue(flags)) return 1;
-    if (ank_get_r_enqueue(g_ank.r0, nS)) return 1;
-    g_ank.haveBase = true;
+    if (ank_get_r_enqueue(K.r0, nS, turb)) return 1;
+    K.haveBase = true;
     return 0;
 }
 
@@ -4655,32 +4747,38 @@ int adflow_gpu_ank_set_base(const double* w, long n, unsigned flags)
 static int ank_mult_check(const char* who, const double* v, const double* y, long n)
 {
     if (need_ready()) return 1;
-    if (!g_ank.haveBase) return fail("%s: no base state (call adflow_gpu_ank_set_base first)", who);
-    if (!g_ank.haveT) return fail("%s: no pseudo-time term (call adflow_gpu_ank_time_step first)", who);
-    if (g_ank.tLevel != 1 || g_ank.tNState != g_ank.nState || g_ank.tCells != g_ank.ncell)
+    const AnkKind& K = ank_last();
+    if (!K.haveBase) return fail("%s: no base state (call adflow_gpu_ank_set_base first)", who);
+    if (!K.haveT)
+        return fail("%s: no pseudo-time term%s (call adflow_gpu_ank_time_step first)", who, g_ank.last ? " of the turbulence KSP" : "");
+    if (K.tLevel != 1 || K.tNState != K.nState || K.tCells != K.ncell)
         return fail("%s: the pseudo-time term was formed for nState = %d on level %d, the base state has nState = %d on level 1", who,
-                    g_ank.tNState, g_ank.tLevel, g_ank.nState);
+                    K.tNState, K.tLevel, K.nState);
     if (!v || !y) return fail("%s: a vector is NULL", who);
     if (v == y) return fail("%s: input and result are the same vector (not done in place)", who);
-    if (n != g_ank.ncell * g_ank.nState)
-        return fail("%s: n=%ld but the base state has %ld rows (nState = %d x %ld owned cells)", who, n, g_ank.ncell * g_ank.nState,
-                    g_ank.nState, g_ank.ncell);
+    if (n != K.ncell * K.nState)
+        return fail("%s: n=%ld but the base state has %ld rows (nState = %d x %ld owned cells)", who, n, K.ncell * K.nState,
+                    K.nState, K.ncell);
     return 0;
 }
 
 // y = (R(w + h v) - r0) / h + T v, h = the MATMFFD_DS step, formed and consumed on the device: no host synchronisation
 static int ank_mult_enqueue(const double* d_v, double* d_y)
 {
-    const long n = g_ank.ncell * g_ank.nState;
-    const int nS = g_ank.nState;
+    const AnkKind& K = ank_last();
+    const bool turb = g_ank.last == 1;
+    const long n = K.ncell * K.nState;
+    const int nS = K.nState;
     double *part = g_ank.red, *hdev = g_ank.red + 4 * 256;
-    launch_ank_step(g_ank.w0, d_v, n, 1.490116119384766e-08, 1e-6, part, hdev, g_stream);
-    if (ank_set_w_enqueue(g_ank.w0, nS, true, d_v, hdev)) return 1;
-    if (ank_res_enqueue(g_ank.flags)) return 1;
+    launch_ank_step(K.w0, d_v, n, 1.490116119384766e-08, 1e-6, part, hdev, g_stream);
+    if (ank_set_w_enqueue(K.w0, nS, true, d_v, hdev, turb)) return 1;
+    if (ank_res_enqueue(K.flags)) return 1;
     LevelTab t;
     if (level_tab(1, &t)) return 1;
-    launch_ank_quotient(t.tab, t.n, t.nx, t.ny, t.nz, nS, d_v, g_ank.r0, g_ank.tsm, g_ank.tCells, g_ank.turbDiag, g_opts.turbResScale, hdev,
-                        d_y, g_stream);
+    if (turb)
+        launch_ank_quotient_turb(t.tab, t.n, t.nx, t.ny, t.nz, d_v, K.r0, K.tsm, K.turbDiag, g_opts.turbResScale, hdev, d_y, g_stream);
+    else
+        launch_ank_quotient(t.tab, t.n, t.nx, t.ny, t.nz, nS, d_v, K.r0, K.tsm, K.tCells, K.turbDiag, g_opts.turbResScale, hdev, d_y, g_stream);
     return 0;
 }
 
@@ -4710,10 +4808,21 @@ int adflow_gpu_ank_mult(const double* v, double* y, long n)
     return 0;
 }
 
+// the kind whose base adflow_gpu_ank_mult / _solve / _last_h act on: the one set last, or the one selected here
+int adflow_gpu_ank_select_base(unsigned flags)
+{
+    if (need_ready()) return 1;
+    if (flags & ~ADFLOW_ANK_TURB) return fail("ank_select_base: flags = %u; accepted is ADFLOW_ANK_TURB", flags);
+    if (!ank_kind(flags).haveBase)
+        return fail("ank_select_base: no base state%s (call adflow_gpu_ank_set_base first)", ank_is_turb(flags) ? " of the turbulence KSP" : "");
+    g_ank.last = ank_is_turb(flags) ? 1 : 0;
+    return 0;
+}
+
 int adflow_gpu_ank_last_h(double* h)
 {
     if (need_ready()) return 1;
-    if (!g_ank.haveBase || !h) return fail("ank_last_h: no base state (call adflow_gpu_ank_set_base first)");
+    if (!ank_last().haveBase || !h) return fail("ank_last_h: no base state (call adflow_gpu_ank_set_base first)");
     HIPCHK(hipMemcpyAsync(h, g_ank.red + 4 * 256, sizeof(double), hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
@@ -4730,8 +4839,8 @@ static int ank_gm_check(int level, const double* b, const double* x, long n, int
     if (level != 1) return fail("ank_solve: level %d; the matrix-free operator acts on level 1", level);
     if (ank_mult_check("ank_solve", b, x, n)) return 1;
     if (pc_check("ank_solve", level, b, x, n, false)) return 1;
-    if (g_pc.nState != g_ank.nState || g_pc.ncell != g_ank.ncell)
-        return fail("ank_solve: the factor was set up for nState = %d, the base state has nState = %d", g_pc.nState, g_ank.nState);
+    if (pc_sel().nState != ank_last().nState || pc_sel().ncell != ank_last().ncell)
+        return fail("ank_solve: the factor was set up for nState = %d, the base state has nState = %d", pc_sel().nState, ank_last().nState);
     if (restart < 1 || maxIts < 0) return fail("ank_solve: restart = %d, maxIts = %d", restart, maxIts);
     if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail("ank_solve: rtol = %g, atol = %g", rtol, atol);
     return 0;
@@ -4770,7 +4879,7 @@ static int ank_phys_check(const double* w, const double* dw, long n, unsigned fl
         return fail("ank_physicality_check: %d ranks in the communicator; the minimum is not reduced across ranks (the mpi_allreduce of "
                     "physicalityCheckANK is the host's)", g_nranks);
 #endif
-    if (flags & ~ADFLOW_ANK_COUPLED) return fail("ank_physicality_check: flags = %u; accepted is ADFLOW_ANK_COUPLED", flags);
+    if (flags & ~ANK_KIND_FLAGS) return fail("ank_physicality_check: flags = %u; accepted are ADFLOW_ANK_COUPLED or ADFLOW_ANK_TURB", flags);
     if (ank_vec_check("ank_physicality_check", w, dw, n, flags, cells, nS)) return 1;
     if (!lambda) return fail("ank_physicality_check: lambda is NULL");
     if (w == dw) return fail("ank_physicality_check: state and update are the same vector");
@@ -4778,12 +4887,13 @@ static int ank_phys_check(const double* w, const double* dw, long n, unsigned fl
     return 0;
 }
 
+// nS = 1 (ADFLOW_ANK_TURB): physicalityCheckANKTurb, the signed-ratio rule on the single entry and no density / energy rule
 static int ank_phys_enqueue(const double* d_w, double* d_dw, long cells, int nS, double physLSTol, double physLSTolTurb, double stepFactor,
                             double stepMin, double lambda0)
 {
     if (ank_red()) return 1;
-    launch_ank_phys(d_w, d_dw, cells, nS, nS > 5 ? 1 : 0, 1.e-25, physLSTol, physLSTolTurb, stepFactor * stepMin, lambda0, g_ank.red + 3 * 256,
-                    g_ank.red + 4 * 256 + 5, g_stream);
+    launch_ank_phys(d_w, d_dw, cells, nS, nS >= 5 ? 1 : 0, nS > 5 ? 5 : nS == 1 ? 0 : -1, 1.e-25, physLSTol, physLSTolTurb, stepFactor * stepMin,
+                    lambda0, g_ank.red + 3 * 256, g_ank.red + 4 * 256 + 5, g_stream);
     return 0;
 }
 
@@ -4808,8 +4918,74 @@ int adflow_gpu_ank_physicality_check(const double* w, double* dw, long n, unsign
     HIPCHK(hipMemcpyAsync(g_vec_dev, w, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(g_vec_dev + n, dw, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
     if (ank_phys_enqueue(g_vec_dev, g_vec_dev + n, cells, nS, physLSTol, physLSTolTurb, stepFactor, stepMin, *lambda)) return 1;
-    if (nS > 5) HIPCHK(hipMemcpyAsync(dw, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    if (nS != 5) HIPCHK(hipMemcpyAsync(dw, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipMemcpyAsync(lambda, g_ank.red + 4 * 256 + 5, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+// computeUnsteadyResANK / computeUnsteadyResANKTurb (:2614-2786): the state is the one adflow_gpu_ank_set_w left (w - omega dW);
+// blocketteRes with its closures, then r = the residual vector of the kind - omega T dW and its norm in one pass (k_ank_unsteady)
+static int ank_unsteady_check(const double* dW, const double* r, long n, unsigned flags, const double* norm, long* cells, int* nS)
+{
+    if (ank_vec_check("ank_unsteady_res", dW, r, n, flags, cells, nS)) return 1;
+    if (dW == r) return fail("ank_unsteady_res: update and result are the same vector (not done in place)");
+#ifndef ADFLOW_NO_RCCL
+    if (g_nranks > 1 && norm)
+        return fail("ank_unsteady_res: %d ranks in the communicator; the norm is not reduced across ranks (pass norm = NULL to the _dev "
+                    "form and reduce on the host)", g_nranks);
+#endif
+    const AnkKind& K = ank_kind(flags);
+    if (!K.haveT)
+        return fail("ank_unsteady_res: no pseudo-time term%s (call adflow_gpu_ank_time_step first)", ank_is_turb(flags) ? " of the turbulence KSP" : "");
+    if (K.tLevel != 1 || K.tNState != *nS || K.tCells != *cells)
+        return fail("ank_unsteady_res: the pseudo-time term was formed for nState = %d on level %d, the vectors have nState = %d on level 1",
+                    K.tNState, K.tLevel, *nS);
+    return 0;
+}
+
+static int ank_unsteady_enqueue(const double* d_dW, double omega, double* d_r, int nS, unsigned flags, bool wantNorm)
+{
+    if (ank_red()) return 1;
+    LevelTab t;
+    if (level_tab(1, &t)) return 1;
+    const long groups = ank_unsteady_groups(t.n, t.nx, t.ny, t.nz);
+    if (g_ank.partCap < groups) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        if (g_ank.part) (void)hipFree(g_ank.part);
+        g_ank.part = nullptr; g_ank.partCap = 0; g_ank.bytesPart = 0;
+        HIPCHK(hipMalloc((void**)&g_ank.part, sizeof(double) * groups));
+        g_ank.partCap = groups; g_ank.bytesPart = sizeof(double) * groups;
+    }
+    if (ank_res_enqueue(flags, true)) return 1;
+    if (level_tab(1, &t)) return 1;
+    const AnkKind& K = ank_kind(flags);
+    launch_ank_unsteady(t.tab, t.n, t.nx, t.ny, t.nz, nS, ank_is_turb(flags) ? 1 : 0, d_dW, K.tsm, K.tCells, K.turbDiag, g_opts.turbResScale, omega,
+                        d_r, g_ank.part, wantNorm ? g_ank.red + 4 * 256 + 6 : nullptr, g_stream);
+    return 0;
+}
+
+int adflow_gpu_ank_unsteady_res_dev(const double* d_dW, double omega, double* d_r, long n, unsigned flags, double* norm)
+{
+    long cells; int nS;
+    if (ank_unsteady_check(d_dW, d_r, n, flags, norm, &cells, &nS)) return 1;
+    if (ank_unsteady_enqueue(d_dW, omega, d_r, nS, flags, norm != nullptr)) return 1;
+    if (!norm) return sync_and_check();          // no reduction, nothing goes to the host: honours adflow_gpu_set_async
+    HIPCHK(hipMemcpyAsync(norm, g_ank.red + 4 * 256 + 6, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int adflow_gpu_ank_unsteady_res(const double* dW, double omega, double* r, long n, unsigned flags, double* norm)
+{
+    long cells; int nS;
+    if (ank_unsteady_check(dW, r, n, flags, norm, &cells, &nS)) return 1;
+    if (vec_reserve((size_t)2 * n)) return 1;
+    HIPCHK(hipMemcpyAsync(g_vec_dev, dW, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    if (ank_unsteady_enqueue(g_vec_dev, omega, g_vec_dev + n, nS, flags, norm != nullptr)) return 1;
+    HIPCHK(hipMemcpyAsync(r, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    if (norm) HIPCHK(hipMemcpyAsync(norm, g_ank.red + 4 * 256 + 6, sizeof(double), hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
 }

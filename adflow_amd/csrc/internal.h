@@ -276,6 +276,7 @@ struct KParams {
     int radiiInMarch;      // the Euler march forms the spectral radii itself (no k_time_step pass in front)
     int metricFromX;       // marching kernels re-form the face normals from the node coordinates (as blocketteResCore, blockette.F90:854-960)
     int lumpedDiss;        // inputDiscretization::lumpedDiss (preconditioner assembly): first-order Roe upwind (fluxes.F90:1536)
+    int approxSA;          // ADFLOW_RES_APPROX_SA: term1 of the SA source is zero (sa.F90:296); no dispatch key, the kernels select
     double sigma;
     double rFil, sfil;
     double vis2, vis4, vis2Coarse, adis, acousticScaleFactor, kappaCoef;
@@ -427,8 +428,18 @@ void launch_ank_time_step(const BlkView* tab, int nslots, int maxnx, int maxny, 
 void launch_ank_quotient(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, int nS, const double* v, const double* r0,
                          const double* tsm, long N, double turbDiag, double turbScale, const double* hdev, double* y, hipStream_t s);
 void launch_ank_step(const double* w, const double* v, long n, double errRel, double umin, double* part, double* hdev, hipStream_t s);
-void launch_ank_phys(const double* w, double* dw, long ncell, int nS, int turb, double eps, double tol, double tolTurb, double turbThreshold,
-                     double lambda0, double* part, double* out, hipStream_t s);
+void launch_ank_phys(const double* w, double* dw, long ncell, int nS, int flow, int lt, double eps, double tol, double tolTurb,
+                     double turbThreshold, double lambda0, double* part, double* out, hipStream_t s);
+// the turbulence KSP (one entry per cell) and the line-search residual with its norm
+void launch_ank_set_w_turb(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, const double* vec, const double* hv,
+                           const double* hdev, const KParams* kp, hipStream_t s);
+void launch_ank_get_r_turb(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, double* vec, double turbScale, hipStream_t s);
+void launch_ank_time_step_turb(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, double cfl, double* tsm, hipStream_t s);
+void launch_ank_quotient_turb(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, const double* v, const double* r0,
+                              const double* tsm, double turbDiag, double turbScale, const double* hdev, double* y, hipStream_t s);
+long ank_unsteady_groups(int nslots, int maxnx, int maxny, int maxnz);
+void launch_ank_unsteady(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, int nS, int turb, const double* dW, const double* tsm,
+                         long N, double turbDiag, double turbScale, double omega, double* r, double* part, double* out, hipStream_t s);
 
 // The level-batched launches fold (block slot, plane) into gridDim.z, which HIP limits to 65535: a launcher whose level has more
 // slots than fit calls itself on consecutive slot ranges (the kernels index the table relative to the pointer they get).

@@ -9,7 +9,11 @@
 //   FormFunction_mf            :2468-2538   R(u) + T u, differenced by MatMFFD (default MATMFFD_DS step); here the linear part T v is
 //                                           taken analytically:  y = (R(w + h v) - r0) / h + T v
 //   physicalityCheckANK        :3013-3210   the largest step that changes density / energy by at most physLSTol (real mode)
-// Out of scope: the Turkel / VLR time-step types, the turbulence KSP (FormFunction_mf_turb, physicalityCheckANKTurb).
+//   the turbulence KSP (ANKTurbSolveKSP :3337-3627), nState = 1, the entry of a cell is nuTilde:
+//   setWANK(wVecTurb, nt1, nt2) :2975-3011, setRVecANKTurb :2935-2973 (dw(itu1) / volRef turbResScale), FormJacobianANKTurb
+//   :2395-2406 (the diagonal dtInv turbResScale / turbCFLScale), FormFunction_mf_turb :2540-2612, physicalityCheckANKTurb :3212-3335
+//   computeUnsteadyResANK / ...Turb :2614-2786   the residual of the backtracking line search, R(w) - omega T deltaW, and its 2-norm
+// Out of scope: the Turkel / VLR time-step types.
 //
 // Every pass is bandwidth-bound, one lane per owned cell.  Vectors are the PETSc layout (block, k, j, i, variable fastest) with
 // nS = nState variables per cell: cell m of the level starts at m nS; the first cell of a block is BlkView::vecOff / nw.
@@ -111,11 +115,64 @@ __global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_quotient(const BlkView* __
     }
 }
 
+// ---- the turbulence KSP: one entry per cell (nuTilde) --------------------------------------------------------------------------------
+// w(itu1) = vec (hv == NULL) or vec + h hv.  The flow variables do not move, so p and rlv stand; EDDY: the eddy viscosity of the cell
+// is re-formed from rho, rlv and the new nuTilde by the function closures_cell uses -- about 5 values per cell instead of the state
+template <bool EDDY>
+__global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_set_w_turb(const BlkView* __restrict__ tab, int nzb, const double* __restrict__ vec,
+                                                                 const double* __restrict__ hv, const double* __restrict__ hdev, KParams kp)
+{
+    const BlkView& b = tab[blockIdx.z / nzb + 1];
+    const AkCell q = ak_cell(b, (int)(blockIdx.z % nzb));
+    if (!q.in) return;
+    const double h = hv ? hdev[0] : 0.0;
+    const double nut = hv ? vec[q.m] + h * hv[q.m] : vec[q.m];
+    b.w[q.c + 5 * b.nbox] = nut;
+    if (EDDY && kp.eddyModel && kp.updateEddy) b.rev[q.c] = sa_eddy_viscosity(kp, b.w[q.c], b.rlv[q.c], nut);
+}
+
+// vec = dw(itu1) / volRef turbScale (setRVecANKTurb)
+__global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_get_r_turb(const BlkView* __restrict__ tab, int nzb, double* __restrict__ vec, double turbScale)
+{
+    const BlkView& b = tab[blockIdx.z / nzb + 1];
+    const AkCell q = ak_cell(b, (int)(blockIdx.z % nzb));
+    if (!q.in) return;
+    const double ovv = 1.0 / b.volRef[q.c];
+    vec[q.m] = b.dw[q.c + 5 * b.nbox] * ovv * turbScale;
+}
+
+// the turbulence T: dtInv = 1 / (cfl dtl volRef) and nothing else, 8 B per cell
+__global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_time_step_turb(const BlkView* __restrict__ tab, int nzb, double cfl, double* __restrict__ tsm)
+{
+    const BlkView& b = tab[blockIdx.z / nzb + 1];
+    const AkCell q = ak_cell(b, (int)(blockIdx.z % nzb));
+    if (!q.in) return;
+    tsm[q.m] = rcp_nr(cfl * b.dtl[q.c] * b.volRef[q.c]);
+}
+
+// y = (dw(itu1) / volRef turbScale - r0) / h + dtInv turbDiag v;  h == 0 (v = 0): y = 0
+__global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_quotient_turb(const BlkView* __restrict__ tab, int nzb, const double* __restrict__ v,
+                                                                    const double* __restrict__ r0, const double* __restrict__ tsm,
+                                                                    double turbDiag, double turbScale, const double* __restrict__ hdev,
+                                                                    double* __restrict__ y)
+{
+    const BlkView& b = tab[blockIdx.z / nzb + 1];
+    const AkCell q = ak_cell(b, (int)(blockIdx.z % nzb));
+    if (!q.in) return;
+    if (hdev[0] == 0.0) {
+        y[q.m] = 0.0;
+        return;
+    }
+    const double ovv = 1.0 / b.volRef[q.c];
+    const double r = b.dw[q.c + 5 * b.nbox] * ovv * turbScale;
+    y[q.m] = (r - r0[q.m]) * hdev[1] + tsm[q.m] * turbDiag * v[q.m];
+}
+
 // ---- reductions: partial results per workgroup, then one finishing workgroup that adds them in a fixed order ------------------------
 template <int NV>
 __device__ __forceinline__ void ak_block_sum(double (&v)[NV], double (*red)[AK_T])
 {
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.y * blockDim.x + threadIdx.x;          // AK_T x 1 and AK_BX x AK_BY workgroups alike
     for (int q = 0; q < NV; ++q) red[q][tid] = v[q];
     __syncthreads();
     for (int s = AK_T / 2; s > 0; s >>= 1) {
@@ -160,23 +217,77 @@ __global__ __launch_bounds__(AK_T) void k_ank_step(const double* __restrict__ pa
     hdev[2] = s[0]; hdev[3] = d; hdev[4] = nrm2;
 }
 
-// physicalityCheckANK: the smallest ratio of the cells of a workgroup to part[workgroup]; a NaN ratio makes the partial NaN
-__global__ __launch_bounds__(AK_T) void k_ank_phys(const double* __restrict__ w, double* __restrict__ dw, long ncell, int nS, int turb,
+// the residual of the backtracking line search (computeUnsteadyResANK / ...Turb): r = setRVecANK / setRVec / setRVecANKTurb of the dw
+// on the device minus omega T dW with T as stored, and the sum of r^2 over the workgroup to part[workgroup of the launch + partOff]:
+// one pass over dw, volRef, tsm and dW.  Every workgroup writes its partial, one without cells a zero.
+template <bool TURB>
+__global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_unsteady(const BlkView* __restrict__ tab, int nzb, int nS, const double* __restrict__ dW,
+                                                               const double* __restrict__ tsm, long N, double turbDiag, double turbScale,
+                                                               double omega, double* __restrict__ r, double* __restrict__ part, long partOff)
+{
+    __shared__ double red[1][AK_T];
+    const BlkView& b = tab[blockIdx.z / nzb + 1];
+    const AkCell q = ak_cell(b, (int)(blockIdx.z % nzb));
+    double s[1] = {0.0};
+    if (q.in) {
+        const double ovv = 1.0 / b.volRef[q.c];
+        const double dtInv = tsm[q.m];
+        if (TURB) {
+            const double steady = b.dw[q.c + 5 * b.nbox] * ovv * turbScale;
+            const double val = steady - omega * (dtInv * turbDiag * dW[q.m]);
+            r[q.m] = val;
+            s[0] = val * val;
+        } else {
+            const long m = q.m * nS;
+            const double rho = tsm[N + q.m], d0 = dW[m];
+            for (int l = 0; l < nS; ++l) {
+                const double t = b.dw[q.c + l * b.nbox] * ovv;
+                const double steady = l < 5 ? t : t * turbScale;
+                const double dl = dW[m + l];
+                double tv;
+                if (l == 0 || l == 4) tv = dtInv * dl;
+                else if (l < 4) tv = dtInv * (tsm[(l + 1) * N + q.m] * d0 + rho * dl);
+                else tv = dtInv * turbDiag * dl;
+                const double val = steady - omega * tv;
+                r[m + l] = val;
+                s[0] += val * val;
+            }
+        }
+    }
+    ak_block_sum<1>(s, red);
+    if (threadIdx.x == 0 && threadIdx.y == 0)
+        part[partOff + ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s[0];
+}
+
+// out[0] = sqrt(sum of np partials): lane t adds part[t], part[t + AK_T], ... in that order, then the tree of ak_block_sum
+__global__ __launch_bounds__(AK_T) void k_ank_norm_finish(const double* __restrict__ part, long np, double* __restrict__ out)
+{
+    __shared__ double red[1][AK_T];
+    double s[1] = {0.0};
+    for (long i = threadIdx.x; i < np; i += AK_T) s[0] += part[i];
+    ak_block_sum<1>(s, red);
+    if (threadIdx.x == 0) out[0] = sqrt(s[0]);
+}
+
+// physicalityCheckANK / physicalityCheckANKTurb: the smallest ratio of the cells of a workgroup to part[workgroup]; a NaN ratio makes
+// the partial NaN.  flow: density and energy (entries 0 and 4) take part; lt: the entry of the turbulence variable (5 coupled, 0 in
+// the turbulence KSP), < 0 none
+__global__ __launch_bounds__(AK_T) void k_ank_phys(const double* __restrict__ w, double* __restrict__ dw, long ncell, int nS, int flow, int lt,
                                                    double eps, double tol, double tolTurb, double turbThreshold, double* __restrict__ part)
 {
     __shared__ double red[2][AK_T];
     double lam = 1.7976931348623157e308, bad = 0.0;
     for (long c = (long)blockIdx.x * AK_T + threadIdx.x; c < ncell; c += (long)gridDim.x * AK_T) {
         const long m = c * nS;
-        for (int l = 0; l < 5; l += 4) {
+        for (int l = 0; flow && l < 5; l += 4) {
             const double ratio = fabs(w[m + l] / (dw[m + l] + eps)) * tol;
             if (ratio != ratio) bad = 1.0;
             lam = fmin(lam, ratio);
         }
-        if (turb) {
-            double ratio = (w[m + 5] / (dw[m + 5] + eps)) * tolTurb;
+        if (lt >= 0) {
+            double ratio = (w[m + lt] / (dw[m + lt] + eps)) * tolTurb;
             if (ratio < turbThreshold) {
-                if (ratio > 0.0) dw[m + 5] = w[m + 5] * tolTurb;
+                if (ratio > 0.0) dw[m + lt] = w[m + lt] * tolTurb;
                 ratio = 1.0;
             }
             if (ratio != ratio) bad = 1.0;
@@ -270,10 +381,67 @@ void launch_ank_step(const double* w, const double* v, long n, double errRel, do
     hipLaunchKernelGGL(k_ank_step, dim3(1), dim3(AK_T), 0, s, part, g, errRel, umin, hdev);
 }
 // part: AK_T doubles
-void launch_ank_phys(const double* w, double* dw, long ncell, int nS, int turb, double eps, double tol, double tolTurb, double turbThreshold,
-                     double lambda0, double* part, double* out, hipStream_t s)
+void launch_ank_phys(const double* w, double* dw, long ncell, int nS, int flow, int lt, double eps, double tol, double tolTurb,
+                     double turbThreshold, double lambda0, double* part, double* out, hipStream_t s)
 {
     const int g = ank_groups(ncell);
-    hipLaunchKernelGGL(k_ank_phys, dim3(g), dim3(AK_T), 0, s, w, dw, ncell, nS, turb, eps, tol, tolTurb, turbThreshold, part);
+    hipLaunchKernelGGL(k_ank_phys, dim3(g), dim3(AK_T), 0, s, w, dw, ncell, nS, flow, lt, eps, tol, tolTurb, turbThreshold, part);
     hipLaunchKernelGGL(k_ank_phys_finish, dim3(1), dim3(AK_T), 0, s, part, g, lambda0, out);
+}
+
+// ---- the turbulence KSP and the line-search residual -------------------------------------------------------------------------------------
+void launch_ank_set_w_turb(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, const double* vec, const double* hv,
+                           const double* hdev, const KParams* kp, hipStream_t s)
+{
+    LEVEL_SPLIT(nslots, maxnz + 4, launch_ank_set_w_turb(tab + s0_, n_, maxnx, maxny, maxnz, vec, hv, hdev, kp, s));
+    if (nslots <= 0) return;
+    if (kp)
+        hipLaunchKernelGGL(k_ank_set_w_turb<true>, ak_grid(nslots, maxnx, maxny, maxnz), dim3(AK_BX, AK_BY, 1), 0, s, tab, maxnz, vec, hv, hdev, *kp);
+    else
+        hipLaunchKernelGGL(k_ank_set_w_turb<false>, ak_grid(nslots, maxnx, maxny, maxnz), dim3(AK_BX, AK_BY, 1), 0, s, tab, maxnz, vec, hv, hdev,
+                           KParams());
+}
+void launch_ank_get_r_turb(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, double* vec, double turbScale, hipStream_t s)
+{
+    LEVEL_SPLIT(nslots, maxnz + 4, launch_ank_get_r_turb(tab + s0_, n_, maxnx, maxny, maxnz, vec, turbScale, s));
+    if (nslots <= 0) return;
+    hipLaunchKernelGGL(k_ank_get_r_turb, ak_grid(nslots, maxnx, maxny, maxnz), dim3(AK_BX, AK_BY, 1), 0, s, tab, maxnz, vec, turbScale);
+}
+void launch_ank_time_step_turb(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, double cfl, double* tsm, hipStream_t s)
+{
+    LEVEL_SPLIT(nslots, maxnz + 4, launch_ank_time_step_turb(tab + s0_, n_, maxnx, maxny, maxnz, cfl, tsm, s));
+    if (nslots <= 0) return;
+    hipLaunchKernelGGL(k_ank_time_step_turb, ak_grid(nslots, maxnx, maxny, maxnz), dim3(AK_BX, AK_BY, 1), 0, s, tab, maxnz, cfl, tsm);
+}
+void launch_ank_quotient_turb(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, const double* v, const double* r0,
+                              const double* tsm, double turbDiag, double turbScale, const double* hdev, double* y, hipStream_t s)
+{
+    LEVEL_SPLIT(nslots, maxnz + 4, launch_ank_quotient_turb(tab + s0_, n_, maxnx, maxny, maxnz, v, r0, tsm, turbDiag, turbScale, hdev, y, s));
+    if (nslots <= 0) return;
+    hipLaunchKernelGGL(k_ank_quotient_turb, ak_grid(nslots, maxnx, maxny, maxnz), dim3(AK_BX, AK_BY, 1), 0, s, tab, maxnz, v, r0, tsm, turbDiag,
+                       turbScale, hdev, y);
+}
+// the workgroups (= partial sums) of launch_ank_unsteady over these slots
+long ank_unsteady_groups(int nslots, int maxnx, int maxny, int maxnz)
+{
+    const dim3 g = ak_grid(1, maxnx, maxny, maxnz);
+    return (long)g.x * g.y * g.z * (nslots > 0 ? nslots : 0);
+}
+// part: ank_unsteady_groups doubles; out (NULL: no norm): 1 double
+void launch_ank_unsteady(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, int nS, int turb, const double* dW, const double* tsm,
+                         long N, double turbDiag, double turbScale, double omega, double* r, double* part, double* out, hipStream_t s)
+{
+    const int per = level_slots_per_launch(maxnz + 4);
+    long off = 0;
+    for (int s0 = 0; s0 < nslots; s0 += per) {
+        const int n = nslots - s0 < per ? nslots - s0 : per;
+        if (turb)
+            hipLaunchKernelGGL(k_ank_unsteady<true>, ak_grid(n, maxnx, maxny, maxnz), dim3(AK_BX, AK_BY, 1), 0, s, tab + s0, maxnz, nS, dW, tsm, N,
+                               turbDiag, turbScale, omega, r, part, off);
+        else
+            hipLaunchKernelGGL(k_ank_unsteady<false>, ak_grid(n, maxnx, maxny, maxnz), dim3(AK_BX, AK_BY, 1), 0, s, tab + s0, maxnz, nS, dW, tsm, N,
+                               turbDiag, turbScale, omega, r, part, off);
+        off += ank_unsteady_groups(n, maxnx, maxny, maxnz);
+    }
+    if (out) hipLaunchKernelGGL(k_ank_norm_finish, dim3(1), dim3(AK_T), 0, s, part, off, out);
 }

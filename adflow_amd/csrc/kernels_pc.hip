@@ -113,6 +113,10 @@ __global__ __launch_bounds__(PC_T) void k_pc_factor(PcTab T, int q0, int cnt)
             }
             if (NS > 5) PCE(D, NS - 1, NS - 1) += dtInv * T.turbDiag;
         }
+    } else if constexpr (NS == 1) {
+        // the turbulence KSP (FormJacobianANKTurb, NKSolvers.F90:2395-2406): dtInv turbResScale / turbCFLScale on the pivot; the
+        // turbulence T stores dtInv only
+        if (T.tsm) D[0] += T.tsm[T.vec[q]] * T.turbDiag;
     }
     for (int s = 0; s < 3; ++s) {
         const int n = T.nbr[(long)s * N + q];

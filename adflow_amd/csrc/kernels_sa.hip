@@ -88,7 +88,8 @@ __global__ __launch_bounds__(SA_BX* SA_BY) void k_sa_residual(const BlkView* __r
     const double gg6 = gg2 * gg2 * gg2;
     const double termFw = pow((1.0 + cw36) / (gg6 + cw36), 1.0 / 6.0);
     const double fwSa = gg * termFw;
-    const double term1 = kp.sa_cb1 * (1.0 - ft2) * ss;
+    const double full1 = kp.sa_cb1 * (1.0 - ft2) * ss;
+    const double term1 = kp.approxSA ? 0.0 : full1;                  // approxSA (sa.F90:296-300); qq has no part of term1
     const double term2 = dist2Inv * (kar2Inv * kp.sa_cb1 * ((1.0 - ft2) * fv2 + ft2) - kp.sa_cw1 * fwSa);
     double dvt = (term1 + term2 * nut) * nut;
     double qq = 0.0;

@@ -4,6 +4,17 @@
 #pragma once
 #include "internal.h"
 
+// computeEddyViscosity for Spalart-Allmaras (turbUtils.F90:657-720) of one cell: the one form of this arithmetic, shared by the
+// closures below and by the turbulence state write of the ANK turbulence KSP (k_ank_set_w_turb), which re-forms nothing else
+__device__ __forceinline__ double sa_eddy_viscosity(const KParams& kp, double rho, double rlv, double nuTilde)
+{
+    const double cv13 = kp.sa_cv1 * kp.sa_cv1 * kp.sa_cv1;
+    const double rnuSA = nuTilde * rho;
+    const double chi = rnuSA / rlv;
+    const double chi3 = chi * chi * chi;
+    return chi3 / (chi3 + cv13) * rnuSA;
+}
+
 template <bool ETOT = false>
 __device__ __forceinline__ void closures_cell(const BlkView& b, int i, int j, int k, const KParams& kp, int* __restrict__ floored)
 {
@@ -30,12 +41,6 @@ __device__ __forceinline__ void closures_cell(const BlkView& b, int i, int j, in
         const double tt = T / TSuth;
         const double rlv = muSuth * ((TSuth + SSuth) / (T + SSuth)) * (tt * sqrt(tt));
         b.rlv[c] = rlv;
-        if (kp.eddyModel && kp.updateEddy) {
-            const double cv13 = kp.sa_cv1 * kp.sa_cv1 * kp.sa_cv1;
-            const double rnuSA = b.w[c + 5 * nb] * rho;
-            const double chi = rnuSA / rlv;
-            const double chi3 = chi * chi * chi;
-            b.rev[c] = chi3 / (chi3 + cv13) * rnuSA;
-        }
+        if (kp.eddyModel && kp.updateEddy) b.rev[c] = sa_eddy_viscosity(kp, rho, rlv, b.w[c + 5 * nb]);
     }
 }

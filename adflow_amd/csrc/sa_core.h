@@ -136,7 +136,8 @@ __device__ __forceinline__ double sa_source(const KParams& kp, const double gu[3
     const double gg6 = gg2 * gg2 * gg2;
     const double termFw = fast_root6((1.0 + cw36) * rcp_nr(gg6 + cw36));
     const double fwSa = gg * termFw;
-    const double term1 = kp.sa_cb1 * (1.0 - ft2) * ss;
+    const double full1 = kp.sa_cb1 * (1.0 - ft2) * ss;
+    const double term1 = kp.approxSA ? 0.0 : full1;                  // approxSA (sa.F90:296-300); qq has no part of term1
     const double term2 = dist2Inv * (kar2Inv * kp.sa_cb1 * ((1.0 - ft2) * fv2 + ft2) - kp.sa_cw1 * fwSa);
     if (qqOut) {
         const double t1 = chi3 + cv13;

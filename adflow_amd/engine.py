@@ -115,12 +115,15 @@ class Engine:
         xSurf = np.ascontiguousarray(xSurf, dtype=np.float64)
         self._chk(self.lib.adflow_gpu_update_wall_distances(level, xSurf.ctypes.data, xSurf.size))
 
-    def setupStateResidualMatrix(self, level=1, usePC=True, frozenTurb=False, useTurbOnly=False, viscPC=False, delta=1e-9, useAD=False):
+    def setupStateResidualMatrix(self, level=1, usePC=True, frozenTurb=False, useTurbOnly=False, viscPC=False, delta=1e-9, useAD=False,
+                                 approxSA=False):
         """adjointUtils::setupStateResidualMatrix (adjointUtils.F90:7-715) without the PETSc calls: the stencil blocks stay on the
         device; jacobianBlocks() brings one block's over.  useAD = False: coloured finite differences with step delta; True: one
-        forward-mode (dual-number) evaluation per colour and state variable, the exact derivative (adjointUtils.F90:227-409)."""
+        forward-mode (dual-number) evaluation per colour and state variable, the exact derivative (adjointUtils.F90:227-409).
+        approxSA: the SA residual of the coloured evaluations without term1 of its source (FormJacobianANK / FormJacobianANKTurb)."""
         flags = (capi.JAC_PC if usePC else 0) | (capi.JAC_FROZEN_TURB if frozenTurb else 0) \
-            | (capi.JAC_TURB_ONLY if useTurbOnly else 0) | (capi.JAC_VISC_PC if viscPC else 0) | (capi.JAC_USE_AD if useAD else 0)
+            | (capi.JAC_TURB_ONLY if useTurbOnly else 0) | (capi.JAC_VISC_PC if viscPC else 0) | (capi.JAC_USE_AD if useAD else 0) \
+            | (capi.JAC_APPROX_SA if approxSA else 0)
         self._chk(self.lib.adflow_gpu_fd_jacobian(level, flags, float(delta)))
 
     def releaseWorkspace(self) -> int:
@@ -224,54 +227,75 @@ class Engine:
                                                       ctypes.byref(its), ctypes.byref(r0), ctypes.byref(rn)))
         return int(its.value), float(r0.value), float(rn.value)
 
-    # ---- the flow update of ANKStep (NKSolvers.F90:3629-4112); vectors carry nState = nw (coupled) or 5 variables per cell ------
-    @staticmethod
-    def _ankFlags(coupled=False, dissApprox=False, viscApprox=False, useBlockettes=False):
-        return (capi.ANK_COUPLED if coupled else 0) | (capi.RES_DISS_APPROX if dissApprox else 0) \
-            | (capi.RES_VISC_APPROX if viscApprox else 0) | (capi.RES_UPWIND_FIRST_ORDER if useBlockettes else 0)
+    def pcSelect(self, slot: int):
+        """the factor slot (0 or 1) pcSetup, ankPcSetup, pcApply, pcInfo, pcRelease, gmresSolve and ankSolve act on"""
+        self._chk(self.lib.adflow_gpu_pc_select(int(slot)))
 
-    def ankNState(self, coupled=False):
+    # ---- ANKStep / ANKTurbSolveKSP (NKSolvers.F90:3337-4112); vectors carry nState = nw (coupled), 1 (turb) or 5 variables per cell
+    @staticmethod
+    def _ankFlags(coupled=False, dissApprox=False, viscApprox=False, useBlockettes=False, turb=False, approxSA=False, turbFirstOrder=False):
+        return (capi.ANK_COUPLED if coupled else 0) | (capi.RES_DISS_APPROX if dissApprox else 0) \
+            | (capi.RES_VISC_APPROX if viscApprox else 0) | (capi.RES_UPWIND_FIRST_ORDER if useBlockettes else 0) \
+            | (capi.ANK_TURB if turb else 0) | (capi.RES_APPROX_SA if approxSA else 0) \
+            | (capi.RES_TURB_FIRST_ORDER if turbFirstOrder else 0)
+
+    def ankNState(self, coupled=False, turb=False):
+        if turb:
+            return 1
         return next(b.nw for (nn, lv, sps), b in self.blocks.items() if lv == 1) if coupled else 5
 
-    def ankSetW(self, w, coupled=False):
-        """setWANK(wVec, 1, nState): w(1:nState) of the owned cells, no clipping"""
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        self._chk(self.lib.adflow_gpu_ank_set_w(w.ctypes.data, w.size, self._ankFlags(coupled)))
+    def _ankCells(self):
+        return sum(b.nx * b.ny * b.nz for (nn, lv, sps), b in self.blocks.items() if lv == 1)
 
-    def ankGetR(self, coupled=False):
-        """setRVecANK (decoupled) / setRVec (coupled) of the residual on the device"""
-        n = self.ankNState(coupled) * sum(b.nx * b.ny * b.nz for (nn, lv, sps), b in self.blocks.items() if lv == 1)
+    def ankSetW(self, w, coupled=False, turb=False):
+        """setWANK(wVec, 1, nState) / setWANK(wVecTurb, nt1, nt2): the owned cells, no clipping"""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        self._chk(self.lib.adflow_gpu_ank_set_w(w.ctypes.data, w.size, self._ankFlags(coupled, turb=turb)))
+
+    def ankGetR(self, coupled=False, turb=False):
+        """setRVecANK (decoupled) / setRVec (coupled) / setRVecANKTurb (turb) of the residual on the device"""
+        n = self.ankNState(coupled, turb) * self._ankCells()
         r = np.zeros(n)
-        self._chk(self.lib.adflow_gpu_ank_get_r(r.ctypes.data, n, self._ankFlags(coupled)))
+        self._chk(self.lib.adflow_gpu_ank_get_r(r.ctypes.data, n, self._ankFlags(coupled, turb=turb)))
         return r
 
-    def ankTimeStep(self, cfl, turbCFLScale=1.0, coupled=False, level=1):
-        """computeTimeStepMat for ANK_charTimeStepType = 'None' from the dtl on the device"""
-        self._chk(self.lib.adflow_gpu_ank_time_step(level, float(cfl), float(turbCFLScale), self._ankFlags(coupled)))
+    def ankTimeStep(self, cfl, turbCFLScale=1.0, coupled=False, level=1, turb=False):
+        """computeTimeStepMat for ANK_charTimeStepType = 'None' from the dtl on the device; turb: the diagonal of the turbulence KSP"""
+        self._chk(self.lib.adflow_gpu_ank_time_step(level, float(cfl), float(turbCFLScale), self._ankFlags(coupled, turb=turb)))
 
-    def ankTimeStepBlocks(self, nn=1, coupled=False, level=1):
+    def ankTimeStepBlocks(self, nn=1, coupled=False, level=1, turb=False):
         """the dense blocks of T of block nn, (nState, nState, nx, ny, nz)"""
         blk = self.blocks[(nn, level, 1)]
-        ns = self.ankNState(coupled)
+        ns = self.ankNState(coupled, turb)
         out = np.zeros((ns, ns, blk.nx, blk.ny, blk.nz), order="F")
-        self._chk(self.lib.adflow_gpu_ank_download_time_step(nn, out.ctypes.data))
+        if turb:
+            self._chk(self.lib.adflow_gpu_ank_download_time_step_turb(nn, out.ctypes.data, capi.ANK_TURB))
+        else:
+            self._chk(self.lib.adflow_gpu_ank_download_time_step(nn, out.ctypes.data))
         return out
 
     def ankPcSetup(self, level=1):
-        """ILU(0) of dRdwPre + timeStepMat into the factor slot of pcSetup (FormJacobianANK)"""
+        """ILU(0) of dRdwPre + timeStepMat into the selected factor slot (FormJacobianANK; FormJacobianANKTurb for a useTurbOnly matrix)"""
         self._chk(self.lib.adflow_gpu_ank_pc_setup(level))
 
-    def ankSetBase(self, w, coupled=False, dissApprox=False, viscApprox=False, useBlockettes=False):
-        """formFunction_mf(wVec, baseRes) + MatMFFDSetBase: the state from w, r0 = R(w) kept on the device"""
+    def ankSetBase(self, w, coupled=False, dissApprox=False, viscApprox=False, useBlockettes=False, turb=False, approxSA=False,
+                   turbFirstOrder=False):
+        """formFunction_mf[_turb](wVec, baseRes) + MatMFFDSetBase: the state from w, r0 = R(w) kept on the device"""
         w = np.ascontiguousarray(w, dtype=np.float64)
-        self._chk(self.lib.adflow_gpu_ank_set_base(w.ctypes.data, w.size, self._ankFlags(coupled, dissApprox, viscApprox, useBlockettes)))
+        self._chk(self.lib.adflow_gpu_ank_set_base(w.ctypes.data, w.size, self._ankFlags(coupled, dissApprox, viscApprox, useBlockettes, turb,
+                                                                                          approxSA, turbFirstOrder)))
 
     def ankMult(self, v):
-        """y = (R(w + h v) - r0) / h + T v with the MATMFFD_DS step h; the device state is the perturbed one afterwards"""
+        """y = (R(w + h v) - r0) / h + T v with the MATMFFD_DS step h, on the base set last; the device state is the perturbed one
+        afterwards"""
         v = np.ascontiguousarray(v, dtype=np.float64)
         y = np.zeros_like(v)
         self._chk(self.lib.adflow_gpu_ank_mult(v.ctypes.data, y.ctypes.data, v.size))
         return y
+
+    def ankSelectBase(self, turb=False):
+        """the kind (flow / turbulence) whose base ankMult, ankSolve and ankLastH act on; by default the one set last"""
+        self._chk(self.lib.adflow_gpu_ank_select_base(capi.ANK_TURB if turb else 0))
 
     def ankMultDev(self, d_v: int, d_y: int, n: int):
         self._chk(self.lib.adflow_gpu_ank_mult_dev(ctypes.c_void_p(d_v), ctypes.c_void_p(d_y), int(n)))
@@ -282,7 +306,7 @@ class Engine:
         return float(h.value)
 
     def ankSolve(self, b, level=1, restart=50, maxIts=200, rtol=1e-8, atol=0.0):
-        """KSPSolve(ANK_KSP, rVec, deltaW): GMRES on ankMult with the factor slot as right preconditioner, from zero; returns
+        """KSPSolve(ANK_KSP, rVec, deltaW): GMRES on ankMult with the selected factor slot as right preconditioner, from zero; returns
         (x, iterations, initial residual norm, true residual norm of x)"""
         b = np.ascontiguousarray(b, dtype=np.float64)
         x = np.zeros_like(b)
@@ -297,29 +321,50 @@ class Engine:
                                                     float(rtol), float(atol), ctypes.byref(its), ctypes.byref(r0), ctypes.byref(rn)))
         return int(its.value), float(r0.value), float(rn.value)
 
-    def ankPhysicalityCheck(self, w, dw, lambda0=1.0, coupled=False, physLSTol=0.2, physLSTolTurb=0.99, stepFactor=1.0, stepMin=0.01):
-        """physicalityCheckANK: returns (lambda, dw with the clipped turbulence entries)"""
+    def ankPhysicalityCheck(self, w, dw, lambda0=1.0, coupled=False, physLSTol=0.2, physLSTolTurb=0.99, stepFactor=1.0, stepMin=0.01,
+                            turb=False):
+        """physicalityCheckANK / physicalityCheckANKTurb: returns (lambda, dw with the clipped turbulence entries)"""
         w = np.ascontiguousarray(w, dtype=np.float64)
         dw = np.array(dw, dtype=np.float64, order="C", copy=True)
         lam = ctypes.c_double(float(lambda0))
-        self._chk(self.lib.adflow_gpu_ank_physicality_check(w.ctypes.data, dw.ctypes.data, w.size, self._ankFlags(coupled), float(physLSTol),
-                                                            float(physLSTolTurb), float(stepFactor), float(stepMin), ctypes.byref(lam)))
+        self._chk(self.lib.adflow_gpu_ank_physicality_check(w.ctypes.data, dw.ctypes.data, w.size, self._ankFlags(coupled, turb=turb),
+                                                            float(physLSTol), float(physLSTolTurb), float(stepFactor), float(stepMin),
+                                                            ctypes.byref(lam)))
         return float(lam.value), dw
 
+    def ankUnsteadyRes(self, dW, omega, coupled=False, turb=False, dissApprox=False, viscApprox=False, useBlockettes=False, approxSA=False,
+                       turbFirstOrder=False):
+        """computeUnsteadyResANK / ...Turb on the state ankSetW left: returns (R(w) - omega T dW, its 2-norm)"""
+        dW = np.ascontiguousarray(dW, dtype=np.float64)
+        r = np.zeros_like(dW)
+        nrm = ctypes.c_double(0.0)
+        flags = self._ankFlags(coupled, dissApprox, viscApprox, useBlockettes, turb, approxSA, turbFirstOrder)
+        self._chk(self.lib.adflow_gpu_ank_unsteady_res(dW.ctypes.data, float(omega), r.ctypes.data, dW.size, flags, ctypes.byref(nrm)))
+        return r, float(nrm.value)
+
+    def ankUnsteadyResDev(self, d_dW: int, omega, d_r: int, n: int, flags=0, norm=True):
+        """the same on device pointers; norm=False skips the reduction (and the synchronisation) and returns None"""
+        nrm = ctypes.c_double(0.0)
+        self._chk(self.lib.adflow_gpu_ank_unsteady_res_dev(ctypes.c_void_p(d_dW), float(omega), ctypes.c_void_p(d_r), int(n), int(flags),
+                                                           ctypes.byref(nrm) if norm else None))
+        return float(nrm.value) if norm else None
+
     def ankRelease(self) -> int:
-        """frees T, the base vectors and the sums; returns the bytes released"""
+        """frees both T, the base vectors and the sums; returns the bytes released"""
         n = ctypes.c_int64(0)
         self._chk(self.lib.adflow_gpu_ank_release(ctypes.byref(n)))
         return int(n.value)
 
     def blocketteRes(self, level=1, updateIntermed=True, flowRes=True, turbRes=True, dissApprox=False, viscApprox=False,
-                     useBlockettes=False, halo=False, closures=False):
+                     useBlockettes=False, halo=False, closures=False, approxSA=False, turbFirstOrder=False):
         """halo: also the part of blocketteRes in front of the core -- boundary conditions and whalo2 (ADFLOW_RES_HALO);
         closures: and the derived values in front of those -- computePressureSimple, computeLamViscosity, computeEddyViscosity
-        (ADFLOW_RES_CLOSURES, blockette.F90:199-203).  Both = the reference's whole blocketteRes."""
+        (ADFLOW_RES_CLOSURES, blockette.F90:199-203).  Both = the reference's whole blocketteRes.  approxSA: term1 of the SA source
+        is zero (sa.F90:296); turbFirstOrder: orderTurb = firstOrder for this call only."""
         flags = (capi.RES_UPDATE_INTERMED if updateIntermed else 0) | (capi.RES_FLOW if flowRes else 0) \
             | (capi.RES_TURB if turbRes else 0) | (32 if dissApprox else 0) | (64 if viscApprox else 0) \
-            | (128 if useBlockettes else 0) | (capi.RES_HALO if halo else 0) | (capi.RES_CLOSURES if closures else 0)
+            | (128 if useBlockettes else 0) | (capi.RES_HALO if halo else 0) | (capi.RES_CLOSURES if closures else 0) \
+            | (capi.RES_APPROX_SA if approxSA else 0) | (capi.RES_TURB_FIRST_ORDER if turbFirstOrder else 0)
         self._chk(self.lib.adflow_gpu_block_res(level, flags))
 
     def bc_register(self, faces, nViscBocos: int = 0, nn: int = 1, level: int = 1, sps: int = 1):

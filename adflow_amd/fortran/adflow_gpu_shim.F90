@@ -14,9 +14,10 @@ module adflowGpuShim
     ! ---- flag bits of adflow_gpu_block_res / adflow_gpu_fd_jacobian (include/adflow_gpu.h) ----
     integer(c_int), parameter :: ADFLOW_RES_UPDATE_INTERMED = 1, ADFLOW_RES_FLOW = 2, ADFLOW_RES_TURB = 4, ADFLOW_RES_CLOSURES = 8, &
                                  ADFLOW_RES_HALO = 16, ADFLOW_RES_DISS_APPROX = 32, ADFLOW_RES_VISC_APPROX = 64, &
-                                 ADFLOW_RES_UPWIND_FIRST_ORDER = 128
+                                 ADFLOW_RES_UPWIND_FIRST_ORDER = 128, ADFLOW_RES_APPROX_SA = 1024, ADFLOW_RES_TURB_FIRST_ORDER = 2048
     integer(c_int), parameter :: ADFLOW_JAC_PC = 1, ADFLOW_JAC_FROZEN_TURB = 2, ADFLOW_JAC_TURB_ONLY = 4, ADFLOW_JAC_VISC_PC = 8, &
-                                 ADFLOW_JAC_USE_AD = 16
+                                 ADFLOW_JAC_USE_AD = 16, ADFLOW_JAC_APPROX_SA = 32
+    integer(c_int), parameter :: ADFLOW_ANK_COUPLED = 256, ADFLOW_ANK_TURB = 512
 
     ! ---- mirror of adflow_opts (include/adflow_gpu.h) -----------------------
     type, bind(C) :: adflow_opts
@@ -489,6 +490,41 @@ module adflowGpuShim
             integer(c_int), value :: flags
             real(c_double), value :: physLSTol, physLSTolTurb, stepFactor, stepMin
             real(c_double), intent(inout) :: lambda
+        end function
+        ! the turbulence T (flags = ADFLOW_ANK_TURB: (1, 1, nx, ny, nz)); the line-search residual computeUnsteadyResANK[Turb]
+        integer(c_int) function adflow_gpu_ank_download_time_step_turb(nn, blocks, flags) &
+            bind(C, name="adflow_gpu_ank_download_time_step_turb")
+            import :: c_int, c_double
+            integer(c_int), value :: nn, flags
+            real(c_double), intent(out) :: blocks(*)
+        end function
+        integer(c_int) function adflow_gpu_ank_unsteady_res(dW, omega, r, n, flags, norm) bind(C, name="adflow_gpu_ank_unsteady_res")
+            import :: c_int, c_long, c_double
+            real(c_double), intent(in) :: dW(*)
+            real(c_double), value :: omega
+            real(c_double), intent(out) :: r(*)
+            integer(c_long), value :: n
+            integer(c_int), value :: flags
+            real(c_double), intent(out) :: norm
+        end function
+        integer(c_int) function adflow_gpu_ank_unsteady_res_dev(dW, omega, r, n, flags, norm) &
+            bind(C, name="adflow_gpu_ank_unsteady_res_dev")
+            import :: c_int, c_long, c_double, c_ptr
+            type(c_ptr), value :: dW, r
+            real(c_double), value :: omega
+            integer(c_long), value :: n
+            integer(c_int), value :: flags
+            type(c_ptr), value :: norm      ! c_loc of a real(c_double), or c_null_ptr: no reduction, honours adflow_gpu_set_async
+        end function
+        ! the kind (0 or ADFLOW_ANK_TURB) whose base adflow_gpu_ank_mult / _solve act on; by default the one set last
+        integer(c_int) function adflow_gpu_ank_select_base(flags) bind(C, name="adflow_gpu_ank_select_base")
+            import :: c_int
+            integer(c_int), value :: flags
+        end function
+        ! the factor slot (0 or 1) the pc_* entries, gmres_solve and ank_solve act on
+        integer(c_int) function adflow_gpu_pc_select(slot) bind(C, name="adflow_gpu_pc_select")
+            import :: c_int
+            integer(c_int), value :: slot
         end function
         integer(c_int) function adflow_gpu_ank_release(bytes) bind(C, name="adflow_gpu_ank_release")
             import :: c_int, c_int64_t

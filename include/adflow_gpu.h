@@ -217,7 +217,13 @@ enum {
     /* with DISS_APPROX and the Roe upwind scheme the two residual cores of the reference differ: blocketteResCore (useBlockettes = T,
      * the default) calls inviscidUpwindFlux(.False.) = first-order reconstruction (blockette.F90:643), blockResCore keeps the
      * limiter (:827).  The host passes this flag when inputDiscretization::useBlockettes is set. */
-    ADFLOW_RES_UPWIND_FIRST_ORDER = 128u
+    ADFLOW_RES_UPWIND_FIRST_ORDER = 128u,
+    /* (256u and 512u are ADFLOW_ANK_COUPLED and ADFLOW_ANK_TURB, which share the flag word of the adflow_gpu_ank_* entries) */
+    /* inputDiscretization::approxSA (set by ANKStep:3848-3852, FormJacobianANK:1978, FormJacobianANKTurb:2364 while
+     * totalR > ANK_secondOrdSwitchTol totalR0): term1 of the SA source is zero (sa.F90:296, blockette.F90:1016, sa_d.f90:454/654) */
+    ADFLOW_RES_APPROX_SA = 1024u,
+    /* orderTurb = firstOrder for this call only (ANKTurbSolveKSP:3411-3412, ANKStep:3855-3856); the option is restored on return */
+    ADFLOW_RES_TURB_FIRST_ORDER = 2048u
 };
 
 /* ---- lifetime ---------------------------------------------------------- */
@@ -431,8 +437,12 @@ int adflow_gpu_abi_sizes2(int* bc_subface_bytes, int* comm_pattern_bytes);
  *                          The dual copies of the level's arrays (about 640 B per box cell) are one slab that is KEPT between calls
  *                          and freed with the blocks (adflow_gpu_block_release / _release_all) or by tuning "ad_cache" = 0; the call
  *                          fails with a message when the device has not that much memory free.
+ *   ADFLOW_JAC_APPROX_SA   the SA residual of the coloured evaluations, finite-difference and forward-mode, runs with
+ *                          ADFLOW_RES_APPROX_SA: the matrices FormJacobianANK (:1978) and FormJacobianANKTurb (:2364) assemble
+ *                          while approxSA is set.  No effect without an SA residual (Euler / NS, ADFLOW_JAC_FROZEN_TURB).
  */
-enum { ADFLOW_JAC_PC = 1u, ADFLOW_JAC_FROZEN_TURB = 2u, ADFLOW_JAC_TURB_ONLY = 4u, ADFLOW_JAC_VISC_PC = 8u, ADFLOW_JAC_USE_AD = 16u };
+enum { ADFLOW_JAC_PC = 1u, ADFLOW_JAC_FROZEN_TURB = 2u, ADFLOW_JAC_TURB_ONLY = 4u, ADFLOW_JAC_VISC_PC = 8u, ADFLOW_JAC_USE_AD = 16u,
+       ADFLOW_JAC_APPROX_SA = 32u };
 int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta);
 /* Hands back the work space an assembly keeps between calls -- the slab of dual arrays of ADFLOW_JAC_USE_AD (about 640 B per box cell:
  * 8.4 GB on the 8 x 160x128x64 mesh) -- and the scratch arrays of adflow_gpu_jacobian_mult to the device allocator: what the host calls when the matrix is assembled and the memory is
@@ -500,6 +510,10 @@ int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes);
 int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, long n);
 int adflow_gpu_pc_apply_dev(int level, int transpose, const double* d_r, double* d_z, long n);
 int adflow_gpu_pc_release(int64_t* bytes);
+/* Two factor slots (ANK_jacobianLag keeps the flow factor and the turbulence factor alive over the same steps): slot 0 or 1, default
+ * 0.  adflow_gpu_pc_setup, _ank_pc_setup, _pc_apply, _pc_info, _pc_release, _gmres_solve and _ank_solve act on the selected slot;
+ * adflow_gpu_block_release and _release_all release both.  A process that never calls it behaves as with one slot. */
+int adflow_gpu_pc_select(int slot);
 /* Restarted GMRES with the factor as RIGHT preconditioner, the KSPSolve of solveAdjoint (adjointAPI.F90:661-863) with the settings
  * of setupStandardKSP (adjointUtils.F90:1374-1562: KSPGMRES, PC_RIGHT, modified Gram-Schmidt):  A M^-1 u = b, x = M^-1 u, with
  * A = adflow_gpu_jacobian_mult on the matrix assembled last (7-, 13-, 27- or 33-point) and M = the factor of adflow_gpu_pc_setup,
@@ -566,25 +580,60 @@ int adflow_gpu_gmres_solve_dev(int level, int transpose, const double* d_b, doub
  *                          mpi_allreduce is the host's.  Synchronous (lambda goes to the host).
  * The rest of the step is the host's, on its device vectors: rVec = adflow_gpu_ank_get_r of the base state, deltaW from
  * adflow_gpu_ank_solve, lambda from adflow_gpu_ank_physicality_check, the `lambda < stepMin` rule, VecAXPY(wVec, -lambda, deltaW),
- * adflow_gpu_ank_set_w(wVec) + residual for the backtracking, the CFL ramp; INTEGRATION.md has the call sites.
+ * adflow_gpu_ank_set_w(wVec) + adflow_gpu_ank_unsteady_res for the backtracking, the CFL ramp; INTEGRATION.md has the call sites.
  * Lifetime: T, the base vectors and the sums are released by adflow_gpu_ank_release (*bytes, may be NULL: what was released),
  * adflow_gpu_block_release and adflow_gpu_release_all; adflow_gpu_release_workspace does not touch them.
- * Out of scope: approxSA (the library has no such switch: the coupled operator uses the full SA source; the decoupled operator has
- * no SA residual and is exact in this respect); the turbulence KSP of ANK (FormFunction_mf_turb, physicalityCheckANKTurb); the
- * Turkel and VLR time-step types; ANK_precondType = 'mg'; more than one rank; ILU(k > 0), RCM and ASM overlap, as above. */
-enum { ADFLOW_ANK_COUPLED = 256u };
+ * approxSA: every entry that evaluates a residual takes ADFLOW_RES_APPROX_SA (and ADFLOW_RES_TURB_FIRST_ORDER) next to the three
+ * approximate-flux flags; the matrices take ADFLOW_JAC_APPROX_SA.
+ *
+ * The turbulence KSP of the decoupled step, ANKTurbSolveKSP (:3337-3627): the same entries with ADFLOW_ANK_TURB, which excludes
+ * ADFLOW_ANK_COUPLED and needs RANS.  Vectors carry nState = nt2 - nt1 + 1 = 1 entry per owned cell, nuTilde.
+ *   adflow_gpu_ank_set_w   setWANK(wVecTurb, nt1, nt2) (:2975-3011): nuTilde of the owned cells, no clipping, nothing else.
+ *   adflow_gpu_ank_get_r   setRVecANKTurb (:2935-2973): dw(itu1) / volRef turbResScale.
+ *   adflow_gpu_ank_time_step   stores dtInv = 1 / (cfl dtl volRef) only, 8 B per cell; the diagonal is dtInv turbResScale /
+ *                          turbCFLScale (FormJacobianANKTurb :2395-2406, FormFunction_mf_turb :2588-2594).  The flow T and the
+ *                          turbulence T are kept side by side; the flag selects one on every entry.
+ *                          adflow_gpu_ank_download_time_step_turb(nn, blocks, flags): with ADFLOW_ANK_TURB the turbulence T of block
+ *                          nn, (1, 1, nx, ny, nz); with flags = 0 what adflow_gpu_ank_download_time_step hands out.
+ *   adflow_gpu_ank_pc_setup    takes the turbulence T when the assembled matrix is an ADFLOW_JAC_TURB_ONLY one (nState = 1: the scalar
+ *                          is added to the pivot, FormJacobianANKTurb), else the flow T; the errors are those above.
+ *   adflow_gpu_ank_set_base / _mult / _solve   FormFunction_mf_turb (:2540-2612): blocketteRes(useFlowRes = F, useStoreWall = F) =
+ *                          ADFLOW_RES_HALO | ADFLOW_RES_TURB with the turbulence boundary conditions and whalo2(1, nt1, nt2);
+ *                          y = (R_t(w + h v) - r0) / h + T_t v with the same MATMFFD_DS h.  The state write re-forms the eddy
+ *                          viscosity of the cell from rho, rlv and the new nuTilde (the arithmetic of computeEddyViscosity in the
+ *                          closures) and nothing else: the flow variables do not move, so the pressure and the laminar viscosity
+ *                          ON THE DEVICE MUST BE THOSE OF THE FLOW STATE (they are after any residual evaluation with closures or
+ *                          any flow entry of this section).  Each kind keeps its own base; mult and solve act on the base set last, or on the
+ *                          one adflow_gpu_ank_select_base(0 or ADFLOW_ANK_TURB) names (an error when that kind has none).
+ *   adflow_gpu_ank_physicality_check   physicalityCheckANKTurb (:3212-3335): the signed-ratio rule above on the single entry, the
+ *                          clipping of dw included; no density / energy rule.
+ * The line search: adflow_gpu_ank_unsteady_res is computeUnsteadyResANK / computeUnsteadyResANKTurb (:2614-2786).  The state is the
+ * one the caller set with adflow_gpu_ank_set_w (w - omega dW).  It evaluates blocketteRes(useTurbRes = ANK_coupled) -- with
+ * ADFLOW_ANK_TURB blocketteRes(useFlowRes = F) -- closures, boundary conditions and whalo2 included, with the real fluxes unless the
+ * approximate flags are passed, and writes r = setRVecANK / setRVec / setRVecANKTurb - omega T dW with the T of the matching kind as
+ * stored (for the flow: of the state T was formed from, as timeStepMat is in the reference), and ||r||_2 to *norm: one pass over dw,
+ * volRef, T and dW; partial sums per workgroup, added in a fixed order by one finishing workgroup, so the norm is the same from run
+ * to run.  Synchronous because of norm; norm == NULL in the _dev form skips the reduction and honours adflow_gpu_set_async.  dw on
+ * the device afterwards holds the steady residual (:2630-2633).  More than one rank with norm != NULL is an error.
+ *
+ * Out of scope: the Eisenstat-Walker, CFL-ramp and lag logic (the host's scalar code); ANK_useTurbDADI (adflow_gpu_sa_solve); the
+ * Turkel and VLR time-step types; ANK_precondType = 'mg'; more than one rank; other turbulence models; ILU(k > 0), RCM and ASM
+ * overlap, as above. */
+enum { ADFLOW_ANK_COUPLED = 256u, ADFLOW_ANK_TURB = 512u };
 int adflow_gpu_ank_set_w(const double* w, long n, unsigned flags);
 int adflow_gpu_ank_set_w_dev(const double* d_w, long n, unsigned flags);
 int adflow_gpu_ank_get_r(double* r, long n, unsigned flags);
 int adflow_gpu_ank_get_r_dev(double* d_r, long n, unsigned flags);
 int adflow_gpu_ank_time_step(int level, double cfl, double turbCFLScale, unsigned flags);
 int adflow_gpu_ank_download_time_step(int nn, double* blocks);
+int adflow_gpu_ank_download_time_step_turb(int nn, double* blocks, unsigned flags);
 int adflow_gpu_ank_pc_setup(int level);
 int adflow_gpu_ank_set_base(const double* w, long n, unsigned flags);
 int adflow_gpu_ank_set_base_dev(const double* d_w, long n, unsigned flags);
 int adflow_gpu_ank_mult(const double* v, double* y, long n);
 int adflow_gpu_ank_mult_dev(const double* d_v, double* d_y, long n);
 int adflow_gpu_ank_last_h(double* h);
+int adflow_gpu_ank_select_base(unsigned flags);
 int adflow_gpu_ank_solve(int level, const double* b, double* x, long n, int restart, int maxIts, double rtol, double atol, int* its,
                          double* rnorm0, double* rnorm);
 int adflow_gpu_ank_solve_dev(int level, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol, double atol, int* its,
@@ -593,6 +642,8 @@ int adflow_gpu_ank_physicality_check(const double* w, double* dw, long n, unsign
                                      double stepFactor, double stepMin, double* lambda);
 int adflow_gpu_ank_physicality_check_dev(const double* d_w, double* d_dw, long n, unsigned flags, double physLSTol, double physLSTolTurb,
                                          double stepFactor, double stepMin, double* lambda);
+int adflow_gpu_ank_unsteady_res(const double* dW, double omega, double* r, long n, unsigned flags, double* norm);
+int adflow_gpu_ank_unsteady_res_dev(const double* d_dW, double omega, double* d_r, long n, unsigned flags, double* norm);
 int adflow_gpu_ank_release(int64_t* bytes);
 
 #ifdef __cplusplus
