@@ -375,16 +375,21 @@ __global__ __launch_bounds__(VS_BX* VS_BY) void k_face_vectors(BlkView b)
     const long c = b.idx(i, j, k);
     const long nb = b.nbox;
     const long si = 1, sj = b.ldi, sk = b.ldk;
-    // cell centre: the mean of the eight corner nodes.  k_visc_gf takes the vector between the centres of two neighbouring cells as
-    // the difference of two of these (3 values per cell instead of the 9 of dI / dJ / dK); against the eight-term sum of
-    // fluxes.F90:2673-2690 the difference carries the rounding of |x| a few times more -- the same order as that sum's own
+    // cell centre RELATIVE TO THE BLOCK'S NODE (1, 1, 1): the mean of the eight corner nodes, each minus that node.  k_visc_gf takes the
+    // vector between the centres of two neighbouring cells as the difference of two of these (3 values per cell instead of the 9 of
+    // dI / dJ / dK) and reads nothing else of them, so the common origin drops out.  The eight-term sum of node-pair differences of
+    // fluxes.F90:2673-2690 rounds at the size of the cell; a difference of two stored centres rounds at the size of what is stored --
+    // with absolute coordinates |x| (1e3 on a production mesh against a wall spacing of 1e-6: 1e-7 of the vector), with the block's
+    // own node subtracted first the extent of the block, wherever the mesh sits
     {
         const long n0 = c - si - sj - sk;
+        const long o = b.idx(1, 1, 1);
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
             const adf_real8* xx = b.x + m * nb;
-            b.xc[c + m * nb] = 0.125 * (((xx[n0] + xx[n0 + si]) + (xx[n0 + sj] + xx[n0 + si + sj])) +
-                                        ((xx[n0 + sk] + xx[n0 + si + sk]) + (xx[n0 + sj + sk] + xx[c])));
+            const adf_real8 x0 = xx[o];
+            b.xc[c + m * nb] = 0.125 * ((((xx[n0] - x0) + (xx[n0 + si] - x0)) + ((xx[n0 + sj] - x0) + (xx[n0 + si + sj] - x0))) +
+                                        (((xx[n0 + sk] - x0) + (xx[n0 + si + sk] - x0)) + ((xx[n0 + sj + sk] - x0) + (xx[c] - x0))));
         }
     }
     if (i > b.il || j > b.jl || k > b.kl) return;

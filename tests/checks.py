@@ -25,6 +25,57 @@ def ref_bind(blk, prm):
     return b
 
 
+SHIFT = (1024.0, -2048.0, 512.0)
+
+
+def _quantised(x, q):
+    """x rounded to multiples of 2^-q"""
+    return np.asfortranarray(np.round(np.asarray(x) * 2.0 ** q) / 2.0 ** q)
+
+
+def translated_pair(blk, q=40, T=SHIFT):
+    """A mesh and its EXACT translate.  blk: a block of make_block(..., origin = 0).  Its nodes are rounded to multiples of 2^-q and
+    the metrics re-formed from the rounded nodes; the second block has the nodes x + T and every other array identical (bit for
+    bit).  For nodes that are multiples of 2^-q and |x| + |T| < 2^(53-q) the sum x + T is exact in fp64, so every difference of two
+    nodes -- all the reference's residual reads of x -- is the same number on both meshes: the reference's output on the shifted
+    block equals its output on the unshifted one, and any change of the library's output between the two is the library's error.
+    (Checks that ADD eight coordinates before they subtract -- cell centroids of volume_block, the wall distance -- need three more
+    bits: q = 36.)  Returns (unshifted, shifted)."""
+    from adflow_amd.synth import face_metrics, cell_volumes
+    if q is None:
+        q = 40
+    T = np.asarray(SHIFT if T is None or T is True else T, dtype=np.float64)
+    b0 = blk.copy()
+    x = _quantised(blk["x"], q)
+    sgn = 1.0 if blk.rightHanded else -1.0
+    sI, sJ, sK = (np.asfortranarray(sgn * s) for s in face_metrics(x))
+    vol = cell_volumes(x)
+    b0["x"], b0["sI"], b0["sJ"], b0["sK"], b0["vol"] = x, sI, sJ, sK, vol
+    b0["volRef"] = vol.copy(order="F")
+    b1 = b0.copy()
+    b1["x"] = np.asfortranarray(x + T)
+    assert np.array_equal(b1["x"] - T, x), "the translation is not exact: fewer bits (q) or a smaller T"
+    for n in b0.a:
+        if n != "x":
+            assert np.array_equal(b0[n], b1[n])
+    return b0, b1
+
+
+def _make_block(*dims_prm, translate=None, quantise=None, **mk):
+    """make_block; with translate = T (True: SHIFT) and / or quantise = q the SHIFTED block of translated_pair"""
+    blk = make_block(*dims_prm, **mk)
+    if translate is None and quantise is None:
+        return blk
+    assert tuple(mk.get("origin", (0.0, 0.0, 0.0))) == (0.0, 0.0, 0.0)
+    return translated_pair(blk, quantise, translate)[1]
+
+
+def assert_translation_invariant(a0, a1, what, tol=1e-14):
+    """the fixture's precondition: the REFERENCE's output on the shifted mesh is its output on the unshifted one"""
+    e = rel_err(np.asarray(a1), np.asarray(a0))
+    assert e <= tol, ("the reference is not translation invariant on this input: narrow the input", what, e)
+
+
 def assert_dw(blk, dw_gpu, dw_ref, nvar=5, tol=TOL, what="dw"):
     for l in range(nvar):
         e = rel_err(owned(blk, dw_gpu[..., l]), owned(blk, dw_ref[..., l]))
@@ -33,17 +84,27 @@ def assert_dw(blk, dw_gpu, dw_ref, nvar=5, tol=TOL, what="dw"):
         assert el <= max(LOCAL_TOL, 1e4 * tol), (what, "local measure", l, el)
 
 
-def check_block_res(engine, dims, prm, seed=1, blk=None, **mk):
+def check_block_res(engine, dims, prm, seed=1, blk=None, translate=None, quantise=None, **mk):
     """blocketteRes core (timeStep + initres + fluxes + sum) vs blockResCore of
-    the reference (blockette.F90:755-852).  blk: a prepared block instead of make_block(dims, ...)."""
+    the reference (blockette.F90:755-852).  blk: a prepared block instead of make_block(dims, ...).
+    translate / quantise: on the shifted block of translated_pair (reference and library both); then also: the reference's dw on
+    the shifted block is its dw on the unshifted one (the fixture's precondition), and the library's dw on the two agree to TOL."""
     from oracle import ref
     lvl = new_level(engine)
     prm = prm.replace(currentLevel=lvl, groundLevel=lvl)
     if blk is None:
         blk = make_block(*dims, prm, seed=seed, **mk)
-    r = ref_bind(blk, prm)
     turb = prm.equations == RANSEquations
+    blk0 = None
+    if translate is not None or quantise is not None:
+        blk0, blk = translated_pair(blk, quantise, translate)
+        r0 = ref_bind(blk0, prm)
+        ref.block_res_core(True, True, turb)
+    r = ref_bind(blk, prm)
     ref.block_res_core(True, True, turb)
+    if blk0 is not None:
+        for l in range(blk.nw):
+            assert_translation_invariant(owned(blk, r0["dw"][..., l]), owned(blk, r["dw"][..., l]), ("dw", l))
     engine.set_options(prm)
     engine.register(blk, nn=1, level=lvl)
     engine.blocketteRes(level=lvl, updateIntermed=True, flowRes=True, turbRes=turb)
@@ -58,6 +119,12 @@ def check_block_res(engine, dims, prm, seed=1, blk=None, **mk):
         else:
             e = rel_err(out, r[name])
         assert e <= TOL, (name, e)
+    if blk0 is not None:
+        dw1 = dw.copy()
+        new_level(engine)
+        engine.register(blk0, nn=1, level=lvl)
+        engine.blocketteRes(level=lvl, updateIntermed=True, flowRes=True, turbRes=turb)
+        assert_dw(blk, dw1, engine.download_residual(1, lvl), blk.nw, what="dw on the shifted block vs dw on the unshifted block")
     return blk, r
 
 
@@ -491,21 +558,54 @@ def check_coordinate_halos_brick(engine, topo, prm, seed=83, **mk):
     """xhalo_block (adjointExtra.F90:365-599) + exchangeCoor (haloExchange.F90:2456-2640) + volume / metric on a periodic
     brick of blocks after the owned nodes moved: the front part of the `useSpatial` branch of blocketteRes."""
     from oracle import ref
+    translate, quantise = mk.get("translate"), mk.get("quantise")
+    shifted = translate is not None or quantise is not None
     blocks, rblocks = setup_brick(engine, topo, prm, seed, **mk)
     npat = topo.patterns(0)[0]
-    ref.set_internal_comm(1, 0, npat)
     engine.comm_register(1, 0, npat)
     _warp_owned_nodes(blocks, seed)
+
+    def reference(rb):
+        ref.set_internal_comm(1, 0, npat)
+        for nn in sorted(rb):
+            ref.call_level("setPointers", 1, nn)
+            ref.call("xhalo_block")
+        ref.call_level("exchangeCoor", 1)
+        for nn in sorted(rb):
+            ref.call_level("setPointers", 1, nn)
+            ref.call("volume_block")
+            ref.call("metric_block")
+
+    geo0 = None
+    if shifted:
+        # the warped nodes quantised again about the shift (q = 36: volume_block adds eight coordinates); the reference's own
+        # sequence on the unshifted nodes first
+        T = np.asarray(SHIFT if translate is None or translate is True else translate)
+        q = 36 if quantise is None else quantise
+        r0 = {}
+        for nn in blocks:
+            x0 = _quantised(blocks[nn]["x"] - T, q)
+            blocks[nn]["x"][...] = x0 + T
+            assert np.array_equal(blocks[nn]["x"] - T, x0)
+            r0[nn] = rblocks[nn].copy()
+            r0[nn]["x"][...] = x0
+        ref.bind_blocks(r0, prm.replace(currentLevel=1, groundLevel=1))
+        reference(r0)
+        geo0 = {nn: {n: r0[nn][n].copy() for n in ("vol", "sI", "sJ", "sK")} for nn in r0}
+        ref.bind_blocks(rblocks, prm.replace(currentLevel=1, groundLevel=1))
+        for L in (1, 2):
+            ref.set_internal_comm(1, L, topo.patterns(L)[0])
     for nn in blocks:
         rblocks[nn]["x"][...] = blocks[nn]["x"]
-    for nn in sorted(rblocks):
-        ref.call_level("setPointers", 1, nn)
-        ref.call("xhalo_block")
-    ref.call_level("exchangeCoor", 1)
-    for nn in sorted(rblocks):
-        ref.call_level("setPointers", 1, nn)
-        ref.call("volume_block")
-        ref.call("metric_block")
+    reference(rblocks)
+    if geo0 is not None:
+        for nn in geo0:
+            assert_translation_invariant(r0[nn]["x"][1:-1, 1:-1, 1:-1] + T, rblocks[nn]["x"][1:-1, 1:-1, 1:-1], (nn, "x"))
+            for n in geo0[nn]:
+                a0, a1 = geo0[nn][n], rblocks[nn][n]
+                if n == "vol":
+                    a0, a1 = a0[1:-1, 1:-1, 1:-1], a1[1:-1, 1:-1, 1:-1]
+                assert_translation_invariant(a0, a1, (nn, n))
     for nn in sorted(blocks):
         engine.upload_coordinates(nn, 1)
     engine.xhalo(1)
@@ -691,7 +791,7 @@ def check_wall_stress(engine, dims, prm, spec, split=(), seed=57, dadi=False, **
     from adflow_amd.synth import make_bocos
     new_level(engine)
     prm = prm.replace(currentLevel=1, groundLevel=1)
-    blk = make_block(*dims, prm, seed=seed, **mk)
+    blk = _make_block(*dims, prm, seed=seed, **mk)          # (mk: translate / quantise -> the shifted block of translated_pair)
     faces, nvisc = make_bocos(blk, prm, spec, seed=seed + 1, split=split)
     assert nvisc > 0
     r = blk.copy()
@@ -718,7 +818,7 @@ def check_wall_stress(engine, dims, prm, spec, split=(), seed=57, dadi=False, **
     assert_dw(blk, dw, r["dw"], 5, what="dw with wall stress storage")
 
 
-def check_update_geometry(engine, dims, prm, spec, seed=81, **mk):
+def check_update_geometry(engine, dims, prm, spec, seed=81, translate=None, quantise=None, **mk):
     """volume_block + metric_block + boundaryNormals (adjointExtra.F90:5-364) after the nodes moved: vol, sI/sJ/sK
     and - through a boundary-condition pass that reads them - the unit normals of the boundary subfaces."""
     from oracle import ref
@@ -734,6 +834,16 @@ def check_update_geometry(engine, dims, prm, spec, seed=81, **mk):
     rng = np.random.default_rng(seed)
     h = 1.0 / max(dims)
     blk["x"] += 0.05 * h * rng.uniform(-1, 1, blk["x"].shape)
+    geo0 = None
+    if translate is not None or quantise is not None:
+        # the warped nodes quantised (volume_block adds eight coordinates: q = 36) and shifted; the reference on the unshifted nodes first
+        b0, b1 = translated_pair(blk, 36 if quantise is None else quantise, translate)
+        r0 = b0.copy()
+        ref.bind_block(r0, prm)
+        ref.call("volume_block")
+        ref.call("metric_block")
+        geo0 = {n: r0[n].copy() for n in ("vol", "sI", "sJ", "sK")}
+        blk["x"][...] = b1["x"]
     r = blk.copy()
     rfaces = [dict(f, norm=f["norm"].copy(order="F")) for f in faces]
     ref.bind_block(r, prm)
@@ -741,6 +851,9 @@ def check_update_geometry(engine, dims, prm, spec, seed=81, **mk):
     ref.call("volume_block")
     ref.call("metric_block")
     ref.call("boundaryNormals")
+    if geo0 is not None:
+        for n in geo0:
+            assert_translation_invariant(geo0[n], r[n], n)
     engine.upload_coordinates(1, 1)
     engine.update_geometry(1)
     for which, name in ((capi.ARR_VOL, "vol"), (capi.ARR_SI, "sI"), (capi.ARR_SJ, "sJ"), (capi.ARR_SK, "sK")):
@@ -757,9 +870,13 @@ def check_update_geometry(engine, dims, prm, spec, seed=81, **mk):
     assert_state(engine, {1: blk}, {1: r}, prm, "BCs with the recomputed boundary normals")
 
 
-def check_wall_distance(engine, dims, prm, seed=83, **mk):
+def check_wall_distance(engine, dims, prm, seed=83, at_wall=False, translate=None, quantise=None, **mk):
     """wallDistance::updateWallDistancesQuickly (wallDistance.F90:36-120) after a mesh warp: d2Wall of the owned cells from the
-    wall association (four surface nodes + (u, v) per cell, cells without a wall in reach = large) and the moved surface nodes."""
+    wall association (four surface nodes + (u, v) per cell, cells without a wall in reach = large) and the moved surface nodes.
+    at_wall: the surface is the block's own kMin node plane and every cell is associated with the quad under it, (u, v) from
+    {0, 1/2, 1}: distances from half the wall spacing upward; the nodes -- and the surface with them -- quantised (q = 36: the cell
+    centre adds eight coordinates) and shifted as in translated_pair, so that the reference's bilinear point, centre and difference
+    are exact and its result on the shifted mesh is its result on the unshifted one (asserted)."""
     from oracle import ref
     new_level(engine)
     prm = prm.replace(currentLevel=1, groundLevel=1)
@@ -767,6 +884,44 @@ def check_wall_distance(engine, dims, prm, seed=83, **mk):
     engine.set_options(prm)
     engine.register(blk, nn=1, level=1)
     rng = np.random.default_rng(seed)
+    if at_wall:
+        il, jl = blk.il, blk.jl
+        ci, cj = np.meshgrid(np.arange(blk.nx), np.arange(blk.ny), indexing="ij")
+        node = lambda i, j: (j - 1) * il + i                                   # surface node of the mesh node (i, j, 1), 1-based
+        quad = np.stack([node(ci + 1, cj + 1), node(ci + 2, cj + 1), node(ci + 2, cj + 2), node(ci + 1, cj + 2)]).astype(np.int32)
+        ind = np.asfortranarray(np.repeat(quad[:, :, :, None], blk.nz, axis=3))
+        ind[0][rng.uniform(size=ind.shape[1:]) < 0.1] = 0
+        uv = np.asfortranarray(rng.integers(0, 3, size=(2, blk.nx, blk.ny, blk.nz)) * 0.5)
+        engine.registerWallAssociation(ind, uv)
+        # the warp moves whole k columns of nodes: the wall spacing stays what the clustering made it
+        blk["x"] += 0.01 * rng.uniform(-1, 1, (blk.ie + 1, blk.je + 1, 1, 3))
+        b0, b1 = translated_pair(blk, 36 if quantise is None else quantise, translate)
+        surf = lambda b: np.ascontiguousarray(b["x"][1:il + 1, 1:jl + 1, 1, :].transpose(1, 0, 2)).reshape(-1)
+        ref.alloc_doms(1, 1)
+        r0 = b0.copy()
+        ref.bind_block(r0, prm)
+        r0["d2Wall"][...] = -1.0
+        ref.update_wall_distances(ind, uv, surf(b0))
+        blk["x"][...] = b1["x"]
+        xSurf = surf(b1)
+        r = blk.copy()
+        ref.bind_block(r, prm)
+        r["d2Wall"][...] = -1.0
+        ref.update_wall_distances(ind, uv, xSurf)
+        far = r["d2Wall"] >= 1e37
+        assert_translation_invariant(np.where(far, 0.0, r0["d2Wall"]), np.where(far, 0.0, r["d2Wall"]), "d2Wall")
+        engine.upload_coordinates(1, 1)
+        engine.updateWallDistancesQuickly(xSurf, 1)
+        out = np.zeros_like(r["d2Wall"])
+        engine.download_array(capi.ARR_D2WALL, out, 1, 1)
+        assert (r["d2Wall"] >= 1e37).sum() == (ind[0] == 0).sum() > 0
+        assert np.array_equal(out >= 1e37, far)
+        assert rel_err(np.where(far, 0.0, out), np.where(far, 0.0, r["d2Wall"])) <= TOL
+        # ... and cell by cell: the global measure is set by the cells far from the wall
+        near = np.where(far, 1.0, r["d2Wall"])
+        assert (np.abs(np.where(far, 1.0, out) - near) / near).max() <= TOL
+        assert 0.0 < r["d2Wall"].min() < 0.05 * np.where(far, 0.0, r["d2Wall"]).max()
+        return
     nsurf = 57
     ind = np.asfortranarray(rng.integers(1, nsurf + 1, size=(4, blk.nx, blk.ny, blk.nz), dtype=np.int32))
     ind[0][rng.uniform(size=ind.shape[1:]) < 0.1] = 0                       # too far away: no association
@@ -815,6 +970,7 @@ def make_brick(topo, prm, seed=1, rank=0, **mk):
     """Blocks of `rank` in a BrickTopology with halos made consistent by the
     same-process copy lists (valid when all blocks live on one rank)."""
     from adflow_amd.topology import apply_local_copies_fast
+    translate, quantise = mk.pop("translate", None), mk.pop("quantise", None)
     lid = topo.local_ids()
     blocks = {}
     for g in topo.blocks_of(rank):
@@ -822,6 +978,8 @@ def make_brick(topo, prm, seed=1, rank=0, **mk):
             blocks[lid[g]] = topo.make_block(g, prm, seed=seed + 17 * g, **mk)
         else:
             blocks[lid[g]] = make_block(topo.nx, topo.ny, topo.nz, prm, seed=seed + 17 * g, **mk)
+        if translate is not None or quantise is not None:      # every block the shifted one of translated_pair (shared nodes stay shared)
+            blocks[lid[g]] = translated_pair(blocks[lid[g]], quantise, translate)[1]
     return blocks
 
 
@@ -1276,7 +1434,7 @@ def setup_block_with_bc(engine, dims, prm, spec, seed, **mk):
     from adflow_amd.topology import CommPattern
     lvl = new_level(engine)
     prm = prm.replace(currentLevel=1, groundLevel=1)
-    blk = make_block(*dims, prm, seed=seed, **mk)
+    blk = _make_block(*dims, prm, seed=seed, **mk)          # (mk: translate / quantise -> the shifted block of translated_pair)
     faces, nvisc = make_bocos(blk, prm, spec, seed=seed + 1)
     r = blk.copy()
     ref.alloc_doms(1, 1)

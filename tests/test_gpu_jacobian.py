@@ -208,3 +208,33 @@ def test_pc_rans_larger_block(engine):
     approximate residual, the scatter through the LDS column with partial rows"""
     rans = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda)
     checks.check_fd_jacobian(engine, (70, 24, 40), rans, WALL, stretch_k=2.0)
+
+
+# ---- meshes far from the origin: the assemblies on the shifted block of checks.translated_pair (nodes quantised, then moved by
+#      (1024, -2048, 512) exactly), clustered to a wall spacing of 1.65e-5, viscous part as large as the inviscid one.  The exact
+#      linearisation runs the dual-number k_visc_gf, which takes its centre-to-centre vectors from the stored cell centres.
+TRANSLATED_DIMS = [(70, 9, 12), (63, 6, 9)]        # (most of the time is the reference's own forward mode: the second shape is kept flat)
+_FAR_MESH = dict(stretch_k=11.0, translate=True)
+
+
+def translated_jacobian_case(engine, dims, which):
+    rans = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda, muSuthDim=1.0)
+    if which == "ad_exact":
+        checks.check_ad_jacobian(engine, dims, rans, WALL, usePC=False, **_FAR_MESH)
+    elif which == "ad_viscpc":
+        checks.check_ad_jacobian(engine, dims, rans.replace(spaceDiscr=dissScalar), WALL, viscPC=True, **_FAR_MESH)
+    elif which == "ad_exact_qcr":
+        checks.check_ad_jacobian(engine, dims, rans.replace(useQCR=True), OPEN, usePC=False, **_FAR_MESH)
+    elif which == "fd_viscpc":
+        checks.check_fd_jacobian(engine, dims, rans.replace(spaceDiscr=dissScalar), WALL, viscPC=True, **_FAR_MESH)
+    else:
+        raise ValueError(which)
+
+
+TRANSLATED_JACOBIANS = ["ad_exact", "ad_viscpc", "ad_exact_qcr", "fd_viscpc"]
+
+
+@pytest.mark.parametrize("which", TRANSLATED_JACOBIANS)
+@pytest.mark.parametrize("dims", TRANSLATED_DIMS)
+def test_translated_jacobian(engine, dims, which):
+    translated_jacobian_case(engine, dims, which)

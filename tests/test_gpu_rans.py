@@ -363,3 +363,61 @@ def test_wall_bounded_brick_through_rccl_self_and_split(engine):
             assert n == 4
     finally:
         engine.set_tuning("comm_self", 0)
+
+
+# ---- meshes far from the origin: the exact translate of a quantised mesh (checks.translated_pair).  The reference's residual on the
+#      shifted block is bit for bit its residual on the unshifted one, so whatever the library's result moves by is the library's
+#      rounding of |x| where the reference rounds the wall spacing.  muSuthDim = 1: the viscous part cannot hide; stretch_k = 8 / 11:
+#      smallest spacing 2.2e-4 / 1.65e-5 of the block.  Shapes: a partial 64-column tile with a partial 4-row tile; 63 wide, 35 planes.
+TRANSLATED_DIMS = [(70, 9, 12), (63, 6, 35)]
+
+
+def translated_block_res_cases(engine, dims, eq, stretch_k):
+    for sd in (upwind, dissScalar, dissMatrix):
+        prm = FlowParams(equations=eq, spaceDiscr=sd, vis4=0.1 if sd == dissMatrix else 0.0156, muSuthDim=1.0)
+        checks.check_block_res(engine, dims, prm, seed=70 + sd, stretch_k=stretch_k, translate=True)
+    if eq == RANSEquations:
+        prm = FlowParams(equations=eq, spaceDiscr=upwind, muSuthDim=1.0)
+        checks.check_block_res(engine, dims, prm.replace(useQCR=True), seed=74, stretch_k=stretch_k, translate=True)
+        checks.check_block_res(engine, dims, prm, seed=75, stretch_k=stretch_k, translate=True, holes=0.05)
+
+
+@pytest.mark.parametrize("stretch_k", [8.0, 11.0])
+@pytest.mark.parametrize("eq", [NSEquations, RANSEquations])
+@pytest.mark.parametrize("dims", TRANSLATED_DIMS)
+def test_translated_block_res(engine, dims, eq, stretch_k):
+    translated_block_res_cases(engine, dims, eq, stretch_k)
+
+
+def translated_viscous_forms_case(engine, dims):
+    """both viscous forms on the shifted block: the gather pair (viscous_tiled = 0) takes the centre-to-centre vectors from node
+    differences like the reference; the marching form (2, the default) from the stored cell centres"""
+    try:
+        for vt in (2, 0):
+            engine.set_tuning("viscous_tiled", vt)
+            for eq in (NSEquations, RANSEquations):
+                prm = FlowParams(equations=eq, spaceDiscr=upwind, muSuthDim=1.0)
+                checks.check_block_res(engine, dims, prm, seed=76 + vt, stretch_k=11.0, translate=True)
+    finally:
+        engine.set_tuning("viscous_tiled", 2)
+
+
+@pytest.mark.parametrize("dims", TRANSLATED_DIMS)
+def test_translated_both_viscous_forms(engine, dims):
+    translated_viscous_forms_case(engine, dims)
+
+
+FAR_ORIGIN = (1e3, -2e3, 5e2)
+
+
+def far_origin_unquantised_case(engine, dims):
+    """the analytic mesh itself at origin = (1e3, -2e3, 5e2), stretch_k = 12 (smallest spacing 6.8e-6), default viscosity: here
+    the reference is not exact either (its node differences carry the nodes' own rounding of |x|); the bars are the project's.
+    Measured worst errors of this case: DESIGN.md, "Correction (meshes far from the origin)" under round 6."""
+    for eq in (NSEquations, RANSEquations):
+        checks.check_block_res(engine, dims, FlowParams(equations=eq, spaceDiscr=upwind), seed=78, stretch_k=12.0, origin=FAR_ORIGIN)
+
+
+@pytest.mark.parametrize("dims", TRANSLATED_DIMS)
+def test_far_origin_unquantised(engine, dims):
+    far_origin_unquantised_case(engine, dims)

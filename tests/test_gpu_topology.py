@@ -77,3 +77,16 @@ def test_mg_cycle_rotated_interfaces(engine):
     checks.check_mg_cycle(engine, ell_topology(), FlowParams(), [0, 1, 0, -1], brick_spec={1: -6, 2: -6, 3: -1, 4: -6, 5: -5, 6: -6})
     rans = FlowParams(equations=RANSEquations, smoother=DADI, resAveraging=noResAveraging, cfl=1.5, nSubiterations=2, nSubIterTurb=2)
     checks.check_mg_cycle(engine, ell_topology(stretch_z=2.0), rans, [0, 1, 0, -1], ncycles=1, brick_spec=WALLS)
+
+
+def translated_rotated_interfaces_case(engine):
+    """blocks of different sizes and orientations inside one analytic map, far from the origin (checks.translated_pair on every block:
+    shared nodes stay shared): xhalo + exchangeCoor + metrics, and the whole blocketteRes with walls"""
+    checks.check_coordinate_halos_brick(engine, ell_topology(), FlowParams(), translate=True)
+    walls = {1: -6, 2: -6, 3: -1, 4: -6, 5: -3, 6: -6}
+    rans = FlowParams(equations=RANSEquations, spaceDiscr=upwind, muSuthDim=1.0)
+    assert checks.check_blockette_res_with_bc(engine, ell_topology(stretch_z=8.0), rans, walls, translate=True) == 2
+
+
+def test_translated_rotated_interfaces(engine):
+    translated_rotated_interfaces_case(engine)

@@ -666,6 +666,54 @@ def test_random_parity_sweep(hostsim_engine):
     assert failure is None, failure
 
 
+# ---- meshes far from the origin (GPU twins in test_gpu_rans.py / _jacobian.py / _bc.py / _topology.py): 8 x 6 x 16 blocks
+_FAR_DIMS = (8, 6, 16)
+
+
+@pytest.mark.parametrize("stretch_k", [8.0, 11.0])
+@pytest.mark.parametrize("eq", [NSEquations, RANSEquations])
+def test_translated_block_res(hostsim_engine, eq, stretch_k):
+    import test_gpu_rans
+    test_gpu_rans.translated_block_res_cases(hostsim_engine, _FAR_DIMS, eq, stretch_k)
+
+
+def test_translated_both_viscous_forms(hostsim_engine):
+    import test_gpu_rans
+    test_gpu_rans.translated_viscous_forms_case(hostsim_engine, _FAR_DIMS)
+
+
+def test_far_origin_unquantised(hostsim_engine):
+    import test_gpu_rans
+    test_gpu_rans.far_origin_unquantised_case(hostsim_engine, _FAR_DIMS)
+
+
+@pytest.mark.parametrize("which", ["ad_exact", "ad_viscpc", "ad_exact_qcr", "fd_viscpc"])
+def test_translated_jacobian(hostsim_engine, which):
+    import test_gpu_jacobian as tj
+    tj.translated_jacobian_case(hostsim_engine, _FAR_DIMS, which)
+
+
+def test_translated_wall_bounded(hostsim_engine):
+    import test_gpu_bc
+    test_gpu_bc.translated_wall_bounded_case(hostsim_engine, _FAR_DIMS)
+
+
+def test_translated_geometry_and_wall_distance(hostsim_engine):
+    import test_gpu_bc
+    test_gpu_bc.translated_geometry_case(hostsim_engine, _FAR_DIMS)
+
+
+def test_translated_coordinate_halos(hostsim_engine):
+    import test_gpu_bc
+    test_gpu_bc.translated_coordinate_halos_case(hostsim_engine, _FAR_DIMS, (1, 1, 2))
+    test_gpu_bc.translated_coordinate_halos_case(hostsim_engine, _FAR_DIMS, (2, 1, 1))
+
+
+def test_translated_rotated_interfaces(hostsim_engine):
+    import test_gpu_topology
+    test_gpu_topology.translated_rotated_interfaces_case(hostsim_engine)
+
+
 def test_documented_tuning_keys_are_the_library_s(hostsim_engine):
     """DESIGN.md 8b lists the tuning keys with their defaults: every one of them is accepted (set to its default), an unknown key is
     refused -- the table and adflow_gpu_set_tuning stay in step"""
