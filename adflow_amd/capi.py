@@ -157,6 +157,7 @@ EXPORTS = [
     "adflow_gpu_fd_jacobian", "adflow_gpu_release_workspace", "adflow_gpu_selftest_math", "adflow_gpu_jacobian_info", "adflow_gpu_download_jacobian", "adflow_gpu_download_jacobian_rows",
     "adflow_gpu_jacobian_mult", "adflow_gpu_jacobian_mult_dev",
     "adflow_gpu_pc_setup", "adflow_gpu_pc_info", "adflow_gpu_pc_apply", "adflow_gpu_pc_apply_dev", "adflow_gpu_pc_release", "adflow_gpu_pc_select",
+    "adflow_gpu_pc_set_fill", "adflow_gpu_pc_info2",
     "adflow_gpu_gmres_solve", "adflow_gpu_gmres_solve_dev",
     "adflow_gpu_ank_set_w", "adflow_gpu_ank_set_w_dev", "adflow_gpu_ank_get_r", "adflow_gpu_ank_get_r_dev", "adflow_gpu_ank_time_step",
     "adflow_gpu_ank_download_time_step", "adflow_gpu_ank_pc_setup", "adflow_gpu_ank_set_base", "adflow_gpu_ank_set_base_dev",
@@ -246,6 +247,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     for f in (lib.adflow_gpu_ank_unsteady_res, lib.adflow_gpu_ank_unsteady_res_dev):
         f.argtypes = [c_void_p, c_double, c_void_p, ctypes.c_long, c_uint, POINTER(c_double)]
     lib.adflow_gpu_pc_select.argtypes = [c_int]
+    lib.adflow_gpu_pc_set_fill.argtypes = [c_int]
+    lib.adflow_gpu_pc_info2.argtypes = [POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), POINTER(ctypes.c_int32)]
     lib.adflow_gpu_ank_select_base.argtypes = [c_uint]
     lib.adflow_gpu_set_tuning.argtypes = [c_char_p, c_int]
     lib.adflow_gpu_abi_sizes.argtypes = [POINTER(c_int), POINTER(c_int)]

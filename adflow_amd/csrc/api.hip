@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <array>
 #include <map>
 #include <string>
 #include <tuple>
@@ -4016,7 +4017,8 @@ int adflow_gpu_jacobian_mult(int level, int transpose, const double* x, double* 
 namespace {
 struct PcFactor {
     bool valid = false;
-    int level = 0, nState = 0, nPlanes = 0;
+    int level = 0, nState = 0, nPlanes = 0;      // nPlanes: hyperplanes at fill 0, dependency level sets at fill 1 and 2
+    int fill = 0, nEnt = 7;                        // levels of fill the factor was built with and its entries per row
     long ncell = 0;
     size_t bytes = 0;
     std::vector<void*> raw;
@@ -4025,6 +4027,7 @@ struct PcFactor {
 };
 PcFactor g_pc_slots[2];              // adflow_gpu_pc_select: e.g. the flow factor and the turbulence factor of ANK_jacobianLag
 int g_pc_slot = 0;
+int g_pc_fill[2] = {0, 0};           // adflow_gpu_pc_set_fill: the fill the next setup of each slot uses (outlives the factors)
 static PcFactor& pc_sel() { return g_pc_slots[g_pc_slot]; }
 struct DevBuf {                       // a device allocation that lives as long as one call
     void* p = nullptr;
@@ -4060,9 +4063,168 @@ int adflow_gpu_pc_select(int slot)
 static int pc_alloc(void** p, size_t bytes)
 {
     *p = nullptr;
-    HIPCHK(hipMalloc(p, bytes));
+    if (hipMalloc(p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return fail("pc_setup: cannot allocate %zu bytes (%.1f MB) for the factor of fill %d; %zu bytes of it are held, no factor is "
+                    "kept", bytes, bytes / 1048576.0, g_pc_fill[g_pc_slot], pc_sel().bytes);
+    }
     pc_sel().raw.push_back(*p);
     pc_sel().bytes += bytes;
+    return 0;
+}
+
+// ---- fill 1 and 2 (kernels_pc_fill.hip) ---------------------------------------------------------------------------------------
+// The level-of-fill pattern of a 7-point stencil in the natural ordering, in offset space: level(d) = min over a lower offset a and an
+// upper offset b with a + b = d of level(a) + level(b) + 1, kept while <= fill (the symbolic ILU(k) of an unbounded grid; inside a
+// block the pattern is this stencil cut at the faces for fill <= 2).  off[]: the offsets (di, dj, dk) in ascending column order,
+// lower entries first, the diagonal in the middle.  Returns the number of entries.
+static int pc_fill_offsets(int fill, std::vector<std::array<int, 3>>& off)
+{
+    typedef std::array<int, 3> O;                  // (dk, dj, di): compares as the natural ordering does
+    std::map<O, int> lev;
+    lev[O{0, 0, 0}] = 0;
+    for (int a = 0; a < 3; ++a)
+        for (int sg = -1; sg <= 1; sg += 2) {
+            O o{0, 0, 0};
+            o[a] = sg;
+            lev[o] = 0;
+        }
+    const O zero{0, 0, 0};
+    for (bool changed = true; changed;) {
+        changed = false;
+        const std::map<O, int> was = lev;
+        for (auto& lo : was)
+            for (auto& up : was) {
+                if (!(lo.first < zero) || !(zero < up.first)) continue;
+                const O d{lo.first[0] + up.first[0], lo.first[1] + up.first[1], lo.first[2] + up.first[2]};
+                const int l = lo.second + up.second + 1;
+                if (l > fill) continue;
+                auto it = lev.find(d);
+                if (it == lev.end() || l < it->second) { lev[d] = l; changed = true; }
+            }
+    }
+    off.clear();
+    for (auto& kv : lev) off.push_back({kv.first[2], kv.first[1], kv.first[0]});
+    return (int)off.size();
+}
+
+static int pc_setup_build_fill(int level, int fill, const int* sten7, const std::vector<JmBlk>& hb, const std::vector<int>& nnOf, long N,
+                               const double* shift, double turbDiag)
+{
+    const int nS = g_jac.nState;
+    std::vector<std::array<int, 3>> off;
+    const int nEnt = pc_fill_offsets(fill, off), nLow = (nEnt - 1) / 2;
+    if (nEnt != (fill == 1 ? 13 : 23)) return fail("pc_setup: internal: the pattern of fill %d has %d offsets", fill, nEnt);
+    PcTab& T = pc_sel().tab;
+    memset(&T, 0, sizeof T);
+    T.ncell = N;
+    for (int q = 0; q < 7; ++q) T.sten[q] = sten7[q];
+    // slot of an entry: lower entries 0..nLow-1, upper entries nLow..2 nLow-1 (both ascending), the diagonal 2 nLow
+    auto slotOf = [&](int e) { return e < nLow ? e : e == nLow ? 2 * nLow : e - 1; };
+    auto find = [&](int di, int dj, int dk) {
+        for (int e = 0; e < nEnt; ++e)
+            if (off[e][0] == di && off[e][1] == dj && off[e][2] == dk) return e;
+        return -1;
+    };
+    for (int e = 0; e < nEnt; ++e) {
+        const auto& o = off[e];
+        const int nz = (o[0] != 0) + (o[1] != 0) + (o[2] != 0);
+        int a = -1;
+        if (nz == 0) a = sten7[6];
+        for (int ax = 0; ax < 3; ++ax)
+            if (nz == 1 && o[ax] == -1) a = sten7[ax];          // the column c - e_ax
+            else if (nz == 1 && o[ax] == 1) a = sten7[3 + ax];
+        T.asmEnt[slotOf(e)] = a;
+    }
+    for (int e = 0; e < nLow; ++e)
+        for (int u = 0; u < nLow; ++u) {
+            const auto &a = off[e], &b = off[nLow + 1 + u];
+            const int t = find(a[0] + b[0], a[1] + b[1], a[2] + b[2]);
+            T.tgt[e * nLow + u] = (signed char)(t < 0 ? -1 : slotOf(t));
+        }
+    // the dependency level sets: 1 + the highest set of a lower entry inside the block (longest path; natural order visits the lower
+    // entries of a row before the row)
+    std::vector<int> lvl(N);
+    int nSets = 0;
+    for (auto& q : hb) {
+        long nat = q.vecOff;
+        for (int k = 0; k < q.nz; ++k)
+            for (int j = 0; j < q.ny; ++j)
+                for (int i = 0; i < q.nx; ++i, ++nat) {
+                    int l = 0;
+                    for (int e = 0; e < nLow; ++e) {
+                        const int ci = i + off[e][0], cj = j + off[e][1], ck = k + off[e][2];
+                        if (ci < 0 || ci >= q.nx || cj < 0 || cj >= q.ny || ck < 0 || ck >= q.nz) continue;
+                        l = std::max(l, lvl[q.vecOff + ((long)ck * q.ny + cj) * q.nx + ci] + 1);
+                    }
+                    lvl[nat] = l;
+                    nSets = std::max(nSets, l + 1);
+                }
+    }
+    std::vector<int> start(nSets + 1, 0);
+    for (long c = 0; c < N; ++c) start[lvl[c] + 1]++;
+    for (int p = 0; p < nSets; ++p) start[p + 1] += start[p];
+    std::vector<int> cur(start.begin(), start.end() - 1), pos(N), nbr((size_t)(nEnt - 1) * N), vec(N), cblk(N), cbox(N);
+    for (size_t s = 0; s < hb.size(); ++s) {       // the order (level set, block, k, j, i)
+        const JmBlk& q = hb[s];
+        long nat = q.vecOff;
+        for (int k = 0; k < q.nz; ++k)
+            for (int j = 0; j < q.ny; ++j)
+                for (int i = 0; i < q.nx; ++i, ++nat) {
+                    const int at = cur[lvl[nat]]++;
+                    pos[nat] = at;
+                    vec[at] = (int)nat;
+                    cblk[at] = (int)s;
+                    cbox[at] = (i + 2) + (j + 2) * q.ldi + (k + 2) * q.ldk;
+                }
+    }
+    for (size_t s = 0; s < hb.size(); ++s) {
+        const JmBlk& q = hb[s];
+        long nat = q.vecOff;
+        for (int k = 0; k < q.nz; ++k)
+            for (int j = 0; j < q.ny; ++j)
+                for (int i = 0; i < q.nx; ++i, ++nat)
+                    for (int e = 0; e < nEnt; ++e) {
+                        if (e == nLow) continue;
+                        const int ci = i + off[e][0], cj = j + off[e][1], ck = k + off[e][2];
+                        const bool in = ci >= 0 && ci < q.nx && cj >= 0 && cj < q.ny && ck >= 0 && ck < q.nz;
+                        nbr[(size_t)slotOf(e) * N + pos[nat]] = in ? pos[q.vecOff + ((long)ck * q.ny + cj) * q.nx + ci] : -1;
+                    }
+    }
+    void *dn, *dv, *db, *dc, *dt, *df;
+    if (pc_alloc((void**)&T.fac, (size_t)N * nEnt * nS * nS * sizeof(double))) return 1;
+    if (pc_alloc((void**)&T.ws, (size_t)N * nS * sizeof(double))) return 1;
+    if (pc_alloc(&dn, sizeof(int) * nbr.size()) || pc_alloc(&dv, sizeof(int) * N) || pc_alloc(&db, sizeof(int) * N) ||
+        pc_alloc(&dc, sizeof(int) * N) || pc_alloc(&dt, sizeof(JmBlk) * hb.size()) || pc_alloc(&df, sizeof(int)))
+        return 1;
+    HIPCHK(hipMemcpy(dn, nbr.data(), sizeof(int) * nbr.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dv, vec.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db, cblk.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dc, cbox.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dt, hb.data(), sizeof(JmBlk) * hb.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(df, 0, sizeof(int), g_stream));
+    T.nbr = (const int*)dn; T.vec = (const int*)dv; T.cblk = (const int*)db; T.cbox = (const int*)dc;
+    T.blk = (const JmBlk*)dt; T.flag = (int*)df;
+    T.tsm = shift; T.turbDiag = turbDiag;
+    const int rcf = launch_pcf_factor(T, nS, nEnt, start, g_stream);
+    T.tsm = nullptr;                              // the sweeps do not read it, and it may be released before the factor
+    if (rcf) return 1;
+    int flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, df, sizeof(int), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    HIPCHK(hipGetLastError());
+    if (flag) {
+        const int at = flag - 1, s = cblk[at];
+        const long loc = vec[at] - hb[s].vecOff;
+        return fail("pc_setup: the pivot block of cell (%d,%d,%d) of block %d is singular or not finite (ILU(%d) in natural order, "
+                    "level %d); no factor is kept", (int)(loc % hb[s].nx) + 2, (int)(loc / hb[s].nx % hb[s].ny) + 2,
+                    (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2, nnOf[s], fill, level);
+    }
+    pc_sel().level = level; pc_sel().nState = nS; pc_sel().nPlanes = nSets; pc_sel().ncell = N;
+    pc_sel().fill = fill; pc_sel().nEnt = nEnt;
+    pc_sel().planeStart = start;
+    pc_sel().valid = true;
     return 0;
 }
 
@@ -4110,6 +4272,9 @@ static int pc_setup_build(int level, const double* shift = nullptr, double turbD
     }
     if ((double)N * nS * 8.0 >= 4294967296.0)
         return fail("pc_setup: %ld cells on level %d: a vector of the factor exceeds the 4 GiB the kernels address from one base", N, level);
+    // (the factor itself may exceed 4 GiB at any fill: its component planes are reached by 64-bit pointer arithmetic, and the 32-bit
+    // byte offset spans the N positions of one plane, which the check above covers)
+    if (g_pc_fill[g_pc_slot] > 0) return pc_setup_build_fill(level, g_pc_fill[g_pc_slot], sten, hb, nnOf, N, shift, turbDiag);
     // the hyperplane order: (i + j + k, block, k, j, i)
     std::vector<int> start(nPlanes + 1, 0);
     for (auto& q : hb)
@@ -4213,12 +4378,38 @@ int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes)
     return 0;
 }
 
+int adflow_gpu_pc_info2(int32_t* fill, int32_t* nEntries, int32_t* nLevelSets)
+{
+    if (!pc_sel().valid) return fail("pc_info2: no factor (call adflow_gpu_pc_setup first)");
+    if (fill) *fill = pc_sel().fill;
+    if (nEntries) *nEntries = pc_sel().nEnt;
+    if (nLevelSets) *nLevelSets = pc_sel().nPlanes;
+    return 0;
+}
+
+int adflow_gpu_pc_set_fill(int fill)
+{
+    if (fill < 0 || fill > 2)
+        return fail("pc_set_fill: fill %d; the block ILU takes 0, 1 or 2 levels of fill (from 3 on the pattern of a block in the natural "
+                    "ordering is no fixed stencil)", fill);
+    g_pc_fill[g_pc_slot] = fill;
+    return 0;
+}
+
 int adflow_gpu_pc_release(int64_t* bytes)
 {
     if (g_stream) HIPCHK(hipStreamSynchronize(g_stream));
     const int64_t n = pc_release();
     if (bytes) *bytes = n;
     return 0;
+}
+
+// z = M^-1 r or M^-T r with the selected factor, whatever its fill
+static int pc_apply_enqueue(int transpose, const double* r, double* z, hipStream_t s)
+{
+    const PcFactor& f = pc_sel();
+    if (f.fill > 0) return launch_pcf_apply(f.tab, f.nState, f.nEnt, transpose, f.planeStart, r, z, s);
+    return launch_pc_apply(f.tab, f.nState, transpose, f.planeStart, r, z, s);
 }
 
 static int pc_check(const char* who, int level, const double* r, const double* z, long n, bool rows = true)
@@ -4237,7 +4428,7 @@ static int pc_check(const char* who, int level, const double* r, const double* z
 int adflow_gpu_pc_apply_dev(int level, int transpose, const double* d_r, double* d_z, long n)
 {
     if (pc_check("pc_apply", level, d_r, d_z, n)) return 1;
-    if (launch_pc_apply(pc_sel().tab, pc_sel().nState, transpose, pc_sel().planeStart, d_r, d_z, g_stream)) return 1;
+    if (pc_apply_enqueue(transpose, d_r, d_z, g_stream)) return 1;
     return sync_and_check();
 }
 
@@ -4246,7 +4437,7 @@ int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, lo
     if (pc_check("pc_apply", level, r, z, n)) return 1;
     if (vec_reserve((size_t)2 * n)) return 1;
     HIPCHK(hipMemcpyAsync(g_vec_dev, r, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (launch_pc_apply(pc_sel().tab, pc_sel().nState, transpose, pc_sel().planeStart, g_vec_dev, g_vec_dev + n, g_stream)) return 1;
+    if (pc_apply_enqueue(transpose, g_vec_dev, g_vec_dev + n, g_stream)) return 1;
     HIPCHK(hipMemcpyAsync(z, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
@@ -4309,7 +4500,7 @@ static int gm_solve(const char* who, const GmOperator& op, int transpose, const 
         bool stop = false;
         for (int j = 0; j < m && !stop; ++j) {
             double* w = V + (size_t)(j + 1) * n;
-            if (launch_pc_apply(pc_sel().tab, pc_sel().nState, transpose, pc_sel().planeStart, V + (size_t)j * n, zt, s)) return 1;
+            if (pc_apply_enqueue(transpose, V + (size_t)j * n, zt, s)) return 1;
             if (op(zt, w)) return 1;
             launch_gm_mgs(w, nullptr, nullptr, V, P[0], nullptr, n, s);
             for (int i = 1; i <= j; ++i)
@@ -4346,7 +4537,7 @@ static int gm_solve(const char* who, const GmOperator& op, int transpose, const 
         }
         for (int i = 0; i < k; ++i) launch_gm_axpby(tv, y[i], V + (size_t)i * n, i == 0 ? 0.0 : 1.0, n, s);
         if (k > 0) {
-            if (launch_pc_apply(pc_sel().tab, pc_sel().nState, transpose, pc_sel().planeStart, tv, zt, s)) return 1;
+            if (pc_apply_enqueue(transpose, tv, zt, s)) return 1;
             launch_gm_axpby(d_x, 1.0, zt, 1.0, n, s);
             zeroX = false;
         }

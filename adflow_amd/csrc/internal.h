@@ -392,9 +392,9 @@ void launch_jac_mult(const JmBlk* tab, int nslots, int maxnx, int maxny, int max
 void launch_jac_mult_t(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, hipStream_t s);
 void launch_jac_halo_accumulate(const JmBlk* tab, const JmAccList& a, int nState, const double* buf, int nbuf, hipStream_t s);
 
-// block ILU(0) of the 7-point matrix (kernels_pc.hip): the factor of a level as its kernels see it.  Position q of the hyperplane
-// order (hyperplane, block, k, j, i) holds fac[q + ((s nState + l) nState + ll) ncell], s = 0..2 L of the lower neighbour along
-// i, j, k, 3..5 U of the upper neighbour, 6 the inverted pivot block
+// block ILU of the 7-point matrix (kernels_pc.hip, kernels_pc_fill.hip): the factor of a level as its kernels see it.  Position q of
+// the hyperplane order (hyperplane, block, k, j, i) holds fac[q + ((s nState + l) nState + ll) ncell]; at fill 0 s = 0..2 L of the
+// lower neighbour along i, j, k, 3..5 U of the upper neighbour, 6 the inverted pivot block (fill 1, 2: the end of the struct)
 #include <vector>
 struct PcTab {
     long ncell;           // owned cells of the level
@@ -409,10 +409,21 @@ struct PcTab {
     int sten[7];          // stencil entries of the assembly: the columns c - e_i, c - e_j, c - e_k, c + e_i, c + e_j, c + e_k, c
     const double* tsm;    // setup only: the pseudo-time term of ANK added to the diagonal blocks (kernels_ank.hip), NULL = none
     double turbDiag;      // S(nt1, nt1) = turbResScale / turbCFLScale of the coupled T
+    // fill 1 and 2 only (kernels_pc_fill.hip): nLow = (entries per row - 1) / 2 lower and as many upper entries, each side in
+    // ascending column order (upper entry u is the mirror of lower entry nLow-1-u); fac slots 0..nLow-1 L, nLow..2 nLow-1 U,
+    // 2 nLow the inverted pivot block; nbr has one column per off-diagonal slot
+    int asmEnt[23];       // stencil entry of the assembly that slot s starts from, -1: a fill entry (starts from zero)
+    signed char tgt[121]; // tgt[e nLow + u]: slot of this row that L_{c,n} U_{n,m} lands in (n: lower entry e, m: upper entry u
+                          // of row n), -1: outside the pattern
 };
 int launch_pc_factor(const PcTab& T, int nState, const std::vector<int>& planeStart, hipStream_t s);
 int launch_pc_apply(const PcTab& T, int nState, int transpose, const std::vector<int>& planeStart, const double* r, double* z,
                     hipStream_t s);
+// block ILU(1) / ILU(2) of the same matrix (kernels_pc_fill.hip): nEnt = 13 or 23 entries per row, levelStart = first position of
+// every dependency level set in the order of the factor, and the end
+int launch_pcf_factor(const PcTab& T, int nState, int nEnt, const std::vector<int>& levelStart, hipStream_t s);
+int launch_pcf_apply(const PcTab& T, int nState, int nEnt, int transpose, const std::vector<int>& levelStart, const double* r,
+                     double* z, hipStream_t s);
 // the vectors of GMRES: one step of modified Gram-Schmidt per launch (partial sums in, partial sums out), see kernels_pc.hip
 int gm_groups(long n);
 void launch_gm_mgs(double* w, const double* v, const double* hp, const double* u, double* out, double* hOut, long n, hipStream_t s);

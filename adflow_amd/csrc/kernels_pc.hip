@@ -4,8 +4,11 @@
 // Reference semantics: the PCApply of setupStandardKSP (adjointUtils.F90:1374-1562) in the configuration PCBJACOBI (= PCASM with
 // overlap 0), one subdomain per structured block, sub-preconditioner ILU with 0 levels in the natural ordering (k, j, i with i
 // fastest) on BAIJ blocks of size nState.  A column on a halo cell, with or without a donor, is not part of a subdomain.
-// Out of scope: ILU(k > 0) and the RCM ordering (the reference's defaults), ASM overlap and couplings across blocks, GMRES across
-// ranks.  (The pseudo-time diagonal term of ANK and the matrix-free operator: adflow_gpu_ank_pc_setup / _ank_solve, kernels_ank.hip.)
+// Fill: natural ordering, fill <= 2.  This file is fill 0; ILU(1) and ILU(2) (adflow_gpu_pc_set_fill; the reference defaults to 2)
+// are in kernels_pc_fill.hip and leave a factor that everything above the two launch_pc_* calls takes unchanged.
+// Out of scope: fill > 2 and the RCM ordering (the reference's default ordering), ASM overlap and couplings across blocks, GMRES
+// across ranks.  (The pseudo-time diagonal term of ANK and the matrix-free operator: adflow_gpu_ank_pc_setup / _ank_solve,
+// kernels_ank.hip.)
 //
 // Arithmetic: eliminating row c of a 7-point stencil in natural order with the rows c - e_i, c - e_j, c - e_k creates no entry
 // inside the pattern but on the diagonal, so
@@ -25,61 +28,7 @@
 
 #define PC_T 64           // one wave per workgroup: a hyperplane of a few thousand cells still spreads over the CUs
 
-#define PCE(a, r, c) a[(c) * NS + (r)]
-
-// a <- a^-1 by LU with partial pivoting on [a | 1] and back substitution, in registers (every index is a compile-time constant;
-// a row exchange is a conditional swap).  Returns false when a pivot is zero or not finite.
-template <int NS>
-__device__ __forceinline__ bool pc_invert(double (&a)[NS * NS])
-{
-    double b[NS * NS];
-#pragma unroll
-    for (int e = 0; e < NS * NS; ++e) b[e] = (e % (NS + 1) == 0) ? 1.0 : 0.0;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-#pragma unroll
-        for (int r = k + 1; r < NS; ++r) {
-            const bool sw = fabs(PCE(a, r, k)) > fabs(PCE(a, k, k));
-#pragma unroll
-            for (int c = k; c < NS; ++c) {
-                const double t = PCE(a, k, c), u = PCE(a, r, c);
-                PCE(a, k, c) = sw ? u : t;
-                PCE(a, r, c) = sw ? t : u;
-            }
-#pragma unroll
-            for (int c = 0; c < NS; ++c) {
-                const double t = PCE(b, k, c), u = PCE(b, r, c);
-                PCE(b, k, c) = sw ? u : t;
-                PCE(b, r, c) = sw ? t : u;
-            }
-        }
-        const double piv = PCE(a, k, k);
-        ok = ok && (fabs(piv) > 0.0) && (fabs(piv) <= 1.7976931348623157e308);
-#pragma unroll
-        for (int r = k + 1; r < NS; ++r) {
-            const double f = PCE(a, r, k) / piv;
-#pragma unroll
-            for (int c = k + 1; c < NS; ++c) PCE(a, r, c) -= f * PCE(a, k, c);
-#pragma unroll
-            for (int c = 0; c < NS; ++c) PCE(b, r, c) -= f * PCE(b, k, c);
-        }
-    }
-#pragma unroll
-    for (int k = NS - 1; k >= 0; --k) {
-        const double piv = PCE(a, k, k);
-#pragma unroll
-        for (int c = 0; c < NS; ++c) {
-            double t = PCE(b, k, c);
-#pragma unroll
-            for (int m = k + 1; m < NS; ++m) t -= PCE(a, k, m) * PCE(b, m, c);
-            PCE(b, k, c) = t / piv;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < NS * NS; ++e) a[e] = b[e];
-    return ok;
-}
+#include "pc_block.h"
 
 // one hyperplane of the factorisation: lanes q0 .. q0 + cnt - 1.  The rows of the lower neighbours are complete (earlier launches)
 template <int NS>

@@ -185,10 +185,21 @@ class Engine:
         self._chk(self.lib.adflow_gpu_pc_setup(level))
 
     def pcInfo(self):
-        """(nState, number of hyperplanes, bytes held) of the factor"""
+        """(nState, number of hyperplanes -- level sets at fill > 0 --, bytes held) of the factor"""
         ns, npl, nb = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
         self._chk(self.lib.adflow_gpu_pc_info(ctypes.byref(ns), ctypes.byref(npl), ctypes.byref(nb)))
         return int(ns.value), int(npl.value), int(nb.value)
+
+    def pcSetFill(self, fill: int):
+        """levels of fill (0, 1 or 2; PCFactorSetLevels) of the next pcSetup / ankPcSetup of the selected slot; a factor that exists
+        keeps its own"""
+        self._chk(self.lib.adflow_gpu_pc_set_fill(int(fill)))
+
+    def pcInfo2(self):
+        """(fill, entries per row: 7, 13 or 23, number of level sets) of the factor"""
+        f, ne, nl = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        self._chk(self.lib.adflow_gpu_pc_info2(ctypes.byref(f), ctypes.byref(ne), ctypes.byref(nl)))
+        return int(f.value), int(ne.value), int(nl.value)
 
     def pcApply(self, r, level=1, transpose=False):
         """z = M^-1 r, or M^-T r with transpose, for the factor of pcSetup; vectors as for jacobianMult"""

@@ -343,6 +343,16 @@ module adflowGpuShim
             integer(c_int32_t), intent(out) :: nState, nPlanes
             integer(c_int64_t), intent(out) :: bytes
         end function
+        ! levels of fill of the next setup of the selected slot (0, 1 or 2: ank_ilufill / nk_ilufill / fillLevel, natural ordering), and
+        ! what the selected factor was built with: fill, entries per row (7, 13, 23), dependency level sets
+        integer(c_int) function adflow_gpu_pc_set_fill(fill) bind(C, name="adflow_gpu_pc_set_fill")
+            import :: c_int
+            integer(c_int), value :: fill
+        end function
+        integer(c_int) function adflow_gpu_pc_info2(fill, nEntries, nLevelSets) bind(C, name="adflow_gpu_pc_info2")
+            import :: c_int, c_int32_t
+            integer(c_int32_t), intent(out) :: fill, nEntries, nLevelSets
+        end function
         integer(c_int) function adflow_gpu_pc_apply(level, transpose, r, z, n) bind(C, name="adflow_gpu_pc_apply")
             import :: c_int, c_long, c_double
             integer(c_int), value :: level, transpose
@@ -933,6 +943,12 @@ contains
         integer(kind=intType), intent(in) :: level
         call gpuCheck(adflow_gpu_pc_setup(int(level, c_int)), "gpuPCSetup")
     end subroutine gpuPCSetup
+
+    ! PCFactorSetLevels: the fill (0, 1, 2) of the next gpuPCSetup of the selected slot, from ank_ilufill / nk_ilufill / fillLevel
+    subroutine gpuPCSetFill(fill)
+        integer(kind=intType), intent(in) :: fill
+        call gpuCheck(adflow_gpu_pc_set_fill(int(fill, c_int)), "gpuPCSetFill")
+    end subroutine gpuPCSetFill
 
     ! the body of a PCSHELL's apply (transposed = .false.) / applyTranspose (.true.): rDev, zDev are the device arrays of the two
     ! PETSc vectors (VECHIP), n their local size

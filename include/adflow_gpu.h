@@ -503,15 +503,28 @@ int adflow_gpu_jacobian_mult_dev(int level, int transpose, const double* d_x, do
  * hyperplanes of the factor and the bytes it holds; an error without a factor.
  * Vectors as for adflow_gpu_jacobian_mult (n = nState x owned cells of the level); host pointers, or device pointers for the _dev
  * form, which honours adflow_gpu_set_async.  r and z must differ.  State, residual and matrix are not touched.
- * Out of scope: ILU(k > 0) and the RCM ordering (the reference's defaults), ASM overlap and couplings across blocks.  (The
+ * Levels of fill (PCFactorSetLevels of setupStandardKSP, adjointUtils.F90:1559; the reference's ANKPCILUFill, NKPCILUFill and
+ * ILUFill default to 2): adflow_gpu_pc_set_fill(fill) sets the fill that the next adflow_gpu_pc_setup / _ank_pc_setup of the
+ * SELECTED slot uses: 0 (the default), 1 or 2; anything else is an error.  A factor that exists keeps the fill it was built with.
+ * In the natural ordering the ILU(1) / ILU(2) pattern of a structured block is a fixed stencil of 13 / 23 offsets cut at the faces
+ * of the block (from fill 3 on it is not, hence the limit); the factor then holds 13 / 23 blocks of nState^2 per cell and a
+ * neighbour table of 12 / 22 columns, and setup and sweeps run over the level sets of the row dependencies (nx + 2 ny + 3 nz - 5
+ * of them for a block at fill 1, nx + 3 ny + 7 nz - 10 at fill 2) in place of the hyperplanes.  Everything that takes a factor
+ * takes one of any fill.  adflow_gpu_pc_info reports the number of level sets as nPlanes and the true bytes;
+ * adflow_gpu_pc_info2: the fill of the selected factor, its entries per row (7, 13 or 23) and its number of level sets (each may
+ * be NULL); an error without a factor.  An allocation that fails leaves no factor, and the message names the size.
+ * Out of scope: fill > 2 and the RCM ordering (the reference's default ordering), ASM overlap and couplings across blocks.  (The
  * pseudo-time diagonal term of ANK: adflow_gpu_ank_pc_setup below, into the same factor slot.) */
 int adflow_gpu_pc_setup(int level);
 int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes);
+int adflow_gpu_pc_set_fill(int fill);
+int adflow_gpu_pc_info2(int32_t* fill, int32_t* nEntries, int32_t* nLevelSets);
 int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, long n);
 int adflow_gpu_pc_apply_dev(int level, int transpose, const double* d_r, double* d_z, long n);
 int adflow_gpu_pc_release(int64_t* bytes);
 /* Two factor slots (ANK_jacobianLag keeps the flow factor and the turbulence factor alive over the same steps): slot 0 or 1, default
- * 0.  adflow_gpu_pc_setup, _ank_pc_setup, _pc_apply, _pc_info, _pc_release, _gmres_solve and _ank_solve act on the selected slot;
+ * 0.  adflow_gpu_pc_setup, _ank_pc_setup, _pc_set_fill, _pc_apply, _pc_info, _pc_info2, _pc_release, _gmres_solve and _ank_solve act on the
+ * selected slot (each slot keeps its own fill);
  * adflow_gpu_block_release and _release_all release both.  A process that never calls it behaves as with one slot. */
 int adflow_gpu_pc_select(int slot);
 /* Restarted GMRES with the factor as RIGHT preconditioner, the KSPSolve of solveAdjoint (adjointAPI.F90:661-863) with the settings

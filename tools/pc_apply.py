@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""The block ILU(0) preconditioner alone (adflow_gpu_pc_setup / adflow_gpu_pc_apply_dev), timed with HIP events: the RANS Roe
+"""The block ILU(fill) preconditioner alone (adflow_gpu_pc_setup / adflow_gpu_pc_apply_dev), timed with HIP events: the RANS Roe
 preconditioner matrix (7-point, forward-mode assembly) on one 160 x 128 x 64 wall-bounded block.  Prints ms for the setup, ms for
-z = M^-1 r and z = M^-T r, ms for y = J x with the same matrix in the same run (one launch over the same bytes: the yardstick), the
-byte floor (7 nState^2 x 8 B per owned cell), TB/s and launches per application; then GMRES on the preconditioner matrix itself:
-iterations and ms to reduce the residual by 1e-8.
-usage: pc_apply.py [n] [nx ny nz]   (n timed applications of each kind, default 10)"""
+z = M^-1 r and z = M^-T r, ms for y = J x with the same matrix in the same run (one launch over the 7-point bytes: the yardstick),
+the byte floor (7, 13 or 23 nState^2 x 8 B per owned cell), TB/s and launches per application; then GMRES on the preconditioner
+matrix itself: iterations and ms to reduce the residual by --rtol (default 1e-8).
+usage: pc_apply.py [--fill 0|1|2] [--rtol 1e-8] [n] [nx ny nz]   (n timed applications of each kind, default 10)"""
 import json
 import os
 import sys
@@ -21,8 +21,17 @@ WALL = {1: -6, 2: -6, 3: -1, 4: -1, 5: -3, 6: -6}
 
 def main():
     import torch
-    n_it = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-    dims = tuple(int(a) for a in sys.argv[2:5]) if len(sys.argv) > 4 else (160, 128, 64)
+    argv, fill, rtol = list(sys.argv[1:]), 0, 1e-8
+    for opt in ("--fill", "--rtol"):
+        if opt in argv:
+            at = argv.index(opt)
+            if opt == "--fill":
+                fill = int(argv[at + 1])
+            else:
+                rtol = float(argv[at + 1])
+            del argv[at:at + 2]
+    n_it = int(argv[0]) if len(argv) > 0 else 10
+    dims = tuple(int(a) for a in argv[1:4]) if len(argv) > 3 else (160, 128, 64)
     eng = Engine(0)
     prm = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda).replace(currentLevel=1, groundLevel=1)
     blk = make_block(*dims, prm, seed=7, stretch_k=2.0)
@@ -39,7 +48,9 @@ def main():
     ns, st = eng.jacobianInfo()
     cells = blk.nx * blk.ny * blk.nz
     n = ns * cells
-    floor = 7 * ns * ns * 8 * cells
+    if fill:                                              # (a library without the entry point still serves fill 0)
+        eng.pcSetFill(fill)
+    floor = {0: 7, 1: 13, 2: 23}[fill] * ns * ns * 8 * cells
     eng.pcSetup(1)                                        # warm-up (allocations, tables)
     eng.sync()
     eng.event_record(1)
@@ -48,7 +59,7 @@ def main():
     eng.sync()
     _, planes, nbytes = eng.pcInfo()
     print(json.dumps({"what": "pc_setup (tables, allocation, factorisation)", "dims": list(dims), "nState": ns, "ms": round(eng.event_elapsed_ms(1, 2), 3),
-                      "hyperplanes": planes, "factor_bytes": nbytes}), flush=True)
+                      "fill": fill, "hyperplanes_or_level_sets": planes, "factor_bytes": nbytes}), flush=True)
     gen = torch.Generator(device="cuda").manual_seed(5)
     x = torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 0.5
     y = torch.empty_like(x)
@@ -78,10 +89,10 @@ def main():
         for timed in (False, True):
             torch.cuda.synchronize()
             eng.event_record(1)
-            its, r0, rn = eng.gmresSolveDev(b.data_ptr(), y.data_ptr(), n, 1, tr, restart=30, maxIts=60, rtol=1e-8)
+            its, r0, rn = eng.gmresSolveDev(b.data_ptr(), y.data_ptr(), n, 1, tr, restart=30, maxIts=60, rtol=rtol)
             eng.event_record(2)
             eng.sync()
-        print(json.dumps({"what": "gmres on the PC matrix, rtol 1e-8", "transpose": tr, "iterations": its, "ms": round(eng.event_elapsed_ms(1, 2), 3),
+        print(json.dumps({"what": f"gmres on the PC matrix, rtol {rtol:g}", "fill": fill, "transpose": tr, "iterations": its, "ms": round(eng.event_elapsed_ms(1, 2), 3),
                           "rnorm0": r0, "true_rnorm": rn}), flush=True)
     eng.pcRelease()
     eng.releaseWorkspace()
