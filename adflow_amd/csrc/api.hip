@@ -3629,6 +3629,57 @@ int for_level1_in_order(const std::function<int(Block*, long)>& fn)
     return 0;
 }
 
+// The staging of a host form: its vectors of n doubles side by side in `base` (g_vec_dev, or an allocation of the call), vector q at
+// s[q].  A host form is: its argument check, stage_open, in(), the enqueue function its _dev twin calls, out(), done() -- the one
+// synchronise, whatever adflow_gpu_set_async says.
+struct Stage {
+    long n = 0;
+    double* base = nullptr;
+    double* operator[](int q) const { return base + (size_t)q * n; }
+    int in(int q, const double* h) const
+    {
+        HIPCHK(hipMemcpyAsync((*this)[q], h, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+        return 0;
+    }
+    int out(double* h, int q) const { return scalars(h, (*this)[q], n); }
+    int scalars(double* h, const double* d, long count) const
+    {
+        HIPCHK(hipMemcpyAsync(h, d, sizeof(double) * count, hipMemcpyDeviceToHost, g_stream));
+        return 0;
+    }
+    int done() const
+    {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        return 0;
+    }
+};
+
+int stage_open(Stage* s, long n, int nvec)
+{
+    if (vec_reserve((size_t)nvec * n)) return 1;
+    s->n = n;
+    s->base = g_vec_dev;
+    return 0;
+}
+
+// the flag the closures of a state write raise where they floored a pressure: there, and cleared on the stream
+int floor_flag_clear()
+{
+    if (!g_floor_flag_dev) HIPCHK(hipMalloc((void**)&g_floor_flag_dev, sizeof(int)));
+    HIPCHK(hipMemsetAsync(g_floor_flag_dev, 0, sizeof(int), g_stream));
+    return 0;
+}
+
+// a state write moved the flow variables of level 1: the sensor and the energy / pressure consistency of its blocks no longer hold
+int flow_state_written()
+{
+    return for_level1_in_order([&](Block* b, long) {
+        b->ss_valid = false;
+        b->etot_consistent = false;
+        return 0;
+    });
+}
+
 int set_w_dev(const double* d_vec, bool withClosures = false)
 {
     const double turbFloor = 1e-6 * g_opts.wInf[5];
@@ -3637,16 +3688,11 @@ int set_w_dev(const double* d_vec, bool withClosures = false)
     // block offsets: BlkView::vecOff; withClosures: the closures blocketteRes would start with, in the same pass
     if (withClosures) {
         KParams kp = make_kparams(1, 1.0, 0);
-        if (!g_floor_flag_dev) HIPCHK(hipMalloc((void**)&g_floor_flag_dev, sizeof(int)));
-        HIPCHK(hipMemsetAsync(g_floor_flag_dev, 0, sizeof(int), g_stream));
+        if (floor_flag_clear()) return 1;
         launch_set_w_closures_level(t.tab, t.n, t.nx, t.ny, t.nz, d_vec, turbFloor, kp, g_floor_flag_dev, g_stream);
     } else
         launch_set_w_level(t.tab, t.n, t.nx, t.ny, t.nz, d_vec, turbFloor, g_stream);
-    return for_level1_in_order([&](Block* b, long) {
-        b->ss_valid = false;
-        b->etot_consistent = false;
-        return 0;
-    });
+    return flow_state_written();
 }
 
 int get_r_dev(double* d_vec, double turbScale, double* d_sums)
@@ -3662,25 +3708,20 @@ int adflow_gpu_set_w_vec(const double* wVec, long n)
 {
     if (need_ready()) return 1;
     if (!wVec || n != level1_dof()) return fail("set_w_vec: n=%ld but the level-1 blocks hold %ld DOF", n, level1_dof());
-    if (vec_reserve((size_t)n)) return 1;
-    HIPCHK(hipMemcpyAsync(g_vec_dev, wVec, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (set_w_dev(g_vec_dev)) return 1;
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    Stage s;
+    return stage_open(&s, n, 1) || s.in(0, wVec) || set_w_dev(s[0]) || s.done();
 }
 
 static int get_vec_common(double* out, long n, double turbScale, double* sumsq2)
 {
     if (need_ready()) return 1;
     if (!out || n != level1_dof()) return fail("get_r_vec: n=%ld but the level-1 blocks hold %ld DOF", n, level1_dof());
-    if (vec_reserve((size_t)n)) return 1;
+    Stage s;
+    if (stage_open(&s, n, 1)) return 1;
     if (!g_norm_dev) HIPCHK(hipMalloc((void**)&g_norm_dev, sizeof(double) * 8));
     HIPCHK(hipMemsetAsync(g_norm_dev, 0, sizeof(double) * 8, g_stream));
-    if (get_r_dev(g_vec_dev, turbScale, sumsq2 ? g_norm_dev : nullptr)) return 1;
-    HIPCHK(hipMemcpyAsync(out, g_vec_dev, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    if (sumsq2) HIPCHK(hipMemcpyAsync(sumsq2, g_norm_dev, sizeof(double) * 2, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    if (get_r_dev(s[0], turbScale, sumsq2 ? g_norm_dev : nullptr) || s.out(out, 0)) return 1;
+    return (sumsq2 && s.scalars(sumsq2, g_norm_dev, 2)) || s.done();
 }
 
 int adflow_gpu_get_r_vec(double* rVec, long n, double* sumsq2) { return get_vec_common(rVec, n, g_opts.turbResScale, sumsq2); }
@@ -3726,12 +3767,8 @@ int adflow_gpu_nk_residual(const double* wVec, double* rVec, long n)
 {
     if (need_ready()) return 1;
     if (!wVec || !rVec || n != level1_dof()) return fail("nk_residual: n=%ld but the level-1 blocks hold %ld DOF", n, level1_dof());
-    if (vec_reserve((size_t)n)) return 1;
-    HIPCHK(hipMemcpyAsync(g_vec_dev, wVec, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (nk_residual_enqueue(g_vec_dev, g_vec_dev)) return 1;
-    HIPCHK(hipMemcpyAsync(rVec, g_vec_dev, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    Stage s;                           // one buffer for w and r (see nk_residual_enqueue)
+    return stage_open(&s, n, 1) || s.in(0, wVec) || nk_residual_enqueue(s[0], s[0]) || s.out(rVec, 0) || s.done();
 }
 
 // ---- products with the assembled matrix (kernels_jacmult.hip): y = J x, y = J^T x on PETSc-layout device vectors ----------------
@@ -4002,13 +4039,9 @@ int adflow_gpu_jacobian_mult_dev(int level, int transpose, const double* d_x, do
 
 int adflow_gpu_jacobian_mult(int level, int transpose, const double* x, double* y, long n)
 {
-    if (jm_check(level, x, y, n)) return 1;
-    if (vec_reserve((size_t)2 * n)) return 1;
-    HIPCHK(hipMemcpyAsync(g_vec_dev, x, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (jm_mult_enqueue(level, transpose, g_vec_dev, g_vec_dev + n)) return 1;
-    HIPCHK(hipMemcpyAsync(y, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    Stage s;
+    return jm_check(level, x, y, n) || stage_open(&s, n, 2) || s.in(0, x) || jm_mult_enqueue(level, transpose, s[0], s[1]) ||
+           s.out(y, 1) || s.done();
 }
 
 // ---- block ILU(0) of the 7-point preconditioner matrix and right-preconditioned GMRES (kernels_pc.hip) --------------------------
@@ -4035,21 +4068,18 @@ struct DevBuf {                       // a device allocation that lives as long 
 };
 }  // namespace
 
-// the selected slot
-static int64_t pc_release()
+static int64_t pc_release(PcFactor& f)
 {
-    const int64_t n = (int64_t)pc_sel().bytes;
-    for (void* p : pc_sel().raw) (void)hipFree(p);
-    pc_sel() = PcFactor();
+    const int64_t n = (int64_t)f.bytes;
+    for (void* p : f.raw) (void)hipFree(p);
+    f = PcFactor();
     return n;
 }
 
 static int64_t pc_release_all()
 {
-    const int was = g_pc_slot;
     int64_t n = 0;
-    for (g_pc_slot = 0; g_pc_slot < 2; ++g_pc_slot) n += pc_release();
-    g_pc_slot = was;
+    for (PcFactor& f : g_pc_slots) n += pc_release(f);
     return n;
 }
 
@@ -4060,17 +4090,18 @@ int adflow_gpu_pc_select(int slot)
     return 0;
 }
 
-static int pc_alloc(void** p, size_t bytes)
+// device memory of the factor f, which is being built with `fill` levels of fill
+static int pc_alloc(PcFactor& f, int fill, void** p, size_t bytes)
 {
     *p = nullptr;
     if (hipMalloc(p, bytes) != hipSuccess) {
         (void)hipGetLastError();
         *p = nullptr;
         return fail("pc_setup: cannot allocate %zu bytes (%.1f MB) for the factor of fill %d; %zu bytes of it are held, no factor is "
-                    "kept", bytes, bytes / 1048576.0, g_pc_fill[g_pc_slot], pc_sel().bytes);
+                    "kept", bytes, bytes / 1048576.0, fill, f.bytes);
     }
-    pc_sel().raw.push_back(*p);
-    pc_sel().bytes += bytes;
+    f.raw.push_back(*p);
+    f.bytes += bytes;
     return 0;
 }
 
@@ -4109,17 +4140,13 @@ static int pc_fill_offsets(int fill, std::vector<std::array<int, 3>>& off)
     return (int)off.size();
 }
 
-static int pc_setup_build_fill(int level, int fill, const int* sten7, const std::vector<JmBlk>& hb, const std::vector<int>& nnOf, long N,
-                               const double* shift, double turbDiag)
+// fill 1 and 2: the off-diagonal slots in the order of kernels_pc_fill.hip (the pattern in ascending column order without the diagonal),
+// and into T the stencil entry of the assembly every slot starts from and the slot every product L U lands in
+static int pc_fill_tables(int fill, const int* sten7, PcTab& T, std::vector<std::array<int, 3>>& slots)
 {
-    const int nS = g_jac.nState;
     std::vector<std::array<int, 3>> off;
     const int nEnt = pc_fill_offsets(fill, off), nLow = (nEnt - 1) / 2;
     if (nEnt != (fill == 1 ? 13 : 23)) return fail("pc_setup: internal: the pattern of fill %d has %d offsets", fill, nEnt);
-    PcTab& T = pc_sel().tab;
-    memset(&T, 0, sizeof T);
-    T.ncell = N;
-    for (int q = 0; q < 7; ++q) T.sten[q] = sten7[q];
     // slot of an entry: lower entries 0..nLow-1, upper entries nLow..2 nLow-1 (both ascending), the diagonal 2 nLow
     auto slotOf = [&](int e) { return e < nLow ? e : e == nLow ? 2 * nLow : e - 1; };
     auto find = [&](int di, int dj, int dk) {
@@ -4143,8 +4170,30 @@ static int pc_setup_build_fill(int level, int fill, const int* sten7, const std:
             const int t = find(a[0] + b[0], a[1] + b[1], a[2] + b[2]);
             T.tgt[e * nLow + u] = (signed char)(t < 0 ? -1 : slotOf(t));
         }
-    // the dependency level sets: 1 + the highest set of a lower entry inside the block (longest path; natural order visits the lower
-    // entries of a row before the row)
+    slots = off;
+    slots.erase(slots.begin() + nLow);
+    return 0;
+}
+
+// The tables of the factor f at any fill, its factorisation and its fields.  The caller has filled ncell, sten, asmEnt and tgt of
+// f.tab; slots[s] = the offset (di, dj, dk) of the column of off-diagonal slot s, the lower entries in the first half, in the order
+// the kernels of this fill number their slots (PcTab, internal.h): nothing is sorted here.  The order of the factor is (set, block, k,
+// j, i), set = 1 + the highest set of a lower entry inside the block (longest path; the natural order visits the lower entries of a
+// row before the row) -- for the 7-point pattern of fill 0 that is i + j + k, the hyperplanes, and fill 0 takes it and its six
+// neighbours directly: the tables are those of the generic loops, which cost its table build a third more time.
+// shift != NULL: the pseudo-time term of ANK (tsm of kernels_ank.hip) is added to the diagonal blocks as the factorisation reads them
+static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::array<int, 3>>& slots, const std::vector<JmBlk>& hb,
+                    const std::vector<int>& nnOf, const double* shift, double turbDiag)
+{
+    const int nS = g_jac.nState, nOff = (int)slots.size(), nLow = nOff / 2, nEnt = nOff + 1;
+    PcTab& T = f.tab;
+    const long N = T.ncell;
+    // the natural number of the column of slot e of the cell (i, j, k), number nat, of block q; -1 outside the block
+    auto column = [&](const JmBlk& q, long nat, int i, int j, int k, int e) -> long {
+        const int di = slots[e][0], dj = slots[e][1], dk = slots[e][2];
+        if (i + di < 0 || i + di >= q.nx || j + dj < 0 || j + dj >= q.ny || k + dk < 0 || k + dk >= q.nz) return -1;
+        return nat + ((long)dk * q.ny + dj) * q.nx + di;
+    };
     std::vector<int> lvl(N);
     int nSets = 0;
     for (auto& q : hb) {
@@ -4152,11 +4201,13 @@ static int pc_setup_build_fill(int level, int fill, const int* sten7, const std:
         for (int k = 0; k < q.nz; ++k)
             for (int j = 0; j < q.ny; ++j)
                 for (int i = 0; i < q.nx; ++i, ++nat) {
-                    int l = 0;
-                    for (int e = 0; e < nLow; ++e) {
-                        const int ci = i + off[e][0], cj = j + off[e][1], ck = k + off[e][2];
-                        if (ci < 0 || ci >= q.nx || cj < 0 || cj >= q.ny || ck < 0 || ck >= q.nz) continue;
-                        l = std::max(l, lvl[q.vecOff + ((long)ck * q.ny + cj) * q.nx + ci] + 1);
+                    int l = i + j + k;            // what the longest path gives at fill 0, without walking it
+                    if (fill > 0) {
+                        l = 0;
+                        for (int e = 0; e < nLow; ++e) {
+                            const long c = column(q, nat, i, j, k, e);
+                            if (c >= 0) l = std::max(l, lvl[c] + 1);
+                        }
                     }
                     lvl[nat] = l;
                     nSets = std::max(nSets, l + 1);
@@ -4165,8 +4216,8 @@ static int pc_setup_build_fill(int level, int fill, const int* sten7, const std:
     std::vector<int> start(nSets + 1, 0);
     for (long c = 0; c < N; ++c) start[lvl[c] + 1]++;
     for (int p = 0; p < nSets; ++p) start[p + 1] += start[p];
-    std::vector<int> cur(start.begin(), start.end() - 1), pos(N), nbr((size_t)(nEnt - 1) * N), vec(N), cblk(N), cbox(N);
-    for (size_t s = 0; s < hb.size(); ++s) {       // the order (level set, block, k, j, i)
+    std::vector<int> cur(start.begin(), start.end() - 1), pos(N), nbr((size_t)nOff * N), vec(N), cblk(N), cbox(N);
+    for (size_t s = 0; s < hb.size(); ++s) {
         const JmBlk& q = hb[s];
         long nat = q.vecOff;
         for (int k = 0; k < q.nz; ++k)
@@ -4179,24 +4230,34 @@ static int pc_setup_build_fill(int level, int fill, const int* sten7, const std:
                     cbox[at] = (i + 2) + (j + 2) * q.ldi + (k + 2) * q.ldk;
                 }
     }
-    for (size_t s = 0; s < hb.size(); ++s) {
-        const JmBlk& q = hb[s];
+    for (auto& q : hb) {
         long nat = q.vecOff;
+        const long sj = q.nx, sk = (long)q.nx * q.ny;
         for (int k = 0; k < q.nz; ++k)
             for (int j = 0; j < q.ny; ++j)
-                for (int i = 0; i < q.nx; ++i, ++nat)
-                    for (int e = 0; e < nEnt; ++e) {
-                        if (e == nLow) continue;
-                        const int ci = i + off[e][0], cj = j + off[e][1], ck = k + off[e][2];
-                        const bool in = ci >= 0 && ci < q.nx && cj >= 0 && cj < q.ny && ck >= 0 && ck < q.nz;
-                        nbr[(size_t)slotOf(e) * N + pos[nat]] = in ? pos[q.vecOff + ((long)ck * q.ny + cj) * q.nx + ci] : -1;
+                for (int i = 0; i < q.nx; ++i, ++nat) {
+                    const long at = pos[nat];
+                    if (fill == 0) {              // the six neighbours directly (-i, -j, -k, +i, +j, +k): the generic loop below
+                        nbr[0 * N + at] = i > 0 ? pos[nat - 1] : -1;      // gives the same table a third slower
+                        nbr[1 * N + at] = j > 0 ? pos[nat - sj] : -1;
+                        nbr[2 * N + at] = k > 0 ? pos[nat - sk] : -1;
+                        nbr[3 * N + at] = i < q.nx - 1 ? pos[nat + 1] : -1;
+                        nbr[4 * N + at] = j < q.ny - 1 ? pos[nat + sj] : -1;
+                        nbr[5 * N + at] = k < q.nz - 1 ? pos[nat + sk] : -1;
+                        continue;
                     }
+                    for (int e = 0; e < nOff; ++e) {
+                        const long c = column(q, nat, i, j, k, e);
+                        nbr[(size_t)e * N + at] = c >= 0 ? pos[c] : -1;
+                    }
+                }
     }
     void *dn, *dv, *db, *dc, *dt, *df;
-    if (pc_alloc((void**)&T.fac, (size_t)N * nEnt * nS * nS * sizeof(double))) return 1;
-    if (pc_alloc((void**)&T.ws, (size_t)N * nS * sizeof(double))) return 1;
-    if (pc_alloc(&dn, sizeof(int) * nbr.size()) || pc_alloc(&dv, sizeof(int) * N) || pc_alloc(&db, sizeof(int) * N) ||
-        pc_alloc(&dc, sizeof(int) * N) || pc_alloc(&dt, sizeof(JmBlk) * hb.size()) || pc_alloc(&df, sizeof(int)))
+    auto alloc = [&](void** p, size_t bytes) { return pc_alloc(f, fill, p, bytes); };
+    if (alloc((void**)&T.fac, (size_t)N * nEnt * nS * nS * sizeof(double))) return 1;
+    if (alloc((void**)&T.ws, (size_t)N * nS * sizeof(double))) return 1;
+    if (alloc(&dn, sizeof(int) * nbr.size()) || alloc(&dv, sizeof(int) * N) || alloc(&db, sizeof(int) * N) || alloc(&dc, sizeof(int) * N) ||
+        alloc(&dt, sizeof(JmBlk) * hb.size()) || alloc(&df, sizeof(int)))
         return 1;
     HIPCHK(hipMemcpy(dn, nbr.data(), sizeof(int) * nbr.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dv, vec.data(), sizeof(int) * N, hipMemcpyHostToDevice));
@@ -4207,7 +4268,7 @@ static int pc_setup_build_fill(int level, int fill, const int* sten7, const std:
     T.nbr = (const int*)dn; T.vec = (const int*)dv; T.cblk = (const int*)db; T.cbox = (const int*)dc;
     T.blk = (const JmBlk*)dt; T.flag = (int*)df;
     T.tsm = shift; T.turbDiag = turbDiag;
-    const int rcf = launch_pcf_factor(T, nS, nEnt, start, g_stream);
+    const int rcf = fill > 0 ? launch_pcf_factor(T, nS, nEnt, start, g_stream) : launch_pc_factor(T, nS, start, g_stream);
     T.tsm = nullptr;                              // the sweeps do not read it, and it may be released before the factor
     if (rcf) return 1;
     int flag = 0;
@@ -4221,15 +4282,15 @@ static int pc_setup_build_fill(int level, int fill, const int* sten7, const std:
                     "level %d); no factor is kept", (int)(loc % hb[s].nx) + 2, (int)(loc / hb[s].nx % hb[s].ny) + 2,
                     (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2, nnOf[s], fill, level);
     }
-    pc_sel().level = level; pc_sel().nState = nS; pc_sel().nPlanes = nSets; pc_sel().ncell = N;
-    pc_sel().fill = fill; pc_sel().nEnt = nEnt;
-    pc_sel().planeStart = start;
-    pc_sel().valid = true;
+    f.level = level; f.nState = nS; f.nPlanes = nSets; f.ncell = N;
+    f.fill = fill; f.nEnt = nEnt;
+    f.planeStart = start;
+    f.valid = true;
     return 0;
 }
 
-// shift != NULL: the pseudo-time term of ANK (tsm of kernels_ank.hip) is added to the diagonal blocks as the factorisation reads them
-static int pc_setup_build(int level, const double* shift = nullptr, double turbDiag = 0.0)
+// the factor f of the assembled 7-point matrix of `level` with `fill` levels of fill
+static int pc_setup_build(PcFactor& f, int fill, int level, const double* shift, double turbDiag)
 {
     const int nS = g_jac.nState;
     int sten[7];
@@ -4251,7 +4312,6 @@ static int pc_setup_build(int level, const double* shift = nullptr, double turbD
     std::vector<JmBlk> hb;
     std::vector<int> nnOf;
     long N = 0;
-    int nPlanes = 0;
     for (auto& kv : byNN) {
         Block* b = kv.second;
         const BlkView& v = b->v;
@@ -4268,105 +4328,50 @@ static int pc_setup_build(int level, const double* shift = nullptr, double turbD
         hb.push_back(q);
         nnOf.push_back(kv.first);
         N += (long)v.nx * v.ny * v.nz;
-        nPlanes = std::max(nPlanes, v.nx + v.ny + v.nz - 2);
     }
     if ((double)N * nS * 8.0 >= 4294967296.0)
         return fail("pc_setup: %ld cells on level %d: a vector of the factor exceeds the 4 GiB the kernels address from one base", N, level);
     // (the factor itself may exceed 4 GiB at any fill: its component planes are reached by 64-bit pointer arithmetic, and the 32-bit
     // byte offset spans the N positions of one plane, which the check above covers)
-    if (g_pc_fill[g_pc_slot] > 0) return pc_setup_build_fill(level, g_pc_fill[g_pc_slot], sten, hb, nnOf, N, shift, turbDiag);
-    // the hyperplane order: (i + j + k, block, k, j, i)
-    std::vector<int> start(nPlanes + 1, 0);
-    for (auto& q : hb)
-        for (int k = 0; k < q.nz; ++k)
-            for (int j = 0; j < q.ny; ++j)
-                for (int i = 0; i < q.nx; ++i) start[i + j + k + 1]++;
-    for (int p = 0; p < nPlanes; ++p) start[p + 1] += start[p];
-    std::vector<int> cur(start.begin(), start.end() - 1), pos(N), nbr(6 * N), vec(N), cblk(N), cbox(N);
-    for (size_t s = 0; s < hb.size(); ++s) {
-        const JmBlk& q = hb[s];
-        long nat = q.vecOff;
-        for (int k = 0; k < q.nz; ++k)
-            for (int j = 0; j < q.ny; ++j)
-                for (int i = 0; i < q.nx; ++i, ++nat) {
-                    const int at = cur[i + j + k]++;
-                    pos[nat] = at;
-                    vec[at] = (int)nat;
-                    cblk[at] = (int)s;
-                    cbox[at] = (i + 2) + (j + 2) * q.ldi + (k + 2) * q.ldk;
-                }
-    }
-    for (size_t s = 0; s < hb.size(); ++s) {
-        const JmBlk& q = hb[s];
-        long nat = q.vecOff;
-        const long sj = q.nx, sk = (long)q.nx * q.ny;
-        for (int k = 0; k < q.nz; ++k)
-            for (int j = 0; j < q.ny; ++j)
-                for (int i = 0; i < q.nx; ++i, ++nat) {
-                    const long at = pos[nat];
-                    nbr[0 * N + at] = i > 0 ? pos[nat - 1] : -1;
-                    nbr[1 * N + at] = j > 0 ? pos[nat - sj] : -1;
-                    nbr[2 * N + at] = k > 0 ? pos[nat - sk] : -1;
-                    nbr[3 * N + at] = i < q.nx - 1 ? pos[nat + 1] : -1;
-                    nbr[4 * N + at] = j < q.ny - 1 ? pos[nat + sj] : -1;
-                    nbr[5 * N + at] = k < q.nz - 1 ? pos[nat + sk] : -1;
-                }
-    }
-    PcTab& T = pc_sel().tab;
+    PcTab& T = f.tab;
     memset(&T, 0, sizeof T);
     T.ncell = N;
     for (int q = 0; q < 7; ++q) T.sten[q] = sten[q];
-    void *dn, *dv, *db, *dc, *dt, *df;
-    if (pc_alloc((void**)&T.fac, (size_t)N * 7 * nS * nS * sizeof(double))) return 1;
-    if (pc_alloc((void**)&T.ws, (size_t)N * nS * sizeof(double))) return 1;
-    if (pc_alloc(&dn, sizeof(int) * 6 * N) || pc_alloc(&dv, sizeof(int) * N) || pc_alloc(&db, sizeof(int) * N) ||
-        pc_alloc(&dc, sizeof(int) * N) || pc_alloc(&dt, sizeof(JmBlk) * hb.size()) || pc_alloc(&df, sizeof(int)))
-        return 1;
-    HIPCHK(hipMemcpy(dn, nbr.data(), sizeof(int) * 6 * N, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dv, vec.data(), sizeof(int) * N, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db, cblk.data(), sizeof(int) * N, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dc, cbox.data(), sizeof(int) * N, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dt, hb.data(), sizeof(JmBlk) * hb.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(df, 0, sizeof(int), g_stream));
-    T.nbr = (const int*)dn; T.vec = (const int*)dv; T.cblk = (const int*)db; T.cbox = (const int*)dc;
-    T.blk = (const JmBlk*)dt; T.flag = (int*)df;
-    T.tsm = shift; T.turbDiag = turbDiag;
-    const int rcf = launch_pc_factor(T, nS, start, g_stream);
-    T.tsm = nullptr;                              // the sweeps do not read it, and it may be released before the factor
-    if (rcf) return 1;
-    int flag = 0;
-    HIPCHK(hipMemcpyAsync(&flag, df, sizeof(int), hipMemcpyDeviceToHost, g_stream));
+    // fill 0 (kernels_pc.hip): the slots -i, -j, -k, +i, +j, +k; asmEnt and tgt stay zero
+    std::vector<std::array<int, 3>> slots = {{-1, 0, 0}, {0, -1, 0}, {0, 0, -1}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    if (fill > 0 && pc_fill_tables(fill, sten, T, slots)) return 1;
+    return pc_build(f, level, fill, slots, hb, nnOf, shift, turbDiag);
+}
+
+static int pc_setup_check(const char* who, int level)
+{
+    if (need_ready()) return 1;
+    if (!g_jac_valid) return fail("%s: no assembled Jacobian (call adflow_gpu_fd_jacobian with ADFLOW_JAC_PC first)", who);
+    if (level != g_jac_level) return fail("%s: level %d is not the level of the assembly (%d)", who, level, g_jac_level);
+    if (g_jac.nStencil != 7)
+        return fail("%s: the assembled matrix has a %d-point stencil; the block ILU(0) takes the 7-point preconditioner matrix "
+                    "(ADFLOW_JAC_PC without ADFLOW_JAC_VISC_PC)", who, g_jac.nStencil);
+    return 0;
+}
+
+// a new factor in the selected slot at the fill set for that slot; nothing is kept when the build fails
+static int pc_setup_selected(int level, const double* shift = nullptr, double turbDiag = 0.0)
+{
+    PcFactor& f = pc_sel();
     HIPCHK(hipStreamSynchronize(g_stream));
-    HIPCHK(hipGetLastError());
-    if (flag) {
-        const int at = flag - 1, s = cblk[at];
-        const long loc = vec[at] - hb[s].vecOff;
-        return fail("pc_setup: the pivot block of cell (%d,%d,%d) of block %d is singular or not finite (ILU(0) in natural order, "
-                    "level %d); no factor is kept", (int)(loc % hb[s].nx) + 2, (int)(loc / hb[s].nx % hb[s].ny) + 2,
-                    (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2, nnOf[s], level);
+    (void)pc_release(f);
+    if (pc_setup_build(f, g_pc_fill[g_pc_slot], level, shift, turbDiag)) {
+        if (g_stream) (void)hipStreamSynchronize(g_stream);
+        (void)pc_release(f);
+        return 1;
     }
-    pc_sel().level = level; pc_sel().nState = nS; pc_sel().nPlanes = nPlanes; pc_sel().ncell = N;
-    pc_sel().planeStart = start;
-    pc_sel().valid = true;
     return 0;
 }
 
 int adflow_gpu_pc_setup(int level)
 {
-    if (need_ready()) return 1;
-    if (!g_jac_valid) return fail("pc_setup: no assembled Jacobian (call adflow_gpu_fd_jacobian with ADFLOW_JAC_PC first)");
-    if (level != g_jac_level) return fail("pc_setup: level %d is not the level of the assembly (%d)", level, g_jac_level);
-    if (g_jac.nStencil != 7)
-        return fail("pc_setup: the assembled matrix has a %d-point stencil; the block ILU(0) takes the 7-point preconditioner matrix "
-                    "(ADFLOW_JAC_PC without ADFLOW_JAC_VISC_PC)", g_jac.nStencil);
-    HIPCHK(hipStreamSynchronize(g_stream));
-    (void)pc_release();
-    if (pc_setup_build(level)) {
-        if (g_stream) (void)hipStreamSynchronize(g_stream);
-        (void)pc_release();
-        return 1;
-    }
-    return 0;
+    if (pc_setup_check("pc_setup", level)) return 1;
+    return pc_setup_selected(level);
 }
 
 int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes)
@@ -4399,7 +4404,7 @@ int adflow_gpu_pc_set_fill(int fill)
 int adflow_gpu_pc_release(int64_t* bytes)
 {
     if (g_stream) HIPCHK(hipStreamSynchronize(g_stream));
-    const int64_t n = pc_release();
+    const int64_t n = pc_release(pc_sel());
     if (bytes) *bytes = n;
     return 0;
 }
@@ -4434,13 +4439,9 @@ int adflow_gpu_pc_apply_dev(int level, int transpose, const double* d_r, double*
 
 int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, long n)
 {
-    if (pc_check("pc_apply", level, r, z, n)) return 1;
-    if (vec_reserve((size_t)2 * n)) return 1;
-    HIPCHK(hipMemcpyAsync(g_vec_dev, r, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (pc_apply_enqueue(transpose, g_vec_dev, g_vec_dev + n, g_stream)) return 1;
-    HIPCHK(hipMemcpyAsync(z, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    Stage s;
+    return pc_check("pc_apply", level, r, z, n) || stage_open(&s, n, 2) || s.in(0, r) || pc_apply_enqueue(transpose, s[0], s[1], g_stream) ||
+           s.out(z, 1) || s.done();
 }
 
 // GMRES(restart) on  A M^-1 u = b, x = M^-1 u  (transpose: A^T M^-T), A = adflow_gpu_jacobian_mult with the matrix on the device,
@@ -4453,10 +4454,11 @@ static int gm_solve(const char* who, const GmOperator& op, int transpose, const 
 {
     const int m = std::max(1, std::min(restart, std::max(maxIts, 1)));
     DevBuf buf;
-    const size_t nv = (size_t)(m + 3) * n, nred = 2 * 256 + (size_t)m + 2;
+    // m + 1 basis vectors, zt, tv; then two buffers of partial sums (read one, write the other) and the Hessenberg column
+    const size_t nv = (size_t)(m + 3) * n, nred = 2 * GM_PARTS + (size_t)m + 2;
     HIPCHK(hipMalloc(&buf.p, (nv + nred) * sizeof(double)));
     double* V = (double*)buf.p;
-    double *zt = V + (size_t)(m + 1) * n, *tv = zt + n, *P[2] = {tv + n, tv + n + 256}, *dH = tv + n + 512;
+    double *zt = V + (size_t)(m + 1) * n, *tv = zt + n, *red = tv + n, *P[2] = {red, red + GM_PARTS}, *dH = red + 2 * GM_PARTS;
     std::vector<double> H(m + 2);
     hipStream_t s = g_stream;
     auto norm = [&](const double* a, double* out) -> int {
@@ -4554,23 +4556,38 @@ static int gm_solve(const char* who, const GmOperator& op, int transpose, const 
     return 0;
 }
 
-static int gm_check(int level, const double* b, const double* x, long n, int restart, int maxIts, double rtol, double atol)
+// The refusals every solve shares: those of the library and the communicator first, those of the caps last, the solve's own about its
+// operands between them.  `who` is the entry, multDev the product a host's KSP would call
+static int gm_check_ranks(const char* who, const char* multDev)
 {
     if (need_ready()) return 1;
 #ifndef ADFLOW_NO_RCCL
     if (g_nranks > 1)
-        return fail("gmres_solve: %d ranks in the communicator; the dot products of the solver are not reduced across ranks (use the "
-                    "host's KSP with adflow_gpu_jacobian_mult_dev and adflow_gpu_pc_apply_dev)", g_nranks);
+        return fail("%s: %d ranks in the communicator; the dot products of the solver are not reduced across ranks (use the "
+                    "host's KSP with %s and adflow_gpu_pc_apply_dev)", who, g_nranks, multDev);
+#else
+    (void)multDev;
 #endif
+    return 0;
+}
+
+static int gm_check_caps(const char* who, int restart, int maxIts, double rtol, double atol)
+{
+    if (restart < 1 || maxIts < 0) return fail("%s: restart = %d, maxIts = %d", who, restart, maxIts);
+    if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail("%s: rtol = %g, atol = %g", who, rtol, atol);
+    return 0;
+}
+
+static int gm_check(int level, const double* b, const double* x, long n, int restart, int maxIts, double rtol, double atol)
+{
+    if (gm_check_ranks("gmres_solve", "adflow_gpu_jacobian_mult_dev")) return 1;
     if (!g_jac_valid) return fail("gmres_solve: no assembled Jacobian (call adflow_gpu_fd_jacobian first)");
     if (pc_check("gmres_solve", level, b, x, n, false)) return 1;
     if (g_jac.nState != pc_sel().nState)
         return fail("gmres_solve: the factor was set up for nState = %d, the assembled matrix has nState = %d", pc_sel().nState, g_jac.nState);
     if (jm_check(level, b, x, n)) return 1;
     if (n != pc_sel().ncell * pc_sel().nState) return fail("gmres_solve: n=%ld but the factor has %ld rows", n, pc_sel().ncell * pc_sel().nState);
-    if (restart < 1 || maxIts < 0) return fail("gmres_solve: restart = %d, maxIts = %d", restart, maxIts);
-    if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail("gmres_solve: rtol = %g, atol = %g", rtol, atol);
-    return 0;
+    return gm_check_caps("gmres_solve", restart, maxIts, rtol, atol);
 }
 
 int adflow_gpu_gmres_solve_dev(int level, int transpose, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol,
@@ -4585,16 +4602,13 @@ int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x,
                            double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
 {
     if (gm_check(level, b, x, n, restart, maxIts, rtol, atol)) return 1;
-    DevBuf buf;
+    DevBuf buf;                        // b and x of this call, not g_vec_dev
     HIPCHK(hipMalloc(&buf.p, sizeof(double) * 2 * n));
-    double *d_b = (double*)buf.p, *d_x = d_b + n;
-    HIPCHK(hipMemcpyAsync(d_b, b, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (useGuess) HIPCHK(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+    const Stage s{n, (double*)buf.p};
+    if (s.in(0, b) || (useGuess && s.in(1, x))) return 1;
     const GmOperator op = [=](const double* v, double* y) { return jm_mult_enqueue(level, transpose, v, y); };
-    if (gm_solve("gmres_solve", op, transpose, d_b, d_x, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm)) return 1;
-    HIPCHK(hipMemcpyAsync(x, d_x, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    return gm_solve("gmres_solve", op, transpose, s[0], s[1], n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm) ||
+           s.out(x, 1) || s.done();
 }
 
 // ---- the approximate Newton-Krylov step (kernels_ank.hip) -------------------------------------------------------------------------
@@ -4620,19 +4634,19 @@ struct AnkKind {
 struct AnkState {
     AnkKind kind[2];                   // 0 flow, 1 turbulence
     int last = 0;                      // the kind of the base set last: adflow_gpu_ank_mult / _solve / _last_h act on it
-    double* red = nullptr;             // 3 x 256 partial sums, 256 partial minima, 8 scalars: h, 1/h, the three sums; lambda; the norm
+    double* red = nullptr;             // ANK_RED doubles: partial sums, partial minima and the scalars (the ANK_RED_.. layout of internal.h)
     double* part = nullptr;            // the partial sums of adflow_gpu_ank_unsteady_res, one per workgroup
     long partCap = 0;
     size_t bytesRed = 0, bytesPart = 0;
 };
 AnkState g_ank;
-const size_t ANK_RED = 4 * 256 + 8;
 const unsigned ANK_RES_FLAGS = ADFLOW_RES_DISS_APPROX | ADFLOW_RES_VISC_APPROX | ADFLOW_RES_UPWIND_FIRST_ORDER | ADFLOW_RES_APPROX_SA |
                                ADFLOW_RES_TURB_FIRST_ORDER;
 const unsigned ANK_KIND_FLAGS = ADFLOW_ANK_COUPLED | ADFLOW_ANK_TURB;
 static bool ank_is_turb(unsigned flags) { return (flags & ADFLOW_ANK_TURB) != 0; }
 static AnkKind& ank_kind(unsigned flags) { return g_ank.kind[ank_is_turb(flags) ? 1 : 0]; }
 static AnkKind& ank_last() { return g_ank.kind[g_ank.last]; }
+static double* ank_scal(AnkScal q) { return g_ank.red + ANK_RED_SCAL + q; }   // a scalar of the buffer; ank_scal(ANK_H) is `hdev`
 }  // namespace
 
 static int64_t ank_release()
@@ -4715,16 +4729,11 @@ static int ank_set_w_enqueue(const double* d_w, int nS, bool withClosures, const
     }
     if (withClosures) {
         KParams kp = make_kparams(1, 1.0, 0);
-        if (!g_floor_flag_dev) HIPCHK(hipMalloc((void**)&g_floor_flag_dev, sizeof(int)));
-        HIPCHK(hipMemsetAsync(g_floor_flag_dev, 0, sizeof(int), g_stream));
+        if (floor_flag_clear()) return 1;
         launch_ank_set_w(t.tab, t.n, t.nx, t.ny, t.nz, nS, d_w, d_v, hdev, &kp, g_floor_flag_dev, g_stream);
     } else
         launch_ank_set_w(t.tab, t.n, t.nx, t.ny, t.nz, nS, d_w, d_v, hdev, nullptr, nullptr, g_stream);
-    return for_level1_in_order([&](Block* b, long) {
-        b->ss_valid = false;
-        b->etot_consistent = false;
-        return 0;
-    });
+    return flow_state_written();
 }
 
 // blocketteRes(useDissApprox, useViscApprox, useTurbRes = ANK_coupled, useStoreWall = F) behind a state write that did the closures;
@@ -4763,12 +4772,9 @@ int adflow_gpu_ank_set_w_dev(const double* d_w, long n, unsigned flags)
 int adflow_gpu_ank_set_w(const double* w, long n, unsigned flags)
 {
     long cells; int nS;
-    if (ank_vec_check("ank_set_w", w, w, n, flags, &cells, &nS)) return 1;
-    if (vec_reserve((size_t)n)) return 1;
-    HIPCHK(hipMemcpyAsync(g_vec_dev, w, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (ank_set_w_enqueue(g_vec_dev, nS, false, nullptr, nullptr, ank_is_turb(flags))) return 1;
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    Stage s;
+    return ank_vec_check("ank_set_w", w, w, n, flags, &cells, &nS) || stage_open(&s, n, 1) || s.in(0, w) ||
+           ank_set_w_enqueue(s[0], nS, false, nullptr, nullptr, ank_is_turb(flags)) || s.done();
 }
 
 int adflow_gpu_ank_get_r_dev(double* d_r, long n, unsigned flags)
@@ -4782,12 +4788,9 @@ int adflow_gpu_ank_get_r_dev(double* d_r, long n, unsigned flags)
 int adflow_gpu_ank_get_r(double* r, long n, unsigned flags)
 {
     long cells; int nS;
-    if (ank_vec_check("ank_get_r", r, r, n, flags, &cells, &nS)) return 1;
-    if (vec_reserve((size_t)n)) return 1;
-    if (ank_get_r_enqueue(g_vec_dev, nS, ank_is_turb(flags))) return 1;
-    HIPCHK(hipMemcpyAsync(r, g_vec_dev, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    Stage s;
+    return ank_vec_check("ank_get_r", r, r, n, flags, &cells, &nS) || stage_open(&s, n, 1) || ank_get_r_enqueue(s[0], nS, ank_is_turb(flags)) ||
+           s.out(r, 0) || s.done();
 }
 
 int adflow_gpu_ank_time_step(int level, double cfl, double turbCFLScale, unsigned flags)
@@ -4863,12 +4866,7 @@ int adflow_gpu_ank_download_time_step_turb(int nn, double* blocks, unsigned flag
 
 int adflow_gpu_ank_pc_setup(int level)
 {
-    if (need_ready()) return 1;
-    if (!g_jac_valid) return fail("ank_pc_setup: no assembled Jacobian (call adflow_gpu_fd_jacobian with ADFLOW_JAC_PC first)");
-    if (level != g_jac_level) return fail("ank_pc_setup: level %d is not the level of the assembly (%d)", level, g_jac_level);
-    if (g_jac.nStencil != 7)
-        return fail("ank_pc_setup: the assembled matrix has a %d-point stencil; the block ILU(0) takes the 7-point preconditioner matrix "
-                    "(ADFLOW_JAC_PC without ADFLOW_JAC_VISC_PC)", g_jac.nStencil);
+    if (pc_setup_check("ank_pc_setup", level)) return 1;
     // an ADFLOW_JAC_TURB_ONLY matrix takes the turbulence T (FormJacobianANKTurb), every other the flow T (FormJacobianANK)
     const bool turb = g_jac.nState == 1;
     const AnkKind& K = g_ank.kind[turb ? 1 : 0];
@@ -4879,14 +4877,7 @@ int adflow_gpu_ank_pc_setup(int level)
     if (K.tNState != g_jac.nState)
         return fail("ank_pc_setup: the pseudo-time term was formed for nState = %d, the assembled matrix has nState = %d", K.tNState,
                     g_jac.nState);
-    HIPCHK(hipStreamSynchronize(g_stream));
-    (void)pc_release();
-    if (pc_setup_build(level, K.tsm, K.turbDiag)) {
-        if (g_stream) (void)hipStreamSynchronize(g_stream);
-        (void)pc_release();
-        return 1;
-    }
-    return 0;
+    return pc_setup_selected(level, K.tsm, K.turbDiag);
 }
 
 static int ank_set_base_enqueue(const double* d_w, long n, long cells, int nS, unsigned flags)
@@ -4927,12 +4918,9 @@ int adflow_gpu_ank_set_base_dev(const double* d_w, long n, unsigned flags)
 int adflow_gpu_ank_set_base(const double* w, long n, unsigned flags)
 {
     long cells; int nS;
-    if (ank_vec_check("ank_set_base", w, w, n, flags, &cells, &nS)) return 1;
-    if (vec_reserve((size_t)n)) return 1;
-    HIPCHK(hipMemcpyAsync(g_vec_dev, w, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (ank_set_base_enqueue(g_vec_dev, n, cells, nS, flags)) return 1;
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    Stage s;
+    return ank_vec_check("ank_set_base", w, w, n, flags, &cells, &nS) || stage_open(&s, n, 1) || s.in(0, w) ||
+           ank_set_base_enqueue(s[0], n, cells, nS, flags) || s.done();
 }
 
 static int ank_mult_check(const char* who, const double* v, const double* y, long n)
@@ -4960,8 +4948,8 @@ static int ank_mult_enqueue(const double* d_v, double* d_y)
     const bool turb = g_ank.last == 1;
     const long n = K.ncell * K.nState;
     const int nS = K.nState;
-    double *part = g_ank.red, *hdev = g_ank.red + 4 * 256;
-    launch_ank_step(K.w0, d_v, n, 1.490116119384766e-08, 1e-6, part, hdev, g_stream);
+    double* hdev = ank_scal(ANK_H);
+    launch_ank_step(K.w0, d_v, n, 1.490116119384766e-08, 1e-6, g_ank.red + ANK_RED_SUMS, hdev, g_stream);
     if (ank_set_w_enqueue(K.w0, nS, true, d_v, hdev, turb)) return 1;
     if (ank_res_enqueue(K.flags)) return 1;
     LevelTab t;
@@ -4987,16 +4975,12 @@ int adflow_gpu_ank_mult(const double* v, double* y, long n)
     for (long i = 0; i < n && zero; ++i) zero = v[i] == 0.0;
     if (zero) {
         memset(y, 0, sizeof(double) * n);
-        HIPCHK(hipMemsetAsync(g_ank.red + 4 * 256, 0, 8 * sizeof(double), g_stream));
+        HIPCHK(hipMemsetAsync(ank_scal(ANK_H), 0, ANK_NSCAL * sizeof(double), g_stream));
         HIPCHK(hipStreamSynchronize(g_stream));
         return 0;
     }
-    if (vec_reserve((size_t)2 * n)) return 1;
-    HIPCHK(hipMemcpyAsync(g_vec_dev, v, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (ank_mult_enqueue(g_vec_dev, g_vec_dev + n)) return 1;
-    HIPCHK(hipMemcpyAsync(y, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    Stage s;
+    return stage_open(&s, n, 2) || s.in(0, v) || ank_mult_enqueue(s[0], s[1]) || s.out(y, 1) || s.done();
 }
 
 // the kind whose base adflow_gpu_ank_mult / _solve / _last_h act on: the one set last, or the one selected here
@@ -5014,35 +4998,27 @@ int adflow_gpu_ank_last_h(double* h)
 {
     if (need_ready()) return 1;
     if (!ank_last().haveBase || !h) return fail("ank_last_h: no base state (call adflow_gpu_ank_set_base first)");
-    HIPCHK(hipMemcpyAsync(h, g_ank.red + 4 * 256, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(h, ank_scal(ANK_H), sizeof(double), hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
 }
 
 static int ank_gm_check(int level, const double* b, const double* x, long n, int restart, int maxIts, double rtol, double atol)
 {
-    if (need_ready()) return 1;
-#ifndef ADFLOW_NO_RCCL
-    if (g_nranks > 1)
-        return fail("ank_solve: %d ranks in the communicator; the dot products of the solver are not reduced across ranks (use the "
-                    "host's KSP with adflow_gpu_ank_mult_dev and adflow_gpu_pc_apply_dev)", g_nranks);
-#endif
+    if (gm_check_ranks("ank_solve", "adflow_gpu_ank_mult_dev")) return 1;
     if (level != 1) return fail("ank_solve: level %d; the matrix-free operator acts on level 1", level);
     if (ank_mult_check("ank_solve", b, x, n)) return 1;
     if (pc_check("ank_solve", level, b, x, n, false)) return 1;
     if (pc_sel().nState != ank_last().nState || pc_sel().ncell != ank_last().ncell)
         return fail("ank_solve: the factor was set up for nState = %d, the base state has nState = %d", pc_sel().nState, ank_last().nState);
-    if (restart < 1 || maxIts < 0) return fail("ank_solve: restart = %d, maxIts = %d", restart, maxIts);
-    if (!(rtol >= 0.0) || !(atol >= 0.0)) return fail("ank_solve: rtol = %g, atol = %g", rtol, atol);
-    return 0;
+    return gm_check_caps("ank_solve", restart, maxIts, rtol, atol);
 }
 
 int adflow_gpu_ank_solve_dev(int level, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol, double atol, int* its,
                              double* rnorm0, double* rnorm)
 {
     if (ank_gm_check(level, d_b, d_x, n, restart, maxIts, rtol, atol)) return 1;
-    const GmOperator op = [](const double* v, double* y) { return ank_mult_enqueue(v, y); };
-    if (gm_solve("ank_solve", op, 0, d_b, d_x, n, restart, maxIts, rtol, atol, 0, its, rnorm0, rnorm)) return 1;
+    if (gm_solve("ank_solve", ank_mult_enqueue, 0, d_b, d_x, n, restart, maxIts, rtol, atol, 0, its, rnorm0, rnorm)) return 1;
     return sync_and_check();
 }
 
@@ -5050,15 +5026,11 @@ int adflow_gpu_ank_solve(int level, const double* b, double* x, long n, int rest
                          double* rnorm0, double* rnorm)
 {
     if (ank_gm_check(level, b, x, n, restart, maxIts, rtol, atol)) return 1;
-    DevBuf buf;
+    DevBuf buf;                        // b and x of this call, not g_vec_dev
     HIPCHK(hipMalloc(&buf.p, sizeof(double) * 2 * n));
-    double *d_b = (double*)buf.p, *d_x = d_b + n;
-    HIPCHK(hipMemcpyAsync(d_b, b, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    const GmOperator op = [](const double* v, double* y) { return ank_mult_enqueue(v, y); };
-    if (gm_solve("ank_solve", op, 0, d_b, d_x, n, restart, maxIts, rtol, atol, 0, its, rnorm0, rnorm)) return 1;
-    HIPCHK(hipMemcpyAsync(x, d_x, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    const Stage s{n, (double*)buf.p};
+    return s.in(0, b) || gm_solve("ank_solve", ank_mult_enqueue, 0, s[0], s[1], n, restart, maxIts, rtol, atol, 0, its, rnorm0, rnorm) ||
+           s.out(x, 1) || s.done();
 }
 
 static int ank_phys_check(const double* w, const double* dw, long n, unsigned flags, double stepFactor, double stepMin, const double* lambda,
@@ -5084,7 +5056,7 @@ static int ank_phys_enqueue(const double* d_w, double* d_dw, long cells, int nS,
 {
     if (ank_red()) return 1;
     launch_ank_phys(d_w, d_dw, cells, nS, nS >= 5 ? 1 : 0, nS > 5 ? 5 : nS == 1 ? 0 : -1, 1.e-25, physLSTol, physLSTolTurb, stepFactor * stepMin,
-                    lambda0, g_ank.red + 3 * 256, g_ank.red + 4 * 256 + 5, g_stream);
+                    lambda0, g_ank.red + ANK_RED_MIN, ank_scal(ANK_LAMBDA), g_stream);
     return 0;
 }
 
@@ -5094,7 +5066,7 @@ int adflow_gpu_ank_physicality_check_dev(const double* d_w, double* d_dw, long n
     long cells; int nS;
     if (ank_phys_check(d_w, d_dw, n, flags, stepFactor, stepMin, lambda, &cells, &nS)) return 1;
     if (ank_phys_enqueue(d_w, d_dw, cells, nS, physLSTol, physLSTolTurb, stepFactor, stepMin, *lambda)) return 1;
-    HIPCHK(hipMemcpyAsync(lambda, g_ank.red + 4 * 256 + 5, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(lambda, ank_scal(ANK_LAMBDA), sizeof(double), hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));      // lambda goes to the host: synchronous whatever adflow_gpu_set_async says
     HIPCHK(hipGetLastError());
     return 0;
@@ -5104,15 +5076,12 @@ int adflow_gpu_ank_physicality_check(const double* w, double* dw, long n, unsign
                                      double stepFactor, double stepMin, double* lambda)
 {
     long cells; int nS;
-    if (ank_phys_check(w, dw, n, flags, stepFactor, stepMin, lambda, &cells, &nS)) return 1;
-    if (vec_reserve((size_t)2 * n)) return 1;
-    HIPCHK(hipMemcpyAsync(g_vec_dev, w, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(g_vec_dev + n, dw, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (ank_phys_enqueue(g_vec_dev, g_vec_dev + n, cells, nS, physLSTol, physLSTolTurb, stepFactor, stepMin, *lambda)) return 1;
-    if (nS != 5) HIPCHK(hipMemcpyAsync(dw, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemcpyAsync(lambda, g_ank.red + 4 * 256 + 5, sizeof(double), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    Stage s;
+    if (ank_phys_check(w, dw, n, flags, stepFactor, stepMin, lambda, &cells, &nS) || stage_open(&s, n, 2) || s.in(0, w) || s.in(1, dw) ||
+        ank_phys_enqueue(s[0], s[1], cells, nS, physLSTol, physLSTolTurb, stepFactor, stepMin, *lambda))
+        return 1;
+    if (nS != 5 && s.out(dw, 1)) return 1;       // only a turbulence entry is ever clipped
+    return s.scalars(lambda, ank_scal(ANK_LAMBDA), 1) || s.done();
 }
 
 // computeUnsteadyResANK / computeUnsteadyResANKTurb (:2614-2786): the state is the one adflow_gpu_ank_set_w left (w - omega dW);
@@ -5152,7 +5121,7 @@ static int ank_unsteady_enqueue(const double* d_dW, double omega, double* d_r, i
     if (level_tab(1, &t)) return 1;
     const AnkKind& K = ank_kind(flags);
     launch_ank_unsteady(t.tab, t.n, t.nx, t.ny, t.nz, nS, ank_is_turb(flags) ? 1 : 0, d_dW, K.tsm, K.tCells, K.turbDiag, g_opts.turbResScale, omega,
-                        d_r, g_ank.part, wantNorm ? g_ank.red + 4 * 256 + 6 : nullptr, g_stream);
+                        d_r, g_ank.part, wantNorm ? ank_scal(ANK_NORM) : nullptr, g_stream);
     return 0;
 }
 
@@ -5162,7 +5131,7 @@ int adflow_gpu_ank_unsteady_res_dev(const double* d_dW, double omega, double* d_
     if (ank_unsteady_check(d_dW, d_r, n, flags, norm, &cells, &nS)) return 1;
     if (ank_unsteady_enqueue(d_dW, omega, d_r, nS, flags, norm != nullptr)) return 1;
     if (!norm) return sync_and_check();          // no reduction, nothing goes to the host: honours adflow_gpu_set_async
-    HIPCHK(hipMemcpyAsync(norm, g_ank.red + 4 * 256 + 6, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(norm, ank_scal(ANK_NORM), sizeof(double), hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     HIPCHK(hipGetLastError());
     return 0;
@@ -5171,14 +5140,11 @@ int adflow_gpu_ank_unsteady_res_dev(const double* d_dW, double omega, double* d_
 int adflow_gpu_ank_unsteady_res(const double* dW, double omega, double* r, long n, unsigned flags, double* norm)
 {
     long cells; int nS;
-    if (ank_unsteady_check(dW, r, n, flags, norm, &cells, &nS)) return 1;
-    if (vec_reserve((size_t)2 * n)) return 1;
-    HIPCHK(hipMemcpyAsync(g_vec_dev, dW, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
-    if (ank_unsteady_enqueue(g_vec_dev, omega, g_vec_dev + n, nS, flags, norm != nullptr)) return 1;
-    HIPCHK(hipMemcpyAsync(r, g_vec_dev + n, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    if (norm) HIPCHK(hipMemcpyAsync(norm, g_ank.red + 4 * 256 + 6, sizeof(double), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return 0;
+    Stage s;
+    if (ank_unsteady_check(dW, r, n, flags, norm, &cells, &nS) || stage_open(&s, n, 2) || s.in(0, dW) ||
+        ank_unsteady_enqueue(s[0], omega, s[1], nS, flags, norm != nullptr) || s.out(r, 1))
+        return 1;
+    return (norm && s.scalars(norm, ank_scal(ANK_NORM), 1)) || s.done();
 }
 
 // turbAPI::turbSolveDDADI (src/turbulence/turbAPI.F90:4-95) for Spalart-Allmaras:

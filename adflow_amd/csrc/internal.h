@@ -393,14 +393,21 @@ void launch_jac_mult_t(const JmBlk* tab, int nslots, int maxnx, int maxny, int m
 void launch_jac_halo_accumulate(const JmBlk* tab, const JmAccList& a, int nState, const double* buf, int nbuf, hipStream_t s);
 
 // block ILU of the 7-point matrix (kernels_pc.hip, kernels_pc_fill.hip): the factor of a level as its kernels see it.  Position q of
-// the hyperplane order (hyperplane, block, k, j, i) holds fac[q + ((s nState + l) nState + ll) ncell]; at fill 0 s = 0..2 L of the
-// lower neighbour along i, j, k, 3..5 U of the upper neighbour, 6 the inverted pivot block (fill 1, 2: the end of the struct)
+// the order of the factor (set, block, k, j, i) holds fac[q + ((s nState + l) nState + ll) ncell].  A set holds the cells whose lower
+// entries all lie in earlier sets (longest path inside the block): the hyperplanes i + j + k at fill 0.  One builder (pc_build of
+// api.hip) makes the tables of every fill from the offsets of the off-diagonal slots s, which the kernels of each fill number their
+// own way; column s of nbr is the neighbour of slot s:
+//   fill 0:    s = 0..2 L of the lower neighbour along i, j, k (columns c - e_i, c - e_j, c - e_k), 3..5 U of the upper neighbour along
+//              i, j, k, 6 the inverted pivot block -- NOT ascending column order, where c - e_k would come first
+//   fill 1, 2: nLow = (entries per row - 1) / 2 lower and as many upper entries, each side in ascending column order (c - e_k before
+//              c - e_j before c - e_i; upper entry u is the mirror of lower entry nLow-1-u): s = 0..nLow-1 L, nLow..2 nLow-1 U, 2 nLow the
+//              inverted pivot block
 #include <vector>
 struct PcTab {
     long ncell;           // owned cells of the level
     double* fac;
-    double* ws;           // nState components in hyperplane order: the vector between and during the two sweeps
-    const int* nbr;       // nbr[e ncell + q]: position of neighbour e (0..2 lower, 3..5 upper), -1 outside the block
+    double* ws;           // nState components in the order of the factor: the vector between and during the two sweeps
+    const int* nbr;       // nbr[s ncell + q]: position of the neighbour of off-diagonal slot s (see above), -1 outside the block
     const int* vec;       // the cell's number in the PETSc layout (block, k, j, i)
     const int* cblk;      // setup only: slot of the cell's block in blk[] and its box index
     const int* cbox;
@@ -409,9 +416,7 @@ struct PcTab {
     int sten[7];          // stencil entries of the assembly: the columns c - e_i, c - e_j, c - e_k, c + e_i, c + e_j, c + e_k, c
     const double* tsm;    // setup only: the pseudo-time term of ANK added to the diagonal blocks (kernels_ank.hip), NULL = none
     double turbDiag;      // S(nt1, nt1) = turbResScale / turbCFLScale of the coupled T
-    // fill 1 and 2 only (kernels_pc_fill.hip): nLow = (entries per row - 1) / 2 lower and as many upper entries, each side in
-    // ascending column order (upper entry u is the mirror of lower entry nLow-1-u); fac slots 0..nLow-1 L, nLow..2 nLow-1 U,
-    // 2 nLow the inverted pivot block; nbr has one column per off-diagonal slot
+    // fill 1 and 2 only (kernels_pc_fill.hip); zero at fill 0
     int asmEnt[23];       // stencil entry of the assembly that slot s starts from, -1: a fill entry (starts from zero)
     signed char tgt[121]; // tgt[e nLow + u]: slot of this row that L_{c,n} U_{n,m} lands in (n: lower entry e, m: upper entry u
                           // of row n), -1: outside the pattern
@@ -425,12 +430,31 @@ int launch_pcf_factor(const PcTab& T, int nState, int nEnt, const std::vector<in
 int launch_pcf_apply(const PcTab& T, int nState, int nEnt, int transpose, const std::vector<int>& levelStart, const double* r,
                      double* z, hipStream_t s);
 // the vectors of GMRES: one step of modified Gram-Schmidt per launch (partial sums in, partial sums out), see kernels_pc.hip
+enum { GM_PARTS = 256 };  // the most partial sums one reduction leaves (GM_T of kernels_pc.hip): the size of a buffer of them
 int gm_groups(long n);
 void launch_gm_mgs(double* w, const double* v, const double* hp, const double* u, double* out, double* hOut, long n, hipStream_t s);
 void launch_gm_sum(const double* hp, long n, double* hOut, hipStream_t s);
 void launch_gm_axpby(double* y, double a, const double* x, double b, long n, hipStream_t s);
 // approximate Newton-Krylov step (kernels_ank.hip): vectors of nS variables per owned cell; kp != NULL: with the closures of blocketteRes
 struct KParams;
+// The reduction buffer of the ANK entries (g_ank.red of api.hip), in doubles: partial results, one per workgroup of a reduction, then
+// the scalars.  Two index spaces, two types: AnkRed are offsets into the buffer, AnkScal are offsets into its scalars.  The kernels
+// take the partial results they write and `hdev` / `out`, pointers into the scalars; hdev = the buffer + ANK_RED_SCAL is indexed by
+// ANK_H .. ANK_SUMS
+enum { ANK_PARTS = 256 };                  // the most workgroups of a reduction (AK_T of kernels_ank.hip)
+enum AnkScal {
+    ANK_H = 0, ANK_HINV = 1,               // the MATMFFD_DS step h and 1 / h (both 0 when v = 0)
+    ANK_SUMS = 2,                          // the three sums h was formed from
+    ANK_LAMBDA = 5,                        // the step the physicality check allows
+    ANK_NORM = 6,                          // the norm of the unsteady residual
+    ANK_NSCAL = 8
+};
+enum AnkRed {
+    ANK_RED_SUMS = 0,                      // 3 x ANK_PARTS partial sums of w.v, |v|_1, |v|_2^2 (launch_ank_step)
+    ANK_RED_MIN = 3 * ANK_PARTS,           // ANK_PARTS partial minima (launch_ank_phys)
+    ANK_RED_SCAL = 4 * ANK_PARTS,          // the ANK_NSCAL scalars
+    ANK_RED = ANK_RED_SCAL + ANK_NSCAL     // doubles in all
+};
 int ank_groups(long n);
 void launch_ank_set_w(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, int nS, const double* vec, const double* hv,
                       const double* hdev, const KParams* kp, int* floored, hipStream_t s);

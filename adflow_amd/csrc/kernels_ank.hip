@@ -25,6 +25,7 @@
 #define AK_BX 64
 #define AK_BY 4
 #define AK_T 256          // threads of a reduction workgroup = the largest number of partial results
+static_assert(AK_T == ANK_PARTS, "the reduction buffer of api.hip is laid out for AK_T partial results");
 
 struct AkCell { int i, j, k; long c, m; bool in; };
 
@@ -44,7 +45,7 @@ __device__ __forceinline__ AkCell ak_cell(const BlkView& b, int kz)
     return q;
 }
 
-// w(1:nS) = vec (hv == NULL) or vec + h hv with h = hdev[0]; CLOS: the closures of blocketteRes in the same pass, each lane reads
+// w(1:nS) = vec (hv == NULL) or vec + h hv with h = hdev[ANK_H]; CLOS: the closures of blocketteRes in the same pass, each lane reads
 // back what it wrote itself (k_set_w_closures_level)
 template <bool CLOS>
 __global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_set_w(const BlkView* __restrict__ tab, int nzb, int nS, const double* __restrict__ vec,
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_set_w(const BlkView* __res
     const AkCell q = ak_cell(b, (int)(blockIdx.z % nzb));
     if (!q.in) return;
     const long m = q.m * nS;
-    const double h = hv ? hdev[0] : 0.0;
+    const double h = hv ? hdev[ANK_H] : 0.0;
     for (int l = 0; l < nS; ++l) b.w[q.c + l * b.nbox] = hv ? vec[m + l] + h * hv[m + l] : vec[m + l];
     if (CLOS) closures_cell<true>(b, q.i, q.j, q.k, kp, floored);
 }
@@ -95,8 +96,8 @@ __global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_quotient(const BlkView* __
     const AkCell q = ak_cell(b, (int)(blockIdx.z % nzb));
     if (!q.in) return;
     const long m = q.m * nS;
-    const double hinv = hdev[1];
-    if (hdev[0] == 0.0) {
+    const double hinv = hdev[ANK_HINV];
+    if (hdev[ANK_H] == 0.0) {
         for (int l = 0; l < nS; ++l) y[m + l] = 0.0;
         return;
     }
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_set_w_turb(const BlkView* 
     const BlkView& b = tab[blockIdx.z / nzb + 1];
     const AkCell q = ak_cell(b, (int)(blockIdx.z % nzb));
     if (!q.in) return;
-    const double h = hv ? hdev[0] : 0.0;
+    const double h = hv ? hdev[ANK_H] : 0.0;
     const double nut = hv ? vec[q.m] + h * hv[q.m] : vec[q.m];
     b.w[q.c + 5 * b.nbox] = nut;
     if (EDDY && kp.eddyModel && kp.updateEddy) b.rev[q.c] = sa_eddy_viscosity(kp, b.w[q.c], b.rlv[q.c], nut);
@@ -159,13 +160,13 @@ __global__ __launch_bounds__(AK_BX* AK_BY) void k_ank_quotient_turb(const BlkVie
     const BlkView& b = tab[blockIdx.z / nzb + 1];
     const AkCell q = ak_cell(b, (int)(blockIdx.z % nzb));
     if (!q.in) return;
-    if (hdev[0] == 0.0) {
+    if (hdev[ANK_H] == 0.0) {
         y[q.m] = 0.0;
         return;
     }
     const double ovv = 1.0 / b.volRef[q.c];
     const double r = b.dw[q.c + 5 * b.nbox] * ovv * turbScale;
-    y[q.m] = (r - r0[q.m]) * hdev[1] + tsm[q.m] * turbDiag * v[q.m];
+    y[q.m] = (r - r0[q.m]) * hdev[ANK_HINV] + tsm[q.m] * turbDiag * v[q.m];
 }
 
 // ---- reductions: partial results per workgroup, then one finishing workgroup that adds them in a fixed order ------------------------
@@ -200,7 +201,7 @@ __global__ __launch_bounds__(AK_T) void k_ank_sums(const double* __restrict__ w,
         for (int q = 0; q < 3; ++q) part[q * AK_T + blockIdx.x] = s[q];
 }
 
-// the step of MATMFFD_DS from the three sums: hdev[0] = h, hdev[1] = 1 / h (both 0 when v = 0), hdev[2..4] = the sums
+// the step of MATMFFD_DS from the three sums: hdev[ANK_H] = h, hdev[ANK_HINV] = 1 / h (both 0 when v = 0), hdev[ANK_SUMS ..] = the sums
 __global__ __launch_bounds__(AK_T) void k_ank_step(const double* __restrict__ part, int np, double errRel, double umin, double* __restrict__ hdev)
 {
     __shared__ double red[3][AK_T];
@@ -212,9 +213,9 @@ __global__ __launch_bounds__(AK_T) void k_ank_step(const double* __restrict__ pa
     const double d = s[1], nrm2 = s[2];
     if (fabs(dot) < umin * d) dot = dot < 0.0 ? -umin * d : umin * d;
     const double h = nrm2 == 0.0 ? 0.0 : errRel * dot / nrm2;
-    hdev[0] = h;
-    hdev[1] = h == 0.0 ? 0.0 : 1.0 / h;
-    hdev[2] = s[0]; hdev[3] = d; hdev[4] = nrm2;
+    hdev[ANK_H] = h;
+    hdev[ANK_HINV] = h == 0.0 ? 0.0 : 1.0 / h;
+    hdev[ANK_SUMS] = s[0]; hdev[ANK_SUMS + 1] = d; hdev[ANK_SUMS + 2] = nrm2;
 }
 
 // the residual of the backtracking line search (computeUnsteadyResANK / ...Turb): r = setRVecANK / setRVec / setRVecANKTurb of the dw

@@ -239,6 +239,7 @@ int launch_pc_apply(const PcTab& T, int nState, int transpose, const std::vector
 
 // ---- the vectors of GMRES: everything stays on the device, one download of a column of the Hessenberg matrix per step -----------
 #define GM_T 256          // threads of a workgroup = the largest number of workgroups (partial sums) of a reduction
+static_assert(GM_T == GM_PARTS, "gm_solve of api.hip sizes its buffers of partial sums for GM_T of them");
 
 __device__ __forceinline__ double gm_block_sum(double v, double* red)
 {

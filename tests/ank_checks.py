@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import checks
+from device_vectors import dev_call
 import jacmult_checks as jm
 import pc_checks as pc
 from adflow_amd import capi
@@ -410,7 +411,148 @@ def check_physicality(engine, topo, coupled, seed=359):
     engine.ankRelease()
 
 
-# ---- 6. refusals and side effects ------------------------------------------------------------------------------------------------
+# ---- 6. the _dev entries against their host twins -----------------------------------------------------------------------------------
+def check_dev_twins(engine, dv, dims=(7, 6, 5), kind="flow", cap=16, seed=431):
+    """every adflow_gpu_ank_*_dev entry on device vectors (dv: device_vectors.HostVectors / TorchVectors) returns bit for bit what its host twin
+    returns from the same inputs and the same device state -- the two forms run the same kernels with the same launch geometry and
+    fixed-order reductions.  kind: 'flow' (nState 5), 'coupled' (6) or 'turb' (1) on one wall-bounded RANS block; the state on the
+    device (w, p, rlv, rev with their halos) is put back before each call of a pair."""
+    import ctypes
+    lib = engine.lib
+    coupled, turb = kind == "coupled", kind == "turb"
+    blk, r, prm = checks.setup_block_with_bc(engine, dims, RANS_COUPLED if coupled else RANS_UPWIND, jm.WALL, seed, stretch_k=2.0)
+    _KEEP[:] = [r]
+    ns = 1 if turb else blk.nw if coupled else 5
+    flags = engine._ankFlags(coupled, turb=turb, approxSA=turb)
+    kflags = engine._ankFlags(coupled, turb=turb)
+    engine.setupStateResidualMatrix(1, True, frozenTurb=kind == "flow", useTurbOnly=turb, useAD=True, approxSA=turb)
+    engine.timeStep(1)
+    engine.ankTimeStep(CFL, TURB_CFL_SCALE, coupled=coupled, turb=turb)
+    engine.ankPcSetup(1)
+    engine.ankSetBase(state_vector(engine, {1: blk}, blk.nw), coupled=True)       # p, rlv and rev of the state on the device
+    engine.download_state(1, 1)
+    start = {name: blk[name].copy() for name in ("w", "p", "rlv", "rev")}
+    w0 = owned_vector({1: blk}, "w", blk.nw)[5::blk.nw].copy() if turb else owned_vector({1: blk}, "w", ns)
+    n = w0.size
+    rng = np.random.default_rng(seed)
+
+    def reset():
+        for name, a in start.items():
+            blk[name][...] = a
+        engine.upload_state(1, 1)
+
+    def chk(rc):
+        engine._chk(rc)
+
+    def state():
+        engine.download_state(1, 1)
+        return blk["w"].copy()
+
+    def evaluate():
+        engine.blocketteRes(1, updateIntermed=False, flowRes=not turb, turbRes=turb or coupled, halo=True, closures=True)
+
+    # set_w and get_r: the state each form leaves, and the vector each form takes from the residual of that state
+    w1 = w0 * (1.0 + 1e-3 * rng.uniform(-1.0, 1.0, n))
+    reset()
+    engine.ankSetW(w1, coupled=coupled, turb=turb)
+    s_host = state()
+    evaluate()
+    r_host = engine.ankGetR(coupled=coupled, turb=turb)
+    reset()
+    d_w1, d_r = dv.put(w1), dv.empty(n)
+    chk(dev_call(engine, dv, lib.adflow_gpu_ank_set_w_dev, dv.ptr(d_w1), n, kflags))
+    assert np.array_equal(state(), s_host, equal_nan=True), (kind, "ank_set_w_dev")
+    evaluate()
+    chk(dev_call(engine, dv, lib.adflow_gpu_ank_get_r_dev, dv.ptr(d_r), n, kflags))
+    assert np.abs(r_host).max() > 0.0
+    assert np.array_equal(dv.get(d_r), r_host), (kind, "ank_get_r_dev")
+
+    # set_base (through the r0 it keeps), mult and last_h
+    v = rng.uniform(-1.0, 1.0, n)
+    reset()
+    engine.ankSetBase(w0, coupled, turb=turb, approxSA=turb)
+    r0_host = engine.ankGetR(coupled=coupled, turb=turb)
+    y_host, h_host = engine.ankMult(v), engine.ankLastH()
+    reset()
+    d_w0, d_v, d_y = dv.put(w0), dv.put(v), dv.empty(n)
+    chk(dev_call(engine, dv, lib.adflow_gpu_ank_set_base_dev, dv.ptr(d_w0), n, flags))
+    assert np.array_equal(engine.ankGetR(coupled=coupled, turb=turb), r0_host), (kind, "ank_set_base_dev")
+    dev_call(engine, dv, engine.ankMultDev, dv.ptr(d_v), dv.ptr(d_y), n)
+    print(f"ank_mult / _dev {kind} {dims}: h = {h_host:.17e} / {engine.ankLastH():.17e}, max|y| = {np.abs(y_host).max():.3e}")
+    assert h_host != 0.0 and np.abs(y_host).max() > 0.0
+    assert engine.ankLastH() == h_host and np.array_equal(dv.get(d_y), y_host), (kind, "ank_mult_dev")
+
+    # solve: b = the residual of the base state
+    b = r0_host
+    kw = dict(restart=cap, maxIts=cap, rtol=1e-4)
+    reset()
+    engine.ankSetBase(w0, coupled, turb=turb, approxSA=turb)
+    x_host, *host = engine.ankSolve(b, 1, **kw)
+    reset()
+    engine.ankSetBase(w0, coupled, turb=turb, approxSA=turb)
+    d_b, d_x = dv.put(b), dv.put(np.full(n, 7.0))
+    dev = dev_call(engine, dv, engine.ankSolveDev, dv.ptr(d_b), dv.ptr(d_x), n, 1, **kw)
+    print(f"ank_solve / _dev {kind} {dims}: (its, rnorm0, rnorm) = {tuple(host)} / {dev}")
+    assert 0 < host[0] <= cap
+    assert tuple(host) == dev and np.array_equal(dv.get(d_x), x_host), (kind, "ank_solve_dev")
+
+    # the step limiter: a density update that limits, turbulence updates that are clipped (written back) and one that limits
+    dw = 1e-3 * rng.uniform(-1.0, 1.0, n) * np.abs(w0)
+    D, W = dw.reshape(-1, ns), w0.reshape(-1, ns)
+    ncell = D.shape[0]
+    if not turb:
+        D[ncell // 3, 0] = -10.0 * W[ncell // 3, 0]
+    if turb or coupled:
+        D[5, ns - 1] = 200.0 * W[5, ns - 1]
+        D[ncell - 7, ns - 1] = 1e4 * W[ncell - 7, ns - 1]
+        D[ncell // 2, ns - 1] = 3.0 * W[ncell // 2, ns - 1]
+    lam_host, out_host = engine.ankPhysicalityCheck(w0, dw, 1.0, coupled, turb=turb)
+    d_dw, lam = dv.put(dw), ctypes.c_double(1.0)
+    chk(dev_call(engine, dv, lib.adflow_gpu_ank_physicality_check_dev, dv.ptr(d_w0), dv.ptr(d_dw), n, kflags, 0.2, 0.99, 1.0, 0.01,
+                 ctypes.byref(lam)))
+    print(f"ank_physicality_check / _dev {kind}: lambda = {lam_host!r} / {lam.value!r}, {int((out_host != dw).sum())} entries clipped")
+    assert 0.0 < lam_host < 1.0 and (out_host != dw).any() == (turb or coupled)
+    assert lam.value == lam_host and np.array_equal(dv.get(d_dw), out_host), (kind, "ank_physicality_check_dev")
+
+    # the line-search residual, with and without its norm
+    dW, omega = 1e-3 * rng.uniform(-1.0, 1.0, n) * np.abs(w0), 0.7
+    reset()
+    engine.ankSetW(w0 - omega * dW, coupled=coupled, turb=turb)
+    rr_host, nrm_host = engine.ankUnsteadyRes(dW, omega, coupled=coupled, turb=turb, approxSA=turb)
+    d_dW = dv.put(dW)
+    for norm in (True, False):
+        reset()
+        engine.ankSetW(w0 - omega * dW, coupled=coupled, turb=turb)
+        d_rr = dv.put(np.full(n, 7.0))
+        nrm = dev_call(engine, dv, engine.ankUnsteadyResDev, dv.ptr(d_dW), omega, dv.ptr(d_rr), n, flags, norm)
+        assert np.array_equal(dv.get(d_rr), rr_host), (kind, "ank_unsteady_res_dev", norm)
+        assert nrm == (nrm_host if norm else None), (kind, nrm, nrm_host)
+    assert nrm_host > 0.0
+    engine.pcRelease()
+    engine.ankRelease()
+    engine.releaseWorkspace()
+
+
+def check_nk_residual_dev_twin(engine, dv, dims=(7, 6, 5), seed=433):
+    """adflow_gpu_nk_residual_dev with two device vectors against adflow_gpu_nk_residual (one staging buffer for w and r), bit for
+    bit, on one wall-bounded RANS block; some turbulence entries lie below the floor of setW"""
+    blk, r, prm = checks.setup_block_with_bc(engine, dims, RANS_UPWIND, jm.WALL, seed, stretch_k=2.0)
+    _KEEP[:] = [r]
+    engine.download_state(1, 1)
+    rng = np.random.default_rng(seed)
+    w = owned_vector({1: blk}, "w", blk.nw)
+    w *= 1.0 + 1e-3 * rng.uniform(-1.0, 1.0, w.size)
+    w[5::7 * blk.nw] = 0.0
+    engine.upload_state(1, 1)
+    r_host = engine.FormFunction_mf(w)
+    engine.upload_state(1, 1)
+    d_w, d_r = dv.put(w), dv.empty(w.size)
+    engine._chk(dev_call(engine, dv, engine.lib.adflow_gpu_nk_residual_dev, dv.ptr(d_w), dv.ptr(d_r), w.size))
+    assert np.abs(r_host).max() > 0.0 and np.isfinite(r_host).all()
+    assert np.array_equal(dv.get(d_r), r_host) and np.array_equal(dv.get(d_w), w)
+
+
+# ---- 7. refusals and side effects ------------------------------------------------------------------------------------------------
 def check_refusals_and_side_effects(engine, dims=(7, 6, 5)):
     lib = engine.lib
     engine.release_all()

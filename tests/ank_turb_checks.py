@@ -408,6 +408,11 @@ def check_unsteady(engine, dims, kind, seed=415, prm=None):
     engine.ankRelease()
 
 
+def check_dev_twins(engine, dv, dims, cap):
+    """the _dev entries of the turbulence kind (nState 1, approxSA) against their host twins, bit for bit: ank_checks.check_dev_twins"""
+    ank.check_dev_twins(engine, dv, dims, "turb", cap, seed=421)
+
+
 # ---- 8. the factor slots ---------------------------------------------------------------------------------------------------------
 def check_slots(engine, dims, seed=417):
     blk, r, prm = setup(engine, dims, seed)

@@ -9,6 +9,7 @@ import ctypes
 import numpy as np
 
 import checks
+from device_vectors import dev_call
 from adflow_amd import capi
 from adflow_amd.params import FlowParams, RANSEquations, dissScalar, upwind, vanAlbeda, minmod
 
@@ -151,6 +152,33 @@ def check_brick(engine, topo, prm, seed=223, rccl_self=False):
         finally:
             engine.set_tuning("comm_self", 0)
     return op
+
+
+def check_dev_twin(engine, dv, topo, dims=(7, 6, 5), seed=233):
+    """adflow_gpu_jacobian_mult_dev on device vectors (dv: device_vectors.HostVectors / TorchVectors) returns bit for bit what
+    adflow_gpu_jacobian_mult returns from the same x: the same kernels, launch geometry and donor-sorted accumulation.  One
+    wall-bounded RANS block at nState 6, 5 and 1, and the blocks of `topo` (halo columns with donors), both transposes"""
+    rng = np.random.default_rng(seed)
+
+    def both(what):
+        n = engine.jacobianInfo()[0] * sum(b.ncells for (nn, lv, sps), b in engine.blocks.items() if lv == 1)
+        for tr in (False, True):
+            x = rng.uniform(-1.0, 1.0, n)
+            y = engine.jacobianMult(x, 1, transpose=tr)
+            dx, dy = dv.put(x), dv.empty(n)
+            dev_call(engine, dv, engine.jacobianMultDev, dv.ptr(dx), dv.ptr(dy), n, 1, tr)
+            assert np.abs(y).max() > 0.0
+            assert np.array_equal(dv.get(dy), y), (what, tr)
+            assert np.array_equal(dv.get(dx), x), (what, tr, "x was written")
+
+    rans = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda)
+    for jac in (dict(), dict(frozenTurb=True), dict(useTurbOnly=True)):
+        keep = checks.setup_block_with_bc(engine, dims, rans, WALL, seed, stretch_k=2.0)    # (the reference's flowDoms point into keep[1])
+        engine.setupStateResidualMatrix(1, True, useAD=True, **jac)
+        both(f"{dims} {jac}")
+    brick_operator(engine, topo, FlowParams(spaceDiscr=upwind), seed)
+    both("brick")
+    engine.releaseWorkspace()
 
 
 def check_refusals_and_side_effects(engine, dims=(7, 6, 5)):

@@ -10,6 +10,7 @@ compared with the longdouble one and may be at most 10 x as far from it as the f
 import numpy as np
 
 import checks
+from device_vectors import dev_call
 import jacmult_checks as jm
 from adflow_amd import capi
 from adflow_amd.params import FlowParams, RANSEquations, dissScalar, upwind, vanAlbeda, minmod
@@ -352,6 +353,53 @@ def check_gmres_on_pc_matrix(engine, dims, cap, restart, seed=281):
         # an iteration limit is not an error
         x3, its3, _, rn3 = engine.gmresSolve(b, 1, transpose=tr, restart=2, maxIts=3, rtol=rtol)
         assert its3 == 3 and rn3 > rtol * nb
+
+
+def assert_apply_dev_twin(engine, dv, n, seed, what):
+    """adflow_gpu_pc_apply_dev on device vectors against adflow_gpu_pc_apply with the factor that stands, bit for bit"""
+    rng = np.random.default_rng(seed)
+    for tr in (False, True):
+        r = rng.uniform(-1.0, 1.0, n)
+        z = engine.pcApply(r, 1, transpose=tr)
+        dr, dz = dv.put(r), dv.empty(n)
+        dev_call(engine, dv, engine.pcApplyDev, dv.ptr(dr), dv.ptr(dz), n, 1, tr)
+        assert np.abs(z).max() > 0.0
+        assert np.array_equal(dv.get(dz), z), (what, tr)
+        assert np.array_equal(dv.get(dr), r), (what, tr, "the right-hand side was written")
+
+
+def check_dev_twins(engine, dv, topo, dims, cap, seed=293):
+    """the _dev entries on device vectors (dv: device_vectors.HostVectors / TorchVectors) return bit for bit what their host twins return:
+    pc_apply at fill 0 on the blocks of `topo` (sets of unequal length in one launch), both transposes; gmres_solve on one
+    wall-bounded RANS block, both transposes, from zero and from a guess: x, its, rnorm0 and rnorm"""
+    blocks, op = jm.brick_operator(engine, topo, FlowParams(spaceDiscr=upwind), seed)
+    engine.pcSetup(1)
+    assert engine.pcInfo2()[0] == 0
+    assert_apply_dev_twin(engine, dv, op.n, seed + 1, f"{len(blocks)} blocks, fill 0")
+    engine.pcRelease()
+    blk, op = single_block(engine, dims, RANS, jm.WALL, 107, stretch_k=2.0)
+    engine.pcSetup(1)
+    rng = np.random.default_rng(seed + 2)
+    for tr in (False, True):
+        b = rng.uniform(-1.0, 1.0, op.n)
+        db = dv.put(b)
+        kw = dict(transpose=tr, restart=cap, maxIts=cap, rtol=1e-8)
+        x, *host = engine.gmresSolve(b, 1, **kw)
+        dx = dv.put(np.full(op.n, 7.0))                                 # without a guess whatever x holds is not read
+        dev = dev_call(engine, dv, engine.gmresSolveDev, dv.ptr(db), dv.ptr(dx), op.n, 1, **kw)
+        print(f"gmres_solve / _dev {dims} transpose={tr}: (its, rnorm0, rnorm) = {tuple(host)} / {dev}")
+        assert 0 < host[0] <= cap
+        assert tuple(host) == dev and np.array_equal(dv.get(dx), x), ("from zero", tr)
+        # a guess three iterations old: uploaded by the host form, read in place by the _dev form
+        x3, its3, _, _ = engine.gmresSolve(b, 1, transpose=tr, restart=2, maxIts=3, rtol=1e-8)
+        assert its3 == 3
+        x, *host = engine.gmresSolve(b, 1, x0=x3, **kw)
+        dx = dv.put(x3)
+        dev = dev_call(engine, dv, engine.gmresSolveDev, dv.ptr(db), dv.ptr(dx), op.n, 1, useGuess=True, **kw)
+        assert host[0] > 0 and tuple(host) == dev and np.array_equal(dv.get(dx), x), ("from a guess", tr)
+        assert np.array_equal(dv.get(db), b)
+    engine.pcRelease()
+    engine.releaseWorkspace()
 
 
 def check_gmres_adjoint_order(engine, dims, cap, seed=283):

@@ -166,6 +166,19 @@ def check_brick(engine, topo, prm, seed=251):
             engine.pcRelease()
 
 
+def check_dev_twin(engine, dv, topo, seed=257):
+    """adflow_gpu_pc_apply_dev on device vectors (dv: device_vectors.HostVectors / TorchVectors) against adflow_gpu_pc_apply at fill 2 on the
+    blocks of `topo`, both transposes, bit for bit"""
+    from adflow_amd.params import upwind
+    blocks, op = jm.brick_operator(engine, topo, FlowParams(spaceDiscr=upwind), seed)
+    with fill_of(engine, 2):
+        engine.pcSetup(1)
+        assert engine.pcInfo2()[:2] == (2, ENTRIES[2])
+        pc.assert_apply_dev_twin(engine, dv, op.n, seed + 1, f"{len(blocks)} blocks, fill 2")
+        engine.pcRelease()
+    engine.releaseWorkspace()
+
+
 def check_ank(engine, dims=(7, 6, 5), seed=311):
     """ankPcSetup at fill 2 against the yardstick on dRdwPre + T, T as adflow_gpu_ank_download_time_step hands it out; then the
     turbulence factor at fill 2 in slot 1 while slot 0 keeps a fill-0 factor"""

@@ -93,3 +93,15 @@ def test_tile_sized_block(engine):
     """RANS decoupled on 70 x 24 x 40: partial waves at size.  The exact operator against J v + T v (the 33-point forward-mode
     blocks), and a 5-iteration solve on the factor's 132 hyperplanes"""
     ank.check_tile_sized(engine, (70, 24, 40))
+
+
+@pytest.mark.parametrize("kind", ["flow", "coupled"])
+def test_dev_forms_return_what_the_host_forms_return(engine, request, kind):
+    """every adflow_gpu_ank_*_dev entry on torch tensors against its host twin, bit for bit: nState 5 and 6"""
+    from device_vectors import device_vectors
+    ank.check_dev_twins(engine, device_vectors(request.config), (7, 6, 5), kind, CAP_RANS)
+
+
+def test_nk_residual_dev_returns_what_the_host_form_returns(engine, request):
+    from device_vectors import device_vectors
+    ank.check_nk_residual_dev_twin(engine, device_vectors(request.config))

@@ -64,3 +64,9 @@ def test_refusals_and_no_side_effects(engine):
 def test_unsteady_residual_several_reduction_workgroups(engine, kind):
     tc.check_unsteady(engine, BIG, kind)
     engine.releaseWorkspace()
+
+
+def test_dev_forms_return_what_the_host_forms_return(engine, request):
+    """the _dev entries of the turbulence kind (nState 1) on torch tensors against their host twins, bit for bit"""
+    from device_vectors import device_vectors
+    tc.check_dev_twins(engine, device_vectors(request.config), (7, 6, 5), CAP)

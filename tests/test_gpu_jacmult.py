@@ -70,3 +70,9 @@ def test_tile_sized_block_and_workspace(engine):
 
 def test_refusals_and_no_side_effects(engine):
     jm.check_refusals_and_side_effects(engine)
+
+
+def test_dev_form_returns_what_the_host_form_returns(engine, request):
+    """adflow_gpu_jacobian_mult_dev on torch tensors against adflow_gpu_jacobian_mult, bit for bit"""
+    from device_vectors import device_vectors
+    jm.check_dev_twin(engine, device_vectors(request.config), ell_topology())

@@ -64,3 +64,10 @@ def test_gmres_on_the_pc_matrix(engine):
 
 def test_gmres_adjoint_order_against_reference_solve(engine):
     pc.check_gmres_adjoint_order(engine, (8, 7, 6), CAP_ADJOINT)
+
+
+def test_dev_forms_return_what_the_host_forms_return(engine, request):
+    """pc_apply_dev (four blocks of unequal size) and gmres_solve_dev (7 x 5 x 4 with the cap of that shape) on torch tensors against
+    their host twins, bit for bit"""
+    from device_vectors import device_vectors
+    pc.check_dev_twins(engine, device_vectors(request.config), ell_topology(), (7, 5, 4), 32)

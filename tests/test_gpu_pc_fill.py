@@ -59,3 +59,9 @@ def test_gmres_on_the_pc_matrix(engine):
 
 def test_refusals_and_fill0_bit_identity(engine):
     pcf.check_refusals_and_fill0_identity(engine)
+
+
+def test_dev_form_returns_what_the_host_form_returns(engine, request):
+    """pc_apply_dev at fill 2 on four blocks of unequal size, torch tensors, against pc_apply bit for bit"""
+    from device_vectors import device_vectors
+    pcf.check_dev_twin(engine, device_vectors(request.config), ell_topology())

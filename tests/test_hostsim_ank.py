@@ -85,3 +85,14 @@ def test_physicality_check_coupled(hostsim_engine):
 
 def test_refusals_and_no_side_effects(hostsim_engine):
     ank.check_refusals_and_side_effects(hostsim_engine)
+
+
+@pytest.mark.parametrize("kind", ["flow", "coupled"])
+def test_dev_forms_return_what_the_host_forms_return(hostsim_engine, kind):
+    from device_vectors import HostVectors
+    ank.check_dev_twins(hostsim_engine, HostVectors(), (7, 6, 5), kind, CAP_RANS)
+
+
+def test_nk_residual_dev_returns_what_the_host_form_returns(hostsim_engine):
+    from device_vectors import HostVectors
+    ank.check_nk_residual_dev_twin(hostsim_engine, HostVectors())

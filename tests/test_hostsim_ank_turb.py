@@ -58,3 +58,8 @@ def test_factor_slots(hostsim_engine):
 
 def test_refusals_and_no_side_effects(hostsim_engine):
     tc.check_refusals_and_side_effects(hostsim_engine)
+
+
+def test_dev_forms_return_what_the_host_forms_return(hostsim_engine):
+    from device_vectors import HostVectors
+    tc.check_dev_twins(hostsim_engine, HostVectors(), (7, 6, 5), CAP)

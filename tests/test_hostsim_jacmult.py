@@ -52,3 +52,8 @@ def test_workspace_released_and_laid_out_again(hostsim_engine):
 
 def test_refusals_and_no_side_effects(hostsim_engine):
     jm.check_refusals_and_side_effects(hostsim_engine)
+
+
+def test_dev_form_returns_what_the_host_form_returns(hostsim_engine):
+    from device_vectors import HostVectors
+    jm.check_dev_twin(hostsim_engine, HostVectors(), ell_topology())

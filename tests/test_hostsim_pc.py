@@ -51,3 +51,8 @@ def test_gmres_on_the_pc_matrix(hostsim_engine):
 
 def test_gmres_adjoint_order_against_reference_solve(hostsim_engine):
     pc.check_gmres_adjoint_order(hostsim_engine, (7, 5, 4), CAP_ADJOINT)
+
+
+def test_dev_forms_return_what_the_host_forms_return(hostsim_engine):
+    from device_vectors import HostVectors
+    pc.check_dev_twins(hostsim_engine, HostVectors(), ell_topology(), (7, 5, 4), CAP_PC)

@@ -57,3 +57,8 @@ def test_gmres_on_the_pc_matrix(hostsim_engine):
 
 def test_refusals_and_fill0_bit_identity(hostsim_engine):
     pcf.check_refusals_and_fill0_identity(hostsim_engine)
+
+
+def test_dev_form_returns_what_the_host_form_returns(hostsim_engine):
+    from device_vectors import HostVectors
+    pcf.check_dev_twin(hostsim_engine, HostVectors(), ell_topology())
