@@ -1022,16 +1022,17 @@ int adflow_gpu_initres(int level, int varStart, int varEnd)
     return sync_and_check();
 }
 
-static int enqueue_flow_fluxes(int level, const KParams& kp, const struct FlowPlan& P, bool needGrad);
+// what this section calls of the sections further down (actuator sources, boundary conditions, wall stress, halo exchange)
 static int source_terms_enqueue(int withBlank);
-
-// residual (residuals.F90:1028) = residual_block of every block; blockResCore (blockette.F90:755) is the same sum of
-// fluxes WITHOUT the low-speed preconditioner of residual_block (residuals.F90:172-331) -> lowSpeed = false there.
 static int wall_stress_enqueue(int level, const KParams& kp, bool formGrad);
-
-// stage0: the reference's rkStage is 0 at this call -> on the ground level viscousFlux also stores the wall stress tensor
-// and heat flux of the viscous subfaces (storeWallTensor, fluxes.F90:2586-2592)
 static bool has_wall_subfaces(int level);
+static int apply_bc_enqueue(int level, int secondHalo);
+static int apply_turb_and_flow_bc_enqueue(int level, int secondHalo, bool turbBC);
+static int ad_apply_bc_enqueue(int level, const KParams& kp, bool turbBC);
+static int halo_exchange_enqueue(int level, int varStart, int varEnd, int commPressure, int commVisc, int nLayers);
+static int halo_exchange_close(int level, int varStart, int varEnd, int commPressure, int nLayers);
+static int comm_exchange_begin(CommPattern* cp, BlkView* tab, unsigned mask, int nvar, bool* remoteOut);
+static int comm_exchange_end(CommPattern* cp, BlkView* tab, unsigned mask, bool remote);
 
 // blocks at rest: no grid velocities, no rotational source (only the generic kernels carry them)
 static bool level_at_rest(int level)
@@ -1053,7 +1054,9 @@ static int ensure_face_vectors(int level)
     return for_level(level, [&](Block* b) { block_face_vectors(b); return 0; });
 }
 
-// the KParams of the evaluation block_res_enqueue(level, flags) runs (the Jacobian assembly plans with the same)
+// the KParams of the evaluation block_res_enqueue(level, flags) runs (the Jacobian assembly plans with the same).  The forward-mode
+// evaluation takes them too: its flags come from adflow_gpu_fd_jacobian alone, which never sets UPDATE_INTERMED (onlyRadii = 1) nor
+// UPWIND_FIRST_ORDER, and g_rvec_target is set only while nk_residual_dev runs (no rvec)
 static KParams res_kparams(int level, unsigned flags)
 {
     KParams kp = make_kparams(level, 1.0, 0);
@@ -1083,6 +1086,187 @@ static FlowFacts flow_facts(int level, const KParams& kp, bool viscApprox, bool 
     return f;
 }
 
+// ---- forward-mode linearisation (kernels_ad.hip): dual copies of the arrays the kernels touch, laid out by ad_prepare below ---------
+struct AdInit { char* dst; const double* src; size_t n, zeroBytes; };   // dual array at dst: (src, 0) for n entries, or zeroBytes of zero
+struct AdBlock { BlkView v; std::vector<AdInit> init; };
+static std::map<Block*, AdBlock> g_ad;
+static BlkView* g_ad_tab = nullptr;        // device table of the level being linearised, slot layout of g_tab[level]
+
+// The two families of launchers of one evaluation in one shape: PLAIN on the library's arrays, DUAL on the dual copies of the forward
+// mode.  The executors below launch what a FlowPlan names through one of them.  What else differs between the modes hangs on `dual`
+// and is said where it happens: only PLAIN records phase marks, checks geom_uploaded, refreshes the entropy sensor, keeps the
+// ss_valid / etot_consistent bookkeeping of the arrays it writes and calls the host hook.
+struct Launchers {
+    using Tiles = void (*)(const BlkView*, const int4*, int, const KParams&, hipStream_t);
+    using TilesRc = int (*)(const BlkView*, const int4*, int, const KParams&, hipStream_t);
+    using Level = void (*)(const BlkView*, int, int, int, int, const KParams&, hipStream_t);
+    using OneBlock = void (*)(const BlkView&, const KParams&, hipStream_t);
+    bool dual;
+    const BlkView& (*view)(Block* b);                                   // the arrays of one block (the level's table: mode_tab)
+    OneBlock closures_halo;
+    int (*bcs)(int level, const KParams& kp, bool turbBC);              // turbulence + mean-flow boundary conditions, both halos
+    Tiles sa_march;
+    Level sa_residual_level;
+    Tiles euler_march;                                                  // (no dual form)
+    TilesRc roe_march, inviscid_march;
+    void (*pc_march)(const BlkView*, const int4*, int, const KParams&, int kch, hipStream_t);
+    Level inviscid_level;
+    void (*visc_gf)(const BlkView*, const int4*, int, const KParams&, bool storeGrad, hipStream_t);
+    Tiles visc_march_approx;
+    OneBlock viscous, viscous_approx;
+};
+static const Launchers PLAIN = {
+    false,
+    [](Block* b) -> const BlkView& { return b->v; },
+    launch_closures_halo,
+    [](int level, const KParams&, bool turbBC) { return apply_turb_and_flow_bc_enqueue(level, 1, turbBC); },
+    [](const BlkView* tab, const int4* tiles, int n, const KParams& kp, hipStream_t s) { launch_sa_march(tab, tiles, n, kp, s, false); },
+    launch_sa_residual_level,
+    launch_euler_march,
+    launch_roe_march, launch_inviscid_march,
+    launch_pc_march,
+    launch_inviscid_level,
+    launch_visc_gf,
+    launch_visc_march_approx,
+    launch_viscous, launch_viscous_approx};
+static const Launchers DUAL = {
+    true,
+    [](Block* b) -> const BlkView& { return g_ad[b].v; },
+    ad_launch_closures_halo,
+    ad_apply_bc_enqueue,
+    ad_launch_sa_march,
+    ad_launch_sa_residual_level,
+    nullptr,
+    ad_launch_roe_march, ad_launch_inviscid_march,
+    ad_launch_pc_march,
+    ad_launch_inviscid_level,
+    [](const BlkView* tab, const int4* tiles, int n, const KParams& kp, bool, hipStream_t s) { ad_launch_visc_gf(tab, tiles, n, kp, s); },
+    ad_launch_visc_march_approx,
+    ad_launch_viscous, ad_launch_viscous_approx};
+
+// block table and launch extents of the level in the arrays of the mode
+static int mode_tab(const Launchers& M, int level, LevelTab* t)
+{
+    if (level_tab(level, t)) return 1;
+    if (M.dual) t->tab = g_ad_tab;
+    return 0;
+}
+
+// the turbulence kernel the plan names
+static int enqueue_turb_residual(const Launchers& M, int level, const FlowPlan& P, const KParams& kp)
+{
+    if (P.turb == TurbK::None) return 0;
+    int rc = for_level(level, [&](Block* b) {
+        if (b->v.nw < 6) return fail("RANS/SA needs nw = 6 (block has %d)", b->v.nw);
+        return 0;
+    });
+    if (rc) return rc;
+    LevelTab t;
+    if (mode_tab(M, level, &t)) return 1;
+    if (P.turb == TurbK::SaMarch) {
+        if (ensure_sa_tiles(level)) return 1;
+        M.sa_march(t.tab, g_sa_tiles[level].first, g_sa_tiles[level].second, kp, g_stream);
+    } else M.sa_residual_level(t.tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
+    return 0;
+}
+
+// one mean-flow kernel of the plan; the tile tables it reads exist (FlowPlan::needTiles / needGfTiles, ensured by the caller)
+static int enqueue_inviscid(const Launchers& M, int level, InviscidK which, const KParams& kv)
+{
+    LevelTab t;
+    if (mode_tab(M, level, &t)) return 1;
+    switch (which) {
+    case InviscidK::EulerMarch:
+        if (!M.euler_march) break;
+        M.euler_march(t.tab, g_tiles[level].first, g_tiles[level].second, kv, g_stream);
+        return 0;
+    case InviscidK::RoeMarch: return M.roe_march(t.tab, g_tiles[level].first, g_tiles[level].second, kv, g_stream);
+    case InviscidK::FaceMarch: return M.inviscid_march(t.tab, g_tiles[level].first, g_tiles[level].second, kv, g_stream);
+    case InviscidK::PcMarch: M.pc_march(t.tab, g_tiles[level].first, g_tiles[level].second, kv, g_march_kch, g_stream); return 0;
+    case InviscidK::LevelGather: M.inviscid_level(t.tab, t.n, t.nx, t.ny, t.nz, kv, g_stream); return 0;
+    case InviscidK::None: return 0;
+    }
+    return fail("forward mode: the plan names a kernel without a dual form (internal error)");
+}
+static int enqueue_viscous(const Launchers& M, int level, ViscousK which, const KParams& kv, bool storeGrad)
+{
+    LevelTab t;
+    if (mode_tab(M, level, &t)) return 1;
+    // (DUAL: ad_prepare formed the face vectors of a viscous level already, block_face_vectors launches nothing)
+    auto per_block = [&](Launchers::OneBlock launch) {
+        return for_level(level, [&](Block* b) { block_face_vectors(b); launch(M.view(b), kv, g_stream); return 0; });
+    };
+    switch (which) {
+    case ViscousK::GfMarch: M.visc_gf(t.tab, g_gf_tiles[level].first, g_gf_tiles[level].second, kv, storeGrad, g_stream); return 0;
+    case ViscousK::ThinLayerMarch: M.visc_march_approx(t.tab, g_tiles[level].first, g_tiles[level].second, kv, g_stream); return 0;
+    case ViscousK::GatherExact: return per_block(M.viscous);
+    case ViscousK::GatherApprox: return per_block(M.viscous_approx);
+    case ViscousK::None: break;
+    }
+    return 0;
+}
+
+// the mean-flow fluxes the plan names, in its order (phase marks, PLAIN only: 4 .. 5 = nodal gradients + viscous fluxes, 5 .. 6 =
+// inviscid fluxes when they follow; bench.py labels them so).  On dual numbers these are the marching kernels compiled a second time
+// (kernels_ad.hip) -- the Roe march of the exact linearisation (3.25 instead of 6 face evaluations and 3.5 instead of 12
+// reconstructions per cell), the per-face march of scalar JST / matrix dissipation (four face evaluations per cell instead of the
+// gather kernel's six), the one-march residual of the preconditioner matrix, k_visc_gf (instead of the dual gather pair
+// k_nodal_gradients + k_viscous: 1.01 ms per pass and 1.3 M cells) -- or the gather kernels behind them
+static int enqueue_flow_fluxes(const Launchers& M, int level, const KParams& kp, const FlowPlan& P, bool needGrad)
+{
+    if (!M.dual) {
+        if (kp.spaceDiscr != ADFLOW_DISS_SCALAR && kp.spaceDiscr != ADFLOW_DISS_MATRIX && kp.spaceDiscr != ADFLOW_UPWIND)
+            return fail("spaceDiscr=%d not supported (1 scalar, 2 matrix, 9 upwind)", kp.spaceDiscr);
+        int nStale = 0, nBlk = 0;
+        int rc = for_level(level, [&](Block* b) {
+            if (!b->geom_uploaded) return fail("geometry of a level-%d block has not been uploaded", level);
+            ++nBlk;
+            if (P.needSensor && !b->ss_valid) ++nStale;
+            return 0;
+        });
+        if (rc) return rc;
+        if (nStale > 0) {
+            // entropy sensor of the blocks whose state changed: one launch when that is every block of the level (the usual case)
+            if (nStale == nBlk) {
+                LevelTab ts;
+                if (level_tab(level, &ts)) return 1;
+                launch_entropy_level(ts.tab, ts.n, ts.nx, ts.ny, ts.nz, g_stream);
+            }
+            for_level(level, [&](Block* b) {
+                if (nStale != nBlk && !b->ss_valid) launch_entropy(b->v, g_stream);
+                b->ss_valid = true;
+                return 0;
+            });
+        }
+    }
+    // dI / dJ / dK: DUAL forms them before any flux kernel, PLAIN in front of the viscous kernel
+    if (M.dual && P.needFaceVectors && ensure_face_vectors(level)) return 1;
+    if ((P.needGfTiles && ensure_gf_tiles(level)) || (P.needTiles && ensure_tiles(level))) return 1;
+    KParams kv = kp;
+    kv.viscFirst = P.viscFirst ? 1 : 0;
+    auto mark = [&](int i) { if (!M.dual) phase_mark(i); };
+    auto inviscid = [&]() { return enqueue_inviscid(M, level, P.inviscid, kv); };
+    auto viscous = [&]() { return enqueue_viscous(M, level, P.viscous, kv, needGrad); };
+    if (P.inviscid == InviscidK::EulerMarch) return inviscid();          // (no viscous part, one phase)
+    const bool pc = P.inviscid == InviscidK::PcMarch;                     // (it carries the viscous part: between the marks 4 and 5)
+    if (pc || P.viscFirst) {
+        if (!M.dual && ensure_face_vectors(level)) return 1;
+        mark(4);
+        if (pc ? inviscid() : viscous()) return 1;
+        mark(5);
+        return pc ? 0 : inviscid();
+    }
+    if (inviscid()) return 1;
+    mark(4);
+    if (!M.dual && P.needFaceVectors && ensure_face_vectors(level)) return 1;
+    if (P.viscous == ViscousK::GfMarch) mark(5);
+    return viscous();
+}
+
+// residual (residuals.F90:1028) = residual_block of every block; blockResCore (blockette.F90:755) is the same sum of
+// fluxes WITHOUT the low-speed preconditioner of residual_block (residuals.F90:172-331) -> lowSpeed = false there.
+// stage0: the reference's rkStage is 0 at this call -> on the ground level viscousFlux also stores the wall stress tensor
+// and heat flux of the viscous subfaces (storeWallTensor, fluxes.F90:2586-2592)
 // needGradHbm: the caller wants the nodal gradients in the block arrays (updateIntermed copy-out, blockette.F90:706-750)
 static int enqueue_flow_residual(int level, const KParams& kp, bool viscApprox = false, bool lowSpeed = true, bool stage0 = true,
                                  bool needGradHbm = false)
@@ -1090,7 +1274,7 @@ static int enqueue_flow_residual(int level, const KParams& kp, bool viscApprox =
     const bool wallStress = stage0 && !viscApprox && kp.viscous && level == g_opts.groundLevel && fabs(kp.rFil) >= 1.e-10 &&
                             has_wall_subfaces(level);
     const FlowPlan P = plan_flow(flow_facts(level, kp, viscApprox, needGradHbm));
-    if (enqueue_flow_fluxes(level, kp, P, needGradHbm)) return 1;
+    if (enqueue_flow_fluxes(PLAIN, level, kp, P, needGradHbm)) return 1;
     if (wallStress)
         if (wall_stress_enqueue(level, kp, P.wallGradOnChip)) return 1;
     // sourceTerms() of the call sites of `residual` (smoothers.F90:74,409, multiGrid.F90:52,887,949): fine level only
@@ -1101,81 +1285,6 @@ static int enqueue_flow_residual(int level, const KParams& kp, bool viscApprox =
         launch_low_speed_precond_level(t.tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
     }
     return 0;
-}
-
-// the mean-flow fluxes the plan names, in its order (phase marks: 4 .. 5 = nodal gradients + viscous fluxes, 5 .. 6 = inviscid fluxes
-// when they follow; bench.py labels them so)
-static int enqueue_flow_fluxes(int level, const KParams& kp, const FlowPlan& P, bool needGrad)
-{
-    if (kp.spaceDiscr != ADFLOW_DISS_SCALAR && kp.spaceDiscr != ADFLOW_DISS_MATRIX && kp.spaceDiscr != ADFLOW_UPWIND)
-        return fail("spaceDiscr=%d not supported (1 scalar, 2 matrix, 9 upwind)", kp.spaceDiscr);
-    int nStale = 0, nBlk = 0;
-    int rc = for_level(level, [&](Block* b) {
-        if (!b->geom_uploaded) return fail("geometry of a level-%d block has not been uploaded", level);
-        ++nBlk;
-        if (P.needSensor && !b->ss_valid) ++nStale;
-        return 0;
-    });
-    if (rc) return rc;
-    if (nStale > 0) {
-        // entropy sensor of the blocks whose state changed: one launch when that is every block of the level (the usual case)
-        if (nStale == nBlk) {
-            LevelTab ts;
-            if (level_tab(level, &ts)) return 1;
-            launch_entropy_level(ts.tab, ts.n, ts.nx, ts.ny, ts.nz, g_stream);
-        }
-        for_level(level, [&](Block* b) {
-            if (nStale != nBlk && !b->ss_valid) launch_entropy(b->v, g_stream);
-            b->ss_valid = true;
-            return 0;
-        });
-    }
-    LevelTab t;
-    if (level_tab(level, &t)) return 1;
-    if ((P.needGfTiles && ensure_gf_tiles(level)) || (P.needTiles && ensure_tiles(level))) return 1;
-    KParams kv = kp;
-    kv.viscFirst = P.viscFirst ? 1 : 0;
-    auto inviscid = [&]() -> int {
-        switch (P.inviscid) {
-        case InviscidK::EulerMarch: launch_euler_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream); return 0;
-        case InviscidK::RoeMarch: return launch_roe_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream);
-        case InviscidK::FaceMarch: return launch_inviscid_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream);
-        case InviscidK::PcMarch: launch_pc_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_march_kch, g_stream); return 0;
-        case InviscidK::LevelGather: launch_inviscid_level(t.tab, t.n, t.nx, t.ny, t.nz, kv, g_stream); return 0;
-        case InviscidK::None: break;
-        }
-        return 0;
-    };
-    auto viscous = [&]() -> int {
-        switch (P.viscous) {
-        case ViscousK::GfMarch: launch_visc_gf(g_tab[level], g_gf_tiles[level].first, g_gf_tiles[level].second, kv, needGrad, g_stream); return 0;
-        case ViscousK::ThinLayerMarch: launch_visc_march_approx(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream); return 0;
-        case ViscousK::GatherExact: return for_level(level, [&](Block* b) { block_face_vectors(b); launch_viscous(b->v, kv, g_stream); return 0; });
-        case ViscousK::GatherApprox: return for_level(level, [&](Block* b) { block_face_vectors(b); launch_viscous_approx(b->v, kv, g_stream); return 0; });
-        case ViscousK::None: break;
-        }
-        return 0;
-    };
-    if (P.inviscid == InviscidK::EulerMarch) return inviscid();          // (no viscous part, one phase)
-    if (P.inviscid == InviscidK::PcMarch) {
-        if (ensure_face_vectors(level)) return 1;
-        phase_mark(4);
-        if (inviscid()) return 1;
-        phase_mark(5);
-        return 0;
-    }
-    if (P.viscFirst) {
-        if (ensure_face_vectors(level)) return 1;
-        phase_mark(4);
-        if (viscous()) return 1;
-        phase_mark(5);
-        return inviscid();
-    }
-    if (inviscid()) return 1;
-    phase_mark(4);
-    if (P.needFaceVectors && ensure_face_vectors(level)) return 1;
-    if (P.viscous == ViscousK::GfMarch) phase_mark(5);
-    return viscous();
 }
 
 int adflow_gpu_residual(int level, int rkStage)
@@ -1193,22 +1302,6 @@ int adflow_gpu_residual(int level, int rkStage)
     if (rc) return rc;
     return sync_and_check();
 }
-
-static int block_res_enqueue(int level, unsigned flags);
-static int apply_bc_enqueue(int level, int secondHalo);
-static int apply_turb_bc_enqueue(int level, int secondHalo);
-static int apply_turb_and_flow_bc_enqueue(int level, int secondHalo, bool turbBC);
-static int turb_bc_treatment_enqueue(int level, const KParams& kp);
-static int turb_bc_apply_enqueue(int level, const KParams& kp, int secondHalo);
-static int bc_coarse_corrections_enqueue(int coarseLevel, double fact);
-static void bc_plan_drop(int level);
-static int halo_exchange_enqueue(int level, int varStart, int varEnd, int commPressure, int commVisc, int nLayers);
-static int early_pressure_exchange_enqueue(int level);
-static int halo_exchange_close(int level, int varStart, int varEnd, int commPressure, int nLayers);
-static int comm_exchange_begin(CommPattern* cp, BlkView* tab, unsigned mask, int nvar, bool* remoteOut);
-static int comm_exchange_end(CommPattern* cp, BlkView* tab, unsigned mask, bool remote);
-static int block_res_split_enqueue(int level, unsigned flags, const KParams& kp, const FlowPlan& P, int lStart, int lEnd, int* taken,
-                                   const std::function<int()>& frontBCs);
 
 // whalo2 + blocketteRes core with the exchange -- and, round 4, the boundary conditions in front of it -- HIDDEN behind the tiles that
 // read no halo cell (round-2 verdict, next 3 iii).  Two queues from the fork behind the derived values:
@@ -1282,9 +1375,7 @@ static int block_res_split_enqueue(int level, unsigned flags, const KParams& kp,
         HIPCHK(hipEventRecord(g_evB, g_streamB));
         launch_visc_gf(g_tab[level], g_gf_tiles_bnd[level].first, g_gf_tiles_bnd[level].second, kv, false, g_stream);
         HIPCHK(hipStreamWaitEvent(g_stream, g_evB1, 0));               // the interior viscous sums are in dw(2:5)
-        if (P.inviscid == InviscidK::RoeMarch ? launch_roe_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream)
-                                              : launch_inviscid_march(g_tab[level], g_tiles[level].first, g_tiles[level].second, kv, g_stream))
-            return 1;
+        if (enqueue_inviscid(PLAIN, level, P.inviscid, kv)) return 1;
         HIPCHK(hipStreamWaitEvent(g_stream, g_evB, 0));                // join
         forked = false;
         return 0;
@@ -1375,20 +1466,8 @@ static int block_res_enqueue(int level, unsigned flags)
         if (rc) return rc;
     }
     phase_mark(2);
-    if (P.turb != TurbK::None) {
-        rc = for_level(level, [&](Block* b) {
-            if (b->v.nw < 6) return fail("RANS/SA needs nw = 6 (block has %d)", b->v.nw);
-            return 0;
-        });
-        if (rc) return rc;
-        LevelTab t;
-        if (level_tab(level, &t)) return 1;
-        if (P.turb == TurbK::SaMarch) {
-            if (ensure_sa_tiles(level)) return 1;
-            if (P.roeWritesTurbRvec) kp.rvecTurbFromDw = 1;
-            launch_sa_march(t.tab, g_sa_tiles[level].first, g_sa_tiles[level].second, kp, g_stream, false);
-        } else launch_sa_residual_level(t.tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
-    }
+    if (P.roeWritesTurbRvec) kp.rvecTurbFromDw = 1;
+    if (enqueue_turb_residual(PLAIN, level, P, kp)) return 1;
     phase_mark(3);
     if (flags & ADFLOW_RES_FLOW) {
         rc = enqueue_flow_residual(level, kp, viscApprox, false, true, (flags & ADFLOW_RES_UPDATE_INTERMED) != 0);
@@ -1453,20 +1532,22 @@ static int source_terms_enqueue(int withBlank)
 }
 
 // referenceShockSensor (adjointUtils.F90:1909-1969): pressure (Euler or matrix dissipation) or entropy
+static int reference_shock_sensor_enqueue(int level)
+{
+    const bool pressure = (g_opts.equations == ADFLOW_EULER) || (g_opts.spaceDiscr == ADFLOW_DISS_MATRIX);
+    return for_level(level, [&](Block* b) {
+        if (pressure) HIPCHK(hipMemcpyAsync(b->v.ss, b->v.p, sizeof(double) * (size_t)b->boxsize, hipMemcpyDeviceToDevice, g_stream));
+        else launch_entropy(b->v, g_stream);
+        return 0;
+    });
+}
+
 int adflow_gpu_reference_shock_sensor(int level)
 {
     if (need_ready()) return 1;
-    const bool pressure = (g_opts.equations == ADFLOW_EULER) || (g_opts.spaceDiscr == ADFLOW_DISS_MATRIX);
-    int rc = for_level(level, [&](Block* b) {
-        if (pressure) {
-            HIPCHK(hipMemcpyAsync(b->v.ss, b->v.p, sizeof(double) * (size_t)b->boxsize, hipMemcpyDeviceToDevice, g_stream));
-        } else {
-            launch_entropy(b->v, g_stream);
-        }
-        b->ss_valid = false;    // the exact viscous kernel recomputes its own sensor after an approximate pass
-        return 0;
-    });
-    if (rc) return rc;
+    if (reference_shock_sensor_enqueue(level)) return 1;
+    // the exact viscous kernel recomputes its own sensor after an approximate pass
+    for_level(level, [&](Block* b) { b->ss_valid = false; return 0; });
     return sync_and_check();
 }
 
@@ -1519,35 +1600,52 @@ static void jac_spec(unsigned flags, bool viscous, bool rans, JacSpec* J)
     }
 }
 
-// masterRoutines::block_res_state (masterRoutines.F90:1214-1283) for every block of the level: closures with halos, turbulence
-// and mean-flow boundary conditions, the residual core, actuator sources.  resScale is applied by the extraction kernel.
-static int block_res_state_enqueue(int level, unsigned resFlags, bool turbBC, bool closuresDone = false)
+// viscPC: block_res_state_d keeps the FULL viscous flux in the preconditioner matrix then (masterRoutines.F90:1380: `.not. lumpedDiss
+// .or. viscPC`) -- unlike the finite-difference path block_res_state, whose viscApprox = lumpedDiss whatever viscPC says (:1269-1270)
+static bool visc_approx(const Launchers& M, unsigned resFlags, bool viscPC)
 {
-    KParams kp = make_kparams(level, 1.0, 0);
+    return (resFlags & ADFLOW_RES_VISC_APPROX) != 0 && !(M.dual && viscPC);
+}
+
+// masterRoutines::block_res_state (masterRoutines.F90:1214-1283) for every block of the level, or block_res_state_d (:1285-1393) on
+// its dual arrays: closures with halos, turbulence and mean-flow boundary conditions, host hook, the residual core -- PLAIN: that of
+// block_res_enqueue with the actuator sources; DUAL: time step (the spectral radii of the scalar dissipation), SA, fluxes.  resScale
+// is applied by the extraction kernel.
+// closuresDone: the state / seed launch of the caller formed pressure and viscosities already
+static int block_res_state_enqueue(const Launchers& M, int level, unsigned resFlags, bool turbBC, bool viscPC, bool closuresDone = false)
+{
+    const KParams kp = res_kparams(level, resFlags);
     int rc = for_level(level, [&](Block* b) {
-        if (!closuresDone) launch_closures_halo(b->v, kp, g_stream);
-        b->ss_valid = false;
-        b->etot_consistent = false;
+        if (!closuresDone) M.closures_halo(M.view(b), kp, g_stream);
+        if (!M.dual) {
+            b->ss_valid = false;
+            b->etot_consistent = false;
+        }
         return 0;
     });
     if (rc) return rc;
-    if (apply_turb_and_flow_bc_enqueue(level, 1, turbBC)) return 1;
-    if (g_bc_callback) {
+    if (M.bcs(level, kp, turbBC)) return 1;
+    // (the forward-mode assembly refuses host hooks before it starts)
+    if (!M.dual && g_bc_callback) {
         HIPCHK(hipStreamSynchronize(g_stream));
         g_bc_callback(level, 1);
     }
-    return block_res_enqueue(level, resFlags);
+    if (!M.dual) return block_res_enqueue(level, resFlags);
+    const FlowPlan P = plan_flow(flow_facts(level, kp, visc_approx(M, resFlags, viscPC), false, true, resFlags));
+    LevelTab t;
+    if (mode_tab(M, level, &t)) return 1;
+    // timeStep_block_d: the NS / RANS kernel also leaves the entropy sensor in ss -- not under dissApprox, where ss keeps the frozen
+    // sensor of referenceShockSensor (value part, derivative 0)
+    if (P.needTimeStep) ad_launch_time_step_level(t.tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
+    if (enqueue_turb_residual(M, level, P, kp)) return 1;
+    return enqueue_flow_fluxes(M, level, kp, P, false);
 }
 
-// ---- forward-mode linearisation (kernels_ad.hip): dual copies of the arrays the gather kernels touch ----------------------------
+// ---- forward-mode linearisation: the slab of the dual arrays ---------------------------------------------------------------------
 // Round 5 (round-4 advisor): ONE slab per level instead of ~57 hipMalloc / hipFree per block and call, kept between calls (tuning
 // "ad_cache", default 1; dropped when a block is released or the level's layout changes) -- on the north-star mesh the 13.5 GB (8.4 GB since the geometry is no longer copied) of
 // dual arrays cost 0-400 ms per assembly to map, depending on the box (profiles/r05_f_bench.json against r05_d) -- and the free
 // memory is checked before the slab is requested.
-struct AdInit { char* dst; const double* src; size_t n, zeroBytes; };   // dual array at dst: (src, 0) for n entries, or zeroBytes of zero
-struct AdBlock { BlkView v; std::vector<AdInit> init; };
-static std::map<Block*, AdBlock> g_ad;
-static BlkView* g_ad_tab = nullptr;        // device table of the level being linearised, slot layout of g_tab[level]
 static char* g_ad_slab = nullptr;
 static size_t g_ad_slab_bytes = 0, g_ad_bump = 0;
 static bool g_ad_measure = false;
@@ -1669,81 +1767,6 @@ static int ad_prepare(int level)
     return 0;
 }
 
-// masterRoutines::block_res_state_d (masterRoutines.F90:1285-1393) on the dual arrays of the level: closures with halos,
-// turbulence + mean-flow boundary conditions, time step (the spectral radii of the scalar dissipation), SA, fluxes.
-// viscPC: block_res_state_d keeps the FULL viscous flux in the preconditioner matrix then (masterRoutines.F90:1380: `.not. lumpedDiss
-// .or. viscPC`) -- unlike the finite-difference path block_res_state, whose viscApprox = lumpedDiss whatever viscPC says (:1269-1270)
-static int ad_apply_bc_enqueue(int level, const KParams& kp, bool turbBC);
-static KParams ad_kparams(int level, unsigned resFlags)
-{
-    KParams kp = make_kparams(level, 1.0, 0);
-    kp.onlyRadii = 1;
-    kp.coarseInit = 0;
-    kp.dissApprox = (resFlags & ADFLOW_RES_DISS_APPROX) ? 1 : 0;
-    kp.approxSA = (resFlags & ADFLOW_RES_APPROX_SA) ? 1 : 0;
-    return kp;
-}
-static bool ad_visc_approx(unsigned resFlags, bool viscPC) { return (resFlags & ADFLOW_RES_VISC_APPROX) != 0 && !viscPC; }
-
-// closuresDone: the seed launch of the caller formed pressure and viscosities already (k_seed_closures)
-static int ad_block_res_state_enqueue(int level, unsigned resFlags, bool turbBC, bool viscPC, bool closuresDone = false)
-{
-    KParams kp = ad_kparams(level, resFlags);
-    const FlowPlan P = plan_flow(flow_facts(level, kp, ad_visc_approx(resFlags, viscPC), false, true, resFlags));
-    LevelTab t;
-    if (level_tab(level, &t)) return 1;
-    int rc = 0;
-    if (!closuresDone) rc = for_level(level, [&](Block* b) {
-        ad_launch_closures_halo(g_ad[b].v, kp, g_stream);
-        return 0;
-    });
-    if (rc) return rc;
-    if (ad_apply_bc_enqueue(level, kp, turbBC)) return 1;
-    // timeStep_block_d: the NS / RANS kernel also leaves the entropy sensor in ss -- not under dissApprox, where ss keeps the frozen
-    // sensor of referenceShockSensor (value part, derivative 0)
-    if (P.needTimeStep) ad_launch_time_step_level(g_ad_tab, t.n, t.nx, t.ny, t.nz, kp, g_stream);
-    switch (P.turb) {
-    case TurbK::SaMarch:      // the marching form on dual numbers (kernels_sa_march.hip)
-        if (ensure_sa_tiles(level)) return 1;
-        ad_launch_sa_march(g_ad_tab, g_sa_tiles[level].first, g_sa_tiles[level].second, kp, g_stream);
-        break;
-    case TurbK::LevelGather: ad_launch_sa_residual_level(g_ad_tab, t.n, t.nx, t.ny, t.nz, kp, g_stream); break;
-    case TurbK::None: break;
-    }
-    // the mean flow on dual numbers: the marching kernels compiled a second time (kernels_ad.hip) in the order of the plain evaluation
-    // -- the Roe march of the exact linearisation (3.25 instead of 6 face evaluations and 3.5 instead of 12 reconstructions per cell),
-    // the per-face march of scalar JST / matrix dissipation (four face evaluations per cell instead of the gather kernel's six), the
-    // one-march residual of the preconditioner matrix, k_visc_gf (instead of the dual gather pair k_nodal_gradients + k_viscous: 1.01 ms
-    // per pass and 1.3 M cells) -- or the gather kernels behind them
-    if (P.needFaceVectors && ensure_face_vectors(level)) return 1;
-    if ((P.needGfTiles && ensure_gf_tiles(level)) || (P.needTiles && ensure_tiles(level))) return 1;
-    KParams kv = kp;
-    kv.viscFirst = P.viscFirst ? 1 : 0;
-    auto inviscid = [&]() -> int {
-        switch (P.inviscid) {
-        case InviscidK::PcMarch: ad_launch_pc_march(g_ad_tab, g_tiles[level].first, g_tiles[level].second, kv, g_march_kch, g_stream); return 0;
-        case InviscidK::RoeMarch: return ad_launch_roe_march(g_ad_tab, g_tiles[level].first, g_tiles[level].second, kv, g_stream);
-        case InviscidK::FaceMarch: return ad_launch_inviscid_march(g_ad_tab, g_tiles[level].first, g_tiles[level].second, kv, g_stream);
-        case InviscidK::LevelGather: ad_launch_inviscid_level(g_ad_tab, t.n, t.nx, t.ny, t.nz, kv, g_stream); return 0;
-        case InviscidK::None: return 0;
-        case InviscidK::EulerMarch: break;
-        }
-        return fail("forward mode: the plan names a kernel without a dual form (internal error)");
-    };
-    auto viscous = [&]() -> int {
-        switch (P.viscous) {
-        case ViscousK::GfMarch: ad_launch_visc_gf(g_ad_tab, g_gf_tiles[level].first, g_gf_tiles[level].second, kv, g_stream); return 0;
-        case ViscousK::ThinLayerMarch: ad_launch_visc_march_approx(g_ad_tab, g_tiles[level].first, g_tiles[level].second, kv, g_stream); return 0;
-        case ViscousK::GatherExact: return for_level(level, [&](Block* b) { ad_launch_viscous(g_ad[b].v, kv, g_stream); return 0; });
-        case ViscousK::GatherApprox: return for_level(level, [&](Block* b) { ad_launch_viscous_approx(g_ad[b].v, kv, g_stream); return 0; });
-        case ViscousK::None: break;
-        }
-        return 0;
-    };
-    if (P.viscFirst) return viscous() || inviscid();
-    return inviscid() || viscous();
-}
-
 // the device table of the snapshot request: per block slot of the level its snapshot array and its scaled reference residual
 static int snap_request_begin(int level, const JacSpec& J)
 {
@@ -1765,18 +1788,31 @@ static int snap_request_begin(int level, const JacSpec& J)
     g_snapreq.on = true;
     return 0;
 }
+namespace {
 struct SnapRequestGuard { ~SnapRequestGuard() { g_snapreq.on = false; } };
+// the switches of the preconditioner matrix (adjointUtils.F90:176-191) for one assembly, handed back on every exit
+struct PcSwitchGuard {
+    const adflow_opts opts;
+    const int lumped;
+    explicit PcSwitchGuard(bool pc) : opts(g_opts), lumped(g_lumped)
+    {
+        if (!pc) return;
+        g_lumped = 1;
+        g_opts.acousticScaleFactor = 1.0;
+        g_opts.orderTurb = 1;                                           // constants::firstOrder
+    }
+    ~PcSwitchGuard() { g_opts = opts; g_lumped = lumped; }
+};
+}  // namespace
 
-int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
+static int jac_check_args(int level, unsigned flags, double delta)
 {
-    if (need_ready()) return 1;
-    SnapRequestGuard snapGuard;        // no exit leaves the request standing
     if (flags & ~(ADFLOW_JAC_PC | ADFLOW_JAC_FROZEN_TURB | ADFLOW_JAC_TURB_ONLY | ADFLOW_JAC_VISC_PC | ADFLOW_JAC_USE_AD | ADFLOW_JAC_APPROX_SA))
         return fail("fd_jacobian: unknown flags 0x%x", flags);
     const bool useAD = (flags & ADFLOW_JAC_USE_AD) != 0;
     if (!useAD && !(delta > 0.0)) return fail("fd_jacobian: delta must be positive");     // forward mode has no step size
     if (useAD) {
-        // forward-mode seeds instead of perturbations (adjointUtils.F90:227-409): gather kernels on dual numbers, blocks at rest
+        // forward-mode seeds instead of perturbations (adjointUtils.F90:227-409): kernels on dual numbers, blocks at rest
         if (!level_at_rest(level)) return fail("fd_jacobian(useAD): moving blocks are not linearised (grid velocities)");
         if (!g_act.empty()) return fail("fd_jacobian(useAD): actuator regions are not linearised");
         if (g_bc_callback) return fail("fd_jacobian(useAD): a host boundary-condition hook cannot be linearised");
@@ -1784,199 +1820,158 @@ int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
             return fail("fd_jacobian(useAD): a host turbulence boundary-condition hook cannot be linearised");
     }
     if (level != g_opts.groundLevel) return fail("fd_jacobian: level %d is not the ground level %d (setupStateResidualMatrix sets both)", level, g_opts.groundLevel);
-    const bool rans = g_opts.equations == ADFLOW_RANS;
-    const bool viscous = rans || g_opts.equations == ADFLOW_NS;
-    if ((flags & ADFLOW_JAC_TURB_ONLY) && !rans) return fail("fd_jacobian: ADFLOW_JAC_TURB_ONLY needs the RANS equations");
+    if ((flags & ADFLOW_JAC_TURB_ONLY) && g_opts.equations != ADFLOW_RANS) return fail("fd_jacobian: ADFLOW_JAC_TURB_ONLY needs the RANS equations");
     if ((flags & ADFLOW_JAC_TURB_ONLY) && (flags & ADFLOW_JAC_FROZEN_TURB)) return fail("fd_jacobian: TURB_ONLY and FROZEN_TURB exclude each other");
-    JacSpec J;
-    jac_spec(flags & ~(ADFLOW_JAC_USE_AD | ADFLOW_JAC_APPROX_SA), viscous, rans, &J);
-    const int ncomp = J.nStencil * J.nState * J.nState;
-    int rc = for_level(level, [&](Block* b) {
+    return 0;
+}
+
+// per block: reference state and residual, the stencil blocks, the snapshots of the nColour evaluations of one state variable
+static int jac_storage(int level, const JacSpec& J)
+{
+    const int ncomp = J.nStencil * J.nState * J.nState, nsnap = J.cn * J.nState;
+    return for_level(level, [&](Block* b) {
         if (!b->wref) {
             if (alloc_arr(b, &b->wref, b->v.nw) || alloc_arr(b, &b->dwref, 6)) return 1;
         }
-        if (b->jac_ncomp != ncomp) {
-            if (b->jac_raw) HIPCHK(hipFree(b->jac_raw));
-            b->jac_raw = nullptr; b->jac = nullptr; b->jac_ncomp = 0;
-            const size_t bytes = (size_t)b->v.nbox * ncomp * sizeof(double) + 256;
-            HIPCHK(hipMalloc(&b->jac_raw, bytes));
-            b->jac = (double*)b->jac_raw + ADF_PAD0;
-            b->jac_ncomp = ncomp;
-        }
         // (no memset of the blocks: k_fd_scatter stores every entry of every owned row, and only owned rows are ever read)
-        // the finite differences of the nColour evaluations of one state variable, scattered into the blocks once per variable
-        const int nsnap = J.cn * J.nState;
-        if (b->snap_ncomp != nsnap) {
-            if (b->snap_raw) HIPCHK(hipFree(b->snap_raw));
-            b->snap_raw = nullptr; b->snap = nullptr; b->snap_ncomp = 0;
-            HIPCHK(hipMalloc(&b->snap_raw, (size_t)b->v.nbox * nsnap * sizeof(double) + 256));
-            b->snap = (double*)b->snap_raw + ADF_PAD0;
-            b->snap_ncomp = nsnap;
-        }
-        return 0;
+        auto resize = [&](void** raw, double** arr, int* have, int want) {
+            if (*have == want) return 0;
+            if (*raw) HIPCHK(hipFree(*raw));
+            *raw = nullptr; *arr = nullptr; *have = 0;
+            HIPCHK(hipMalloc(raw, (size_t)b->v.nbox * want * sizeof(double) + 256));
+            *arr = (double*)*raw + ADF_PAD0;
+            *have = want;
+            return 0;
+        };
+        if (resize(&b->jac_raw, &b->jac, &b->jac_ncomp, ncomp)) return 1;
+        return resize(&b->snap_raw, &b->snap, &b->snap_ncomp, nsnap);
     });
-    if (rc) return rc;
+}
+
+// The coloured sweep of both assemblies: for every state variable l and colour, the seed launch puts the state of the evaluation in place
+// (PLAIN: wref + delta on component l of the cells of the colour; DUAL: seed = 1 there, halos included), block_res_state runs, and the
+// scaled residual (its derivative) is the snapshot of the colour; once per variable the snapshots are scattered into the column l of
+// every stencil block (PLAIN: as finite differences against dwref).  The reference loops colours outside and state variables inside;
+// every (colour, variable) evaluation is independent, so the loops are exchanged here: the nColour evaluations of one variable are
+// kept (dense) and scattered into the blocks together.
+// oneComponent: inside the sweep of one state variable over the colours only that component of the state changes; the others are
+// written at its first colour only (the caller says when that is allowed)
+static int coloured_sweep(const Launchers& M, int level, const JacSpec& J, unsigned resFlags, bool turbBC, bool viscPC, bool oneComponent,
+                          double delta)
+{
+    SnapRequestGuard snapGuard;        // no exit leaves the request standing
+    // (the seed kernel reads only options of kp that no flag of the evaluation changes)
+    const KParams kp = res_kparams(level, resFlags);
+    // the marching kernels of the preconditioner matrix write the snapshot of an evaluation themselves (KParams::snapTab): not with
+    // actuator regions (their sources are added to dw behind the core).  The plan is that of the KParams and flags every coloured
+    // evaluation below builds again.  The launchers report what they wrote (adf_note_snap): a host prediction that turns out wrong
+    // is an error instead of a matrix built from stale memory
+    const FlowPlan P = plan_flow(flow_facts(level, kp, visc_approx(M, resFlags, viscPC), false, M.dual, resFlags));
+    const int need = ((resFlags & ADFLOW_RES_FLOW) ? 1 : 0) | ((resFlags & ADFLOW_RES_TURB) ? 2 : 0);
+    const bool snapInMarch = g_act.empty() && (!(need & 1) || P.flowSnapInMarch) && (!(need & 2) || P.turbSnapInMarch);
+    if (snapInMarch && snap_request_begin(level, J)) return 1;
+    for (int l = J.lStart; l < J.lStart + J.nState; ++l) {
+        for (int col = 0; col < J.cn; ++col) {
+            g_snapreq.col = col;
+            for_level(level, [&](Block* b) {
+                if (M.dual) ad_launch_seed_closures(b->v, g_ad[b].v, l, col, J, kp, g_stream, oneComponent && col > 0);
+                else launch_fd_state_closures(b->v, b->wref, l, col, J, delta, kp, g_stream, oneComponent && col > 0);
+                return 0;
+            });
+            g_snap_done = 0;
+            if (block_res_state_enqueue(M, level, resFlags, turbBC, viscPC, true)) return 1;
+            if (snapInMarch && (g_snap_done & need) != need)
+                return fail("fd_jacobian: the marching kernels were expected to write the snapshot of the evaluation (need %d, written %d)", need, g_snap_done);
+            if (!snapInMarch)
+                for_level(level, [&](Block* b) {
+                    double* snap = b->snap + (size_t)col * J.nState * b->v.nbox;
+                    if (M.dual) ad_launch_snap(b->v, g_ad[b].v.dw, snap, J, g_opts.turbResScale, g_stream);
+                    else launch_fd_snap(b->v, snap, J, g_opts.turbResScale, g_stream);
+                    return 0;
+                });
+        }
+        for_level(level, [&](Block* b) {
+            launch_fd_scatter(b->v, b->snap, b->jac, l, J, M.dual ? nullptr : b->dwref, M.dual ? 0.0 : 1.0 / delta, g_stream);
+            return 0;
+        });
+    }
+    return 0;
+}
+
+int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta)
+{
+    if (need_ready() || jac_check_args(level, flags, delta)) return 1;
+    const bool useAD = (flags & ADFLOW_JAC_USE_AD) != 0;
+    const Launchers& M = useAD ? DUAL : PLAIN;
+    const bool rans = g_opts.equations == ADFLOW_RANS;
+    JacSpec J;
+    jac_spec(flags & ~(ADFLOW_JAC_USE_AD | ADFLOW_JAC_APPROX_SA), rans || g_opts.equations == ADFLOW_NS, rans, &J);
+    if (jac_storage(level, J)) return 1;
     g_jac_valid = false;
 
     // whalo2(1, 1, nw, T, T, T) (adjointUtils.F90:113)
     if (g_comm.count(std::make_pair(level, 2)))
         if (halo_exchange_enqueue(level, 1, rans ? 6 : 5, 1, 1, 2)) return 1;
 
-    // the switches of the preconditioner matrix (adjointUtils.F90:176-191), restored below
-    const adflow_opts saved = g_opts;
-    const int savedLumped = g_lumped;
+    const bool pc = (flags & ADFLOW_JAC_PC) != 0;
+    PcSwitchGuard switches(pc);
     unsigned resFlags = 0;
     if (!(flags & ADFLOW_JAC_TURB_ONLY)) resFlags |= ADFLOW_RES_FLOW;
-    const bool turbRes = rans && !(flags & ADFLOW_JAC_FROZEN_TURB);
-    if (turbRes) resFlags |= ADFLOW_RES_TURB;
-    if (turbRes && (flags & ADFLOW_JAC_APPROX_SA)) resFlags |= ADFLOW_RES_APPROX_SA;     // FormJacobianANK:1978, FormJacobianANKTurb:2364
-    if (flags & ADFLOW_JAC_PC) {
-        g_lumped = 1;
-        g_opts.acousticScaleFactor = 1.0;
-        g_opts.orderTurb = 1;                                           // constants::firstOrder
-        resFlags |= ADFLOW_RES_DISS_APPROX | ADFLOW_RES_VISC_APPROX;     // dissApprox = viscApprox = lumpedDiss
-        // referenceShockSensor on the unperturbed state (adjointUtils.F90:258-260): the sensor is not linearised
-        const bool pressure = (g_opts.equations == ADFLOW_EULER) || (g_opts.spaceDiscr == ADFLOW_DISS_MATRIX);
-        rc = for_level(level, [&](Block* b) {
-            if (pressure) HIPCHK(hipMemcpyAsync(b->v.ss, b->v.p, sizeof(double) * (size_t)b->boxsize, hipMemcpyDeviceToDevice, g_stream));
-            else launch_entropy(b->v, g_stream);
-            return 0;
-        });
-    }
     // frozenTurb: equations = NSEquations (adjointUtils.F90:218-222) -- no turbulence boundary conditions, no SA residual; the eddy
     // viscosity is still recomputed from nuTilde because eddyModel stays set (turbUtils.F90:604-612)
     const bool turbBC = rans && !(flags & ADFLOW_JAC_FROZEN_TURB);
-    auto restore = [&]() { g_opts = saved; g_lumped = savedLumped; };
-    // Inside the sweep of one state variable over the colours only that component of the state changes; the others are written at its
-    // first colour only.  What then differs from a full rewrite is the content of halos BEFORE the boundary conditions of the
+    if (turbBC) resFlags |= ADFLOW_RES_TURB;
+    if (turbBC && (flags & ADFLOW_JAC_APPROX_SA)) resFlags |= ADFLOW_RES_APPROX_SA;     // FormJacobianANK:1978, FormJacobianANKTurb:2364
+    int rc = 0;
+    if (pc) {
+        resFlags |= ADFLOW_RES_DISS_APPROX | ADFLOW_RES_VISC_APPROX;     // dissApprox = viscApprox = lumpedDiss
+        // referenceShockSensor on the unperturbed state (adjointUtils.F90:258-260): the sensor is not linearised
+        rc = reference_shock_sensor_enqueue(level);
+    }
+    // What differs from a full rewrite of the state at every colour is the content of halos BEFORE the boundary conditions of the
     // evaluation overwrite them (the output of the previous evaluation instead of the reference state): face halos are functions of
     // the interior alone, but the halo cells along block EDGES are written by one subface from what another left there, in an order
     // -- so the shortcut is taken for the preconditioner matrix, whose 7-point stencils never reach an edge halo, and not with a host hook
     // (... nor for viscPC, whose full viscous flux reads edge and corner halos through its 27-point stencil: round-5 advisor)
-    const bool oneComponent = (flags & ADFLOW_JAC_PC) && !(flags & ADFLOW_JAC_VISC_PC) && !g_bc_callback && !g_turb_bc_callback;
+    const bool viscPC = (flags & ADFLOW_JAC_VISC_PC) != 0;
+    const bool oneComponent = pc && !viscPC && !g_bc_callback && !g_turb_bc_callback;
 
-    // the snapshot entries of an evaluation come from the marches only when the host's prediction of the kernel dispatch was right:
-    // the launchers report what they wrote (adf_note_snap) and a mismatch is an error instead of a matrix built from stale memory
-    auto snap_written = [&](int resFlags_) -> int {
-        const int need = ((resFlags_ & ADFLOW_RES_FLOW) ? 1 : 0) | ((resFlags_ & ADFLOW_RES_TURB) ? 2 : 0);
-        if ((g_snap_done & need) != need)
-            return fail("fd_jacobian: the marching kernels were expected to write the snapshot of the evaluation (need %d, written %d)", need, g_snap_done);
-        return 0;
-    };
+    bool haveRef = false;           // wref holds the reference state: an error further down still puts the state back
     if (useAD) {
-        // one forward-mode evaluation per (colour, state variable): seed = 1 on component l of the cells of the colour (halos
-        // included), block_res_state_d, the derivative of the scaled residual is the column of every stencil block
         if (!rc) rc = ad_prepare(level);
-        // the marching kernels of the preconditioner matrix write the snapshot of a pass themselves (KParams::snapTab)
-        const bool viscPC = (flags & ADFLOW_JAC_VISC_PC) != 0;
-        bool snapInMarch = false;
-        if (!rc) {
-            const FlowPlan P = plan_flow(flow_facts(level, ad_kparams(level, resFlags), ad_visc_approx(resFlags, viscPC), false, true, resFlags));
-            snapInMarch = (!(resFlags & ADFLOW_RES_FLOW) || P.flowSnapInMarch) && (!(resFlags & ADFLOW_RES_TURB) || P.turbSnapInMarch);
-            if (snapInMarch) rc = snap_request_begin(level, J);
-        }
-        for (int l = J.lStart; l < J.lStart + J.nState && !rc; ++l) {
-            for (int col = 0; col < J.cn && !rc; ++col) {
-                g_snapreq.col = col;
-                const KParams kps = ad_kparams(level, resFlags);
-                rc = for_level(level, [&](Block* b) {
-                    ad_launch_seed_closures(b->v, g_ad[b].v, l, col, J, kps, g_stream, oneComponent && col > 0);
-                    return 0;
-                });
-                g_snap_done = 0;
-                if (!rc) rc = ad_block_res_state_enqueue(level, resFlags, turbBC, (flags & ADFLOW_JAC_VISC_PC) != 0, true);
-                if (!rc && snapInMarch) rc = snap_written(resFlags);
-                if (!rc && !snapInMarch) rc = for_level(level, [&](Block* b) {
-                    ad_launch_snap(b->v, g_ad[b].v.dw, b->snap + (size_t)col * J.nState * b->v.nbox, J, g_opts.turbResScale, g_stream);
-                    return 0;
-                });
-            }
-            if (!rc) rc = for_level(level, [&](Block* b) {
-                launch_fd_scatter(b->v, b->snap, b->jac, l, J, nullptr, 0.0, g_stream);
-                return 0;
-            });
-        }
-        g_snapreq.on = false;
+    } else {
+        // setFDReference (adjointUtils.F90:1971-2024): reference residual, then the reference state INCLUDING the halos the boundary
+        // conditions just wrote
+        if (!rc) rc = block_res_state_enqueue(PLAIN, level, resFlags, turbBC, viscPC);
+        if (!rc) rc = for_level(level, [&](Block* b) {
+            launch_fd_copy(b->v, b->wref, b->v.w, b->v.nw, g_stream);
+            launch_fd_extract(b->v, b->dwref, b->jac, -1, 0, J, 0.0, g_opts.turbResScale, g_stream);
+            return 0;
+        });
+        haveRef = !rc;
+    }
+    if (!rc) rc = coloured_sweep(M, level, J, resFlags, turbBC, viscPC, oneComponent, delta);
+    if (useAD) {
         if (!rc) rc = sync_and_check();
         else (void)hipStreamSynchronize(g_stream);
         if (!g_ad_cache || rc) ad_drop();
-        restore();
-        if (rc) return rc;
-        g_jac = J;
-        g_jac_level = level;
-        g_jac_valid = true;
-        return 0;
-    }
-
-    // setFDReference (adjointUtils.F90:1971-2024): reference residual, then the reference state INCLUDING the halos the boundary
-    // conditions just wrote
-    bool haveRef = false;           // wref holds the reference state: an error further down still puts the state back
-    if (!rc) rc = block_res_state_enqueue(level, resFlags, turbBC);
-    if (!rc) rc = for_level(level, [&](Block* b) {
-        launch_fd_copy(b->v, b->wref, b->v.w, b->v.nw, g_stream);
-        launch_fd_extract(b->v, b->dwref, b->jac, -1, 0, J, 0.0, g_opts.turbResScale, g_stream);
-        return 0;
-    });
-    if (!rc) haveRef = true;
-    const double deltaInv = 1.0 / delta;
-    // the reference loops colours outside and state variables inside; every (colour, variable) evaluation is independent, so the
-    // loops are exchanged here: the nColour evaluations of one variable are kept (dense) and scattered into the blocks together
-    // (the state-perturbation kernel reads only options of kpc that no flag of the evaluation changes)
-    const KParams kpc = res_kparams(level, resFlags);
-    // the marching kernels of the preconditioner matrix write the snapshot of an evaluation themselves (KParams::snapTab): not with
-    // actuator regions (their sources are added to dw behind the core).  The plan is that of the KParams and flags every coloured
-    // evaluation below builds again (block_res_enqueue)
-    bool snapInMarch = false;
-    if (!rc) {
-        const FlowPlan P = plan_flow(flow_facts(level, kpc, (resFlags & ADFLOW_RES_VISC_APPROX) != 0, false, false, resFlags));
-        snapInMarch = g_act.empty() && (!(resFlags & ADFLOW_RES_FLOW) || P.flowSnapInMarch) && (!(resFlags & ADFLOW_RES_TURB) || P.turbSnapInMarch);
-        if (snapInMarch) rc = snap_request_begin(level, J);
-    }
-    for (int l = J.lStart; l < J.lStart + J.nState && !rc; ++l) {
-        for (int col = 0; col < J.cn && !rc; ++col) {
-            g_snapreq.col = col;
-            rc = for_level(level, [&](Block* b) {
-                launch_fd_state_closures(b->v, b->wref, l, col, J, delta, kpc, g_stream, oneComponent && col > 0);
-                return 0;
-            });
-            g_snap_done = 0;
-            if (!rc) rc = block_res_state_enqueue(level, resFlags, turbBC, true);
-            if (!rc && snapInMarch) rc = snap_written(resFlags);
-            if (!rc && !snapInMarch) rc = for_level(level, [&](Block* b) {
-                launch_fd_snap(b->v, b->snap + (size_t)col * J.nState * b->v.nbox, J, g_opts.turbResScale, g_stream);
-                return 0;
-            });
-        }
-        if (!rc) rc = for_level(level, [&](Block* b) {
-            launch_fd_scatter(b->v, b->snap, b->jac, l, J, b->dwref, deltaInv, g_stream);
-            return 0;
-        });
-    }
-    g_snapreq.on = false;
-    // resetFDReference (adjointUtils.F90:2026-2058): w back, dw = the (scaled) reference residual
-    if (!rc) rc = for_level(level, [&](Block* b) {
-        launch_fd_state(b->v, b->wref, 0, -1, J, 0.0, g_stream);
-        launch_fd_extract(b->v, b->dwref, b->jac, -2, 0, J, 0.0, g_opts.turbResScale, g_stream);
-        b->ss_valid = false;
-        b->etot_consistent = false;
-        return 0;
-    });
-    if (rc && haveRef) {
-        // the sweep stopped half way: the level must not keep a perturbed state (the error text of the failed call is kept)
+    } else if (haveRef) {
+        // resetFDReference (adjointUtils.F90:2026-2058): w back, dw = the (scaled) reference residual -- after a sweep that stopped
+        // half way the state alone: the level must not keep a perturbed one (the error text of the failed call is kept)
         for_level(level, [&](Block* b) {
             launch_fd_state(b->v, b->wref, 0, -1, J, 0.0, g_stream);
+            if (!rc) launch_fd_extract(b->v, b->dwref, b->jac, -2, 0, J, 0.0, g_opts.turbResScale, g_stream);
             b->ss_valid = false;
             b->etot_consistent = false;
             return 0;
         });
-        (void)hipStreamSynchronize(g_stream);
+        if (rc) (void)hipStreamSynchronize(g_stream);
     }
-    restore();
     if (rc) return rc;
     g_jac = J;
     g_jac_level = level;
     g_jac_valid = true;
-    return sync_and_check();
+    return useAD ? 0 : sync_and_check();        // (forward mode synchronised before it decided about its slab)
 }
 
 int adflow_gpu_release_workspace(int64_t* bytes)

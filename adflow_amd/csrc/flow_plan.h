@@ -1,6 +1,6 @@
 // The kernel dispatch of one mean-flow (+ SA) evaluation as a value.  plan_flow() is the ONE place where scheme, level, flags and the
-// kernel-selection tuning keys turn into kernels: the executors of api.hip (enqueue_flow_fluxes, block_res_enqueue,
-// block_res_split_enqueue, ad_block_res_state_enqueue) launch what the plan names, and the Jacobian assembly reads from the same plan
+// kernel-selection tuning keys turn into kernels: the executors of api.hip (enqueue_turb_residual, enqueue_flow_fluxes, on
+// the plain or the dual launchers; block_res_split_enqueue) launch what the plan names, and the Jacobian assembly reads from the same plan
 // whether the marches write its snapshot.  Host only: no HIP types, no globals, no side effects.  The rules are those the executors
 // held one by one; tests/test_dispatch_plan.py pins the launches they produce.
 #pragma once

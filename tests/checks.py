@@ -430,6 +430,26 @@ def check_ad_jacobian(engine, dims, prm, spec, usePC=True, frozenTurb=False, use
     return Jg, Jr, st
 
 
+def check_assembly_leaves_no_trace(engine, dims, prm, spec, seed=107, **mk):
+    """The preconditioner assembly evaluates with switches of its own -- orderTurb = firstOrder, acousticScaleFactor = 1, lumped
+    dissipation (adjointUtils.F90:176-191) -- and hands all three back on every exit: the default residual of the re-uploaded state
+    after an assembly, by finite differences and by forward mode, is BITWISE the one before it.  The comparison sees a switch only
+    where prm differs from the switched value AND the residual reads it: orderTurb with every scheme, the lumped dissipation through
+    the limiter of the upwind scheme, acousticScaleFactor through the spectral radii, which only the scalar dissipation reads."""
+    blk, r, prm = setup_block_with_bc(engine, dims, prm, spec, seed, **mk)
+
+    def residual():
+        engine.upload_state(1, 1)
+        engine.blocketteRes(1)
+        return engine.download_residual(1, 1).copy(order="F")
+    dw0 = residual()
+    assert np.isfinite(owned(blk, dw0)).all() and np.abs(owned(blk, dw0)).max() > 0.0
+    for useAD in (False, True):
+        engine.setupStateResidualMatrix(1, usePC=True, delta=1e-5, useAD=useAD)
+        dw = residual()
+        assert np.array_equal(owned(blk, dw), owned(blk, dw0)), ("useAD", useAD, np.abs(owned(blk, dw) - owned(blk, dw0)).max())
+
+
 def check_jacobian_several_blocks(engine, prm, blocks_spec, seed=91, quick=False, **mk):
     """The preconditioner matrix of a LEVEL of several blocks of different sizes (slot numbers with a gap), by finite differences and
     by forward mode: the marching path of round 5 -- k_pc_march + k_sa_march over the level's tile tables, the snapshot entries

@@ -196,6 +196,13 @@ def test_ad_pc_equal_states_across_a_face(engine):
     checks.check_fd_jacobian(engine, (5, 6, 4), rans, spec, seed=284201, stretch_k=2.0)
 
 
+def test_assembly_leaves_no_trace(engine):
+    """the switches of the preconditioner matrix are handed back by both assemblies (checks.check_assembly_leaves_no_trace)"""
+    rans = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda, orderTurb=secondOrder, acousticScaleFactor=0.5)
+    for sd in (upwind, dissScalar):         # (the limiter of the lumped dissipation / the spectral radii of acousticScaleFactor)
+        checks.check_assembly_leaves_no_trace(engine, (6, 5, 4), rans.replace(spaceDiscr=sd), WALL, stretch_k=2.0)
+
+
 def test_reference_step(engine):
     """delta = 1e-9 as the reference: rounding differences of two correct residuals are amplified by 1e9, so only ~1e-6 of the
     largest entry is resolvable by ANY implementation (the reference against itself with another compiler flag included)"""

@@ -521,6 +521,13 @@ def test_fd_jacobian_pc_rans(hostsim_engine):
     checks.check_fd_jacobian(hostsim_engine, (5, 4, 4), rans.replace(spaceDiscr=dissScalar), _JAC_WALL, viscPC=True, stretch_k=2.0)
 
 
+def test_assembly_leaves_no_trace(hostsim_engine):
+    """the switches of the preconditioner matrix are handed back by both assemblies (checks.check_assembly_leaves_no_trace)"""
+    rans = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda, orderTurb=secondOrder, acousticScaleFactor=0.5)
+    for sd in (upwind, dissScalar):         # (the limiter of the lumped dissipation / the spectral radii of acousticScaleFactor)
+        checks.check_assembly_leaves_no_trace(hostsim_engine, (6, 5, 4), rans.replace(spaceDiscr=sd), _JAC_WALL, stretch_k=2.0)
+
+
 def test_fd_jacobian_exact(hostsim_engine):
     """dR/dw (usePC = F): 13 colours (Euler) and 35 colours (viscous), the reference's own step 1e-9 at the accuracy it resolves"""
     checks.check_fd_jacobian(hostsim_engine, (6, 6, 5), FlowParams(spaceDiscr=dissScalar), _JAC_EULER, usePC=False)
