@@ -826,6 +826,9 @@ int adflow_gpu_wall_distance_register(int nn, int level, int sps, const int32_t*
     }
     HIPCHK(hipMemcpyAsync(b->wd_ind, surfNodeIndices, n * 4 * sizeof(int32_t), hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(b->wd_uv, uv, n * 2 * sizeof(double), hipMemcpyHostToDevice, g_stream));
+    // the caller's arrays: consumed when the entry returns, whatever adflow_gpu_set_async says (from page-locked memory the copies
+    // are truly asynchronous)
+    HIPCHK(hipStreamSynchronize(g_stream));
     return sync_and_check();
 }
 
@@ -850,7 +853,12 @@ int adflow_gpu_update_wall_distances(int level, const double* xSurf, int64_t n)
         HIPCHK(hipMalloc((void**)&g_xsurf, sizeof(double) * (size_t)n));
         g_xsurf_n = (size_t)n;
     }
-    if (n > 0) HIPCHK(hipMemcpyAsync(g_xsurf, xSurf, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, g_stream));
+    if (n > 0) {
+        // the caller refills xSurf after every warp: it is consumed before the entry returns, whatever adflow_gpu_set_async says;
+        // the kernels behind the copy are only enqueued
+        HIPCHK(hipMemcpyAsync(g_xsurf, xSurf, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+    }
     bool any = false;
     int rc = for_level(level, [&](Block* b) {
         if (!b->wd_ind) return 0;
@@ -3630,21 +3638,27 @@ int for_level1_in_order(const std::function<int(Block*, long)>& fn)
 struct Stage {
     long n = 0;
     double* base = nullptr;
+    mutable bool pending = false;      // a copy from or into one of the caller's host arrays is in the queue
+    // an exit in front of done() (a refusal after in()): the caller's arrays are not read or written once the entry has returned
+    ~Stage() { if (pending) (void)hipStreamSynchronize(g_stream); }
     double* operator[](int q) const { return base + (size_t)q * n; }
     int in(int q, const double* h) const
     {
         HIPCHK(hipMemcpyAsync((*this)[q], h, sizeof(double) * n, hipMemcpyHostToDevice, g_stream));
+        pending = true;
         return 0;
     }
     int out(double* h, int q) const { return scalars(h, (*this)[q], n); }
     int scalars(double* h, const double* d, long count) const
     {
         HIPCHK(hipMemcpyAsync(h, d, sizeof(double) * count, hipMemcpyDeviceToHost, g_stream));
+        pending = true;
         return 0;
     }
     int done() const
     {
         HIPCHK(hipStreamSynchronize(g_stream));
+        pending = false;
         return 0;
     }
 };

@@ -270,6 +270,14 @@ class Engine:
         self._chk(self.lib.adflow_gpu_ank_get_r(r.ctypes.data, n, self._ankFlags(coupled, turb=turb)))
         return r
 
+    def ankSetWDev(self, d_w: int, n: int, flags=0):
+        """ankSetW on a device pointer; flags: ADFLOW_ANK_COUPLED / ADFLOW_ANK_TURB (_ankFlags)"""
+        self._chk(self.lib.adflow_gpu_ank_set_w_dev(ctypes.c_void_p(d_w), int(n), int(flags)))
+
+    def ankGetRDev(self, d_r: int, n: int, flags=0):
+        """ankGetR into a device pointer"""
+        self._chk(self.lib.adflow_gpu_ank_get_r_dev(ctypes.c_void_p(d_r), int(n), int(flags)))
+
     def ankTimeStep(self, cfl, turbCFLScale=1.0, coupled=False, level=1, turb=False):
         """computeTimeStepMat for ANK_charTimeStepType = 'None' from the dtl on the device; turb: the diagonal of the turbulence KSP"""
         self._chk(self.lib.adflow_gpu_ank_time_step(level, float(cfl), float(turbCFLScale), self._ankFlags(coupled, turb=turb)))
@@ -295,6 +303,10 @@ class Engine:
         w = np.ascontiguousarray(w, dtype=np.float64)
         self._chk(self.lib.adflow_gpu_ank_set_base(w.ctypes.data, w.size, self._ankFlags(coupled, dissApprox, viscApprox, useBlockettes, turb,
                                                                                           approxSA, turbFirstOrder)))
+
+    def ankSetBaseDev(self, d_w: int, n: int, flags=0):
+        """ankSetBase on a device pointer; flags: the kind and the residual flags (_ankFlags)"""
+        self._chk(self.lib.adflow_gpu_ank_set_base_dev(ctypes.c_void_p(d_w), int(n), int(flags)))
 
     def ankMult(self, v):
         """y = (R(w + h v) - r0) / h + T v with the MATMFFD_DS step h, on the base set last; the device state is the perturbed one
@@ -342,6 +354,14 @@ class Engine:
                                                             float(physLSTol), float(physLSTolTurb), float(stepFactor), float(stepMin),
                                                             ctypes.byref(lam)))
         return float(lam.value), dw
+
+    def ankPhysicalityCheckDev(self, d_w: int, d_dw: int, n: int, flags=0, lambda0=1.0, physLSTol=0.2, physLSTolTurb=0.99, stepFactor=1.0,
+                               stepMin=0.01) -> float:
+        """the same on device pointers: d_dw is clipped in place, lambda comes back (synchronous: it goes to the host)"""
+        lam = ctypes.c_double(float(lambda0))
+        self._chk(self.lib.adflow_gpu_ank_physicality_check_dev(ctypes.c_void_p(d_w), ctypes.c_void_p(d_dw), int(n), int(flags), float(physLSTol),
+                                                                float(physLSTolTurb), float(stepFactor), float(stepMin), ctypes.byref(lam)))
+        return float(lam.value)
 
     def ankUnsteadyRes(self, dW, omega, coupled=False, turb=False, dissApprox=False, viscApprox=False, useBlockettes=False, approxSA=False,
                        turbFirstOrder=False):
@@ -497,6 +517,10 @@ class Engine:
         r = np.zeros_like(wVec)
         self._chk(self.lib.adflow_gpu_nk_residual(wVec.ctypes.data, r.ctypes.data, wVec.size))
         return r
+
+    def FormFunction_mf_dev(self, d_wVec: int, d_rVec: int, n: int):
+        """the same on device pointers (two device vectors of n doubles)"""
+        self._chk(self.lib.adflow_gpu_nk_residual_dev(ctypes.c_void_p(d_wVec), ctypes.c_void_p(d_rVec), int(n)))
 
     # ---- multigrid ----------------------------------------------------------
     def transferToCoarseGrid(self, level=1):

@@ -410,7 +410,13 @@ int adflow_gpu_march_stats(int level, double* out, int n);
  * "euler_march" (default 1): k-marching fused kernel for Euler + scalar JST; the full list with defaults: DESIGN.md section 8b */
 int adflow_gpu_set_tuning(const char* key, int value);
 /* on != 0: hot-path entry points only ENQUEUE on the library stream (no host
- * sync at return); the caller orders with adflow_gpu_sync().  Default off. */
+ * sync at return); the caller orders with adflow_gpu_sync().  Default off.
+ * The mode covers device work only.  An entry that takes a pointer to a HOST array of the caller (the upload_ / download_ entries,
+ * the host forms of the vector entries, bc_register, comm_register, wall_distance_register, update_wall_distances, halo_pack /
+ * halo_unpack, mg_cycle's cycling) has consumed -- or filled -- that array when it returns, in either mode and also when it returns
+ * an error: the caller may reuse or free it at once.  Only the _dev forms, whose vectors live on the device, leave reads and writes
+ * of their arguments in the queue; those are ordered by the stream, and by adflow_gpu_sync() against the host.  An entry that hands
+ * a value back to the host (a norm, lambda, an iteration count, ank_last_h) synchronises whatever the mode is. */
 int adflow_gpu_set_async(int on);
 /* sizeof(adflow_opts), sizeof(adflow_block_desc) as compiled: lets a foreign-
  * language binding verify its mirror of the two structs */

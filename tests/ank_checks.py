@@ -78,25 +78,31 @@ def numpy_T(engine, blocks, prm, coupled, cfl=CFL, turbCFLScale=TURB_CFL_SCALE):
     return out
 
 
+def assert_T_block(Tl, Tn, what):
+    """the library's T of one block against the formula's: the structural zeros are zero, 16 eps on the rest; returns the largest
+    relative difference"""
+    assert Tl.shape == Tn.shape, (Tl.shape, Tn.shape)
+    zero = Tn == 0.0
+    nz = np.zeros(Tl.shape[:2], bool)
+    nz[0, 0] = nz[4, 4] = True
+    for l in (1, 2, 3):
+        nz[l, 0] = nz[l, l] = True
+    if Tl.shape[0] > 5:
+        nz[5, 5] = True
+    assert not Tl[~nz].any(), (what, "structural zeros")
+    rel = np.abs(Tl[nz] - Tn[nz]) / np.abs(Tn[nz])
+    print(f"T {what}: nState = {Tl.shape[0]}, max relative difference {rel.max() / EPS:.2f} eps, max|T| = {np.abs(Tl).max():.3e}")
+    assert rel.max() <= 16 * EPS, (what, rel.max() / EPS)
+    assert np.abs(Tl[nz]).min() > 0.0 and not (zero & nz[:, :, None, None, None]).any()
+    return float(rel.max())
+
+
 def assert_T(engine, blocks, prm, coupled, what):
     engine.timeStep(1)
     engine.ankTimeStep(CFL, TURB_CFL_SCALE, coupled)
     Tn = numpy_T(engine, blocks, prm, coupled)
     for nn in blocks:
-        Tl = engine.ankTimeStepBlocks(nn, coupled)
-        assert Tl.shape == Tn[nn].shape, (Tl.shape, Tn[nn].shape)
-        zero = Tn[nn] == 0.0
-        nz = np.zeros(Tl.shape[:2], bool)
-        nz[0, 0] = nz[4, 4] = True
-        for l in (1, 2, 3):
-            nz[l, 0] = nz[l, l] = True
-        if Tl.shape[0] > 5:
-            nz[5, 5] = True
-        assert not Tl[~nz].any(), (what, nn, "structural zeros")
-        rel = np.abs(Tl[nz] - Tn[nn][nz]) / np.abs(Tn[nn][nz])
-        print(f"T {what} block {nn}: nState = {Tl.shape[0]}, max relative difference {rel.max() / EPS:.2f} eps, max|T| = {np.abs(Tl).max():.3e}")
-        assert rel.max() <= 16 * EPS, (what, nn, rel.max() / EPS)
-        assert np.abs(Tl[nz]).min() > 0.0 and not (zero & nz[:, :, None, None, None]).any()
+        assert_T_block(engine.ankTimeStepBlocks(nn, coupled), Tn[nn], f"{what} block {nn}")
     return Tn
 
 
@@ -234,6 +240,20 @@ def setup_operator(engine, dims, prm, spec, coupled, approx, seed, **mk):
     return blk, Rref, op, Tn, w0
 
 
+def assert_product(what, y, v, h, op, Tn, blk, quotient):
+    """the bar of the operator: max|y - (J v + T v)| <= MARGIN x the same distance of the reference's own difference quotient with
+    the same step, quotient(h, v) = (R(w + h v) - r0) / h.  Returns (the yardstick product, the bar, the library's distance)"""
+    Tv = T_times(Tn, {1: blk}, v)
+    yard = op.apply(v) + Tv
+    yref = quotient(h, v) + Tv
+    e_lib, e_ref = float(np.abs(y - yard).max()), float(np.abs(yref - yard).max())
+    print(f"operator {what}: h = {h:.3e}, max|y - (J + T) v| = {e_lib:.3e}, reference quotient {e_ref:.3e}, ratio "
+          f"{e_lib / max(e_ref, 1e-300):.3f}, max|y| = {np.abs(yard).max():.3e}, max|T v| = {np.abs(Tv).max():.3e}")
+    assert e_lib <= MARGIN * e_ref, (what, e_lib, e_ref)
+    assert np.abs(yard).max() > 0.0
+    return yard, MARGIN * e_ref, e_lib
+
+
 def assert_operator(engine, blk, Rref, op, Tn, w0, seed, what):
     """max|ankMult(v) - (J v + T v)| <= MARGIN x the same distance of the reference's own difference quotient (same flags, same h)"""
     rng = np.random.default_rng(seed)
@@ -242,14 +262,7 @@ def assert_operator(engine, blk, Rref, op, Tn, w0, seed, what):
     h = engine.ankLastH()
     hn = ds_step(w0, v)
     assert abs(h - hn) <= 1e-12 * abs(hn), (h, hn)
-    Tv = T_times(Tn, {1: blk}, v)
-    yard = op.apply(v) + Tv
-    yref = (Rref(w0 + h * v) - Rref.r0) / h + Tv
-    e_lib, e_ref = float(np.abs(y - yard).max()), float(np.abs(yref - yard).max())
-    print(f"operator {what}: h = {h:.3e}, max|y - (J + T) v| = {e_lib:.3e}, reference quotient {e_ref:.3e}, ratio "
-          f"{e_lib / max(e_ref, 1e-300):.3f}, max|y| = {np.abs(yard).max():.3e}, max|T v| = {np.abs(Tv).max():.3e}")
-    assert e_lib <= MARGIN * e_ref, (what, e_lib, e_ref)
-    assert np.abs(yard).max() > 0.0
+    yard, _, e_lib = assert_product(what, y, v, h, op, Tn, blk, lambda h, v: (Rref(w0 + h * v) - Rref.r0) / h)
     return v, y, e_lib / float(np.abs(yard).max())
 
 
@@ -321,19 +334,26 @@ def check_solve(engine, dims, prm, spec, cap, seed=347, **mk):
     b = engine.ankGetR()
     nb = float(np.linalg.norm(b))
     assert nb > 0.0 and np.abs(b - Rref.r0).max() <= 1e-9 * np.abs(Rref.r0).max()
-    k_ref = pc.scipy_gmres_iterations(lambda v: ops.apply(v), pc.NumpyILU0(ops, np.float64), b, False, rtol, cap, cap)
     x, its, r0, rn = engine.ankSolve(b, 1, restart=cap, maxIts=cap, rtol=rtol)
-    true = float(np.linalg.norm(b - ops.apply(x)))
+    assert_solve(f"ankSolve {dims}", its, r0, b, x, ops, cap, rtol)
     rn_np = float(np.linalg.norm(b - engine.ankMult(x)))
-    print(f"ankSolve {dims}: {its} iterations (scipy {k_ref}, cap {cap}), ||b - A x|| / ||b|| = {true / nb:.3e}, reported {rn / nb:.3e}, "
-          f"through ankMult {rn_np / nb:.3e}")
+    print(f"ankSolve {dims}: reported {rn / nb:.3e}, through ankMult {rn_np / nb:.3e}")
+    assert abs(rn - rn_np) <= 1e-10 * rn_np, (rn, rn_np)
+    engine.pcRelease()
+    engine.ankRelease()
+
+
+def assert_solve(what, its, r0, b, x, ops, cap, rtol):
+    """the bars of a solve on the numpy operator ops = J + T: scipy's gmres with the shifted NumpyILU0 as right preconditioner needs
+    at most cap / 2 iterations, the library at most cap; rnorm0 = ||b|| to 1e-12; ||b - A x|| <= 2 rtol ||b||"""
+    nb = float(np.linalg.norm(b))
+    k_ref = pc.scipy_gmres_iterations(lambda v: ops.apply(v), pc.NumpyILU0(ops, np.float64), b, False, rtol, cap, cap)
+    true = float(np.linalg.norm(b - ops.apply(x)))
+    print(f"{what}: {its} iterations (scipy {k_ref}, cap {cap}), ||b - A x|| / ||b|| = {true / nb:.3e} (bar {2 * rtol:.0e})")
     assert 2 * k_ref <= cap, ("the cap leaves no factor 2 over scipy's count", k_ref, cap)
     assert 0 < its <= cap, (its, cap)
     assert abs(r0 - nb) <= 1e-12 * nb
     assert true <= 2 * rtol * nb, (true, nb)
-    assert abs(rn - rn_np) <= 1e-10 * rn_np, (rn, rn_np)
-    engine.pcRelease()
-    engine.ankRelease()
 
 
 # ---- 5. the step limiter ---------------------------------------------------------------------------------------------------------

@@ -942,12 +942,23 @@ def check_wall_distance(engine, dims, prm, seed=83, at_wall=False, translate=Non
         assert (np.abs(np.where(far, 1.0, out) - near) / near).max() <= TOL
         assert 0.0 < r["d2Wall"].min() < 0.05 * np.where(far, 0.0, r["d2Wall"]).max()
         return
+    blk, ind, uv, xSurf, r = wall_distance_case(blk, prm, rng, dims)
+    engine.registerWallAssociation(ind, uv)
+    engine.upload_coordinates(1, 1)
+    engine.updateWallDistancesQuickly(xSurf, 1)
+    assert_wall_distance(engine, r, ind)
+
+
+def wall_distance_case(blk, prm, rng, dims):
+    """the general case of check_wall_distance up to the reference's result, for the block `blk`: a random
+    association with 57 surface nodes, the mesh and the surface warped, the reference's d2Wall in r.  Nothing of it is handed to the
+    engine yet.  Returns (blk, surfNodeIndices, uv, xSurf, r)."""
+    from oracle import ref
     nsurf = 57
     ind = np.asfortranarray(rng.integers(1, nsurf + 1, size=(4, blk.nx, blk.ny, blk.nz), dtype=np.int32))
     ind[0][rng.uniform(size=ind.shape[1:]) < 0.1] = 0                       # too far away: no association
     uv = np.asfortranarray(rng.uniform(0.0, 1.0, size=(2, blk.nx, blk.ny, blk.nz)))
     uv[:, 0, 0, 0] = (0.0, 1.0)
-    engine.registerWallAssociation(ind, uv)
     # warp the mesh and the surface, then update
     h = 1.0 / max(dims)
     blk["x"] += 0.05 * h * rng.uniform(-1, 1, blk["x"].shape)
@@ -957,33 +968,70 @@ def check_wall_distance(engine, dims, prm, seed=83, at_wall=False, translate=Non
     ref.bind_block(r, prm)
     r["d2Wall"][...] = -1.0
     ref.update_wall_distances(ind, uv, xSurf)
-    engine.upload_coordinates(1, 1)
-    engine.updateWallDistancesQuickly(xSurf, 1)
+    return blk, ind, uv, xSurf, r
+
+
+def assert_wall_distance(engine, r, ind):
+    """d2Wall on the device against the reference's r of wall_distance_case; returns the error"""
     out = np.zeros_like(r["d2Wall"])
     engine.download_array(capi.ARR_D2WALL, out, 1, 1)
     assert (r["d2Wall"] >= 1e37).sum() == (ind[0] == 0).sum() > 0
     assert np.array_equal(out >= 1e37, r["d2Wall"] >= 1e37)
     far = r["d2Wall"] >= 1e37
-    assert rel_err(np.where(far, 0.0, out), np.where(far, 0.0, r["d2Wall"])) <= TOL
+    e = rel_err(np.where(far, 0.0, out), np.where(far, 0.0, r["d2Wall"]))
+    assert e <= TOL, e
     assert r["d2Wall"].min() > 0.0
+    return e
 
 
-def check_smoother_with_bc(engine, dims, prm, spec, seed=61, nsweeps=2, **mk):
+def _sweeps(nsweeps, ref_sweep, gpu_sweep, compare, chain):
+    """nsweeps x (reference, library, comparison); chain (a callable that gives a context manager, e.g. the enqueue-only mode of
+    tests/async_checks.py): every sweep of the reference first, then every sweep of the library inside ONE chain() with nothing
+    in between, and the comparison once, at the end"""
+    if chain is None:
+        for sweep in range(nsweeps):
+            ref_sweep()
+            gpu_sweep()
+            compare(f"sweep {sweep}")
+        return
+    for sweep in range(nsweeps):
+        ref_sweep()
+    with chain():
+        for sweep in range(nsweeps):
+            gpu_sweep()
+    compare(f"{nsweeps} sweeps back to back")
+
+
+def check_smoother_with_bc(engine, dims, prm, spec, seed=61, nsweeps=2, chain=None, sa_solve=False, **mk):
     """RungeKuttaSmoother / DADISmoother on ONE block whose six faces are physical boundaries: the device
-    applies applyAllBC between update and halo exchange (smoothers.F90:369,680) exactly where the reference does."""
+    applies applyAllBC between update and halo exchange (smoothers.F90:369,680) exactly where the reference does.
+    sa_solve: every sweep ends with turbSolveDDADI (the sequence of check_sa_solve_with_bc); chain: see _sweeps.
+    Returns the block, holding the state downloaded last."""
     from oracle import ref
     blk, r, prm = setup_block_with_bc(engine, dims, prm, spec, seed, **mk)
     name = "RungeKuttaSmoother" if prm.smoother == RungeKutta else "DADISmoother"
-    for sweep in range(nsweeps):
+
+    def ref_sweep():
         ref.load().ref_set_int(b"rkStage", 0)
         ref.call_level("timeStep", 1, 0)
         ref.call_level("initres", 1, 1, 5)
         ref.call_level("residual", 1)
         ref.call_level(name, 1)
+        if sa_solve:
+            for it in range(prm.nSubIterTurb):
+                ref.call_level("setPointers", 1, 1)
+                ref.call("sa_block", 0)
+                ref.load().ref_call_level(b"whalo2_turb", 1, 6, 6)
+
+    def gpu_sweep():
         engine.timeStep(1, False)
         engine.residual(1, 0)
         getattr(engine, name)(1)
-        assert_state(engine, {1: blk}, {1: r}, prm, f"{name} with BCs, sweep {sweep}")
+        if sa_solve:
+            engine.turbSolveDDADI(1)
+
+    _sweeps(nsweeps, ref_sweep, gpu_sweep, lambda what: assert_state(engine, {1: blk}, {1: r}, prm, f"{name} with BCs, {what}"), chain)
+    return blk
 
 
 def make_brick(topo, prm, seed=1, rank=0, **mk):
@@ -1182,39 +1230,50 @@ def check_vacuum_smoother(engine, topo, prm, seed=7, frac=2e-4, **mk):
     return clipped
 
 
-def check_rk_smoother(engine, topo, prm, seed=7, nsweeps=1, **mk):
+def check_rk_smoother(engine, topo, prm, seed=7, nsweeps=1, chain=None, **mk):
     """RungeKuttaSmoother (smoothers.F90:4-88) incl. halo exchange between stages,
-    on a periodic brick (no physical boundaries)."""
+    on a periodic brick (no physical boundaries).  chain: see _sweeps.  Returns the blocks, holding the state downloaded last."""
     from oracle import ref
     prm = prm.replace(smoother=RungeKutta)
     blocks, rblocks = setup_brick(engine, topo, prm, seed, **mk)
-    for sweep in range(nsweeps):
+
+    def ref_sweep():
         ref.load().ref_set_int(b"rkStage", 0)
         ref.call_level("timeStep", 1, 0)
         ref.call_level("initres", 1, 1, 5)
         ref.call_level("residual", 1)
         ref.call_level("RungeKuttaSmoother", 1)
+
+    def gpu_sweep():
         engine.timeStep(1, False)
         engine.residual(1, 0)
         engine.RungeKuttaSmoother(1)
-        assert_state(engine, blocks, rblocks, prm, f"RK sweep {sweep}")
+
+    _sweeps(nsweeps, ref_sweep, gpu_sweep, lambda what: assert_state(engine, blocks, rblocks, prm, f"RK {what}"), chain)
+    return blocks
 
 
-def check_dadi_smoother(engine, topo, prm, seed=9, nsweeps=1, **mk):
-    """DADISmoother (smoothers.F90:383-693, computedwDADI residuals.F90:1062)."""
+def check_dadi_smoother(engine, topo, prm, seed=9, nsweeps=1, chain=None, **mk):
+    """DADISmoother (smoothers.F90:383-693, computedwDADI residuals.F90:1062).  chain: see _sweeps.  Returns the blocks, holding the
+    state downloaded last."""
     from oracle import ref
     prm = prm.replace(smoother=DADI)
     blocks, rblocks = setup_brick(engine, topo, prm, seed, **mk)
-    for sweep in range(nsweeps):
+
+    def ref_sweep():
         ref.load().ref_set_int(b"rkStage", 0)
         ref.call_level("timeStep", 1, 0)
         ref.call_level("initres", 1, 1, 5)
         ref.call_level("residual", 1)
         ref.call_level("DADISmoother", 1)
+
+    def gpu_sweep():
         engine.timeStep(1, False)
         engine.residual(1, 0)
         engine.DADISmoother(1)
-        assert_state(engine, blocks, rblocks, prm, f"DADI sweep {sweep}")
+
+    _sweeps(nsweeps, ref_sweep, gpu_sweep, lambda what: assert_state(engine, blocks, rblocks, prm, f"DADI {what}"), chain)
+    return blocks
 
 
 def setup_multilevel_brick(engine, topo, prm, nlevels=2, seed=1, bc_spec=None, bc_split=None, brick_spec=None, **mk):
@@ -1336,9 +1395,12 @@ def check_mg_transfer(engine, topo, prm, seed=11, irregular=None, **mk):
 
 
 def check_mg_cycle(engine, topo, prm, cycling, ncycles=2, seed=13, nlevels=2, bc_spec=None, bc_split=None, irregular=None,
-                   brick_spec=None, allow_degenerate=False, **mk):
+                   brick_spec=None, allow_degenerate=False, chain=None, **mk):
     """executeMGCycle (multiGrid.F90:825-955) for a given cycling strategy.
-    irregular: (half-weight cells at block ends, in the interior) the coarsening must produce (count_half_weight_cells)."""
+    irregular: (half-weight cells at block ends, in the interior) the coarsening must produce (count_half_weight_cells).
+    chain (a callable that gives a context manager, e.g. the enqueue-only mode of tests/async_checks.py): the entry condition and
+    every cycle of the library inside ONE chain() with nothing in between, compared once after the last cycle.
+    Returns (fine blocks holding the state downloaded last, {nn: dw downloaded last})."""
     from oracle import ref
     levels, rlevels = setup_multilevel_brick(engine, topo, prm, nlevels, seed, bc_spec=bc_spec, bc_split=bc_split, brick_spec=brick_spec,
                                              **mk)
@@ -1351,11 +1413,9 @@ def check_mg_cycle(engine, topo, prm, cycling, ncycles=2, seed=13, nlevels=2, bc
     ref.call_level("timeStep", 1, 0)
     ref.call_level("initres", 1, 1, 5)
     ref.call_level("residual", 1)
-    engine.timeStep(1, False)
-    engine.residual(1, 0)
-    for n in range(ncycles):
-        ref.call_level("executeMGCycle", 1)
-        engine.executeMGCycle(cycling)
+    dws = {}
+
+    def compare(n):
         # With physical boundaries the reference's coarse levels scribble over the corner of the FINE rlv array
         # (setPointers aliases rlv to level 1, utils.F90:3420) and the symmetry 2nd-halo pass then copies such a
         # value into 2nd-halo EDGE cells before the wall/farfield pass repairs its source.  No stencil of an owned
@@ -1364,28 +1424,46 @@ def check_mg_cycle(engine, topo, prm, cycling, ncycles=2, seed=13, nlevels=2, bc
                      rlv_no_edges=bool(brick_spec), nonfinite_ok=allow_degenerate)
         for nn, b in fine.items():
             dw = engine.download_residual(nn, 1)
+            dws[nn] = dw.copy()
             if allow_degenerate and not np.isfinite(owned(b, rfine[nn]["dw"])).all():
                 # (random sweeps: a cycle on a tiny coarse level can make the REFERENCE produce NaN; then only the pattern is compared)
                 assert np.array_equal(np.isfinite(owned(b, dw)), np.isfinite(owned(b, rfine[nn]["dw"])))
-                return
+                return False
             assert_dw(b, dw, rfine[nn]["dw"], 5, what=f"residual after cycle {n}")
+        return True
+
+    if chain is not None:
+        for n in range(ncycles):
+            ref.call_level("executeMGCycle", 1)
+        with chain():
+            engine.timeStep(1, False)
+            engine.residual(1, 0)
+            for n in range(ncycles):
+                engine.executeMGCycle(cycling)
+        compare(ncycles - 1)
+        return fine, dws
+    engine.timeStep(1, False)
+    engine.residual(1, 0)
+    for n in range(ncycles):
+        ref.call_level("executeMGCycle", 1)
+        engine.executeMGCycle(cycling)
+        if not compare(n):
+            return fine, dws
+    return fine, dws
 
 
-def check_nk_residual(engine, topo, prm, seed=21, bc_spec=None, floor_p=False, **mk):
-    """FormFunction_mf = setW + blocketteRes + setRVec (NKSolvers.F90:437-461,1262-1376):
-    the vector glue is restated in numpy (NKSolvers.F90 needs PETSc), every
-    arithmetic step in between is the reference's own routine.
-    floor_p: some cells of the vector carry so little energy that computePressureSimple floors their pressure: whalo2 then hands the
-    VECTOR's energy to the neighbours' halos and recomputes the owned one from the floored pressure (haloExchange.F90:178-196)"""
-    from oracle import ref
+def nk_setup(engine, topo, prm, seed=21, bc_spec=None, **mk):
+    """the blocks of check_nk_residual on the engine and in the reference: (blocks, reference blocks, prm)"""
     if bc_spec:      # one block, physical boundaries applied on the device inside blocketteRes
         blk, r, prm = setup_block_with_bc(engine, (topo.nx, topo.ny, topo.nz), prm, bc_spec, seed, **mk)
-        blocks, rblocks = {1: blk}, {1: r}
-    else:
-        blocks, rblocks = setup_brick(engine, topo, prm, seed, **mk)
-    rng = np.random.default_rng(seed)
+        return {1: blk}, {1: r}, prm
+    blocks, rblocks = setup_brick(engine, topo, prm, seed, **mk)
+    return blocks, rblocks, prm
+
+
+def nk_state_vector(blocks, prm, rng, floor_p=False):
+    """the blocks' state perturbed by 1e-3 relative, in PETSc order: block, k, j, i, variable fastest"""
     nw = prm.nw
-    # state vector in PETSc order: block, k, j, i, variable fastest
     parts = []
     for nn in sorted(blocks):
         b = blocks[nn]
@@ -1397,8 +1475,14 @@ def check_nk_residual(engine, topo, prm, seed=21, bc_spec=None, floor_p=False, *
             sel = slice(3, None, 5)
             wv[sel, 4] = 0.4 * wv[sel, 0] * (wv[sel, 1] ** 2 + wv[sel, 2] ** 2 + wv[sel, 3] ** 2)     # below the kinetic energy: p < 0
         parts.append(wv.reshape(-1))
-    wVec = np.concatenate(parts)
-    # --- reference side
+    return np.concatenate(parts)
+
+
+def nk_reference(rblocks, prm, wVec, bc_spec=None):
+    """the reference half of check_nk_residual for one vector: FormFunction_mf(wVec) on the reference's blocks, the vector glue
+    restated in numpy; may be called once per vector of a chain"""
+    from oracle import ref
+    nw = prm.nw
     winf = prm.wInf()
     off = 0
     for nn in sorted(rblocks):
@@ -1428,14 +1512,38 @@ def check_nk_residual(engine, topo, prm, seed=21, bc_spec=None, floor_p=False, *
         if nw > 5:
             res[..., 5] *= prm.turbResScale
         rparts.append(np.ascontiguousarray(np.transpose(res, (2, 1, 0, 3))).reshape(-1))
-    rRef = np.concatenate(rparts)
-    # --- GPU side
-    rGpu = engine.FormFunction_mf(wVec)
+    return np.concatenate(rparts)
+
+
+def assert_rvec(rGpu, rRef, nw, what="rVec"):
+    """the bar of check_nk_residual: every variable of the vector to TOL in the global measure; returns the largest error"""
     rr = rGpu.reshape(-1, nw)
     rf = rRef.reshape(-1, nw)
+    worst = 0.0
     for l in range(nw):
         e = rel_err(rr[:, l], rf[:, l])
-        assert e <= TOL, ("rVec", l, e)
+        assert e <= TOL, (what, l, e)
+        worst = max(worst, e)
+    return worst
+
+
+def check_nk_residual(engine, topo, prm, seed=21, bc_spec=None, floor_p=False, **mk):
+    """FormFunction_mf = setW + blocketteRes + setRVec (NKSolvers.F90:437-461,1262-1376):
+    the vector glue is restated in numpy (NKSolvers.F90 needs PETSc), every
+    arithmetic step in between is the reference's own routine.
+    floor_p: some cells of the vector carry so little energy that computePressureSimple floors their pressure: whalo2 then hands the
+    VECTOR's energy to the neighbours' halos and recomputes the owned one from the floored pressure (haloExchange.F90:178-196)"""
+    blocks, rblocks, prm = nk_setup(engine, topo, prm, seed, bc_spec, **mk)
+    rng = np.random.default_rng(seed)
+    nw = prm.nw
+    wVec = nk_state_vector(blocks, prm, rng, floor_p)
+    # --- reference side
+    rRef = nk_reference(rblocks, prm, wVec, bc_spec)
+    # --- GPU side
+    rGpu = engine.FormFunction_mf(wVec)
+    assert_rvec(rGpu, rRef, nw)
+    rr = rGpu.reshape(-1, nw)
+    rf = rRef.reshape(-1, nw)
     # getRes (no turbResScale) and setRVec norms
     r2, sf, st = engine.setRVec(wVec.size)
     assert rel_err(r2, rGpu) <= 1e-14       # setRVec as its own pass vs inside the kernels that complete dw: rounding of 1 / volRef

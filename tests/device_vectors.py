@@ -35,6 +35,10 @@ class HostVectors:
     def sync(self):
         pass
 
+    def pinned(self, a):
+        """a caller's host array: here a plain copy (the emulator's copies are synchronous)"""
+        return np.array(a, order="F" if a.ndim > 1 and a.flags["F_CONTIGUOUS"] else "C", copy=True)
+
 
 class TorchVectors:
     """torch float64 tensors on the GPU, handed over by data_ptr(); torch's stream is not the library's: sync() around every call"""
@@ -56,6 +60,14 @@ class TorchVectors:
 
     def sync(self):
         self.torch.cuda.synchronize()
+
+    def pinned(self, a):
+        """a caller's host array in page-locked memory (a copy of `a` with its shape and order, viewed through numpy): a
+        hipMemcpyAsync from it is truly asynchronous"""
+        fortran = a.ndim > 1 and a.flags["F_CONTIGUOUS"]
+        flat = self.torch.from_numpy(np.array(a.reshape(-1, order="F" if fortran else "C"), copy=True)).pin_memory()
+        assert flat.is_pinned()
+        return flat.numpy().reshape(a.shape, order="F" if fortran else "C")
 
 
 def device_vectors(config):
