@@ -20,6 +20,7 @@ from . import params as P
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libadflow_gpu.so")
 MAX_RK = 8
+MAX_NVEC = 32                     # ADFLOW_GPU_MAX_NVEC
 
 
 class AdflowOpts(ctypes.Structure):
@@ -159,6 +160,8 @@ EXPORTS = [
     "adflow_gpu_pc_setup", "adflow_gpu_pc_info", "adflow_gpu_pc_apply", "adflow_gpu_pc_apply_dev", "adflow_gpu_pc_release", "adflow_gpu_pc_select",
     "adflow_gpu_pc_set_fill", "adflow_gpu_pc_info2",
     "adflow_gpu_gmres_solve", "adflow_gpu_gmres_solve_dev",
+    "adflow_gpu_jacobian_mult_multi", "adflow_gpu_jacobian_mult_multi_dev", "adflow_gpu_pc_apply_multi", "adflow_gpu_pc_apply_multi_dev",
+    "adflow_gpu_gmres_solve_multi", "adflow_gpu_gmres_solve_multi_dev",
     "adflow_gpu_ank_set_w", "adflow_gpu_ank_set_w_dev", "adflow_gpu_ank_get_r", "adflow_gpu_ank_get_r_dev", "adflow_gpu_ank_time_step",
     "adflow_gpu_ank_download_time_step", "adflow_gpu_ank_pc_setup", "adflow_gpu_ank_set_base", "adflow_gpu_ank_set_base_dev",
     "adflow_gpu_ank_mult", "adflow_gpu_ank_mult_dev", "adflow_gpu_ank_last_h", "adflow_gpu_ank_solve", "adflow_gpu_ank_solve_dev",
@@ -228,6 +231,12 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     for f in (lib.adflow_gpu_gmres_solve, lib.adflow_gpu_gmres_solve_dev):
         f.argtypes = [c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_double, c_double, c_int,
                       POINTER(c_int), POINTER(c_double), POINTER(c_double)]
+    for f in (lib.adflow_gpu_jacobian_mult_multi, lib.adflow_gpu_jacobian_mult_multi_dev, lib.adflow_gpu_pc_apply_multi,
+              lib.adflow_gpu_pc_apply_multi_dev):
+        f.argtypes = [c_int, c_int, c_int, c_void_p, ctypes.c_long, c_void_p, ctypes.c_long, ctypes.c_long]
+    for f in (lib.adflow_gpu_gmres_solve_multi, lib.adflow_gpu_gmres_solve_multi_dev):
+        f.argtypes = [c_int, c_int, c_int, c_void_p, ctypes.c_long, c_void_p, ctypes.c_long, ctypes.c_long, c_int, c_int, c_double,
+                      c_double, c_int, c_void_p, c_void_p, c_void_p]
     for f in (lib.adflow_gpu_ank_set_w, lib.adflow_gpu_ank_set_w_dev, lib.adflow_gpu_ank_get_r, lib.adflow_gpu_ank_get_r_dev,
               lib.adflow_gpu_ank_set_base, lib.adflow_gpu_ank_set_base_dev):
         f.argtypes = [c_void_p, ctypes.c_long, c_uint]

@@ -3785,14 +3785,17 @@ int adflow_gpu_nk_residual(const double* wVec, double* rVec, long n)
 namespace {
 struct JmWork {
     int level = 0, nState = 0, nslots = 0, nx = 0, ny = 0, nz = 0;
+    int nv = 0;                        // vectors xs and ys hold side by side: 1 until a multi-vector product asked for more
     long ndof = 0;                     // nState x owned cells of the level
     long zeroGen = -1;                 // g_state_gen at which the halos of xs were last cleared
     size_t bytes = 0;
     std::vector<long> sig;             // what the work space was laid out for
-    std::vector<void*> raw;            // one allocation per block: xs, ys (nState components each)
+    std::vector<void*> raw;            // one allocation per block: xs, ys (nv vectors of nState components each)
     std::vector<JmBlk> h;              // host copy of the table, indexed by nn
+    // nv tables each, one behind the other, table v with xs / ys of vector v (the kernels that take one vector run on any of them)
     JmBlk* tab = nullptr;
     BlkView *tabX = nullptr, *tabY = nullptr;    // the level's block table with w -> xs / ys: the halo kernels on a foreign array
+    size_t slots() const { return h.size(); }
 };
 JmWork g_jm;
 }  // namespace
@@ -3808,8 +3811,9 @@ static int64_t jm_release()
     return n;
 }
 
-// scratch arrays and tables of the product on `level` (kept between calls; laid out again when blocks or matrix changed)
-static int jm_prepare(int level)
+// scratch arrays and tables of the product on `level` for nv vectors at once (kept between calls at the widest nv asked for; laid out
+// again when blocks or matrix changed)
+static int jm_prepare(int level, int nv = 1)
 {
     const int nS = g_jac.nState;
     std::vector<long> sig = {level, nS};
@@ -3828,22 +3832,28 @@ static int jm_prepare(int level)
             sig.push_back(kv.second->v.nbox);
             maxnn = std::max(maxnn, std::get<2>(kv.first));
         }
-    if (g_jm.tab && sig == g_jm.sig) return 0;
+    if (g_jm.tab && sig == g_jm.sig && nv <= g_jm.nv) return 0;
+    if (g_jm.tab && sig == g_jm.sig) nv = std::max(nv, g_jm.nv);
     HIPCHK(hipStreamSynchronize(g_stream));
     (void)jm_release();
-    g_jm.level = level; g_jm.nState = nS; g_jm.nslots = maxnn;
+    g_jm.level = level; g_jm.nState = nS; g_jm.nslots = maxnn; g_jm.nv = nv;
     g_jm.h.assign(maxnn + 1, JmBlk());
     memset(g_jm.h.data(), 0, sizeof(JmBlk) * g_jm.h.size());
-    std::vector<BlkView> hx(maxnn + 1), hy(maxnn + 1);
+    const size_t nt = (size_t)maxnn + 1;
+    std::vector<BlkView> hx(nt * nv), hy(nt * nv);
     memset(hx.data(), 0, sizeof(BlkView) * hx.size());
     memset(hy.data(), 0, sizeof(BlkView) * hy.size());
     for (auto& kv : g_blocks) {
         if (std::get<0>(kv.first) != level) continue;
         Block* b = kv.second;
         const BlkView& v = b->v;
-        const size_t bytes = (size_t)v.nbox * 2 * nS * sizeof(double) + 256;
+        const size_t bytes = (size_t)v.nbox * 2 * nS * nv * sizeof(double) + 256;
         void* raw = nullptr;
-        HIPCHK(hipMalloc(&raw, bytes));
+        if (hipMalloc(&raw, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)jm_release();
+            return fail("jacobian_mult: cannot allocate %zu bytes of scratch for %d vectors on a block of %ld box cells", bytes, nv, v.nbox);
+        }
         g_jm.raw.push_back(raw);
         g_jm.bytes += bytes;
         HIPCHK(hipMemsetAsync(raw, 0, bytes, g_stream));
@@ -3852,18 +3862,32 @@ static int jm_prepare(int level)
         q.ldi = v.ldi; q.ldk = v.ldk; q.nbox = v.nbox;
         q.jac = b->jac;
         q.xs = (double*)raw + ADF_PAD0;
-        q.ys = q.xs + (size_t)v.nbox * nS;
-        hx[std::get<2>(kv.first)] = v; hx[std::get<2>(kv.first)].w = q.xs;
-        hy[std::get<2>(kv.first)] = v; hy[std::get<2>(kv.first)].w = q.ys;
+        q.ys = q.xs + (size_t)v.nbox * nS * nv;
+        for (int c = 0; c < nv; ++c) {
+            BlkView &x = hx[c * nt + std::get<2>(kv.first)], &y = hy[c * nt + std::get<2>(kv.first)];
+            x = v; x.w = q.xs + (size_t)v.nbox * nS * c;
+            y = v; y.w = q.ys + (size_t)v.nbox * nS * c;
+        }
         g_jm.nx = std::max(g_jm.nx, v.nx); g_jm.ny = std::max(g_jm.ny, v.ny); g_jm.nz = std::max(g_jm.nz, v.nz);
     }
     long off = 0;                     // PETSc vector order: block nn ascending (NKSolvers.F90:1240-1253), nState entries per cell
     for (auto& q : g_jm.h) { q.vecOff = off; off += (long)q.nx * q.ny * q.nz * nS; }
     g_jm.ndof = off;
-    HIPCHK(hipMalloc((void**)&g_jm.tab, sizeof(JmBlk) * g_jm.h.size()));
-    HIPCHK(hipMalloc((void**)&g_jm.tabX, sizeof(BlkView) * hx.size()));
-    HIPCHK(hipMalloc((void**)&g_jm.tabY, sizeof(BlkView) * hy.size()));
-    HIPCHK(hipMemcpy(g_jm.tab, g_jm.h.data(), sizeof(JmBlk) * g_jm.h.size(), hipMemcpyHostToDevice));
+    std::vector<JmBlk> ht(nt * nv);
+    for (int c = 0; c < nv; ++c)
+        for (size_t q = 0; q < nt; ++q) {
+            JmBlk& t = ht[c * nt + q];
+            t = g_jm.h[q];
+            if (t.xs) { t.xs += (size_t)t.nbox * nS * c; t.ys += (size_t)t.nbox * nS * c; }
+        }
+    if (hipMalloc((void**)&g_jm.tab, sizeof(JmBlk) * ht.size()) != hipSuccess ||
+        hipMalloc((void**)&g_jm.tabX, sizeof(BlkView) * hx.size()) != hipSuccess ||
+        hipMalloc((void**)&g_jm.tabY, sizeof(BlkView) * hy.size()) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)jm_release();           // the scratch arrays as well: a later call lays everything out again
+        return fail("jacobian_mult: cannot allocate the block tables of %d vectors (%zu blocks); no scratch is held", nv, nt);
+    }
+    HIPCHK(hipMemcpy(g_jm.tab, ht.data(), sizeof(JmBlk) * ht.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(g_jm.tabX, hx.data(), sizeof(BlkView) * hx.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(g_jm.tabY, hy.data(), sizeof(BlkView) * hy.size(), hipMemcpyHostToDevice));
     g_jm.sig = sig;
@@ -3948,13 +3972,17 @@ static int jm_pattern(int level, CommPattern** out)
     return 0;
 }
 
-static int jm_mult_enqueue(int level, int transpose, const double* d_x, double* d_y)
+// y = J x (J^T x) for nv = 1 .. JM_MAXW vectors in one pass over the matrix: column v of x and y starts v ldx / v ldy doubles behind
+// column 0.  The vectors travel through the scratch arrays, the exchange and the reverse accumulation one at a time with the kernels
+// of one vector (the halo is small); the product kernels read every block once for all of them
+static int jm_mult_enqueue(int level, int transpose, const double* d_x, double* d_y, int nv = 1, long ldx = 0, long ldy = 0)
 {
-    if (jm_prepare(level)) return 1;
+    if (jm_prepare(level, nv)) return 1;
     CommPattern* cp;
     if (jm_pattern(level, &cp)) return 1;
     const int nS = g_jm.nState;
     const unsigned mask = (1u << nS) - 1u;
+    const size_t nt = g_jm.slots();
     JmStencil S;
     S.n = g_jac.nStencil;
     for (int s = 0; s < S.n; ++s)
@@ -3965,27 +3993,29 @@ static int jm_mult_enqueue(int level, int transpose, const double* d_x, double* 
     if (g_jm.zeroGen != g_state_gen) {
         // patterns may have changed: a halo that lost its donor must read as zero again
         for (auto& q : g_jm.h)
-            if (q.xs) HIPCHK(hipMemsetAsync(q.xs - ADF_PAD0, 0, ((size_t)q.nbox * nS + ADF_PAD0) * sizeof(double), g_stream));
+            if (q.xs) HIPCHK(hipMemsetAsync(q.xs - ADF_PAD0, 0, ((size_t)q.nbox * nS * g_jm.nv + ADF_PAD0) * sizeof(double), g_stream));
         g_jm.zeroGen = g_state_gen;
     }
-    launch_jm_scatter(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, d_x, g_stream);
+    for (int v = 0; v < nv; ++v)
+        launch_jm_scatter(g_jm.tab + v * nt, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, d_x + v * ldx, g_stream);
     if (!transpose) {
-        if (cp) {
+        for (int v = 0; cp && v < nv; ++v) {
             bool remote = false;
-            if (comm_exchange_begin(cp, g_jm.tabX, mask, nS, &remote)) return 1;
+            if (comm_exchange_begin(cp, g_jm.tabX + v * nt, mask, nS, &remote)) return 1;
 #ifndef ADFLOW_NO_RCCL
             if (remote && g_overlap) HIPCHK(hipStreamWaitEvent(g_stream, g_evComm, 0));
 #endif
-            for (auto& l : cp->recvs) launch_halo_unpack(g_jm.tabX, l.blkA, l.offA, l.n, mask, l.buf, g_stream);
+            for (auto& l : cp->recvs) launch_halo_unpack(g_jm.tabX + v * nt, l.blkA, l.offA, l.n, mask, l.buf, g_stream);
         }
-        launch_jac_mult(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, S, d_y, g_stream);
+        launch_jac_mult(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, S, d_y, g_stream, nv, ldy);
         return 0;
     }
-    launch_jac_mult_t(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, S, g_stream);
-    if (cp) {
-        if (jm_acc_lists(cp)) return 1;
+    launch_jac_mult_t(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, S, g_stream, nv);
+    if (cp && jm_acc_lists(cp)) return 1;
+    for (int v = 0; cp && v < nv; ++v) {
+        const JmBlk* tab = g_jm.tab + v * nt;
         // the messages of the forward exchange the other way: the halos of the receive lists go back to the ranks they came from
-        for (auto& l : cp->recvs) launch_halo_pack(g_jm.tabY, l.blkA, l.offA, l.n, mask, l.buf, g_stream);
+        for (auto& l : cp->recvs) launch_halo_pack(g_jm.tabY + v * nt, l.blkA, l.offA, l.n, mask, l.buf, g_stream);
         const bool remote = !cp->sends.empty() || !cp->recvs.empty();
         if (remote) {
 #ifndef ADFLOW_NO_RCCL
@@ -4008,33 +4038,34 @@ static int jm_mult_enqueue(int level, int transpose, const double* d_x, double* 
         }
         // same-process pairs while the messages are in flight, then the messages in the order of the send lists: every donor is
         // updated by one lane per list, the lists one after the other
-        launch_jac_halo_accumulate(g_jm.tab, cp->acc[0], nS, nullptr, 0, g_stream);
+        launch_jac_halo_accumulate(tab, cp->acc[0], nS, nullptr, 0, g_stream);
 #ifndef ADFLOW_NO_RCCL
         if (remote && g_overlap) HIPCHK(hipStreamWaitEvent(g_stream, g_evComm, 0));
 #endif
         for (size_t i = 0; i < cp->sends.size(); ++i)
-            launch_jac_halo_accumulate(g_jm.tab, cp->acc[1 + i], nS, cp->sends[i].buf, cp->sends[i].n, g_stream);
+            launch_jac_halo_accumulate(tab, cp->acc[1 + i], nS, cp->sends[i].buf, cp->sends[i].n, g_stream);
     }
-    launch_jm_gather(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, d_y, g_stream);
+    for (int v = 0; v < nv; ++v)
+        launch_jm_gather(g_jm.tab + v * nt, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, d_y + v * ldy, g_stream);
     return 0;
 }
 
-static int jm_check(int level, const double* x, const double* y, long n)
+static int jm_check(int level, const double* x, const double* y, long n, const char* who = "jacobian_mult")
 {
     if (need_ready()) return 1;
-    if (!g_jac_valid) return fail("jacobian_mult: no assembled Jacobian (call adflow_gpu_fd_jacobian first)");
-    if (level != g_jac_level) return fail("jacobian_mult: level %d is not the level of the assembly (%d)", level, g_jac_level);
-    if (!x || !y) return fail("jacobian_mult: %s is NULL", !x ? "x" : "y");
-    if (x == y) return fail("jacobian_mult: x and y are the same vector (the product is not done in place)");
+    if (!g_jac_valid) return fail("%s: no assembled Jacobian (call adflow_gpu_fd_jacobian first)", who);
+    if (level != g_jac_level) return fail("%s: level %d is not the level of the assembly (%d)", who, level, g_jac_level);
+    if (!x || !y) return fail("%s: %s is NULL", who, !x ? "x" : "y");
+    if (x == y) return fail("%s: x and y are the same vector (the product is not done in place)", who);
     long cells = 0;
     int rc = for_level(level, [&](Block* b) {
-        if (!b->jac) return fail("jacobian_mult: a block of level %d has no assembled blocks (registered after the assembly?)", level);
+        if (!b->jac) return fail("%s: a block of level %d has no assembled blocks (registered after the assembly?)", who, level);
         cells += (long)b->v.nx * b->v.ny * b->v.nz;
         return 0;
     });
     if (rc) return rc;
     if (n != cells * g_jac.nState)
-        return fail("jacobian_mult: n=%ld but the matrix of level %d has %ld rows (nState = %d x %ld owned cells)", n, level,
+        return fail("%s: n=%ld but the matrix of level %d has %ld rows (nState = %d x %ld owned cells)", who, n, level,
                     cells * g_jac.nState, g_jac.nState, cells);
     return 0;
 }
@@ -4053,6 +4084,64 @@ int adflow_gpu_jacobian_mult(int level, int transpose, const double* x, double* 
            s.out(y, 1) || s.done();
 }
 
+// ---- several vectors at once: the product, the ILU application and GMRES on nvec columns that lie ld doubles apart ---------------
+// What every multi entry checks of its two sets of columns: nvec, the leading dimensions and that no column of the one set shares
+// memory with a column of the other (column a of `in` with column b of `out` included).  `who` is the entry
+static_assert(GM_MAXV == ADFLOW_GPU_MAX_NVEC, "GmCoef of kernels_pc.hip holds a coefficient for every column of a call");
+static int multi_check(const char* who, int nvec, const double* in, long ldin, const double* out, long ldout, long n)
+{
+    if (nvec < 1 || nvec > ADFLOW_GPU_MAX_NVEC)
+        return fail("%s: nvec = %d; one call takes 1 to %d columns", who, nvec, ADFLOW_GPU_MAX_NVEC);
+    if (n < 0 || ldin < n || ldout < n)
+        return fail("%s: leading dimensions %ld and %ld, but a column holds n = %ld entries (ld >= n)", who, ldin, ldout, n);
+    if (!in || !out) return 0;        // the entry's own check names the NULL
+    const uintptr_t pi = (uintptr_t)in, po = (uintptr_t)out, len = (uintptr_t)n * sizeof(double);
+    for (int a = 0; a < nvec; ++a)
+        for (int b = 0; b < nvec; ++b) {
+            const uintptr_t ia = pi + (uintptr_t)a * ldin * sizeof(double), ob = po + (uintptr_t)b * ldout * sizeof(double);
+            if (ia < ob + len && ob < ia + len)
+                return fail("%s: column %d of the input and column %d of the result overlap (not done in place)", who, a, b);
+        }
+    return 0;
+}
+
+// A host form with columns: set q of nvec columns side by side (ld = n) in the staging area, column c at s[q nvec + c]
+static int stage_in_columns(const Stage& s, int q0, const double* h, long ld, int nvec)
+{
+    for (int c = 0; c < nvec; ++c)
+        if (s.in(q0 + c, h + c * ld)) return 1;
+    return 0;
+}
+static int stage_out_columns(const Stage& s, double* h, long ld, int q0, int nvec)
+{
+    for (int c = 0; c < nvec; ++c)
+        if (s.out(h + c * ld, q0 + c)) return 1;
+    return 0;
+}
+
+// the columns in groups of at most JM_MAXW, each group one pass over the matrix; one column is the product it always was
+static int jm_mult_multi_enqueue(int level, int transpose, int nvec, const double* d_x, long ldx, double* d_y, long ldy)
+{
+    for (int c = 0; c < nvec; c += JM_MAXW)
+        if (jm_mult_enqueue(level, transpose, d_x + c * ldx, d_y + c * ldy, std::min<int>(JM_MAXW, nvec - c), ldx, ldy)) return 1;
+    return 0;
+}
+
+int adflow_gpu_jacobian_mult_multi_dev(int level, int transpose, int nvec, const double* d_X, long ldx, double* d_Y, long ldy, long n)
+{
+    if (multi_check("jacobian_mult_multi", nvec, d_X, ldx, d_Y, ldy, n) || jm_check(level, d_X, d_Y, n, "jacobian_mult_multi")) return 1;
+    if (jm_mult_multi_enqueue(level, transpose, nvec, d_X, ldx, d_Y, ldy)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_jacobian_mult_multi(int level, int transpose, int nvec, const double* X, long ldx, double* Y, long ldy, long n)
+{
+    Stage s;
+    return multi_check("jacobian_mult_multi", nvec, X, ldx, Y, ldy, n) || jm_check(level, X, Y, n, "jacobian_mult_multi") ||
+           stage_open(&s, n, 2 * nvec) || stage_in_columns(s, 0, X, ldx, nvec) ||
+           jm_mult_multi_enqueue(level, transpose, nvec, s[0], n, s[nvec], n) || stage_out_columns(s, Y, ldy, nvec, nvec) || s.done();
+}
+
 // ---- block ILU(0) of the 7-point preconditioner matrix and right-preconditioned GMRES (kernels_pc.hip) --------------------------
 // The PCApply and the KSPSolve of setupStandardKSP (adjointUtils.F90:1374-1562) in the configuration PCBJACOBI / ILU(0) / natural
 // ordering, one subdomain per block; see the header for what is out of scope.
@@ -4062,6 +4151,7 @@ struct PcFactor {
     int level = 0, nState = 0, nPlanes = 0;      // nPlanes: hyperplanes at fill 0, dependency level sets at fill 1 and 2
     int fill = 0, nEnt = 7;                        // levels of fill the factor was built with and its entries per row
     long ncell = 0;
+    int wsWidth = 1;                  // vectors the work space serves at once: tab.ws, and tab.wsx for the others (pc_ws_reserve)
     size_t bytes = 0;
     std::vector<void*> raw;
     std::vector<int> planeStart;      // first position of every hyperplane in the order of the factor, and the end
@@ -4418,12 +4508,51 @@ int adflow_gpu_pc_release(int64_t* bytes)
     return 0;
 }
 
-// z = M^-1 r or M^-T r with the selected factor, whatever its fill
-static int pc_apply_enqueue(int transpose, const double* r, double* z, hipStream_t s)
+// z = M^-1 r or M^-T r with the selected factor, whatever its fill, for nv = 1 .. PC_MAXW columns ldr / ldz apart in the same launches
+static int pc_apply_enqueue(int transpose, const double* r, double* z, hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0)
 {
     const PcFactor& f = pc_sel();
-    if (f.fill > 0) return launch_pcf_apply(f.tab, f.nState, f.nEnt, transpose, f.planeStart, r, z, s);
-    return launch_pc_apply(f.tab, f.nState, transpose, f.planeStart, r, z, s);
+    if (f.fill > 0) return launch_pcf_apply(f.tab, f.nState, f.nEnt, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
+    return launch_pc_apply(f.tab, f.nState, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
+}
+
+// The work space of the selected factor for nv vectors at once: the part beyond the first vector is allocated at the first
+// multi-vector application, kept at the widest group asked for, counted by adflow_gpu_pc_info and released with the factor
+static int pc_ws_reserve(const char* who, int nv)
+{
+    PcFactor& f = pc_sel();
+    if (nv <= f.wsWidth) return 0;
+    HIPCHK(hipStreamSynchronize(g_stream));            // sweeps in the queue may still use the part that is replaced
+    const size_t per = (size_t)f.ncell * f.nState * sizeof(double);
+    if (f.tab.wsx) {
+        (void)hipFree(f.tab.wsx);
+        f.raw.erase(std::find(f.raw.begin(), f.raw.end(), (void*)f.tab.wsx));
+        f.bytes -= per * (f.wsWidth - 1);
+        f.tab.wsx = nullptr;
+        f.wsWidth = 1;
+    }
+    void* p = nullptr;
+    if (hipMalloc(&p, per * (nv - 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("%s: cannot allocate %zu bytes of work space for %d vectors at once; the factor stands as it was", who, per * (nv - 1), nv);
+    }
+    f.raw.push_back(p);
+    f.bytes += per * (nv - 1);
+    f.tab.wsx = (double*)p;
+    f.wsWidth = nv;
+    return 0;
+}
+
+// the columns in groups of at most PC_MAXW, each group one chain of launches; one column is the application it always was
+static int pc_apply_multi_enqueue(const char* who, int transpose, int nvec, const double* r, long ldr, double* z, long ldz, hipStream_t s)
+{
+    // fill 2: one column per chain of launches, the kernels of the single entry -- its sweeps of several vectors are not shipped
+    // (kernels_pc_fill.hip), so there the multi entry costs what the single calls cost
+    const int width = pc_sel().fill == 2 ? 1 : (int)PC_MAXW;
+    if (pc_ws_reserve(who, std::min(width, nvec))) return 1;
+    for (int c = 0; c < nvec; c += width)
+        if (pc_apply_enqueue(transpose, r + c * ldr, z + c * ldz, s, std::min(width, nvec - c), ldr, ldz)) return 1;
+    return 0;
 }
 
 static int pc_check(const char* who, int level, const double* r, const double* z, long n, bool rows = true)
@@ -4453,10 +4582,66 @@ int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, lo
            s.out(z, 1) || s.done();
 }
 
+int adflow_gpu_pc_apply_multi_dev(int level, int transpose, int nvec, const double* d_R, long ldr, double* d_Z, long ldz, long n)
+{
+    if (multi_check("pc_apply_multi", nvec, d_R, ldr, d_Z, ldz, n) || pc_check("pc_apply_multi", level, d_R, d_Z, n)) return 1;
+    if (pc_apply_multi_enqueue("pc_apply_multi", transpose, nvec, d_R, ldr, d_Z, ldz, g_stream)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_pc_apply_multi(int level, int transpose, int nvec, const double* R, long ldr, double* Z, long ldz, long n)
+{
+    Stage s;
+    return multi_check("pc_apply_multi", nvec, R, ldr, Z, ldz, n) || pc_check("pc_apply_multi", level, R, Z, n) ||
+           stage_open(&s, n, 2 * nvec) || stage_in_columns(s, 0, R, ldr, nvec) ||
+           pc_apply_multi_enqueue("pc_apply_multi", transpose, nvec, s[0], n, s[nvec], n, g_stream) ||
+           stage_out_columns(s, Z, ldz, nvec, nvec) || s.done();
+}
+
 // GMRES(restart) on  A M^-1 u = b, x = M^-1 u  (transpose: A^T M^-T), A = adflow_gpu_jacobian_mult with the matrix on the device,
 // M = the factor.  Basis, dots and updates on the device (one launch per basis vector of a modified Gram-Schmidt step, one
 // download of the new Hessenberg column per step); Hessenberg matrix and Givens rotations on the host.
 // op(v, y) enqueues y = A v: jm_mult_enqueue on the assembled matrix, or the matrix-free operator of ANK (ank_mult_enqueue).
+// The least-squares problem of one right-hand side on the host: the Hessenberg matrix column by column through its Givens rotations
+struct GmLsq {
+    std::vector<std::vector<double>> R;
+    std::vector<double> cs, sn, g, y;
+    explicit GmLsq(int m) : R(m), cs(m), sn(m), g(m + 1), y(m) {}
+    void start(double beta)
+    {
+        g.assign(g.size(), 0.0);
+        g[0] = beta;
+    }
+    // column j: H[i stride], i = 0 .. j, and the norm hn of the new vector; returns the residual norm of the recurrence
+    double column(const double* H, long stride, int j, double hn)
+    {
+        std::vector<double>& c = R[j];
+        c.resize(j + 1);
+        for (int i = 0; i <= j; ++i) c[i] = H[i * stride];
+        for (int i = 0; i < j; ++i) {
+            const double a = c[i], b = c[i + 1];
+            c[i] = cs[i] * a + sn[i] * b;
+            c[i + 1] = -sn[i] * a + cs[i] * b;
+        }
+        const double d = hypot(c[j], hn);
+        cs[j] = d > 0.0 ? c[j] / d : 1.0;
+        sn[j] = d > 0.0 ? hn / d : 0.0;
+        c[j] = d;
+        g[j + 1] = -sn[j] * g[j];
+        g[j] = cs[j] * g[j];
+        return fabs(g[j + 1]);
+    }
+    // y: the coefficients of the first k basis vectors
+    void solve(int k)
+    {
+        for (int i = k - 1; i >= 0; --i) {
+            double t = g[i];
+            for (int q = i + 1; q < k; ++q) t -= R[q][i] * y[q];
+            y[i] = R[i][i] != 0.0 ? t / R[i][i] : 0.0;
+        }
+    }
+};
+
 typedef std::function<int(const double*, double*)> GmOperator;
 static int gm_solve(const char* who, const GmOperator& op, int transpose, const double* d_b, double* d_x, long n, int restart, int maxIts,
                     double rtol, double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
@@ -4495,8 +4680,7 @@ static int gm_solve(const char* who, const GmOperator& op, int transpose, const 
     if (!useGuess) HIPCHK(hipMemsetAsync(d_x, 0, sizeof(double) * n, s));
     int total = 0;
     bool first = true, zeroX = !useGuess;
-    std::vector<std::vector<double>> R(m);
-    std::vector<double> cs(m), sn(m), g(m + 1), y(m);
+    GmLsq q(m);
     for (;;) {
         if (residual(V, zeroX)) return 1;
         if (norm(V, &beta)) return 1;
@@ -4505,8 +4689,7 @@ static int gm_solve(const char* who, const GmOperator& op, int transpose, const 
         res = beta;
         if (beta <= tol || total >= maxIts) break;
         launch_gm_axpby(V, 1.0 / beta, V, 0.0, n, s);
-        g.assign(m + 1, 0.0);
-        g[0] = beta;
+        q.start(beta);
         int k = 0;
         bool stop = false;
         for (int j = 0; j < m && !stop; ++j) {
@@ -4522,31 +4705,14 @@ static int gm_solve(const char* who, const GmOperator& op, int transpose, const 
             HIPCHK(hipStreamSynchronize(s));
             const double hn = sqrt(std::max(H[j + 1], 0.0));
             if (!(H[j + 1] == H[j + 1])) return fail("%s: the Krylov vector of iteration %d is not finite", who, total + 1);
-            std::vector<double>& c = R[j];
-            c.assign(H.begin(), H.begin() + j + 1);
-            for (int i = 0; i < j; ++i) {
-                const double a = c[i], b = c[i + 1];
-                c[i] = cs[i] * a + sn[i] * b;
-                c[i + 1] = -sn[i] * a + cs[i] * b;
-            }
-            const double d = hypot(c[j], hn);
-            cs[j] = d > 0.0 ? c[j] / d : 1.0;
-            sn[j] = d > 0.0 ? hn / d : 0.0;
-            c[j] = d;
-            g[j + 1] = -sn[j] * g[j];
-            g[j] = cs[j] * g[j];
-            res = fabs(g[j + 1]);
+            res = q.column(H.data(), 1, j, hn);
             ++total;
             k = j + 1;
             if (hn > 0.0) launch_gm_axpby(w, 1.0 / hn, w, 0.0, n, s);
             stop = res <= tol || total >= maxIts || !(hn > 0.0);
         }
-        for (int i = k - 1; i >= 0; --i) {
-            double t = g[i];
-            for (int q = i + 1; q < k; ++q) t -= R[q][i] * y[q];
-            y[i] = R[i][i] != 0.0 ? t / R[i][i] : 0.0;
-        }
-        for (int i = 0; i < k; ++i) launch_gm_axpby(tv, y[i], V + (size_t)i * n, i == 0 ? 0.0 : 1.0, n, s);
+        q.solve(k);
+        for (int i = 0; i < k; ++i) launch_gm_axpby(tv, q.y[i], V + (size_t)i * n, i == 0 ? 0.0 : 1.0, n, s);
         if (k > 0) {
             if (pc_apply_enqueue(transpose, tv, zt, s)) return 1;
             launch_gm_axpby(d_x, 1.0, zt, 1.0, n, s);
@@ -4618,6 +4784,189 @@ int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x,
     const GmOperator op = [=](const double* v, double* y) { return jm_mult_enqueue(level, transpose, v, y); };
     return gm_solve("gmres_solve", op, transpose, s[0], s[1], n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm) ||
            s.out(x, 1) || s.done();
+}
+
+// nvec right-hand sides on the assembled matrix with the selected factor, in lock-step: every iteration is ONE application of M^-1
+// and ONE product for all columns, every launch of the Gram-Schmidt chain carries all columns (each with its own partial sums, added
+// in the order of gm_solve), and one download and one synchronise bring the Hessenberg columns of all of them.  The host keeps a GmLsq,
+// a tolerance and a count per column, and a column ends exactly where gm_solve would end it; from then on its basis vectors are zeros
+// (M^-1 0 = 0, J 0 = 0: nothing that is not finite), its x is not touched (GmCoef: a = 0, b = 1), and the residual evaluation at the
+// next restart boundary -- which the columns that go on need anyway -- gives its true residual norm.
+// Work space: (restart + 3) nvec vectors; basis vector j of column c at V + (j nvec + c) n.
+static int gm_solve_multi(const char* who, int level, int transpose, int nvec, const double* d_B, long ldb, double* d_X, long ldx, long n,
+                          int restart, int maxIts, double rtol, double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
+{
+    const int m = std::max(1, std::min(restart, std::max(maxIts, 1)));
+    DevBuf buf;
+    const size_t nv = (size_t)(m + 3) * nvec * n, nred = (size_t)nvec * (2 * GM_PARTS + m + 2);
+    if (hipMalloc(&buf.p, (nv + nred) * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        buf.p = nullptr;
+        return fail("%s: cannot allocate %zu bytes for the (restart + 3) x nvec = %d x %d vectors of %ld entries; nothing is held", who,
+                    (nv + nred) * sizeof(double), m + 3, nvec, n);
+    }
+    const size_t cn = (size_t)nvec * n;                  // one vector of every column
+    double* V = (double*)buf.p;
+    double *zt = V + (size_t)(m + 1) * cn, *tv = zt + cn, *red = tv + cn, *P[2] = {red, red + (size_t)nvec * GM_PARTS},
+           *dH = red + (size_t)2 * nvec * GM_PARTS;     // dH[i nvec + c]: entry i of the Hessenberg column of column c
+    std::vector<double> H((size_t)(m + 2) * nvec);
+    hipStream_t s = g_stream;
+    auto norms = [&](const double* a, long lda, double* out) -> int {      // out[c] = ||a_c||
+        launch_gm_mgs_multi(const_cast<double*>(a), nullptr, nullptr, nullptr, P[0], nullptr, n, lda, nvec, s);
+        launch_gm_sum_multi(P[0], n, dH, nvec, s);
+        HIPCHK(hipMemcpyAsync(H.data(), dH, sizeof(double) * nvec, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int c = 0; c < nvec; ++c) out[c] = (H[c] == H[c]) ? sqrt(std::max(H[c], 0.0)) : H[c];      // NaN stays NaN
+        return 0;
+    };
+    auto pc = [&](const double* r, double* z) { return pc_apply_multi_enqueue(who, transpose, nvec, r, n, z, n, s); };
+    GmCoef all;
+    for (int c = 0; c < GM_MAXV; ++c) { all.a[c] = 1.0; all.b[c] = -1.0; }
+    enum { RUNNING, STOPPED, DONE };  // STOPPED: ended inside the cycle, its true residual comes with the next residual evaluation
+    struct Col { GmLsq q; int state = RUNNING, total = 0, k = 0; double tol = 0.0, res = 0.0; explicit Col(int m) : q(m) {} };
+    std::vector<Col> col(nvec, Col(m));
+    std::vector<double> nrm(nvec);
+    if (norms(d_B, ldb, nrm.data())) return 1;
+    for (int c = 0; c < nvec; ++c) {
+        if (!(nrm[c] == nrm[c])) return fail("%s: the right-hand side of column %d is not finite", who, c);
+        col[c].tol = std::max(rtol * nrm[c], atol);
+    }
+    if (!useGuess)
+        for (int c = 0; c < nvec; ++c) HIPCHK(hipMemsetAsync(d_X + c * ldx, 0, sizeof(double) * n, s));
+    bool first = true, zeroX = !useGuess;
+    for (;;) {
+        // r = b - A x of every column: the start of a cycle for the columns that run, the true residual for those that stopped
+        if (zeroX) {
+            for (int c = 0; c < nvec; ++c) HIPCHK(hipMemcpyAsync(V + (size_t)c * n, d_B + c * ldb, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+        } else {
+            if (jm_mult_multi_enqueue(level, transpose, nvec, d_X, ldx, V, n)) return 1;
+            launch_gm_axpby_multi(V, n, d_B, ldb, all, n, nvec, s);
+        }
+        if (norms(V, n, nrm.data())) return 1;
+        GmCoef k;
+        int running = 0;
+        for (int c = 0; c < nvec; ++c) {
+            Col& q = col[c];
+            if (first && rnorm0) rnorm0[c] = nrm[c];
+            k.a[c] = 0.0; k.b[c] = 1.0;
+            if (q.state == DONE) continue;
+            q.res = nrm[c];
+            if (q.state == STOPPED) { q.state = DONE; continue; }
+            if (!(nrm[c] == nrm[c])) return fail("%s: the residual of column %d is not finite after %d iterations", who, c, q.total);
+            if (nrm[c] <= q.tol || q.total >= maxIts) { q.state = DONE; continue; }
+            k.a[c] = 1.0 / nrm[c]; k.b[c] = 0.0;
+            q.q.start(nrm[c]);
+            q.k = 0;
+            ++running;
+        }
+        first = false;
+        if (!running) break;
+        for (int c = 0; c < nvec; ++c)
+            if (col[c].state == DONE) HIPCHK(hipMemsetAsync(V + (size_t)c * n, 0, sizeof(double) * n, s));
+        launch_gm_axpby_multi(V, n, V, n, k, n, nvec, s);
+        std::vector<char> inCycle(nvec);
+        for (int c = 0; c < nvec; ++c) inCycle[c] = col[c].state == RUNNING;
+        int kmax = 0;
+        for (int j = 0; j < m && running; ++j) {
+            double* w = V + (size_t)(j + 1) * cn;
+            if (pc(V + (size_t)j * cn, zt)) return 1;
+            if (jm_mult_multi_enqueue(level, transpose, nvec, zt, n, w, n)) return 1;
+            launch_gm_mgs_multi(w, nullptr, nullptr, V, P[0], nullptr, n, n, nvec, s);
+            for (int i = 1; i <= j; ++i)
+                launch_gm_mgs_multi(w, V + (size_t)(i - 1) * cn, P[(i - 1) & 1], V + (size_t)i * cn, P[i & 1], dH + (size_t)(i - 1) * nvec, n, n,
+                                    nvec, s);
+            launch_gm_mgs_multi(w, V + (size_t)j * cn, P[j & 1], nullptr, P[(j + 1) & 1], dH + (size_t)j * nvec, n, n, nvec, s);
+            launch_gm_sum_multi(P[(j + 1) & 1], n, dH + (size_t)(j + 1) * nvec, nvec, s);
+            HIPCHK(hipMemcpyAsync(H.data(), dH, sizeof(double) * (j + 2) * nvec, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            kmax = j + 1;
+            for (int c = 0; c < nvec; ++c) {
+                Col& q = col[c];
+                k.a[c] = 0.0; k.b[c] = 1.0;
+                if (q.state != RUNNING) continue;
+                const double h2 = H[(size_t)(j + 1) * nvec + c], hn = sqrt(std::max(h2, 0.0));
+                if (!(h2 == h2)) return fail("%s: the Krylov vector of iteration %d of column %d is not finite", who, q.total + 1, c);
+                q.res = q.q.column(H.data() + c, nvec, j, hn);
+                ++q.total;
+                q.k = j + 1;
+                if (q.res <= q.tol || q.total >= maxIts || !(hn > 0.0)) {
+                    q.state = STOPPED;
+                    --running;
+                    HIPCHK(hipMemsetAsync(w + (size_t)c * n, 0, sizeof(double) * n, s));
+                } else {
+                    k.a[c] = 1.0 / hn; k.b[c] = 0.0;
+                }
+            }
+            if (running) launch_gm_axpby_multi(w, n, w, n, k, n, nvec, s);
+        }
+        // x += M^-1 (V y) for the columns of this cycle, each with the coefficients of its own k basis vectors
+        for (int c = 0; c < nvec; ++c)
+            if (inCycle[c]) col[c].q.solve(col[c].k);
+        for (int i = 0; i < kmax; ++i) {
+            for (int c = 0; c < nvec; ++c) {
+                const bool on = inCycle[c] && i < col[c].k;
+                k.a[c] = on ? col[c].q.y[i] : 0.0;
+                k.b[c] = (i == 0) ? 0.0 : 1.0;               // i == 0 sets every column of tv: zero where no cycle ran
+            }
+            launch_gm_axpby_multi(tv, n, V + (size_t)i * cn, n, k, n, nvec, s);
+        }
+        if (pc(tv, zt)) return 1;
+        for (int c = 0; c < nvec; ++c) { k.a[c] = inCycle[c] ? 1.0 : 0.0; k.b[c] = 1.0; }
+        launch_gm_axpby_multi(d_X, ldx, zt, n, k, n, nvec, s);
+        zeroX = false;
+    }
+    for (int c = 0; c < nvec; ++c) {
+        if (its) its[c] = col[c].total;
+        if (rnorm) rnorm[c] = col[c].res;
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int gm_check_multi(int level, int nvec, const double* B, long ldb, const double* X, long ldx, long n, int restart, int maxIts,
+                          double rtol, double atol)
+{
+    const char* who = "gmres_solve_multi";
+    if (gm_check_ranks(who, "adflow_gpu_jacobian_mult_multi_dev")) return 1;
+    if (multi_check(who, nvec, B, ldb, X, ldx, n)) return 1;
+    if (!g_jac_valid) return fail("%s: no assembled Jacobian (call adflow_gpu_fd_jacobian first)", who);
+    if (pc_check(who, level, B, X, n, false)) return 1;
+    if (g_jac.nState != pc_sel().nState)
+        return fail("%s: the factor was set up for nState = %d, the assembled matrix has nState = %d", who, pc_sel().nState, g_jac.nState);
+    if (jm_check(level, B, X, n, who)) return 1;
+    if (n != pc_sel().ncell * pc_sel().nState) return fail("%s: n=%ld but the factor has %ld rows", who, n, pc_sel().ncell * pc_sel().nState);
+    return gm_check_caps(who, restart, maxIts, rtol, atol);
+}
+
+int adflow_gpu_gmres_solve_multi_dev(int level, int transpose, int nvec, const double* d_B, long ldb, double* d_X, long ldx, long n,
+                                     int restart, int maxIts, double rtol, double atol, int useGuess, int* its, double* rnorm0,
+                                     double* rnorm)
+{
+    if (gm_check_multi(level, nvec, d_B, ldb, d_X, ldx, n, restart, maxIts, rtol, atol)) return 1;
+    if (nvec == 1) {                   // one column: the single solver, to the bit
+        const GmOperator op = [=](const double* v, double* y) { return jm_mult_enqueue(level, transpose, v, y); };
+        return gm_solve("gmres_solve_multi", op, transpose, d_B, d_X, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm);
+    }
+    return gm_solve_multi("gmres_solve_multi", level, transpose, nvec, d_B, ldb, d_X, ldx, n, restart, maxIts, rtol, atol, useGuess, its,
+                          rnorm0, rnorm);
+}
+
+int adflow_gpu_gmres_solve_multi(int level, int transpose, int nvec, const double* B, long ldb, double* X, long ldx, long n, int restart,
+                                 int maxIts, double rtol, double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
+{
+    if (gm_check_multi(level, nvec, B, ldb, X, ldx, n, restart, maxIts, rtol, atol)) return 1;
+    DevBuf buf;                        // B and X of this call side by side, not g_vec_dev
+    if (hipMalloc(&buf.p, sizeof(double) * 2 * nvec * n) != hipSuccess) {
+        (void)hipGetLastError();
+        buf.p = nullptr;
+        return fail("gmres_solve_multi: cannot allocate %zu bytes for %d right-hand sides and solutions of %ld entries",
+                    sizeof(double) * 2 * nvec * n, nvec, n);
+    }
+    const Stage s{n, (double*)buf.p};
+    if (stage_in_columns(s, 0, B, ldb, nvec) || (useGuess && stage_in_columns(s, nvec, X, ldx, nvec))) return 1;
+    return adflow_gpu_gmres_solve_multi_dev(level, transpose, nvec, s[0], n, s[nvec], n, n, restart, maxIts, rtol, atol, useGuess, its,
+                                            rnorm0, rnorm) ||
+           stage_out_columns(s, X, ldx, nvec, nvec) || s.done();
 }
 
 // ---- the approximate Newton-Krylov step (kernels_ank.hip) -------------------------------------------------------------------------

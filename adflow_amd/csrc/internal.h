@@ -388,8 +388,24 @@ struct JmAccList {
 };
 void launch_jm_scatter(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const double* x, hipStream_t s);
 void launch_jm_gather(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, double* y, hipStream_t s);
-void launch_jac_mult(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, double* y, hipStream_t s);
-void launch_jac_mult_t(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, hipStream_t s);
+// The vector count of the multi-vector kernels (1 .. 4) as the compile-time constant NV_ of the statement that follows; used by the
+// launchers of kernels_jacmult.hip, kernels_pc.hip and kernels_pc_fill.hip inside their dispatch on nState.  ONFAIL: what a launcher
+// does with a count it has no kernel for
+#define ADF_DISPATCH_NV(nv, ONFAIL, ...)                                               \
+    switch (nv) {                                                                      \
+    case 1: { constexpr int NV_ = 1; __VA_ARGS__; } break;                             \
+    case 2: { constexpr int NV_ = 2; __VA_ARGS__; } break;                             \
+    case 3: { constexpr int NV_ = 3; __VA_ARGS__; } break;                             \
+    case 4: { constexpr int NV_ = 4; __VA_ARGS__; } break;                             \
+    default: ONFAIL;                                                                   \
+    }
+// nv = 1 .. JM_MAXW vectors in one pass over the matrix: vector v of xs / ys lies nState components behind vector v - 1, column v of y
+// starts v ldy doubles behind column 0
+enum { JM_MAXW = 4 };
+void launch_jac_mult(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, double* y, hipStream_t s,
+                     int nv = 1, long ldy = 0);
+void launch_jac_mult_t(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, hipStream_t s,
+                       int nv = 1);
 void launch_jac_halo_accumulate(const JmBlk* tab, const JmAccList& a, int nState, const double* buf, int nbuf, hipStream_t s);
 
 // block ILU of the 7-point matrix (kernels_pc.hip, kernels_pc_fill.hip): the factor of a level as its kernels see it.  Position q of
@@ -420,21 +436,33 @@ struct PcTab {
     int asmEnt[23];       // stencil entry of the assembly that slot s starts from, -1: a fill entry (starts from zero)
     signed char tgt[121]; // tgt[e nLow + u]: slot of this row that L_{c,n} U_{n,m} lands in (n: lower entry e, m: upper entry u
                           // of row n), -1: outside the pattern
+    double* wsx;          // the work space of vectors 1 .. of a multi-vector application, laid out like ws; NULL until the first one
 };
 int launch_pc_factor(const PcTab& T, int nState, const std::vector<int>& planeStart, hipStream_t s);
+// nv = 1 .. PC_MAXW vectors through the same launches: column v of r and z starts v ldr / v ldz doubles behind column 0 and uses the
+// work space ws (v = 0) or wsx (v - 1); nv = 1 is the application of one vector
+enum { PC_MAXW = 4 };
 int launch_pc_apply(const PcTab& T, int nState, int transpose, const std::vector<int>& planeStart, const double* r, double* z,
-                    hipStream_t s);
+                    hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0);
 // block ILU(1) / ILU(2) of the same matrix (kernels_pc_fill.hip): nEnt = 13 or 23 entries per row, levelStart = first position of
 // every dependency level set in the order of the factor, and the end
 int launch_pcf_factor(const PcTab& T, int nState, int nEnt, const std::vector<int>& levelStart, hipStream_t s);
 int launch_pcf_apply(const PcTab& T, int nState, int nEnt, int transpose, const std::vector<int>& levelStart, const double* r,
-                     double* z, hipStream_t s);
+                     double* z, hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0);
 // the vectors of GMRES: one step of modified Gram-Schmidt per launch (partial sums in, partial sums out), see kernels_pc.hip
 enum { GM_PARTS = 256 };  // the most partial sums one reduction leaves (GM_T of kernels_pc.hip): the size of a buffer of them
 int gm_groups(long n);
 void launch_gm_mgs(double* w, const double* v, const double* hp, const double* u, double* out, double* hOut, long n, hipStream_t s);
 void launch_gm_sum(const double* hp, long n, double* hOut, hipStream_t s);
 void launch_gm_axpby(double* y, double a, const double* x, double b, long n, hipStream_t s);
+// the columns of a multi solve in lock-step (column c of a vector starts c ld doubles behind column 0; partial sums of column c at
+// c GM_PARTS; hOut[c]); GmCoef: the coefficients of every column of one update, a = 0 with b = 1 leaves the column untouched
+enum { GM_MAXV = 32 };    // the most columns of one call (ADFLOW_GPU_MAX_NVEC of the header)
+struct GmCoef { double a[GM_MAXV], b[GM_MAXV]; };
+void launch_gm_mgs_multi(double* w, const double* v, const double* hp, const double* u, double* out, double* hOut, long n, long ld,
+                         int nvec, hipStream_t s);
+void launch_gm_sum_multi(const double* hp, long n, double* hOut, int nvec, hipStream_t s);
+void launch_gm_axpby_multi(double* y, long ldy, const double* x, long ldx, const GmCoef& k, long n, int nvec, hipStream_t s);
 // approximate Newton-Krylov step (kernels_ank.hip): vectors of nS variables per owned cell; kp != NULL: with the closures of blocketteRes
 struct KParams;
 // The reduction buffer of the ANK entries (g_ank.red of api.hip), in doubles: partial results, one per workgroup of a reduction, then

@@ -18,6 +18,11 @@
 //               order -- the result does not depend on the execution order)
 // One stencil entry of a lane is nState^2 independent 8-byte loads (36 for RANS) issued together: 18 KB in flight per wave, several
 // waves per SIMD -- the streaming regime without any staging.
+//
+// Several vectors at once (adflow_gpu_jacobian_mult_multi): both product kernels take a vector count NV = 1 .. 4 -- the nState^2 loads
+// of a stencil entry are issued once and feed nState x NV accumulators, so NV products cost one pass over the matrix.  xs and ys hold
+// the vectors one behind the other (vector v: components v nState .. of the same box layout); scatter, exchange, reverse accumulation
+// and gather run per vector with the kernels of one vector (tables per vector), each donor still updated in its fixed order.
 #include "internal.h"
 
 #define JM_BX 64
@@ -62,9 +67,13 @@ __global__ __launch_bounds__(JM_BX* JM_BY) void k_jm_gather(const JmBlk* __restr
 // y(row) = sum_s B_s(row) x(row - d_s): one lane per owned row cell, nState accumulators.  The columns of an owned row lie inside
 // the halo'd box for every stencil of the assembly (offsets of at most two cells along an axis).
 // The blocks of one stencil entry are addressed from a uniform base with 32-bit byte offsets (ldg): nState^2 planes of one block
-// stay below 4 GiB (the launcher checks)
-template <int NS>
-__global__ __launch_bounds__(JM_BX* JM_BY) void k_jac_mult(const JmBlk* __restrict__ tab, int nzb, JmStencil S, double* __restrict__ y)
+// stay below 4 GiB (the launcher checks).
+// NV vectors at once (adflow_gpu_jacobian_mult_multi): every block is loaded once and applied to the NV vectors, nState x NV
+// accumulators per lane.  Vector v is the nState components of xs behind those of vector v - 1 and column v of y, ldy apart;
+// NV = 1 is the product of one vector as it always was.
+template <int NS, int NV = 1>
+__global__ __launch_bounds__(JM_BX* JM_BY) void k_jac_mult(const JmBlk* __restrict__ tab, int nzb, JmStencil S, double* __restrict__ y,
+                                                           long ldy)
 {
     const JmBlk b = tab[blockIdx.z / nzb + 1];
     const int i = blockIdx.x * JM_BX + threadIdx.x + 2;
@@ -73,32 +82,42 @@ __global__ __launch_bounds__(JM_BX* JM_BY) void k_jac_mult(const JmBlk* __restri
     if (i > b.il || j > b.jl || k > b.kl) return;
     const int c = i + j * b.ldi + k * b.ldk;
     const unsigned nb8 = (unsigned)b.nbox * 8u;
-    GPTR(const double) xs = (GPTR(const double))b.xs;
-    double acc[NS];
+    GPTR(const double) xs[NV];
 #pragma unroll
-    for (int ll = 0; ll < NS; ++ll) acc[ll] = 0.0;
+    for (int v = 0; v < NV; ++v) xs[v] = (GPTR(const double))(b.xs + (long)v * NS * b.nbox);
+    double acc[NV][NS];
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int ll = 0; ll < NS; ++ll) acc[v][ll] = 0.0;
     for (int s = 0; s < S.n; ++s) {
         GPTR(const double) B = (GPTR(const double))(b.jac + (long)s * (NS * NS) * b.nbox);
         const unsigned cx = (unsigned)(c - (S.d[s][0] + S.d[s][1] * b.ldi + S.d[s][2] * b.ldk)) * 8u;
-        double xv[NS], bv[NS * NS];
+        double xv[NV][NS], bv[NS * NS];
 #pragma unroll
-        for (int l = 0; l < NS; ++l) xv[l] = ldg(xs, cx + l * nb8);
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int l = 0; l < NS; ++l) xv[v][l] = ldg(xs[v], cx + l * nb8);
 #pragma unroll
         for (int e = 0; e < NS * NS; ++e) bv[e] = ldg(B, (unsigned)c * 8u + e * nb8);
 #pragma unroll
-        for (int l = 0; l < NS; ++l)
+        for (int v = 0; v < NV; ++v)
 #pragma unroll
-            for (int ll = 0; ll < NS; ++ll) acc[ll] += bv[l * NS + ll] * xv[l];
+            for (int l = 0; l < NS; ++l)
+#pragma unroll
+                for (int ll = 0; ll < NS; ++ll) acc[v][ll] += bv[l * NS + ll] * xv[v][l];
     }
     const long m = b.vecOff + (((long)(k - 2) * b.ny + (j - 2)) * b.nx + (i - 2)) * NS;
 #pragma unroll
-    for (int ll = 0; ll < NS; ++ll) y[m + ll] = acc[ll];
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int ll = 0; ll < NS; ++ll) y[v * ldy + m + ll] = acc[v][ll];
 }
 
 // ys(col) = sum_s B_s(col + d_s)^T x(col + d_s) over the OWNED rows col + d_s, for every cell of the halo'd box (owned cells and
 // both halo layers).  The rows of a wave share j and k: a stencil entry whose row plane lies outside the owned range is skipped by
-// the whole wave, the i range by the lane
-template <int NS>
+// the whole wave, the i range by the lane.  NV vectors as in k_jac_mult; vector v of ys lies behind vector v - 1
+template <int NS, int NV = 1>
 __global__ __launch_bounds__(JM_BX* JM_BY) void k_jac_mult_t(const JmBlk* __restrict__ tab, int nzb, JmStencil S)
 {
     const JmBlk b = tab[blockIdx.z / nzb + 1];
@@ -108,28 +127,38 @@ __global__ __launch_bounds__(JM_BX* JM_BY) void k_jac_mult_t(const JmBlk* __rest
     if (b.nx == 0 || i < 0 || i > b.ib || j > b.jb || k > b.kb) return;
     const int c = i + j * b.ldi + k * b.ldk;
     const unsigned nb8 = (unsigned)b.nbox * 8u;
-    GPTR(const double) xs = (GPTR(const double))b.xs;
-    double acc[NS];
+    GPTR(const double) xs[NV];
 #pragma unroll
-    for (int l = 0; l < NS; ++l) acc[l] = 0.0;
+    for (int v = 0; v < NV; ++v) xs[v] = (GPTR(const double))(b.xs + (long)v * NS * b.nbox);
+    double acc[NV][NS];
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int l = 0; l < NS; ++l) acc[v][l] = 0.0;
     for (int s = 0; s < S.n; ++s) {
         const int ri = i + S.d[s][0], rj = j + S.d[s][1], rk = k + S.d[s][2];
         if (rj < 2 || rj > b.jl || rk < 2 || rk > b.kl) continue;
         if (ri < 2 || ri > b.il) continue;
         GPTR(const double) B = (GPTR(const double))(b.jac + (long)s * (NS * NS) * b.nbox);
         const unsigned cr = (unsigned)(c + S.d[s][0] + S.d[s][1] * b.ldi + S.d[s][2] * b.ldk) * 8u;
-        double xv[NS], bv[NS * NS];
+        double xv[NV][NS], bv[NS * NS];
 #pragma unroll
-        for (int m = 0; m < NS; ++m) xv[m] = ldg(xs, cr + m * nb8);
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int m = 0; m < NS; ++m) xv[v][m] = ldg(xs[v], cr + m * nb8);
 #pragma unroll
         for (int e = 0; e < NS * NS; ++e) bv[e] = ldg(B, cr + e * nb8);
 #pragma unroll
-        for (int l = 0; l < NS; ++l)
+        for (int v = 0; v < NV; ++v)
 #pragma unroll
-            for (int m = 0; m < NS; ++m) acc[l] += bv[l * NS + m] * xv[m];
+            for (int l = 0; l < NS; ++l)
+#pragma unroll
+                for (int m = 0; m < NS; ++m) acc[v][l] += bv[l * NS + m] * xv[v][m];
     }
 #pragma unroll
-    for (int l = 0; l < NS; ++l) b.ys[c + l * b.nbox] = acc[l];
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int l = 0; l < NS; ++l) b.ys[c + (long)(v * NS + l) * b.nbox] = acc[v][l];
 }
 
 // the reverse exchange: target t (an owned cell, the donor of the forward exchange) += its sources in list order.  buf == NULL:
@@ -190,17 +219,30 @@ void launch_jm_gather(const JmBlk* tab, int nslots, int maxnx, int maxny, int ma
     if (nslots <= 0) return;
     JM_DISPATCH(k_jm_gather, jm_own_grid(nslots, maxnx, maxny, maxnz), tab, maxnz, y)
 }
-void launch_jac_mult(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, double* y, hipStream_t s)
+// the two product kernels for nState and the nv = 1 .. JM_MAXW vectors of one pass over the matrix
+#define JM_LAUNCH_NV(KERNEL, NS, GRID, ...)                                                                                     \
+    ADF_DISPATCH_NV(nv, (void)adf_fail("jacobian_mult: no kernel for this number of vectors"),                                  \
+                    hipLaunchKernelGGL((KERNEL<NS, NV_>), GRID, dim3(JM_BX, JM_BY, 1), 0, s, __VA_ARGS__))
+#define JM_DISPATCH_NV(KERNEL, GRID, ...)                                                                                       \
+    switch (nState) {                                                                                                           \
+    case 1: JM_LAUNCH_NV(KERNEL, 1, GRID, __VA_ARGS__) break;                                                                   \
+    case 5: JM_LAUNCH_NV(KERNEL, 5, GRID, __VA_ARGS__) break;                                                                   \
+    case 6: JM_LAUNCH_NV(KERNEL, 6, GRID, __VA_ARGS__) break;                                                                   \
+    default: (void)adf_fail("jacobian_mult: no kernel for this nState"); break;                                                 \
+    }
+
+void launch_jac_mult(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, double* y, hipStream_t s,
+                     int nv, long ldy)
 {
-    LEVEL_SPLIT(nslots, maxnz + 4, launch_jac_mult(tab + s0_, n_, maxnx, maxny, maxnz, nState, S, y, s));
+    LEVEL_SPLIT(nslots, maxnz + 4, launch_jac_mult(tab + s0_, n_, maxnx, maxny, maxnz, nState, S, y, s, nv, ldy));
     if (nslots <= 0) return;
-    JM_DISPATCH(k_jac_mult, jm_own_grid(nslots, maxnx, maxny, maxnz), tab, maxnz, S, y)
+    JM_DISPATCH_NV(k_jac_mult, jm_own_grid(nslots, maxnx, maxny, maxnz), tab, maxnz, S, y, ldy)
 }
-void launch_jac_mult_t(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, hipStream_t s)
+void launch_jac_mult_t(const JmBlk* tab, int nslots, int maxnx, int maxny, int maxnz, int nState, const JmStencil& S, hipStream_t s, int nv)
 {
-    LEVEL_SPLIT(nslots, maxnz + 4, launch_jac_mult_t(tab + s0_, n_, maxnx, maxny, maxnz, nState, S, s));
+    LEVEL_SPLIT(nslots, maxnz + 4, launch_jac_mult_t(tab + s0_, n_, maxnx, maxny, maxnz, nState, S, s, nv));
     if (nslots <= 0) return;
-    JM_DISPATCH(k_jac_mult_t, jm_box_grid(nslots, maxnx, maxny, maxnz), tab, maxnz + 4, S)
+    JM_DISPATCH_NV(k_jac_mult_t, jm_box_grid(nslots, maxnx, maxny, maxnz), tab, maxnz + 4, S)
 }
 
 void launch_jac_halo_accumulate(const JmBlk* tab, const JmAccList& a, int nState, const double* buf, int nbuf, hipStream_t s)

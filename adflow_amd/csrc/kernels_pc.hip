@@ -24,6 +24,11 @@
 // nbr[e N + q]: position of neighbour e (0..2 lower, 3..5 upper) or -1 outside the block; vec[q]: the cell's number in the PETSc
 // layout.  Only the neighbour values of the vector are gathered (ws, hyperplane order, component-major); the transposed sweeps
 // read the blocks at the neighbours' positions, which are monotone in q along a hyperplane.
+//
+// Several vectors at once (adflow_gpu_pc_apply_multi, adflow_gpu_gmres_solve_multi): k_pc_sweep takes a vector count NV = 1 .. 4 --
+// the same launches per hyperplane, neighbour positions and factor blocks loaded once, neighbour values, accumulators and the D^-1
+// product per vector (vector 0 in ws, the others in wsx, which the factor gets at its first multi-vector application).  The GMRES
+// kernels have _multi twins with the column in blockIdx.y: every column keeps its own partial sums, added in the single solver's order.
 #include "internal.h"
 
 #define PC_T 64           // one wave per workgroup: a hyperplane of a few thousand cells still spreads over the CUs
@@ -124,8 +129,12 @@ __global__ __launch_bounds__(PC_T) void k_pc_factor(PcTab T, int q0, int cnt)
 // neighbours, input ws, output also to z.
 //   TR = 0:  forward  y_c = r_c - sum L_{c,n} y_n            backward  z_c = D_c^-1 (y_c - sum U_{c,n} z_n)      (blocks of c)
 //   TR = 1:  forward  y_c = D_c^-T (r_c - sum U_{n,c}^T y_n)  backward  z_c = y_c - sum L_{n,c}^T z_n             (blocks of n)
-template <int NS, int TR, int BACK>
-__global__ __launch_bounds__(PC_T) void k_pc_sweep(PcTab T, int q0, int cnt, const double* __restrict__ r, double* __restrict__ z)
+// NV vectors at once (adflow_gpu_pc_apply_multi): neighbour position and factor block are loaded once, the neighbour values, the
+// accumulators and the D^-1 product are per vector; column v of r and z starts v ldr / v ldz doubles behind column 0.  NV = 1 is the
+// sweep of one vector as it always was.
+template <int NS, int TR, int BACK, int NV = 1>
+__global__ __launch_bounds__(PC_T) void k_pc_sweep(PcTab T, int q0, int cnt, const double* __restrict__ r, double* __restrict__ z, long ldr,
+                                                   long ldz)
 {
     const int t = blockIdx.x * PC_T + threadIdx.x;
     if (t >= cnt) return;
@@ -133,15 +142,21 @@ __global__ __launch_bounds__(PC_T) void k_pc_sweep(PcTab T, int q0, int cnt, con
     const long N = T.ncell;
     const unsigned N8 = (unsigned)N * 8u;
     GPTR(const double) F = (GPTR(const double))T.fac;
-    GPTR(double) W = (GPTR(double))T.ws;
+    GPTR(double) W[NV];          // vector 0 in the work space of the factor, the others in its extra part
+#pragma unroll
+    for (int v = 0; v < NV; ++v) W[v] = (GPTR(double))(v == 0 ? T.ws : T.wsx + (long)(v - 1) * NS * N);
     const long m = (long)T.vec[q] * NS;
-    double acc[NS];
+    double acc[NV][NS];
     if (BACK) {
 #pragma unroll
-        for (int l = 0; l < NS; ++l) acc[l] = ldg(W, q8 + l * N8);
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int l = 0; l < NS; ++l) acc[v][l] = ldg(W[v], q8 + l * N8);
     } else {
 #pragma unroll
-        for (int l = 0; l < NS; ++l) acc[l] = r[m + l];
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int l = 0; l < NS; ++l) acc[v][l] = r[v * ldr + m + l];
     }
     // the blocks of the sweep: TR = 0 the cell's own L (forward) / U (backward); TR = 1 the neighbour's U (forward) / L (backward)
     const int slot0 = (TR != BACK) ? 3 : 0;
@@ -151,49 +166,62 @@ __global__ __launch_bounds__(PC_T) void k_pc_sweep(PcTab T, int q0, int cnt, con
         if (n < 0) continue;
         const unsigned n8 = (unsigned)n * 8u, at = TR ? n8 : q8;
         GPTR(const double) Fs = F + (long)(slot0 + s) * (NS * NS) * N;
-        double xv[NS], bv[NS * NS];
+        double xv[NV][NS], bv[NS * NS];
 #pragma unroll
-        for (int l = 0; l < NS; ++l) xv[l] = ldg(W, n8 + l * N8);
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int l = 0; l < NS; ++l) xv[v][l] = ldg(W[v], n8 + l * N8);
 #pragma unroll
         for (int e = 0; e < NS * NS; ++e) bv[e] = ldg(Fs + e * N, at);
-        if (TR) {
 #pragma unroll
-            for (int l = 0; l < NS; ++l)
+        for (int v = 0; v < NV; ++v) {
+            if (TR) {
 #pragma unroll
-                for (int ll = 0; ll < NS; ++ll) acc[l] -= PCE(bv, ll, l) * xv[ll];
-        } else {
+                for (int l = 0; l < NS; ++l)
 #pragma unroll
-            for (int l = 0; l < NS; ++l)
+                    for (int ll = 0; ll < NS; ++ll) acc[v][l] -= PCE(bv, ll, l) * xv[v][ll];
+            } else {
 #pragma unroll
-                for (int ll = 0; ll < NS; ++ll) acc[ll] -= PCE(bv, ll, l) * xv[l];
+                for (int l = 0; l < NS; ++l)
+#pragma unroll
+                    for (int ll = 0; ll < NS; ++ll) acc[v][ll] -= PCE(bv, ll, l) * xv[v][l];
+            }
         }
     }
     if (TR != BACK) {
         GPTR(const double) Fd = F + (long)6 * (NS * NS) * N;
-        double bv[NS * NS], o[NS];
+        double bv[NS * NS];
 #pragma unroll
         for (int e = 0; e < NS * NS; ++e) bv[e] = ldg(Fd + e * N, q8);
 #pragma unroll
-        for (int l = 0; l < NS; ++l) o[l] = 0.0;
-        if (TR) {
+        for (int v = 0; v < NV; ++v) {
+            double o[NS];
 #pragma unroll
-            for (int l = 0; l < NS; ++l)
+            for (int l = 0; l < NS; ++l) o[l] = 0.0;
+            if (TR) {
 #pragma unroll
-                for (int ll = 0; ll < NS; ++ll) o[l] += PCE(bv, ll, l) * acc[ll];
-        } else {
+                for (int l = 0; l < NS; ++l)
 #pragma unroll
-            for (int l = 0; l < NS; ++l)
+                    for (int ll = 0; ll < NS; ++ll) o[l] += PCE(bv, ll, l) * acc[v][ll];
+            } else {
 #pragma unroll
-                for (int ll = 0; ll < NS; ++ll) o[ll] += PCE(bv, ll, l) * acc[l];
+                for (int l = 0; l < NS; ++l)
+#pragma unroll
+                    for (int ll = 0; ll < NS; ++ll) o[ll] += PCE(bv, ll, l) * acc[v][l];
+            }
+#pragma unroll
+            for (int l = 0; l < NS; ++l) acc[v][l] = o[l];
         }
-#pragma unroll
-        for (int l = 0; l < NS; ++l) acc[l] = o[l];
     }
 #pragma unroll
-    for (int l = 0; l < NS; ++l) stg(W, q8 + l * N8, acc[l]);
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int l = 0; l < NS; ++l) stg(W[v], q8 + l * N8, acc[v][l]);
     if (BACK) {
 #pragma unroll
-        for (int l = 0; l < NS; ++l) z[m + l] = acc[l];
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int l = 0; l < NS; ++l) z[v * ldz + m + l] = acc[v][l];
     }
 }
 
@@ -215,25 +243,29 @@ int launch_pc_factor(const PcTab& T, int nState, const std::vector<int>& planeSt
     return 0;
 }
 
-template <int NS, int TR>
-static void pc_apply_planes(const PcTab& T, const std::vector<int>& planeStart, const double* r, double* z, hipStream_t s)
+template <int NS, int TR, int NV>
+static void pc_apply_planes(const PcTab& T, const std::vector<int>& planeStart, const double* r, double* z, long ldr, long ldz, hipStream_t s)
 {
     const int np = (int)planeStart.size() - 1;
     for (int p = 0; p < np; ++p) {
         const int q0 = planeStart[p], cnt = planeStart[p + 1] - q0;
-        if (cnt > 0) hipLaunchKernelGGL((k_pc_sweep<NS, TR, 0>), dim3((cnt + PC_T - 1) / PC_T), dim3(PC_T), 0, s, T, q0, cnt, r, z);
+        if (cnt > 0)
+            hipLaunchKernelGGL((k_pc_sweep<NS, TR, 0, NV>), dim3((cnt + PC_T - 1) / PC_T), dim3(PC_T), 0, s, T, q0, cnt, r, z, ldr, ldz);
     }
     for (int p = np - 1; p >= 0; --p) {
         const int q0 = planeStart[p], cnt = planeStart[p + 1] - q0;
-        if (cnt > 0) hipLaunchKernelGGL((k_pc_sweep<NS, TR, 1>), dim3((cnt + PC_T - 1) / PC_T), dim3(PC_T), 0, s, T, q0, cnt, r, z);
+        if (cnt > 0)
+            hipLaunchKernelGGL((k_pc_sweep<NS, TR, 1, NV>), dim3((cnt + PC_T - 1) / PC_T), dim3(PC_T), 0, s, T, q0, cnt, r, z, ldr, ldz);
     }
 }
 
+#define PC_DISPATCH_NV(nv, ...) ADF_DISPATCH_NV(nv, return adf_fail("pc: no kernel for this number of vectors"), __VA_ARGS__)
+
 int launch_pc_apply(const PcTab& T, int nState, int transpose, const std::vector<int>& planeStart, const double* r, double* z,
-                    hipStream_t s)
+                    hipStream_t s, int nv, long ldr, long ldz)
 {
-    if (transpose) { PC_DISPATCH(nState, pc_apply_planes<NS_, 1>(T, planeStart, r, z, s)) }
-    else { PC_DISPATCH(nState, pc_apply_planes<NS_, 0>(T, planeStart, r, z, s)) }
+    if (transpose) { PC_DISPATCH(nState, PC_DISPATCH_NV(nv, pc_apply_planes<NS_, 1, NV_>(T, planeStart, r, z, ldr, ldz, s))) }
+    else { PC_DISPATCH(nState, PC_DISPATCH_NV(nv, pc_apply_planes<NS_, 0, NV_>(T, planeStart, r, z, ldr, ldz, s))) }
     return 0;
 }
 
@@ -259,10 +291,9 @@ __device__ __forceinline__ double gm_block_sum(double v, double* red)
 // in the same order; workgroup 0 stores h to *hOut), w -= h v, and the partial sums of <w, u> (u == NULL: <w, w>) go to out[].
 // v == NULL: no update, only the dot product.  The dot with basis vector i + 1 needs the update with vector i: MGS allows no wider
 // batch than this chain, which costs one launch per basis vector and no trip to the host.
-__global__ __launch_bounds__(GM_T) void k_gm_mgs(double* w, const double* v, const double* hp, const double* u, double* out,
-                                                 double* hOut, long n)
+__device__ __forceinline__ void gm_mgs_column(double* w, const double* v, const double* hp, const double* u, double* out, double* hOut,
+                                              long n, double* red)
 {
-    __shared__ double red[GM_T];
     const int tid = threadIdx.x;
     double h = 0.0;
     if (v) {
@@ -282,6 +313,24 @@ __global__ __launch_bounds__(GM_T) void k_gm_mgs(double* w, const double* v, con
     if (tid == 0) out[blockIdx.x] = sum;
 }
 
+__global__ __launch_bounds__(GM_T) void k_gm_mgs(double* w, const double* v, const double* hp, const double* u, double* out,
+                                                 double* hOut, long n)
+{
+    __shared__ double red[GM_T];
+    gm_mgs_column(w, v, hp, u, out, hOut, n, red);
+}
+
+// The columns of adflow_gpu_gmres_solve_multi in lock-step: the same step for column blockIdx.y of w, v and u (ld doubles apart),
+// with its own GM_PARTS partial sums in hp and out, added in the order of the single solver; its h goes to hOut[column]
+__global__ __launch_bounds__(GM_T) void k_gm_mgs_multi(double* w, const double* v, const double* hp, const double* u, double* out,
+                                                       double* hOut, long n, long ld)
+{
+    __shared__ double red[GM_T];
+    const long c = blockIdx.y;
+    gm_mgs_column(w + c * ld, v ? v + c * ld : nullptr, v ? hp + c * GM_PARTS : nullptr, u ? u + c * ld : nullptr, out + c * GM_PARTS,
+                  v ? hOut + c : nullptr, n, red);
+}
+
 // the last partial sums of a chain
 __global__ __launch_bounds__(GM_T) void k_gm_sum(const double* hp, int np, double* hOut)
 {
@@ -296,6 +345,25 @@ __global__ __launch_bounds__(GM_T) void k_gm_axpby(double* y, double a, const do
     const long i = (long)blockIdx.x * GM_T + threadIdx.x;
     if (i >= n) return;
     y[i] = (b == 0.0) ? a * x[i] : a * x[i] + b * y[i];
+}
+
+// the same for the columns of a multi solve: partial sums of column c at hp + c GM_PARTS, its sum to hOut[c]
+__global__ __launch_bounds__(GM_T) void k_gm_sum_multi(const double* hp, int np, double* hOut)
+{
+    __shared__ double red[GM_T];
+    const double h = gm_block_sum((int)threadIdx.x < np ? hp[blockIdx.x * GM_PARTS + threadIdx.x] : 0.0, red);
+    if (threadIdx.x == 0) hOut[blockIdx.x] = h;
+}
+
+// y_c = a_c x_c + b_c y_c for column c = blockIdx.y (b_c == 0: y_c is not read); a column with a_c = 0, b_c = 1 is not touched at all:
+// that is how a column that has finished is left as it is
+__global__ __launch_bounds__(GM_T) void k_gm_axpby_multi(double* y, long ldy, const double* x, long ldx, GmCoef k, long n)
+{
+    const long i = (long)blockIdx.x * GM_T + threadIdx.x;
+    const int c = blockIdx.y;
+    const double a = k.a[c], b = k.b[c];
+    if (i >= n || (a == 0.0 && b == 1.0)) return;
+    y[c * ldy + i] = (b == 0.0) ? a * x[c * ldx + i] : a * x[c * ldx + i] + b * y[c * ldy + i];
 }
 
 int gm_groups(long n)
@@ -315,4 +383,18 @@ void launch_gm_axpby(double* y, double a, const double* x, double b, long n, hip
 {
     if (n <= 0) return;
     hipLaunchKernelGGL(k_gm_axpby, dim3((unsigned)((n + GM_T - 1) / GM_T)), dim3(GM_T), 0, s, y, a, x, b, n);
+}
+void launch_gm_mgs_multi(double* w, const double* v, const double* hp, const double* u, double* out, double* hOut, long n, long ld,
+                         int nvec, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_gm_mgs_multi, dim3(gm_groups(n), nvec), dim3(GM_T), 0, s, w, v, hp, u, out, hOut, n, ld);
+}
+void launch_gm_sum_multi(const double* hp, long n, double* hOut, int nvec, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_gm_sum_multi, dim3(nvec), dim3(GM_T), 0, s, hp, gm_groups(n), hOut);
+}
+void launch_gm_axpby_multi(double* y, long ldy, const double* x, long ldx, const GmCoef& k, long n, int nvec, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_gm_axpby_multi, dim3((unsigned)((n + GM_T - 1) / GM_T), nvec), dim3(GM_T), 0, s, y, ldy, x, ldx, k, n);
 }

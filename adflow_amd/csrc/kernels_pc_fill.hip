@@ -25,6 +25,10 @@
 // so a wave streams every component plane coalesced; nbr[s N + q] is the position of the cell of off-diagonal slot s or -1 outside the
 // block.  Plane offsets are 64-bit pointer arithmetic, the 32-bit byte offset spans the positions of one plane only: the factor may
 // exceed 4 GiB as long as one vector of the level does not (checked in pc_setup_build).
+//
+// Several vectors at once: k_pcf_sweep takes the vector count NV = 1 .. 4 of k_pc_sweep -- the dependent chain of position and block
+// loads of an entry is walked once per lane for all NV vectors.  Instantiated at fill 1 (13 entries); at fill 2 the sweeps exist for one
+// vector and adflow_gpu_pc_apply_multi applies the factor column by column (no measurement stands behind a wider fill-2 sweep).
 #include "internal.h"
 #include "pc_block.h"
 
@@ -142,8 +146,11 @@ __global__ __launch_bounds__(PCF_T) void k_pcf_factor(PcTab T, int q0, int cnt)
 // one level set of a triangular sweep, the four forms of k_pc_sweep (kernels_pc.hip) over nLow entries; one neighbour block is live
 // at a time.  TR = 1 reads the blocks of the neighbours' rows: the entry of row n that points back to c is the mirror of the entry
 // of row c that points to n.
-template <int NS, int NE, int TR, int BACK>
-__global__ __launch_bounds__(PCF_T) void k_pcf_sweep(PcTab T, int q0, int cnt, const double* __restrict__ r, double* __restrict__ z)
+// NV vectors at once exactly as k_pc_sweep takes them: the chain of position and block loads is shared, the vector loads and the
+// products are per vector
+template <int NS, int NE, int TR, int BACK, int NV = 1>
+__global__ __launch_bounds__(PCF_T) void k_pcf_sweep(PcTab T, int q0, int cnt, const double* __restrict__ r, double* __restrict__ z, long ldr,
+                                                     long ldz)
 {
     constexpr int NL = (NE - 1) / 2, NB = NS * NS;
     const int t = blockIdx.x * PCF_T + threadIdx.x;
@@ -152,15 +159,21 @@ __global__ __launch_bounds__(PCF_T) void k_pcf_sweep(PcTab T, int q0, int cnt, c
     const long N = T.ncell;
     const unsigned N8 = (unsigned)N * 8u;
     GPTR(const double) F = (GPTR(const double))T.fac;
-    GPTR(double) W = (GPTR(double))T.ws;
+    GPTR(double) W[NV];          // vector 0 in the work space of the factor, the others in its extra part
+#pragma unroll
+    for (int v = 0; v < NV; ++v) W[v] = (GPTR(double))(v == 0 ? T.ws : T.wsx + (long)(v - 1) * NS * N);
     const long m = (long)T.vec[q] * NS;
-    double acc[NS];
+    double acc[NV][NS];
     if (BACK) {
 #pragma unroll
-        for (int l = 0; l < NS; ++l) acc[l] = ldg(W, q8 + l * N8);
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int l = 0; l < NS; ++l) acc[v][l] = ldg(W[v], q8 + l * N8);
     } else {
 #pragma unroll
-        for (int l = 0; l < NS; ++l) acc[l] = r[m + l];
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int l = 0; l < NS; ++l) acc[v][l] = r[v * ldr + m + l];
     }
 #pragma nounroll
     for (int e = 0; e < NL; ++e) {
@@ -170,49 +183,62 @@ __global__ __launch_bounds__(PCF_T) void k_pcf_sweep(PcTab T, int q0, int cnt, c
         const unsigned n8 = (unsigned)n * 8u, at = TR ? n8 : q8;
         const int slot = TR ? (BACK ? NL - 1 - e : 2 * NL - 1 - e) : col;
         GPTR(const double) Fs = F + (long)slot * NB * N;
-        double xv[NS], bv[NB];
+        double xv[NV][NS], bv[NB];
 #pragma unroll
-        for (int l = 0; l < NS; ++l) xv[l] = ldg(W, n8 + l * N8);
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int l = 0; l < NS; ++l) xv[v][l] = ldg(W[v], n8 + l * N8);
 #pragma unroll
         for (int i = 0; i < NB; ++i) bv[i] = ldg(Fs + i * N, at);
-        if (TR) {
 #pragma unroll
-            for (int l = 0; l < NS; ++l)
+        for (int v = 0; v < NV; ++v) {
+            if (TR) {
 #pragma unroll
-                for (int ll = 0; ll < NS; ++ll) acc[l] -= PCE(bv, ll, l) * xv[ll];
-        } else {
+                for (int l = 0; l < NS; ++l)
 #pragma unroll
-            for (int l = 0; l < NS; ++l)
+                    for (int ll = 0; ll < NS; ++ll) acc[v][l] -= PCE(bv, ll, l) * xv[v][ll];
+            } else {
 #pragma unroll
-                for (int ll = 0; ll < NS; ++ll) acc[ll] -= PCE(bv, ll, l) * xv[l];
+                for (int l = 0; l < NS; ++l)
+#pragma unroll
+                    for (int ll = 0; ll < NS; ++ll) acc[v][ll] -= PCE(bv, ll, l) * xv[v][l];
+            }
         }
     }
     if (TR != BACK) {
         GPTR(const double) Fd = F + (long)(2 * NL) * NB * N;
-        double bv[NB], o[NS];
+        double bv[NB];
 #pragma unroll
         for (int i = 0; i < NB; ++i) bv[i] = ldg(Fd + i * N, q8);
 #pragma unroll
-        for (int l = 0; l < NS; ++l) o[l] = 0.0;
-        if (TR) {
+        for (int v = 0; v < NV; ++v) {
+            double o[NS];
 #pragma unroll
-            for (int l = 0; l < NS; ++l)
+            for (int l = 0; l < NS; ++l) o[l] = 0.0;
+            if (TR) {
 #pragma unroll
-                for (int ll = 0; ll < NS; ++ll) o[l] += PCE(bv, ll, l) * acc[ll];
-        } else {
+                for (int l = 0; l < NS; ++l)
 #pragma unroll
-            for (int l = 0; l < NS; ++l)
+                    for (int ll = 0; ll < NS; ++ll) o[l] += PCE(bv, ll, l) * acc[v][ll];
+            } else {
 #pragma unroll
-                for (int ll = 0; ll < NS; ++ll) o[ll] += PCE(bv, ll, l) * acc[l];
+                for (int l = 0; l < NS; ++l)
+#pragma unroll
+                    for (int ll = 0; ll < NS; ++ll) o[ll] += PCE(bv, ll, l) * acc[v][l];
+            }
+#pragma unroll
+            for (int l = 0; l < NS; ++l) acc[v][l] = o[l];
         }
-#pragma unroll
-        for (int l = 0; l < NS; ++l) acc[l] = o[l];
     }
 #pragma unroll
-    for (int l = 0; l < NS; ++l) stg(W, q8 + l * N8, acc[l]);
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int l = 0; l < NS; ++l) stg(W[v], q8 + l * N8, acc[v][l]);
     if (BACK) {
 #pragma unroll
-        for (int l = 0; l < NS; ++l) z[m + l] = acc[l];
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int l = 0; l < NS; ++l) z[v * ldz + m + l] = acc[v][l];
     }
 }
 
@@ -238,26 +264,44 @@ int launch_pcf_factor(const PcTab& T, int nState, int nEnt, const std::vector<in
     return 0;
 }
 
-template <int NS, int NE, int TR>
-static void pcf_apply_sets(const PcTab& T, const std::vector<int>& levelStart, const double* r, double* z, hipStream_t s)
+template <int NS, int NE, int TR, int NV>
+static void pcf_apply_sets(const PcTab& T, const std::vector<int>& levelStart, const double* r, double* z, long ldr, long ldz, hipStream_t s)
 {
     const int np = (int)levelStart.size() - 1;
     for (int p = 0; p < np; ++p) {
         const int q0 = levelStart[p], cnt = levelStart[p + 1] - q0;
         if (cnt > 0)
-            hipLaunchKernelGGL((k_pcf_sweep<NS, NE, TR, 0>), dim3((cnt + PCF_T - 1) / PCF_T), dim3(PCF_T), 0, s, T, q0, cnt, r, z);
+            hipLaunchKernelGGL((k_pcf_sweep<NS, NE, TR, 0, NV>), dim3((cnt + PCF_T - 1) / PCF_T), dim3(PCF_T), 0, s, T, q0, cnt, r, z, ldr,
+                               ldz);
     }
     for (int p = np - 1; p >= 0; --p) {
         const int q0 = levelStart[p], cnt = levelStart[p + 1] - q0;
         if (cnt > 0)
-            hipLaunchKernelGGL((k_pcf_sweep<NS, NE, TR, 1>), dim3((cnt + PCF_T - 1) / PCF_T), dim3(PCF_T), 0, s, T, q0, cnt, r, z);
+            hipLaunchKernelGGL((k_pcf_sweep<NS, NE, TR, 1, NV>), dim3((cnt + PCF_T - 1) / PCF_T), dim3(PCF_T), 0, s, T, q0, cnt, r, z, ldr,
+                               ldz);
     }
 }
 
-int launch_pcf_apply(const PcTab& T, int nState, int nEnt, int transpose, const std::vector<int>& levelStart, const double* r,
-                     double* z, hipStream_t s)
+#define PCF_DISPATCH_NV(nv, ...) ADF_DISPATCH_NV(nv, return adf_fail("pc: no kernel for this number of vectors"), __VA_ARGS__)
+
+// several vectors at fill 1 only: the fill-2 sweeps (23 entries) are instantiated for one vector (api.hip serves fill 2 column by column)
+template <int NS, int NE, int TR>
+static int pcf_apply_nv(const PcTab& T, const std::vector<int>& levelStart, const double* r, double* z, long ldr, long ldz, hipStream_t s,
+                        int nv)
 {
-    if (transpose) { PCF_DISPATCH(nState, nEnt, pcf_apply_sets<NS_, NE_, 1>(T, levelStart, r, z, s)) }
-    else { PCF_DISPATCH(nState, nEnt, pcf_apply_sets<NS_, NE_, 0>(T, levelStart, r, z, s)) }
+    if constexpr (NE == 23) {
+        if (nv != 1) return adf_fail("pc: the fill-2 sweeps take one vector");
+        pcf_apply_sets<NS, NE, TR, 1>(T, levelStart, r, z, ldr, ldz, s);
+    } else {
+        PCF_DISPATCH_NV(nv, pcf_apply_sets<NS, NE, TR, NV_>(T, levelStart, r, z, ldr, ldz, s))
+    }
+    return 0;
+}
+
+int launch_pcf_apply(const PcTab& T, int nState, int nEnt, int transpose, const std::vector<int>& levelStart, const double* r,
+                     double* z, hipStream_t s, int nv, long ldr, long ldz)
+{
+    if (transpose) { PCF_DISPATCH(nState, nEnt, return pcf_apply_nv<NS_, NE_, 1>(T, levelStart, r, z, ldr, ldz, s, nv)) }
+    else { PCF_DISPATCH(nState, nEnt, return pcf_apply_nv<NS_, NE_, 0>(T, levelStart, r, z, ldr, ldz, s, nv)) }
     return 0;
 }

@@ -238,6 +238,63 @@ class Engine:
                                                       ctypes.byref(its), ctypes.byref(r0), ctypes.byref(rn)))
         return int(its.value), float(r0.value), float(rn.value)
 
+    # ---- several right-hand sides at once: columns as the rows of a C-contiguous (nvec, n) array, so ld = n
+    @staticmethod
+    def _columns(A):
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.ndim != 2:
+            raise ValueError("the columns of a multi entry are the rows of an array of shape (nvec, n)")
+        return A
+
+    def jacobianMultMulti(self, X, level=1, transpose=False):
+        """Y[c] = J X[c] (J^T X[c]) for the nvec rows of X in one pass over the matrix per group of 4 (jacobianMult per column)"""
+        X = self._columns(X)
+        Y = np.zeros_like(X)
+        nvec, n = X.shape
+        self._chk(self.lib.adflow_gpu_jacobian_mult_multi(level, int(bool(transpose)), nvec, X.ctypes.data, n, Y.ctypes.data, n, n))
+        return Y
+
+    def jacobianMultMultiDev(self, d_X: int, ldx: int, d_Y: int, ldy: int, nvec: int, n: int, level=1, transpose=False):
+        """the same on device pointers: column c at d_X + 8 c ldx bytes (ld >= n)"""
+        self._chk(self.lib.adflow_gpu_jacobian_mult_multi_dev(level, int(bool(transpose)), int(nvec), ctypes.c_void_p(d_X), int(ldx),
+                                                              ctypes.c_void_p(d_Y), int(ldy), int(n)))
+
+    def pcApplyMulti(self, R, level=1, transpose=False):
+        """Z[c] = M^-1 R[c] (M^-T R[c]) for the nvec rows of R through the level sets once per group of 4 (pcApply per column)"""
+        R = self._columns(R)
+        Z = np.zeros_like(R)
+        nvec, n = R.shape
+        self._chk(self.lib.adflow_gpu_pc_apply_multi(level, int(bool(transpose)), nvec, R.ctypes.data, n, Z.ctypes.data, n, n))
+        return Z
+
+    def pcApplyMultiDev(self, d_R: int, ldr: int, d_Z: int, ldz: int, nvec: int, n: int, level=1, transpose=False):
+        """the same on device pointers"""
+        self._chk(self.lib.adflow_gpu_pc_apply_multi_dev(level, int(bool(transpose)), int(nvec), ctypes.c_void_p(d_R), int(ldr),
+                                                         ctypes.c_void_p(d_Z), int(ldz), int(n)))
+
+    def gmresSolveMulti(self, B, level=1, transpose=False, restart=50, maxIts=200, rtol=1e-8, atol=0.0, x0=None):
+        """gmresSolve for the nvec rows of B in lock-step; returns (X, its[], rnorm0[], rnorm[]), every column as its own gmresSolve
+        would leave it (x0: an array like B with the initial guess of every column)"""
+        B = self._columns(B)
+        X = np.zeros_like(B) if x0 is None else np.array(x0, dtype=np.float64, order="C", copy=True)
+        assert X.shape == B.shape
+        nvec, n = B.shape
+        its, r0, rn = np.zeros(nvec, dtype=np.int32), np.zeros(nvec), np.zeros(nvec)
+        self._chk(self.lib.adflow_gpu_gmres_solve_multi(level, int(bool(transpose)), nvec, B.ctypes.data, n, X.ctypes.data, n, n,
+                                                        int(restart), int(maxIts), float(rtol), float(atol), int(x0 is not None),
+                                                        its.ctypes.data, r0.ctypes.data, rn.ctypes.data))
+        return X, its, r0, rn
+
+    def gmresSolveMultiDev(self, d_B: int, ldb: int, d_X: int, ldx: int, nvec: int, n: int, level=1, transpose=False, restart=50,
+                           maxIts=200, rtol=1e-8, atol=0.0, useGuess=False):
+        """the same on device pointers; returns (its[], rnorm0[], rnorm[])"""
+        its, r0, rn = np.zeros(nvec, dtype=np.int32), np.zeros(nvec), np.zeros(nvec)
+        self._chk(self.lib.adflow_gpu_gmres_solve_multi_dev(level, int(bool(transpose)), int(nvec), ctypes.c_void_p(d_B), int(ldb),
+                                                            ctypes.c_void_p(d_X), int(ldx), int(n), int(restart), int(maxIts),
+                                                            float(rtol), float(atol), int(bool(useGuess)), its.ctypes.data,
+                                                            r0.ctypes.data, rn.ctypes.data))
+        return its, r0, rn
+
     def pcSelect(self, slot: int):
         """the factor slot (0 or 1) pcSetup, ankPcSetup, pcApply, pcInfo, pcRelease, gmresSolve and ankSolve act on"""
         self._chk(self.lib.adflow_gpu_pc_select(int(slot)))

@@ -393,6 +393,61 @@ module adflowGpuShim
             integer(c_int), intent(out) :: its
             real(c_double), intent(out) :: rnorm0, rnorm
         end function
+        ! several right-hand sides at once (the adjoints of several functions, the seeds of solveAdjointForRHS / solveDirectForRHS):
+        ! column c is the n doubles at X + c ld, ld >= n, every column as the single entry takes its vector; its, rnorm0, rnorm: nvec
+        ! entries each
+        integer(c_int) function adflow_gpu_jacobian_mult_multi(level, transpose, nvec, x, ldx, y, ldy, n) &
+            bind(C, name="adflow_gpu_jacobian_mult_multi")
+            import :: c_int, c_long, c_double
+            integer(c_int), value :: level, transpose, nvec
+            real(c_double), intent(in) :: x(*)
+            real(c_double), intent(out) :: y(*)
+            integer(c_long), value :: ldx, ldy, n
+        end function
+        integer(c_int) function adflow_gpu_jacobian_mult_multi_dev(level, transpose, nvec, x, ldx, y, ldy, n) &
+            bind(C, name="adflow_gpu_jacobian_mult_multi_dev")
+            import :: c_int, c_ptr, c_long
+            integer(c_int), value :: level, transpose, nvec
+            type(c_ptr), value :: x, y
+            integer(c_long), value :: ldx, ldy, n
+        end function
+        integer(c_int) function adflow_gpu_pc_apply_multi(level, transpose, nvec, r, ldr, z, ldz, n) &
+            bind(C, name="adflow_gpu_pc_apply_multi")
+            import :: c_int, c_long, c_double
+            integer(c_int), value :: level, transpose, nvec
+            real(c_double), intent(in) :: r(*)
+            real(c_double), intent(out) :: z(*)
+            integer(c_long), value :: ldr, ldz, n
+        end function
+        integer(c_int) function adflow_gpu_pc_apply_multi_dev(level, transpose, nvec, r, ldr, z, ldz, n) &
+            bind(C, name="adflow_gpu_pc_apply_multi_dev")
+            import :: c_int, c_ptr, c_long
+            integer(c_int), value :: level, transpose, nvec
+            type(c_ptr), value :: r, z
+            integer(c_long), value :: ldr, ldz, n
+        end function
+        integer(c_int) function adflow_gpu_gmres_solve_multi(level, transpose, nvec, b, ldb, x, ldx, n, restart, maxIts, rtol, atol, &
+                                                             useGuess, its, rnorm0, rnorm) bind(C, name="adflow_gpu_gmres_solve_multi")
+            import :: c_int, c_long, c_double
+            integer(c_int), value :: level, transpose, nvec, restart, maxIts, useGuess
+            real(c_double), intent(in) :: b(*)
+            real(c_double), intent(inout) :: x(*)
+            integer(c_long), value :: ldb, ldx, n
+            real(c_double), value :: rtol, atol
+            integer(c_int), intent(out) :: its(*)
+            real(c_double), intent(out) :: rnorm0(*), rnorm(*)
+        end function
+        integer(c_int) function adflow_gpu_gmres_solve_multi_dev(level, transpose, nvec, b, ldb, x, ldx, n, restart, maxIts, rtol, atol, &
+                                                                 useGuess, its, rnorm0, rnorm) &
+            bind(C, name="adflow_gpu_gmres_solve_multi_dev")
+            import :: c_int, c_ptr, c_long, c_double
+            integer(c_int), value :: level, transpose, nvec, restart, maxIts, useGuess
+            type(c_ptr), value :: b, x
+            integer(c_long), value :: ldb, ldx, n
+            real(c_double), value :: rtol, atol
+            integer(c_int), intent(out) :: its(*)
+            real(c_double), intent(out) :: rnorm0(*), rnorm(*)
+        end function
         ! the flow update of ANKStep (NKSolvers.F90:3629-4112): setWANK / setRVecANK, computeTimeStepMat ('None'), the ILU(0) of
         ! dRdwPre + timeStepMat, the matrix-free operator of FormFunction_mf under MatMFFD, KSPSolve, physicalityCheckANK.
         ! flags: ADFLOW_ANK_COUPLED = 256 (nState = nw, else 5) plus the ADFLOW_RES_*_APPROX flags of the residual; one rank only
@@ -962,5 +1017,58 @@ contains
         if (transposed) tr = 1_c_int
         call gpuCheck(adflow_gpu_pc_apply_dev(int(level, c_int), tr, rDev, zDev, int(n, c_long)), "gpuPCApply")
     end subroutine gpuPCApply
+
+    ! ---- several right-hand sides at once ---------------------------------------------------------------------------------------
+    ! The vectors of one call lie ld >= n doubles apart in ONE device array (e.g. the arrays of nvec VECHIP vectors created over one
+    ! allocation with VecCreateSeqHIPWithArray, or a dense Mat's array): xDev, yDev point to column 0.
+
+    ! nvec products in one pass over the assembled matrix: the MatMatMult of a MatShell, or the loop over gpuJacobianMult
+    subroutine gpuJacobianMultMulti(level, transposed, nvec, xDev, ldx, yDev, ldy, n)
+        integer(kind=intType), intent(in) :: level, nvec, ldx, ldy, n
+        logical, intent(in) :: transposed
+        type(c_ptr), intent(in) :: xDev, yDev
+        integer(c_int) :: tr
+        tr = 0_c_int
+        if (transposed) tr = 1_c_int
+        call gpuCheck(adflow_gpu_jacobian_mult_multi_dev(int(level, c_int), tr, int(nvec, c_int), xDev, int(ldx, c_long), yDev, &
+                                                         int(ldy, c_long), int(n, c_long)), "gpuJacobianMultMulti")
+    end subroutine gpuJacobianMultMulti
+
+    ! nvec applications of the factor through its level sets once: PCMatApply of a PCSHELL, or the loop over gpuPCApply
+    subroutine gpuPCApplyMulti(level, transposed, nvec, rDev, ldr, zDev, ldz, n)
+        integer(kind=intType), intent(in) :: level, nvec, ldr, ldz, n
+        logical, intent(in) :: transposed
+        type(c_ptr), intent(in) :: rDev, zDev
+        integer(c_int) :: tr
+        tr = 0_c_int
+        if (transposed) tr = 1_c_int
+        call gpuCheck(adflow_gpu_pc_apply_multi_dev(int(level, c_int), tr, int(nvec, c_int), rDev, int(ldr, c_long), zDev, &
+                                                    int(ldz, c_long), int(n, c_long)), "gpuPCApplyMulti")
+    end subroutine gpuPCApplyMulti
+
+    ! nvec KSPSolves in lock-step, in place of the loop over the functions in front of solveAdjoint (transposed = .true.) and of the
+    ! calls of solveAdjointForRHS / solveDirectForRHS per seed; its, rnorm0, rnorm: one entry per column; one rank only
+    subroutine gpuGMRESSolveMulti(level, transposed, nvec, bDev, ldb, xDev, ldx, n, restart, maxIts, rtol, atol, useGuess, its, &
+                                  rnorm0, rnorm)
+        integer(kind=intType), intent(in) :: level, nvec, ldb, ldx, n, restart, maxIts
+        logical, intent(in) :: transposed, useGuess
+        type(c_ptr), intent(in) :: bDev, xDev
+        real(kind=realType), intent(in) :: rtol, atol
+        integer(kind=intType), intent(out) :: its(nvec)
+        real(kind=realType), intent(out) :: rnorm0(nvec), rnorm(nvec)
+        integer(c_int) :: tr, ug, itsC(nvec)
+        real(c_double) :: r0C(nvec), rC(nvec)
+        tr = 0_c_int
+        if (transposed) tr = 1_c_int
+        ug = 0_c_int
+        if (useGuess) ug = 1_c_int
+        call gpuCheck(adflow_gpu_gmres_solve_multi_dev(int(level, c_int), tr, int(nvec, c_int), bDev, int(ldb, c_long), xDev, &
+                                                       int(ldx, c_long), int(n, c_long), int(restart, c_int), int(maxIts, c_int), &
+                                                       real(rtol, c_double), real(atol, c_double), ug, itsC, r0C, rC), &
+                      "gpuGMRESSolveMulti")
+        its = int(itsC, intType)
+        rnorm0 = real(r0C, realType)
+        rnorm = real(rC, realType)
+    end subroutine gpuGMRESSolveMulti
 
 end module adflowGpuShim

@@ -551,6 +551,51 @@ int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x,
 int adflow_gpu_gmres_solve_dev(int level, int transpose, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol,
                                double atol, int useGuess, int* its, double* rnorm0, double* rnorm);
 
+/* ---- several right-hand sides at once: the product, the ILU application and GMRES on nvec columns -------------------------------
+ * The adjoints of several functions (the loop in front of solveAdjoint, pyADflow.py:1723-1743) and the seeds of solveAdjointForRHS /
+ * solveDirectForRHS (adjointAPI.F90:265-428) share one matrix and one factor; these entries take their vectors together.  Column c is
+ * the n doubles at X + c ld, ld >= n, each in the layout of adflow_gpu_set_w_vec exactly like a vector of the single entries: the
+ * vectors lie one behind the other (not interleaved), so a host hands over its existing Vec arrays.  Host pointers, or device
+ * pointers for the _dev forms, which honour adflow_gpu_set_async where their single twins do (product and application; the solver
+ * synchronises every iteration).
+ * Every column behaves as the single entry does on that column -- same matrix, same selected factor slot of any fill (one of
+ * adflow_gpu_ank_pc_setup included), same transposes; nvec = 1 runs the kernels of the single entry and is bit-identical to it.
+ * Wider calls run kernels that read every matrix or factor block once for up to 4 vectors and go through the level sets once;
+ * more than 4 columns are served in groups of 4 and a rest (7 = 4 + 3), at most ADFLOW_GPU_MAX_NVEC per call (a factor of fill 2
+ * is applied column by column with the kernels of one vector).  Their results
+ * agree with the single entries to rounding, and a column does not depend on what the other columns hold.
+ *   adflow_gpu_jacobian_mult_multi   Y_c = J X_c (J^T X_c), one pass over the matrix per group.  The scratch arrays of the product
+ *                          grow to the widest group used (adflow_gpu_release_workspace counts and frees them as before).
+ *   adflow_gpu_pc_apply_multi        Z_c = M^-1 R_c (M^-T R_c), one launch per level set for all blocks and all columns of a group.
+ *                          The work space of the other vectors of a group is allocated at the first multi application of a factor
+ *                          and kept at the widest group used: it belongs to the factor, adflow_gpu_pc_info counts it from then
+ *                          on, and it is released with the factor.  A process that never calls a multi entry holds the bytes it
+ *                          always held.
+ *   adflow_gpu_gmres_solve_multi     nvec independent right-preconditioned GMRES(restart) iterations in lock-step: one multi
+ *                          application and one multi product per iteration, every launch of the Gram-Schmidt chain for all columns
+ *                          (partial sums per column, added in the order of the single solver), one download and one synchronise per
+ *                          iteration.  Tolerance max(rtol ||B_c||, atol), Hessenberg matrix, rotations and count are per column, and a
+ *                          column stops where its own adflow_gpu_gmres_solve would (tolerance met, breakdown, maxIts): its X_c is
+ *                          formed from its own Krylov space at that iteration and not touched afterwards, while the others go on.
+ *                          The restart boundaries are shared (every column starts at iteration 0).  its, rnorm0, rnorm: nvec entries
+ *                          each, each may be NULL; rnorm[c] is the true residual of X_c.  Work space of (restart + 3) nvec vectors
+ *                          is allocated for the call; if that fails the error names the size and nothing is held.
+ * Errors: everything the single entries refuse, named by the multi entry; nvec < 1 or > ADFLOW_GPU_MAX_NVEC; ld < n; a column of the
+ * input that shares memory with a column of the result (column a of the one with column b of the other included); for the solver a
+ * right-hand side that is not finite (the column is named) and more than one rank.
+ * Out of scope: the ANK entries stay single-vector (adflow_gpu_ank_mult is one residual evaluation per vector: nothing to share);
+ * the solver across ranks, as for adflow_gpu_gmres_solve; columns with different matrices or factors. */
+#define ADFLOW_GPU_MAX_NVEC 32
+int adflow_gpu_jacobian_mult_multi(int level, int transpose, int nvec, const double* X, long ldx, double* Y, long ldy, long n);
+int adflow_gpu_jacobian_mult_multi_dev(int level, int transpose, int nvec, const double* d_X, long ldx, double* d_Y, long ldy, long n);
+int adflow_gpu_pc_apply_multi(int level, int transpose, int nvec, const double* R, long ldr, double* Z, long ldz, long n);
+int adflow_gpu_pc_apply_multi_dev(int level, int transpose, int nvec, const double* d_R, long ldr, double* d_Z, long ldz, long n);
+int adflow_gpu_gmres_solve_multi(int level, int transpose, int nvec, const double* B, long ldb, double* X, long ldx, long n, int restart,
+                                 int maxIts, double rtol, double atol, int useGuess, int* its, double* rnorm0, double* rnorm);
+int adflow_gpu_gmres_solve_multi_dev(int level, int transpose, int nvec, const double* d_B, long ldb, double* d_X, long ldx, long n,
+                                     int restart, int maxIts, double rtol, double atol, int useGuess, int* its, double* rnorm0,
+                                     double* rnorm);
+
 /* ---- the flow update of the approximate Newton-Krylov step, NKSolver::ANKStep (src/NKSolver/NKSolvers.F90:3629-4112) --------------
  * Everything acts on the level-1 blocks of the process.  Vectors: the layout of adflow_gpu_set_w_vec (block, k, j, i, variable
  * fastest) with nState variables per owned cell, n = nState x owned cells: nState = nw with ADFLOW_ANK_COUPLED, else 5 -- the flow

@@ -3,7 +3,10 @@
 events: the RANS Roe preconditioner matrix (7-point, forward-mode assembly) on one 160 x 128 x 64 wall-bounded block and the exact
 dR/dw (33-point) on a 96 x 64 x 48 block.  Prints ms per product, the bytes of the byte floor (nStencil nState^2 x 8 B per owned
 cell: one pass over the matrix), TB/s and the fraction of the measured copy ceiling (profiles/r06_fin6_calibration.json).
-usage: jac_mult.py [n]   (n timed products of each kind, default 20)"""
+--nvec N adds, on the 160 x 128 x 64 block and in the same process: Y = J X and J^T X for N columns through
+adflow_gpu_jacobian_mult_multi_dev (one call) against N calls of adflow_gpu_jacobian_mult_dev, with the GB/s on the matrix of the multi
+call, and the wall time of GMRES (block ILU(0)) for N right-hand sides through adflow_gpu_gmres_solve_multi_dev against N single solves.
+usage: jac_mult.py [--nvec N] [n]   (n timed products of each kind, default 20)"""
 import json
 import os
 import sys
@@ -21,7 +24,7 @@ from adflow_amd.topology import CommPattern  # noqa: E402
 WALL = {1: -6, 2: -6, 3: -1, 4: -1, 5: -3, 6: -6}
 
 
-def case(eng, torch, dims, usePC, n_it, ceiling):
+def case(eng, torch, dims, usePC, n_it, ceiling, nvec=0):
     prm = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda).replace(currentLevel=1, groundLevel=1)
     blk = make_block(*dims, prm, seed=7, stretch_k=2.0)
     faces, nvisc = make_bocos(blk, prm, WALL, seed=8)
@@ -58,16 +61,62 @@ def case(eng, torch, dims, usePC, n_it, ceiling):
                               "of_copy_ceiling": round(tbs / ceiling, 3), "checksum": float(y.abs().sum().item())}), flush=True)
     finally:
         eng.set_async(False)
+    if nvec > 1:
+        multi_columns(eng, torch, gen, n, nvec, n_it, floor)
     eng.releaseWorkspace()
+
+
+def multi_columns(eng, torch, gen, n, nvec, n_it, floor):
+    """nvec columns through the multi entries against nvec calls of the single entries, same process, same matrix"""
+    from pc_apply import gmres_columns
+    X = torch.rand(nvec * n, dtype=torch.float64, device="cuda", generator=gen) - 0.5
+    Y = torch.empty_like(X)
+    torch.cuda.synchronize()
+    groups = (nvec + 3) // 4                              # a call reads the matrix once per group of at most 4 columns
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        eng.event_record(1)
+        for _ in range(n_it):
+            fn()
+        eng.event_record(2)
+        eng.sync()
+        return eng.event_elapsed_ms(1, 2) / n_it
+
+    eng.set_async(True)
+    try:
+        for tr in (False, True):
+            def single():
+                for c in range(nvec):
+                    eng.jacobianMultDev(X.data_ptr() + 8 * c * n, Y.data_ptr() + 8 * c * n, n, 1, tr)
+            ms_s = timed(single)
+            sum_s = float(Y.abs().sum().item())
+            ms_m = timed(lambda: eng.jacobianMultMultiDev(X.data_ptr(), n, Y.data_ptr(), n, nvec, n, 1, tr))
+            print(json.dumps({"product": "J^T X" if tr else "J X", "nvec": nvec, "ms_multi": round(ms_m, 4), "ms_nvec_single_calls": round(ms_s, 4),
+                              "multi_over_single": round(ms_m / ms_s, 3),
+                              "GB_per_s_on_the_matrix": round(groups * floor / (ms_m * 1e-3) / 1e9, 1),
+                              "checksum": float(Y.abs().sum().item()), "checksum_single_calls": sum_s}), flush=True)
+    finally:
+        eng.set_async(False)
+    eng.pcSetup(1)
+    gmres_columns(eng, torch, X, Y, n, nvec, "PC 7-point matrix, fill 0", 1e-8)
+    eng.pcRelease()
 
 
 def main():
     import torch
+    argv, nvec = list(sys.argv[1:]), 0
+    if "--nvec" in argv:
+        at = argv.index("--nvec")
+        nvec = int(argv[at + 1])
+        del argv[at:at + 2]
+    sys.argv[1:] = argv
     n_it = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     with open(os.path.join(ROOT, "profiles", "r06_fin6_calibration.json")) as f:
         ceiling = json.load(f)["copy16u8_1gib_gbs"] / 1e3
     eng = Engine(0)
-    case(eng, torch, (160, 128, 64), True, n_it, ceiling)
+    case(eng, torch, (160, 128, 64), True, n_it, ceiling, nvec)
     case(eng, torch, (96, 64, 48), False, n_it, ceiling)
     eng.close()
 

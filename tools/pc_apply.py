@@ -4,7 +4,10 @@ preconditioner matrix (7-point, forward-mode assembly) on one 160 x 128 x 64 wal
 z = M^-1 r and z = M^-T r, ms for y = J x with the same matrix in the same run (one launch over the 7-point bytes: the yardstick),
 the byte floor (7, 13 or 23 nState^2 x 8 B per owned cell), TB/s and launches per application; then GMRES on the preconditioner
 matrix itself: iterations and ms to reduce the residual by --rtol (default 1e-8).
-usage: pc_apply.py [--fill 0|1|2] [--rtol 1e-8] [n] [nx ny nz]   (n timed applications of each kind, default 10)"""
+--nvec N adds, in the same process: Z = M^-1 R and M^-T R for N columns through adflow_gpu_pc_apply_multi_dev (one call) against N
+calls of adflow_gpu_pc_apply_dev, with the time per launch and the GB/s on the factor of the multi call, and the wall time of GMRES
+for N right-hand sides through adflow_gpu_gmres_solve_multi_dev against N calls of adflow_gpu_gmres_solve_dev.
+usage: pc_apply.py [--fill 0|1|2] [--rtol 1e-8] [--nvec N] [n] [nx ny nz]   (n timed applications of each kind, default 10)"""
 import json
 import os
 import sys
@@ -21,12 +24,14 @@ WALL = {1: -6, 2: -6, 3: -1, 4: -1, 5: -3, 6: -6}
 
 def main():
     import torch
-    argv, fill, rtol = list(sys.argv[1:]), 0, 1e-8
-    for opt in ("--fill", "--rtol"):
+    argv, fill, rtol, nvec = list(sys.argv[1:]), 0, 1e-8, 0
+    for opt in ("--fill", "--rtol", "--nvec"):
         if opt in argv:
             at = argv.index(opt)
             if opt == "--fill":
                 fill = int(argv[at + 1])
+            elif opt == "--nvec":
+                nvec = int(argv[at + 1])
             else:
                 rtol = float(argv[at + 1])
             del argv[at:at + 2]
@@ -94,9 +99,70 @@ def main():
             eng.sync()
         print(json.dumps({"what": f"gmres on the PC matrix, rtol {rtol:g}", "fill": fill, "transpose": tr, "iterations": its, "ms": round(eng.event_elapsed_ms(1, 2), 3),
                           "rnorm0": r0, "true_rnorm": rn}), flush=True)
+    if nvec > 1:
+        multi_columns(eng, torch, gen, n, nvec, n_it, fill, planes, floor, rtol)
     eng.pcRelease()
     eng.releaseWorkspace()
     eng.close()
+
+
+def multi_columns(eng, torch, gen, n, nvec, n_it, fill, planes, floor, rtol):
+    """nvec columns through the multi entries against nvec calls of the single entries, same process, same factor"""
+    X = torch.rand(nvec * n, dtype=torch.float64, device="cuda", generator=gen) - 0.5
+    Y = torch.empty_like(X)
+    torch.cuda.synchronize()
+    # a call serves the columns in groups of at most 4; a fill-2 factor column by column
+    groups = nvec if fill == 2 else (nvec + 3) // 4
+
+    def timed(fn, reps):
+        for _ in range(2):
+            fn()
+        eng.event_record(1)
+        for _ in range(reps):
+            fn()
+        eng.event_record(2)
+        eng.sync()
+        return eng.event_elapsed_ms(1, 2) / reps
+
+    eng.set_async(True)
+    try:
+        for tr in (False, True):
+            def single():
+                for c in range(nvec):
+                    eng.pcApplyDev(X.data_ptr() + 8 * c * n, Y.data_ptr() + 8 * c * n, n, 1, tr)
+            ms_s = timed(single, n_it)
+            sum_s = float(Y.abs().sum().item())
+            ms_m = timed(lambda: eng.pcApplyMultiDev(X.data_ptr(), n, Y.data_ptr(), n, nvec, n, 1, tr), n_it)
+            launches = 2 * planes * groups
+            print(json.dumps({"what": "M^-T R" if tr else "M^-1 R", "fill": fill, "nvec": nvec, "ms_multi": round(ms_m, 4),
+                              "ms_nvec_single_calls": round(ms_s, 4), "multi_over_single": round(ms_m / ms_s, 3), "launches": launches,
+                              "us_per_launch": round(1e3 * ms_m / launches, 2),
+                              "GB_per_s_on_the_factor": round(groups * floor / (ms_m * 1e-3) / 1e9, 1),
+                              "checksum": float(Y.abs().sum().item()), "checksum_single_calls": sum_s}), flush=True)
+    finally:
+        eng.set_async(False)
+    gmres_columns(eng, torch, X, Y, n, nvec, fill, rtol)
+
+
+def gmres_columns(eng, torch, B, X, n, nvec, what, rtol):
+    """wall time of GMRES for nvec right-hand sides: one lock-step call against nvec single solves"""
+    kw = dict(restart=30, maxIts=60, rtol=rtol)
+    for tr in (False, True):
+        for _ in range(2):                                # the second run is the timed one
+            torch.cuda.synchronize()
+            eng.event_record(1)
+            its_s = [eng.gmresSolveDev(B.data_ptr() + 8 * c * n, X.data_ptr() + 8 * c * n, n, 1, tr, **kw)[0] for c in range(nvec)]
+            eng.event_record(2)
+            eng.sync()
+            ms_s = eng.event_elapsed_ms(1, 2)
+            eng.event_record(1)
+            its_m = eng.gmresSolveMultiDev(B.data_ptr(), n, X.data_ptr(), n, nvec, n, 1, tr, **kw)[0]
+            eng.event_record(2)
+            eng.sync()
+            ms_m = eng.event_elapsed_ms(1, 2)
+        print(json.dumps({"what": f"gmres, {nvec} right-hand sides, rtol {rtol:g}", "case": what, "transpose": tr, "ms_multi": round(ms_m, 3),
+                          "ms_nvec_single_solves": round(ms_s, 3), "multi_over_single": round(ms_m / ms_s, 3),
+                          "iterations_multi": [int(i) for i in its_m], "iterations_single": its_s}), flush=True)
 
 
 if __name__ == "__main__":
