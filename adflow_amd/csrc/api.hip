@@ -4156,7 +4156,28 @@ struct PcFactor {
     std::vector<void*> raw;
     std::vector<int> planeStart;      // first position of every hyperplane in the order of the factor, and the end
     PcTab tab;
+    struct PcMg* mg = nullptr;        // adflow_gpu_pc_set_mg with levels > 1: the hierarchy this factor is level 1 of (owned)
 };
+// The multigrid hierarchy of a slot (kernels_pc_mg.hip).  Level 1 is lv[0]: its matrix is the slot's own copy of the in-block 7-point
+// blocks (T included) and its factor is the PcFactor that owns this hierarchy; the levels below carry their own factor.
+struct PcMgLevel {
+    std::vector<JmBlk> hb;            // the blocks of the level in its own box layout: jac = its matrix, vecOff = first cell
+    JmBlk* dtab = nullptr;            // the same on the device
+    long ncell = 0;
+    int maxnx = 0, maxny = 0, maxnz = 0;
+    double* v[4] = {nullptr, nullptr, nullptr, nullptr};      // rhs, sol, res, x of the cycle
+    PcFactor fac;                     // levels >= 2
+};
+struct PcMg {
+    int nSmooth = 1, fillCoarse = 0;
+    PcMgSten sten;
+    std::vector<int> nnOf;            // block number of every slot of the tables
+    std::vector<PcMgLevel> lv;
+    std::vector<void*> raw;           // matrices, vectors and tables of the levels (the factors own theirs)
+    size_t bytes = 0;
+};
+struct PcMgSetting { int levels = 1, nSmooth = 1, fillCoarse = 0; };
+PcMgSetting g_pc_mg[2];              // adflow_gpu_pc_set_mg: what the next setup of each slot builds (outlives the factors)
 PcFactor g_pc_slots[2];              // adflow_gpu_pc_select: e.g. the flow factor and the turbulence factor of ANK_jacobianLag
 int g_pc_slot = 0;
 int g_pc_fill[2] = {0, 0};           // adflow_gpu_pc_set_fill: the fill the next setup of each slot uses (outlives the factors)
@@ -4167,9 +4188,26 @@ struct DevBuf {                       // a device allocation that lives as long 
 };
 }  // namespace
 
+// everything the factor holds, the hierarchy below it included
+static size_t pc_bytes(const PcFactor& f)
+{
+    size_t n = f.bytes;
+    if (f.mg) {
+        n += f.mg->bytes;
+        for (const PcMgLevel& l : f.mg->lv) n += l.fac.bytes;
+    }
+    return n;
+}
+
 static int64_t pc_release(PcFactor& f)
 {
-    const int64_t n = (int64_t)f.bytes;
+    const int64_t n = (int64_t)pc_bytes(f);
+    if (f.mg) {
+        for (PcMgLevel& l : f.mg->lv)
+            for (void* p : l.fac.raw) (void)hipFree(p);
+        for (void* p : f.mg->raw) (void)hipFree(p);
+        delete f.mg;
+    }
     for (void* p : f.raw) (void)hipFree(p);
     f = PcFactor();
     return n;
@@ -4281,8 +4319,9 @@ static int pc_fill_tables(int fill, const int* sten7, PcTab& T, std::vector<std:
 // row before the row) -- for the 7-point pattern of fill 0 that is i + j + k, the hyperplanes, and fill 0 takes it and its six
 // neighbours directly: the tables are those of the generic loops, which cost its table build a third more time.
 // shift != NULL: the pseudo-time term of ANK (tsm of kernels_ank.hip) is added to the diagonal blocks as the factorisation reads them
+// mgLevel > 0: hb are the blocks of that level of a multigrid hierarchy (their own box layout and matrix), named in the message
 static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::array<int, 3>>& slots, const std::vector<JmBlk>& hb,
-                    const std::vector<int>& nnOf, const double* shift, double turbDiag)
+                    const std::vector<int>& nnOf, const double* shift, double turbDiag, int mgLevel = 0)
 {
     const int nS = g_jac.nState, nOff = (int)slots.size(), nLow = nOff / 2, nEnt = nOff + 1;
     PcTab& T = f.tab;
@@ -4377,6 +4416,10 @@ static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::arr
     if (flag) {
         const int at = flag - 1, s = cblk[at];
         const long loc = vec[at] - hb[s].vecOff;
+        if (mgLevel > 0)
+            return fail("pc_setup: the pivot block of cell (%d,%d,%d) of block %d on multigrid level %d is singular or not finite (ILU(%d) "
+                        "in natural order, level %d); nothing is kept", (int)(loc % hb[s].nx) + 2, (int)(loc / hb[s].nx % hb[s].ny) + 2,
+                        (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2, nnOf[s], mgLevel, fill, level);
         return fail("pc_setup: the pivot block of cell (%d,%d,%d) of block %d is singular or not finite (ILU(%d) in natural order, "
                     "level %d); no factor is kept", (int)(loc % hb[s].nx) + 2, (int)(loc / hb[s].nx % hb[s].ny) + 2,
                     (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2, nnOf[s], fill, level);
@@ -4388,11 +4431,11 @@ static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::arr
     return 0;
 }
 
-// the factor f of the assembled 7-point matrix of `level` with `fill` levels of fill
-static int pc_setup_build(PcFactor& f, int fill, int level, const double* shift, double turbDiag)
+// the seven points of the assembled stencil in the order of PcTab::sten and the blocks of `level` as the factor kernels see the
+// assembly (vecOff: the first CELL of the block in the PETSc layout); N: the owned cells of the level
+static int pc_level_blocks(int level, int* sten, std::vector<JmBlk>& hb, std::vector<int>& nnOf, long& N)
 {
     const int nS = g_jac.nState;
-    int sten[7];
     for (int q = 0; q < 7; ++q) sten[q] = -1;
     for (int s = 0; s < g_jac.nStencil; ++s) {
         const int* d = g_jac.st[s];               // the column of entry s is the row cell - d
@@ -4408,9 +4451,7 @@ static int pc_setup_build(PcFactor& f, int fill, int level, const double* shift,
     for (auto& kv : g_blocks)
         if (std::get<0>(kv.first) == level) byNN[std::get<2>(kv.first)] = kv.second;
     if (byNN.empty()) return fail("no block registered on level %d", level);
-    std::vector<JmBlk> hb;
-    std::vector<int> nnOf;
-    long N = 0;
+    N = 0;
     for (auto& kv : byNN) {
         Block* b = kv.second;
         const BlkView& v = b->v;
@@ -4432,14 +4473,140 @@ static int pc_setup_build(PcFactor& f, int fill, int level, const double* shift,
         return fail("pc_setup: %ld cells on level %d: a vector of the factor exceeds the 4 GiB the kernels address from one base", N, level);
     // (the factor itself may exceed 4 GiB at any fill: its component planes are reached by 64-bit pointer arithmetic, and the 32-bit
     // byte offset spans the N positions of one plane, which the check above covers)
+    return 0;
+}
+
+// the table of f for N cells at `fill` and the offsets of its off-diagonal slots: what pc_build expects to find
+static int pc_tab_init(PcFactor& f, int fill, long N, const int* sten, std::vector<std::array<int, 3>>& slots)
+{
     PcTab& T = f.tab;
     memset(&T, 0, sizeof T);
     T.ncell = N;
     for (int q = 0; q < 7; ++q) T.sten[q] = sten[q];
     // fill 0 (kernels_pc.hip): the slots -i, -j, -k, +i, +j, +k; asmEnt and tgt stay zero
-    std::vector<std::array<int, 3>> slots = {{-1, 0, 0}, {0, -1, 0}, {0, 0, -1}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    slots = {{-1, 0, 0}, {0, -1, 0}, {0, 0, -1}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
     if (fill > 0 && pc_fill_tables(fill, sten, T, slots)) return 1;
+    return 0;
+}
+
+// the factor f of the assembled 7-point matrix of `level` with `fill` levels of fill
+static int pc_setup_build(PcFactor& f, int fill, int level, const double* shift, double turbDiag)
+{
+    int sten[7];
+    std::vector<JmBlk> hb;
+    std::vector<int> nnOf;
+    long N = 0;
+    std::vector<std::array<int, 3>> slots;
+    if (pc_level_blocks(level, sten, hb, nnOf, N) || pc_tab_init(f, fill, N, sten, slots)) return 1;
     return pc_build(f, level, fill, slots, hb, nnOf, shift, turbDiag);
+}
+
+// ---- the multigrid hierarchy (adflow_gpu_pc_set_mg; kernels_pc_mg.hip) -------------------------------------------------------------
+// The `mg` preconditioner of amg.F90, block-local like the factor: A_1 = the in-block 7-point matrix (+ T), A_{l+1} = P^T A_l P over
+// 2 x 2 x 2 aggregates per block, one block ILU per level (fill of the slot on level 1, fillCoarse below), the cycle of
+// amg.F90:712-759.  Every level keeps the blocks in the order of level 1, natural ordering inside a block.
+static int pc_mg_alloc(PcMg& M, void** p, size_t bytes, const char* what, int mgLevel)
+{
+    *p = nullptr;
+    if (hipMalloc(p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return fail("pc_setup: cannot allocate %zu bytes (%.1f MB) for the %s of multigrid level %d; nothing is kept", bytes,
+                    bytes / 1048576.0, what, mgLevel);
+    }
+    M.raw.push_back(*p);
+    M.bytes += bytes;
+    return 0;
+}
+
+static int pc_mg_setup_build(PcFactor& f, int fill, const PcMgSetting& set, int level, const double* shift, double turbDiag)
+{
+    const int nS = g_jac.nState;
+    int sten[7];
+    std::vector<JmBlk> asmb;
+    std::vector<int> nnOf;
+    long N = 0;
+    if (pc_level_blocks(level, sten, asmb, nnOf, N)) return 1;
+    PcMg* Mp = new PcMg;
+    f.mg = Mp;                                    // from here on pc_release(f) frees whatever the hierarchy holds
+    PcMg& M = *Mp;
+    M.nSmooth = set.nSmooth; M.fillCoarse = set.fillCoarse; M.nnOf = nnOf;
+    for (int q = 0; q < 7; ++q) M.sten.s[q] = sten[q];
+    M.lv.resize(set.levels);
+    const int nb = (int)asmb.size();
+    // the sizes of every level (amg.F90:140-155) and its own box layout: two halo layers, ldi and ldk even
+    for (int l = 0; l < set.levels; ++l) {
+        PcMgLevel& L = M.lv[l];
+        long off = 0;
+        for (int s = 0; s < nb; ++s) {
+            JmBlk q;
+            memset(&q, 0, sizeof q);
+            if (l == 0) { q.nx = asmb[s].nx; q.ny = asmb[s].ny; q.nz = asmb[s].nz; }
+            else {
+                const JmBlk& p = M.lv[l - 1].hb[s];
+                q.nx = (p.nx + 1) / 2; q.ny = (p.ny + 1) / 2; q.nz = (p.nz + 1) / 2;
+            }
+            q.il = q.nx + 1; q.jl = q.ny + 1; q.kl = q.nz + 1; q.ib = q.nx + 3; q.jb = q.ny + 3; q.kb = q.nz + 3;
+            q.ldi = (q.nx + 5) & ~1;
+            q.ldk = q.ldi * (q.ny + 4);
+            q.nbox = (long)q.ldk * (q.nz + 4);
+            q.vecOff = off;
+            if ((double)q.nbox * nS * nS * 8.0 >= 4294967296.0)
+                return fail("pc_setup: block of %ld box cells on multigrid level %d: nState^2 planes exceed the 4 GiB the kernels address "
+                            "from one base", q.nbox, l + 1);
+            off += (long)q.nx * q.ny * q.nz;
+            L.maxnx = std::max(L.maxnx, q.nx); L.maxny = std::max(L.maxny, q.ny); L.maxnz = std::max(L.maxnz, q.nz);
+            L.hb.push_back(q);
+        }
+        L.ncell = off;
+        // the coarsening launch carries the nState^2 block components above the j tiles of the coarse level in gridDim.y
+        if (l > 0 && (long)((L.maxny + 3) / 4) * nS * nS > 65535)
+            return fail("pc_setup: multigrid level %d has a block of %d cells along j: the coarsening launch takes at most %d",
+                        l + 1, L.maxny, 4 * (65535 / (nS * nS)));
+        if (l > 0 && L.ncell == M.lv[l - 1].ncell)
+            return fail("pc_setup: multigrid level %d would have the %ld cells of level %d (every block is 1 x 1 x 1 there): ask for at "
+                        "most %d levels; nothing is kept", l + 1, L.ncell, l, l);
+    }
+    // matrices (zeroed: the halo layers and the second half of a pair past the end of a row are loaded, never used), tables, vectors
+    for (int l = 0; l < set.levels; ++l) {
+        PcMgLevel& L = M.lv[l];
+        size_t nd = 0;
+        for (auto& q : L.hb) nd += (size_t)7 * nS * nS * q.nbox;
+        double* mat = nullptr;
+        if (pc_mg_alloc(M, (void**)&mat, nd * sizeof(double), "matrix", l + 1)) return 1;
+        HIPCHK(hipMemsetAsync(mat, 0, nd * sizeof(double), g_stream));
+        size_t at = 0;
+        for (auto& q : L.hb) {
+            q.jac = mat + at;
+            at += (size_t)7 * nS * nS * q.nbox;
+        }
+        if (pc_mg_alloc(M, (void**)&L.dtab, sizeof(JmBlk) * nb, "block table", l + 1)) return 1;
+        HIPCHK(hipMemcpy(L.dtab, L.hb.data(), sizeof(JmBlk) * nb, hipMemcpyHostToDevice));
+        for (int v = 0; v < 4; ++v)
+            if (pc_mg_alloc(M, (void**)&L.v[v], (size_t)L.ncell * nS * sizeof(double), "vectors", l + 1)) return 1;
+    }
+    // level 1: the copy of the in-block blocks with T on the diagonal, then its factor -- of the copy, so without a shift
+    {
+        DevBuf src;
+        if (hipMalloc(&src.p, sizeof(JmBlk) * nb) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("pc_setup: cannot allocate %zu bytes for the block table of the assembly; nothing is kept", sizeof(JmBlk) * nb);
+        }
+        HIPCHK(hipMemcpy(src.p, asmb.data(), sizeof(JmBlk) * nb, hipMemcpyHostToDevice));
+        PcMgLevel& L = M.lv[0];
+        launch_mg_fine_copy((const JmBlk*)src.p, L.dtab, nb, L.maxnx, L.maxny, L.maxnz, nS, M.sten, shift, turbDiag, N, g_stream);
+        HIPCHK(hipStreamSynchronize(g_stream));   // the table of the assembly is freed on return
+    }
+    std::vector<std::array<int, 3>> slots;
+    if (pc_tab_init(f, fill, N, sten, slots) || pc_build(f, level, fill, slots, M.lv[0].hb, nnOf, nullptr, 0.0, 1)) return 1;
+    for (int l = 1; l < set.levels; ++l) {
+        PcMgLevel &F = M.lv[l - 1], &C = M.lv[l];
+        launch_mg_coarsen(F.dtab, C.dtab, nb, C.maxnx, C.maxny, C.maxnz, nS, M.sten, g_stream);
+        if (pc_tab_init(C.fac, set.fillCoarse, C.ncell, sten, slots) ||
+            pc_build(C.fac, level, set.fillCoarse, slots, C.hb, nnOf, nullptr, 0.0, l + 1))
+            return 1;
+    }
+    return 0;
 }
 
 static int pc_setup_check(const char* who, int level)
@@ -4459,7 +4626,9 @@ static int pc_setup_selected(int level, const double* shift = nullptr, double tu
     PcFactor& f = pc_sel();
     HIPCHK(hipStreamSynchronize(g_stream));
     (void)pc_release(f);
-    if (pc_setup_build(f, g_pc_fill[g_pc_slot], level, shift, turbDiag)) {
+    const PcMgSetting& mg = g_pc_mg[g_pc_slot];
+    if (mg.levels > 1 ? pc_mg_setup_build(f, g_pc_fill[g_pc_slot], mg, level, shift, turbDiag)
+                      : pc_setup_build(f, g_pc_fill[g_pc_slot], level, shift, turbDiag)) {
         if (g_stream) (void)hipStreamSynchronize(g_stream);
         (void)pc_release(f);
         return 1;
@@ -4478,7 +4647,7 @@ int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes)
     if (!pc_sel().valid) return fail("pc_info: no factor (call adflow_gpu_pc_setup first)");
     if (nState) *nState = pc_sel().nState;
     if (nPlanes) *nPlanes = pc_sel().nPlanes;
-    if (bytes) *bytes = (int64_t)pc_sel().bytes;
+    if (bytes) *bytes = (int64_t)pc_bytes(pc_sel());
     return 0;
 }
 
@@ -4500,6 +4669,60 @@ int adflow_gpu_pc_set_fill(int fill)
     return 0;
 }
 
+int adflow_gpu_pc_set_mg(int levels, int nSmooth, int fillCoarse)
+{
+    if (levels < 1 || levels > 10)
+        return fail("pc_set_mg: %d levels; the hierarchy takes 1 (no multigrid) to 10 levels (coarseRows(2:10) of amg.F90)", levels);
+    if (nSmooth < 1) return fail("pc_set_mg: nSmooth = %d; the smoother takes at least one iteration", nSmooth);
+    if (fillCoarse < 0 || fillCoarse > 2)
+        return fail("pc_set_mg: fillCoarse = %d; the block ILU of the coarse levels takes 0, 1 or 2 levels of fill", fillCoarse);
+    g_pc_mg[g_pc_slot].levels = levels;
+    g_pc_mg[g_pc_slot].nSmooth = nSmooth;
+    g_pc_mg[g_pc_slot].fillCoarse = fillCoarse;
+    return 0;
+}
+
+int adflow_gpu_pc_mg_info(int32_t* levels, int32_t* nSmooth, int32_t* fillCoarse, int64_t* cells)
+{
+    const PcFactor& f = pc_sel();
+    if (!f.valid) return fail("pc_mg_info: no factor (call adflow_gpu_pc_setup first)");
+    if (levels) *levels = f.mg ? (int32_t)f.mg->lv.size() : 1;
+    if (nSmooth) *nSmooth = f.mg ? f.mg->nSmooth : 1;
+    if (fillCoarse) *fillCoarse = f.mg ? f.mg->fillCoarse : 0;
+    if (cells) {
+        if (!f.mg) cells[0] = f.ncell;
+        else
+            for (size_t l = 0; l < f.mg->lv.size(); ++l) cells[l] = f.mg->lv[l].ncell;
+    }
+    return 0;
+}
+
+int adflow_gpu_pc_mg_download(int mgLevel, int nn, double* blocks)
+{
+    const PcFactor& f = pc_sel();
+    if (!f.valid) return fail("pc_mg_download: no factor (call adflow_gpu_pc_setup first)");
+    if (!f.mg) return fail("pc_mg_download: the factor of the selected slot has no hierarchy (adflow_gpu_pc_set_mg with levels > 1 first)");
+    const PcMg& M = *f.mg;
+    if (mgLevel < 1 || mgLevel > (int)M.lv.size())
+        return fail("pc_mg_download: multigrid level %d; the hierarchy has the levels 1 .. %d", mgLevel, (int)M.lv.size());
+    if (!blocks) return fail("pc_mg_download: blocks is NULL");
+    const PcMgLevel& L = M.lv[mgLevel - 1];
+    size_t s = 0;
+    while (s < M.nnOf.size() && M.nnOf[s] != nn) ++s;
+    if (s == M.nnOf.size()) return fail("pc_mg_download: block %d is not part of the hierarchy", nn);
+    const JmBlk& q = L.hb[s];
+    const size_t ncomp = (size_t)7 * f.nState * f.nState;
+    std::vector<double> box(ncomp * q.nbox);
+    HIPCHK(hipStreamSynchronize(g_stream));
+    HIPCHK(hipMemcpy(box.data(), q.jac, box.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < ncomp; ++e)
+        for (int k = 0; k < q.nz; ++k)
+            for (int j = 0; j < q.ny; ++j)
+                for (int i = 0; i < q.nx; ++i)
+                    blocks[((e * q.nz + k) * q.ny + j) * q.nx + i] = box[e * q.nbox + (i + 2) + (long)(j + 2) * q.ldi + (long)(k + 2) * q.ldk];
+    return 0;
+}
+
 int adflow_gpu_pc_release(int64_t* bytes)
 {
     if (g_stream) HIPCHK(hipStreamSynchronize(g_stream));
@@ -4509,11 +4732,58 @@ int adflow_gpu_pc_release(int64_t* bytes)
 }
 
 // z = M^-1 r or M^-T r with the selected factor, whatever its fill, for nv = 1 .. PC_MAXW columns ldr / ldz apart in the same launches
+static int pc_factor_apply(const PcFactor& f, int transpose, const double* r, double* z, hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0)
+{
+    if (f.fill > 0) return launch_pcf_apply(f.tab, f.nState, f.nEnt, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
+    return launch_pc_apply(f.tab, f.nState, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
+}
+
+// The smoother of level l (0-based) of the hierarchy of f: Richardson from zero, nSmooth iterations, one ILU application each
+// (setupShellPC):  x = M^-1 b,  then  x += M^-1 (b - A x).  t: a vector of the level that is free; the sweep turns it into the
+// correction in place (the forward sweep has read all of its input before the backward sweep writes the first output).
+static int pc_mg_smooth(const PcFactor& f, int l, int transpose, const double* b, double* x, double* t, hipStream_t s)
+{
+    const PcMg& M = *f.mg;
+    const PcMgLevel& L = M.lv[l];
+    const PcFactor& fac = l == 0 ? f : L.fac;
+    const int nb = (int)L.hb.size();
+    if (pc_factor_apply(fac, transpose, b, x, s)) return 1;
+    for (int it = 1; it < M.nSmooth; ++it) {
+        launch_mg_residual(L.dtab, nullptr, nb, L.maxnx, L.maxny, L.maxnz, f.nState, transpose, M.sten, b, x, nullptr, t, s);
+        if (pc_factor_apply(fac, transpose, t, t, s)) return 1;
+        launch_gm_axpby(x, 1.0, t, 1.0, L.ncell * f.nState, s);
+    }
+    return 0;
+}
+
+// y = MG(r, l) of amg.F90:712-759 for level l (0-based) of the hierarchy of f, which is not its last one: the coarse level first, the
+// smoother of this level afterwards.  Launches on s only; the vectors are those of the levels (no allocation, no synchronise).
+//   launches: restriction, the cycle or the smoother below, prolongation fused with the residual, the smoother, y += x
+static int pc_mg_cycle(const PcFactor& f, int l, int transpose, const double* r, double* y, hipStream_t s)
+{
+    const PcMg& M = *f.mg;
+    const PcMgLevel &F = M.lv[l], &C = M.lv[l + 1];
+    const int nb = (int)F.hb.size(), nS = f.nState;
+    launch_mg_restrict(F.dtab, C.dtab, nb, C.maxnx, C.maxny, C.maxnz, nS, r, C.v[0], s);
+    if (l + 2 == (int)M.lv.size() ? pc_mg_smooth(f, l + 1, transpose, C.v[0], C.v[1], C.v[2], s)
+                                  : pc_mg_cycle(f, l + 1, transpose, C.v[0], C.v[1], s))
+        return 1;
+    launch_mg_residual(F.dtab, C.dtab, nb, F.maxnx, F.maxny, F.maxnz, nS, transpose, M.sten, r, C.v[1], y, F.v[2], s);
+    // r is dead from here: below level 1 it is v[0] of this level, which the smoother may use; level 1 has a v[0] of its own
+    if (pc_mg_smooth(f, l, transpose, F.v[2], F.v[3], F.v[0], s)) return 1;
+    launch_gm_axpby(y, 1.0, F.v[3], 1.0, F.ncell * nS, s);
+    return 0;
+}
+
+// The one place an application of the selected slot is dispatched: the cycle of its hierarchy, or its factor
 static int pc_apply_enqueue(int transpose, const double* r, double* z, hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0)
 {
     const PcFactor& f = pc_sel();
-    if (f.fill > 0) return launch_pcf_apply(f.tab, f.nState, f.nEnt, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
-    return launch_pc_apply(f.tab, f.nState, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
+    if (f.mg) {
+        if (nv != 1) return fail("pc_apply: internal: the multigrid cycle takes one vector");
+        return pc_mg_cycle(f, 0, transpose, r, z, s);
+    }
+    return pc_factor_apply(f, transpose, r, z, s, nv, ldr, ldz);
 }
 
 // The work space of the selected factor for nv vectors at once: the part beyond the first vector is allocated at the first
@@ -4548,7 +4818,8 @@ static int pc_apply_multi_enqueue(const char* who, int transpose, int nvec, cons
 {
     // fill 2: one column per chain of launches, the kernels of the single entry -- its sweeps of several vectors are not shipped
     // (kernels_pc_fill.hip), so there the multi entry costs what the single calls cost
-    const int width = pc_sel().fill == 2 ? 1 : (int)PC_MAXW;
+    // a hierarchy: one column per cycle as well (a cycle of several vectors is not built)
+    const int width = (pc_sel().fill == 2 || pc_sel().mg) ? 1 : (int)PC_MAXW;
     if (pc_ws_reserve(who, std::min(width, nvec))) return 1;
     for (int c = 0; c < nvec; c += width)
         if (pc_apply_enqueue(transpose, r + c * ldr, z + c * ldz, s, std::min(width, nvec - c), ldr, ldz)) return 1;

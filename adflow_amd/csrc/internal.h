@@ -449,6 +449,19 @@ int launch_pc_apply(const PcTab& T, int nState, int transpose, const std::vector
 int launch_pcf_factor(const PcTab& T, int nState, int nEnt, const std::vector<int>& levelStart, hipStream_t s);
 int launch_pcf_apply(const PcTab& T, int nState, int nEnt, int transpose, const std::vector<int>& levelStart, const double* r,
                      double* z, hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0);
+// the multigrid preconditioner (kernels_pc_mg.hip): every level keeps its 7-point matrix in the box layout of JmBlk (jac = the blocks
+// of the level, vecOff = the first CELL of the block in the vectors of the level) with the stencil entries of the assembly;
+// PcMgSten: those entries in the order of PcTab::sten.  Tables hold one JmBlk per block, the same slot on every level; maxn*: the
+// largest extents of the level the lanes run over
+struct PcMgSten { int s[7]; };
+void launch_mg_fine_copy(const JmBlk* src, const JmBlk* dst, int nslots, int maxnx, int maxny, int maxnz, int nState, const PcMgSten& S,
+                         const double* tsm, double turbDiag, long N, hipStream_t s);
+void launch_mg_coarsen(const JmBlk* fine, const JmBlk* coarse, int nslots, int maxnx, int maxny, int maxnz, int nState, const PcMgSten& S,
+                       hipStream_t s);
+void launch_mg_restrict(const JmBlk* fine, const JmBlk* coarse, int nslots, int maxnx, int maxny, int maxnz, int nState, const double* r,
+                        double* rhs, hipStream_t s);
+void launch_mg_residual(const JmBlk* tab, const JmBlk* coarse, int nslots, int maxnx, int maxny, int maxnz, int nState, int transpose,
+                        const PcMgSten& S, const double* r, const double* x, double* y, double* res, hipStream_t s);
 // the vectors of GMRES: one step of modified Gram-Schmidt per launch (partial sums in, partial sums out), see kernels_pc.hip
 enum { GM_PARTS = 256 };  // the most partial sums one reduction leaves (GM_T of kernels_pc.hip): the size of a buffer of them
 int gm_groups(long n);

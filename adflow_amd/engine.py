@@ -201,6 +201,32 @@ class Engine:
         self._chk(self.lib.adflow_gpu_pc_info2(ctypes.byref(f), ctypes.byref(ne), ctypes.byref(nl)))
         return int(f.value), int(ne.value), int(nl.value)
 
+    def pcSetMg(self, levels: int, nSmooth: int = 1, fillCoarse: int = 0):
+        """the multigrid preconditioner of amg.F90 (precondType = 'mg') for the next pcSetup / ankPcSetup of the selected slot: `levels`
+        levels of 2 x 2 x 2 aggregates per block (1: the plain factor), nSmooth Richardson iterations of the ILU smoother per level,
+        fillCoarse levels of fill on the levels below the first (the first keeps pcSetFill's)"""
+        self._chk(self.lib.adflow_gpu_pc_set_mg(int(levels), int(nSmooth), int(fillCoarse)))
+
+    def pcMgInfo(self):
+        """(levels, nSmooth, fillCoarse, cells of every level) of the factor or hierarchy of the selected slot"""
+        lv, nsm, fc = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        self._chk(self.lib.adflow_gpu_pc_mg_info(ctypes.byref(lv), ctypes.byref(nsm), ctypes.byref(fc), None))
+        cells = np.zeros(lv.value, dtype=np.int64)
+        self._chk(self.lib.adflow_gpu_pc_mg_info(None, None, None, cells.ctypes.data))
+        return int(lv.value), int(nsm.value), int(fc.value), tuple(int(c) for c in cells)
+
+    def pcMgMatrix(self, mgLevel: int, nn=1, level=1, sps=1):
+        """(nx_l, ny_l, nz_l, nState, nState, 7): the blocks of block nn on level mgLevel of the hierarchy, laid out as jacobianBlocks;
+        mgLevel = 1 is the owned copy of the in-block blocks (T included)"""
+        ns = self.pcInfo()[0]
+        blk = self.blocks[(nn, level, sps)]
+        d = [blk.nx, blk.ny, blk.nz]
+        for _ in range(int(mgLevel) - 1):
+            d = [(n + 1) // 2 for n in d]
+        out = np.zeros((d[0], d[1], d[2], ns, ns, 7), order="F")
+        self._chk(self.lib.adflow_gpu_pc_mg_download(int(mgLevel), nn, out.ctypes.data))
+        return out
+
     def pcApply(self, r, level=1, transpose=False):
         """z = M^-1 r, or M^-T r with transpose, for the factor of pcSetup; vectors as for jacobianMult"""
         r = np.ascontiguousarray(r, dtype=np.float64)

@@ -353,6 +353,22 @@ module adflowGpuShim
             import :: c_int, c_int32_t
             integer(c_int32_t), intent(out) :: fill, nEntries, nLevelSets
         end function
+        ! the multigrid preconditioner of amg.F90 (precondType = 'mg') for the next setup of the selected slot: AMGLevels, AMGNSmooth and
+        ! the fill of the coarse levels; what the selected slot holds; the blocks of one block on one level (nx_l, ny_l, nz_l, nState, nState, 7)
+        integer(c_int) function adflow_gpu_pc_set_mg(levels, nSmooth, fillCoarse) bind(C, name="adflow_gpu_pc_set_mg")
+            import :: c_int
+            integer(c_int), value :: levels, nSmooth, fillCoarse
+        end function
+        integer(c_int) function adflow_gpu_pc_mg_info(levels, nSmooth, fillCoarse, cells) bind(C, name="adflow_gpu_pc_mg_info")
+            import :: c_int, c_int32_t, c_int64_t
+            integer(c_int32_t), intent(out) :: levels, nSmooth, fillCoarse
+            integer(c_int64_t), intent(out) :: cells(*)
+        end function
+        integer(c_int) function adflow_gpu_pc_mg_download(mgLevel, nn, blocks) bind(C, name="adflow_gpu_pc_mg_download")
+            import :: c_int, c_double
+            integer(c_int), value :: mgLevel, nn
+            real(c_double), intent(out) :: blocks(*)
+        end function
         integer(c_int) function adflow_gpu_pc_apply(level, transpose, r, z, n) bind(C, name="adflow_gpu_pc_apply")
             import :: c_int, c_long, c_double
             integer(c_int), value :: level, transpose
@@ -1004,6 +1020,14 @@ contains
         integer(kind=intType), intent(in) :: fill
         call gpuCheck(adflow_gpu_pc_set_fill(int(fill, c_int)), "gpuPCSetFill")
     end subroutine gpuPCSetFill
+
+    ! precondType = 'mg' (setupAMG / setupShellPC / applyShellPC of amg.F90): the next gpuPCSetup / gpuANKPCSetup of the selected slot
+    ! builds `levels` levels (ANKAMGLevels, NKAMGLevels, adjointAMGLevels) smoothed nSmooth times (...AMGNSmooth) with an ILU of
+    ! fillCoarse levels of fill below the first level; levels = 1 is the plain factor
+    subroutine gpuPCSetMG(levels, nSmooth, fillCoarse)
+        integer(kind=intType), intent(in) :: levels, nSmooth, fillCoarse
+        call gpuCheck(adflow_gpu_pc_set_mg(int(levels, c_int), int(nSmooth, c_int), int(fillCoarse, c_int)), "gpuPCSetMG")
+    end subroutine gpuPCSetMG
 
     ! the body of a PCSHELL's apply (transposed = .false.) / applyTranspose (.true.): rDev, zDev are the device arrays of the two
     ! PETSc vectors (VECHIP), n their local size

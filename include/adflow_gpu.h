@@ -533,6 +533,45 @@ int adflow_gpu_pc_release(int64_t* bytes);
  * selected slot (each slot keeps its own fill);
  * adflow_gpu_block_release and _release_all release both.  A process that never calls it behaves as with one slot. */
 int adflow_gpu_pc_select(int slot);
+/* Multigrid preconditioner: the `mg` preconditioner of the reference (precondType = 'mg', amg.F90; ANKAMGLevels, NKAMGLevels,
+ * adjointAMGLevels default 2, ...AMGNSmooth default 1), block-local like the factor.  A = the matrix the factor is built from: the
+ * assembled 7-point matrix restricted to the columns inside the row's own block, with the pseudo-time term T on the diagonal blocks
+ * when the setup is adflow_gpu_ank_pc_setup.  Levels l = 1 .. L, level 1 the fine one:
+ *   sizes       per block and direction n -> n/2 if even, (n+1)/2 if odd, 1 stays 1 (amg.F90:140-155)
+ *   aggregates  the fine cell (i, j, k), 0-based, of a block belongs to the coarse cell (i/2, j/2, k/2) of the same block (:222-226);
+ *               the blocks follow each other in the vectors of every level in the order of level 1, natural ordering inside a block
+ *   matrices    A_{l+1} = P^T A_l P, P the piecewise-constant prolongation: the plain sum of the reference's MatSetValuesBlocked(...,
+ *               ADD_VALUES) on the coarse indices (adjointUtils.F90:683-710).  7-point again: the diagonal block of a coarse cell is
+ *               the sum of its children's diagonal blocks and of every entry between two of them, the entry towards a neighbouring
+ *               aggregate the sum of the children's entries across that face -- summed in one fixed order
+ *   smoother    S_l(b) (setupShellPC: Richardson from zero, nSmooth iterations, one local ILU application each):  x = M_l^-1 b, then
+ *               nSmooth - 1 times x += M_l^-1 (b - A_l x);  M_l = the block ILU of A_l in the natural ordering, with the fill of the
+ *               slot (adflow_gpu_pc_set_fill) on level 1 and fillCoarse on the levels below
+ *   cycle       MG(r, k) (amg.F90:712-759):  rhs = P^T r;  sol = S_{k+1}(rhs) if k + 1 = L, else MG(rhs, k + 1);  y = P sol;
+ *               res = r - A_k y;  y += S_k(res).  The preconditioner is z = MG(r, 1): the coarse level first, smoothing afterwards.
+ *   transpose   the same cycle on A^T, with A_l^T and M_l^-T everywhere (the reference assembles the transposed matrices into the same
+ *               hierarchy); it is NOT the transpose of the cycle.
+ * outerPreConIts and innerPreConIts[Coarse] are 1.  Out of scope: couplings across blocks and ranks, ASM overlap, the RCM ordering.
+ * adflow_gpu_pc_set_mg(levels, nSmooth, fillCoarse) sets what the next adflow_gpu_pc_setup / _ank_pc_setup of the SELECTED slot
+ * builds; each slot keeps its own setting, like its fill.  levels = 1 (the default) is the plain factor, with nSmooth and fillCoarse
+ * ignored.  Errors: levels outside 1 .. 10, nSmooth < 1, fillCoarse outside 0 .. 2.  With levels > 1 the setup builds the hierarchy
+ * into the slot; it is an error, naming the level, when level l + 1 would have as many cells as level l (every block is 1 x 1 x 1
+ * there); a singular pivot block names the multigrid level as well as block and cell; an allocation that fails names its size; nothing
+ * is kept on failure.  The slot owns all the cycle needs: a copy of the fine in-block blocks (T included; the assembled blocks are
+ * overwritten by the next assembly), the coarse matrices, one factor per level and four vectors per level.  adflow_gpu_pc_info counts
+ * all of it (nPlanes: the level sets of the level-1 factor), adflow_gpu_pc_release, _block_release and _release_all free it,
+ * adflow_gpu_release_workspace does not touch it.  Everything that takes a factor takes a hierarchy: adflow_gpu_pc_apply[_dev],
+ * _gmres_solve[_dev], _ank_solve[_dev]; an application launches on the library's stream only, allocates nothing and does not
+ * synchronise (the _dev form stays enqueue-only under adflow_gpu_set_async(1)).  The _multi entries serve the columns of a hierarchy
+ * ONE AT A TIME through the single cycle, as they do at fill 2: they cost what the single calls cost.
+ * adflow_gpu_pc_mg_info: levels, nSmooth, fillCoarse of the selected slot's factor (1, 1, 0 for a plain factor) and the cells of every
+ * level (cells: `levels` entries; each pointer may be NULL); an error without a factor.
+ * adflow_gpu_pc_mg_download: the blocks of block nn on multigrid level mgLevel, blocks(nx_l, ny_l, nz_l, nState, nState, 7)
+ * column-major with the stencil order of adflow_gpu_jacobian_info -- the layout of adflow_gpu_download_jacobian; mgLevel = 1 is the
+ * owned fine copy (entries whose column lies outside the block are zero).  An error without a hierarchy. */
+int adflow_gpu_pc_set_mg(int levels, int nSmooth, int fillCoarse);
+int adflow_gpu_pc_mg_info(int32_t* levels, int32_t* nSmooth, int32_t* fillCoarse, int64_t* cells);
+int adflow_gpu_pc_mg_download(int mgLevel, int nn, double* blocks);
 /* Restarted GMRES with the factor as RIGHT preconditioner, the KSPSolve of solveAdjoint (adjointAPI.F90:661-863) with the settings
  * of setupStandardKSP (adjointUtils.F90:1374-1562: KSPGMRES, PC_RIGHT, modified Gram-Schmidt):  A M^-1 u = b, x = M^-1 u, with
  * A = adflow_gpu_jacobian_mult on the matrix assembled last (7-, 13-, 27- or 33-point) and M = the factor of adflow_gpu_pc_setup,

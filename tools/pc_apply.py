@@ -7,7 +7,12 @@ matrix itself: iterations and ms to reduce the residual by --rtol (default 1e-8)
 --nvec N adds, in the same process: Z = M^-1 R and M^-T R for N columns through adflow_gpu_pc_apply_multi_dev (one call) against N
 calls of adflow_gpu_pc_apply_dev, with the time per launch and the GB/s on the factor of the multi call, and the wall time of GMRES
 for N right-hand sides through adflow_gpu_gmres_solve_multi_dev against N calls of adflow_gpu_gmres_solve_dev.
-usage: pc_apply.py [--fill 0|1|2] [--rtol 1e-8] [--nvec N] [n] [nx ny nz]   (n timed applications of each kind, default 10)"""
+--mg L [--nsmooth N --fill-coarse F] makes the setup a multigrid hierarchy of L levels (adflow_gpu_pc_set_mg: the cycle of amg.F90,
+N Richardson iterations of the ILU smoother per level, fill F below the first level): the same lines, with the cells of every level,
+the bytes the hierarchy holds and the launches of one cycle; floor_bytes is then one pass over the matrix and the factor of every
+level per smoothing iteration.  Without --mg nothing changes.
+usage: pc_apply.py [--fill 0|1|2] [--mg L [--nsmooth N] [--fill-coarse F]] [--rtol 1e-8] [--nvec N] [n] [nx ny nz]
+       (n timed applications of each kind, default 10)"""
 import json
 import os
 import sys
@@ -25,13 +30,20 @@ WALL = {1: -6, 2: -6, 3: -1, 4: -1, 5: -3, 6: -6}
 def main():
     import torch
     argv, fill, rtol, nvec = list(sys.argv[1:]), 0, 1e-8, 0
-    for opt in ("--fill", "--rtol", "--nvec"):
+    mg, nsmooth, fillc = 1, 1, 0
+    for opt in ("--fill", "--rtol", "--nvec", "--mg", "--nsmooth", "--fill-coarse"):
         if opt in argv:
             at = argv.index(opt)
             if opt == "--fill":
                 fill = int(argv[at + 1])
             elif opt == "--nvec":
                 nvec = int(argv[at + 1])
+            elif opt == "--mg":
+                mg = int(argv[at + 1])
+            elif opt == "--nsmooth":
+                nsmooth = int(argv[at + 1])
+            elif opt == "--fill-coarse":
+                fillc = int(argv[at + 1])
             else:
                 rtol = float(argv[at + 1])
             del argv[at:at + 2]
@@ -56,6 +68,8 @@ def main():
     if fill:                                              # (a library without the entry point still serves fill 0)
         eng.pcSetFill(fill)
     floor = {0: 7, 1: 13, 2: 23}[fill] * ns * ns * 8 * cells
+    if mg > 1:
+        eng.pcSetMg(mg, nsmooth, fillc)
     eng.pcSetup(1)                                        # warm-up (allocations, tables)
     eng.sync()
     eng.event_record(1)
@@ -65,6 +79,8 @@ def main():
     _, planes, nbytes = eng.pcInfo()
     print(json.dumps({"what": "pc_setup (tables, allocation, factorisation)", "dims": list(dims), "nState": ns, "ms": round(eng.event_elapsed_ms(1, 2), 3),
                       "fill": fill, "hyperplanes_or_level_sets": planes, "factor_bytes": nbytes}), flush=True)
+    if mg > 1:
+        planes, floor = cycle_cost(eng, dims, ns, fill, planes)
     gen = torch.Generator(device="cuda").manual_seed(5)
     x = torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 0.5
     y = torch.empty_like(x)
@@ -85,7 +101,7 @@ def main():
             ms = eng.event_elapsed_ms(1, 2) / n_it
             ms_of[what] = ms
             print(json.dumps({"what": what, "ms": round(ms, 4), "floor_bytes": floor, "TB_per_s": round(floor / (ms * 1e-3) / 1e12, 3),
-                              "launches": launches, "ratio_to_J_x": round(ms / ms_of["J x"], 2),
+                              "launches": int(launches), "ratio_to_J_x": round(ms / ms_of["J x"], 2),
                               "checksum": float(y.abs().sum().item())}), flush=True)
     finally:
         eng.set_async(False)
@@ -104,6 +120,27 @@ def main():
     eng.pcRelease()
     eng.releaseWorkspace()
     eng.close()
+
+
+def cycle_cost(eng, dims, ns, fill, planes1):
+    """half the launches of one cycle (the callers print 2 x) and its byte floor, from the sizes adflow_gpu_pc_mg_info reports: per
+    level nSmooth ILU applications (two sweeps over the level sets each) and nSmooth passes over the 7-point matrix (the fused
+    prolongation / residual or the residual of a Richardson iteration; none for the first iteration of the last level); per level but
+    the last the restriction, the fused pass and y += x, and a residual and x += d per further Richardson iteration"""
+    levels, nsmooth, fillc, cells = eng.pcMgInfo()
+    ent = {0: 7, 1: 13, 2: 23}
+    sets = {0: lambda a, b, c: a + b + c - 2, 1: lambda a, b, c: a + 2 * b + 3 * c - 5, 2: lambda a, b, c: a + 3 * b + 7 * c - 10}
+    launches, floor, d = 0, 0, list(dims)
+    for l in range(levels):
+        f = fill if l == 0 else fillc
+        npl = planes1 if l == 0 else sets[f](*d)
+        last = l == levels - 1
+        launches += 2 * npl * nsmooth + (0 if last else 3) + 2 * (nsmooth - 1)
+        floor += cells[l] * ns * ns * 8 * (ent[f] * nsmooth + 7 * (nsmooth - (1 if last else 0)))
+        d = [(a + 1) // 2 for a in d]
+    print(json.dumps({"what": "hierarchy", "levels": levels, "nSmooth": nsmooth, "fillCoarse": fillc, "cells": list(cells),
+                      "launches_per_cycle": launches, "floor_bytes_per_cycle": floor}), flush=True)
+    return launches / 2, floor
 
 
 def multi_columns(eng, torch, gen, n, nvec, n_it, fill, planes, floor, rtol):
