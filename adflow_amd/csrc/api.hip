@@ -4150,6 +4150,8 @@ struct PcFactor {
     bool valid = false;
     int level = 0, nState = 0, nPlanes = 0;      // nPlanes: hyperplanes at fill 0, dependency level sets at fill 1 and 2
     int fill = 0, nEnt = 7;                        // levels of fill the factor was built with and its entries per row
+    int coupled = 0;                  // adflow_gpu_pc_set_coupled: 1 = one subdomain for the level (kernels_pc_coupled.hip)
+    long nCross = 0;                  // entries of M whose column lies behind a block interface (coupled only)
     long ncell = 0;
     int wsWidth = 1;                  // vectors the work space serves at once: tab.ws, and tab.wsx for the others (pc_ws_reserve)
     size_t bytes = 0;
@@ -4181,6 +4183,7 @@ PcMgSetting g_pc_mg[2];              // adflow_gpu_pc_set_mg: what the next setu
 PcFactor g_pc_slots[2];              // adflow_gpu_pc_select: e.g. the flow factor and the turbulence factor of ANK_jacobianLag
 int g_pc_slot = 0;
 int g_pc_fill[2] = {0, 0};           // adflow_gpu_pc_set_fill: the fill the next setup of each slot uses (outlives the factors)
+int g_pc_coupled[2] = {0, 0};        // adflow_gpu_pc_set_coupled: 1 = the next setup of the slot factors the whole level as one subdomain
 static PcFactor& pc_sel() { return g_pc_slots[g_pc_slot]; }
 struct DevBuf {                       // a device allocation that lives as long as one call
     void* p = nullptr;
@@ -4320,8 +4323,12 @@ static int pc_fill_tables(int fill, const int* sten7, PcTab& T, std::vector<std:
 // neighbours directly: the tables are those of the generic loops, which cost its table build a third more time.
 // shift != NULL: the pseudo-time term of ANK (tsm of kernels_ank.hip) is added to the diagonal blocks as the factorisation reads them
 // mgLevel > 0: hb are the blocks of that level of a multigrid hierarchy (their own box layout and matrix), named in the message
+// ccol != NULL (fill 0 only): one subdomain for the level (kernels_pc_coupled.hip).  ccol[d N + c] is the natural number of the column
+// of slot d of cell c in whichever block it lies (pc_coupled_columns), -1: none.  A neighbour is lower when its number is smaller;
+// the sets are the longest path over the lower neighbours of the whole level, and the word of every cell (PcTab::cw) goes with nbr[].
 static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::array<int, 3>>& slots, const std::vector<JmBlk>& hb,
-                    const std::vector<int>& nnOf, const double* shift, double turbDiag, int mgLevel = 0)
+                    const std::vector<int>& nnOf, const double* shift, double turbDiag, int mgLevel = 0,
+                    const std::vector<int>* ccol = nullptr)
 {
     const int nS = g_jac.nState, nOff = (int)slots.size(), nLow = nOff / 2, nEnt = nOff + 1;
     PcTab& T = f.tab;
@@ -4340,7 +4347,13 @@ static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::arr
             for (int j = 0; j < q.ny; ++j)
                 for (int i = 0; i < q.nx; ++i, ++nat) {
                     int l = i + j + k;            // what the longest path gives at fill 0, without walking it
-                    if (fill > 0) {
+                    if (ccol) {
+                        l = 0;
+                        for (int e = 0; e < nOff; ++e) {
+                            const long c = (*ccol)[(size_t)e * N + nat];
+                            if (c >= 0 && c < nat) l = std::max(l, lvl[c] + 1);
+                        }
+                    } else if (fill > 0) {
                         l = 0;
                         for (int e = 0; e < nLow; ++e) {
                             const long c = column(q, nat, i, j, k, e);
@@ -4355,6 +4368,7 @@ static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::arr
     for (long c = 0; c < N; ++c) start[lvl[c] + 1]++;
     for (int p = 0; p < nSets; ++p) start[p + 1] += start[p];
     std::vector<int> cur(start.begin(), start.end() - 1), pos(N), nbr((size_t)nOff * N), vec(N), cblk(N), cbox(N);
+    std::vector<unsigned> cw(ccol ? N : 0);
     for (size_t s = 0; s < hb.size(); ++s) {
         const JmBlk& q = hb[s];
         long nat = q.vecOff;
@@ -4375,6 +4389,23 @@ static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::arr
             for (int j = 0; j < q.ny; ++j)
                 for (int i = 0; i < q.nx; ++i, ++nat) {
                     const long at = pos[nat];
+                    if (ccol) {
+                        unsigned w = 0;
+                        for (int e = 0; e < nOff; ++e) {
+                            const long c = (*ccol)[(size_t)e * N + nat];
+                            nbr[(size_t)e * N + at] = c >= 0 ? pos[c] : -1;
+                            if (c < 0) continue;
+                            if (c < nat) w |= 1u << e;
+                            // the way back: the opposite direction inside a block, any across an interface (pc_coupled_columns has
+                            // checked that there is exactly one)
+                            int b = (e + 3) % 6, tries = 0;
+                            while ((*ccol)[(size_t)b * N + c] != nat && ++tries < 6) b = (b + 1) % 6;
+                            if (tries == 6) return fail("pc_setup: internal: a column of the level does not lead back to its row");
+                            w |= (unsigned)b << (6 + 3 * e);
+                        }
+                        cw[at] = w;
+                        continue;
+                    }
                     if (fill == 0) {              // the six neighbours directly (-i, -j, -k, +i, +j, +k): the generic loop below
                         nbr[0 * N + at] = i > 0 ? pos[nat - 1] : -1;      // gives the same table a third slower
                         nbr[1 * N + at] = j > 0 ? pos[nat - sj] : -1;
@@ -4390,8 +4421,13 @@ static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::arr
                     }
                 }
     }
-    void *dn, *dv, *db, *dc, *dt, *df;
+    void *dn, *dv, *db, *dc, *dt, *df, *dw = nullptr;
     auto alloc = [&](void** p, size_t bytes) { return pc_alloc(f, fill, p, bytes); };
+    if (ccol) {
+        if (alloc(&dw, sizeof(unsigned) * N)) return 1;
+        HIPCHK(hipMemcpy(dw, cw.data(), sizeof(unsigned) * N, hipMemcpyHostToDevice));
+    }
+    T.cw = (const unsigned*)dw;
     if (alloc((void**)&T.fac, (size_t)N * nEnt * nS * nS * sizeof(double))) return 1;
     if (alloc((void**)&T.ws, (size_t)N * nS * sizeof(double))) return 1;
     if (alloc(&dn, sizeof(int) * nbr.size()) || alloc(&dv, sizeof(int) * N) || alloc(&db, sizeof(int) * N) || alloc(&dc, sizeof(int) * N) ||
@@ -4406,7 +4442,8 @@ static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::arr
     T.nbr = (const int*)dn; T.vec = (const int*)dv; T.cblk = (const int*)db; T.cbox = (const int*)dc;
     T.blk = (const JmBlk*)dt; T.flag = (int*)df;
     T.tsm = shift; T.turbDiag = turbDiag;
-    const int rcf = fill > 0 ? launch_pcf_factor(T, nS, nEnt, start, g_stream) : launch_pc_factor(T, nS, start, g_stream);
+    const int rcf = ccol ? launch_pcc_factor(T, nS, start, g_stream)
+                  : fill > 0 ? launch_pcf_factor(T, nS, nEnt, start, g_stream) : launch_pc_factor(T, nS, start, g_stream);
     T.tsm = nullptr;                              // the sweeps do not read it, and it may be released before the factor
     if (rcf) return 1;
     int flag = 0;
@@ -4426,6 +4463,7 @@ static int pc_build(PcFactor& f, int level, int fill, const std::vector<std::arr
     }
     f.level = level; f.nState = nS; f.nPlanes = nSets; f.ncell = N;
     f.fill = fill; f.nEnt = nEnt;
+    f.coupled = ccol ? 1 : 0;
     f.planeStart = start;
     f.valid = true;
     return 0;
@@ -4489,8 +4527,122 @@ static int pc_tab_init(PcFactor& f, int fill, long N, const int* sten, std::vect
     return 0;
 }
 
-// the factor f of the assembled 7-point matrix of `level` with `fill` levels of fill
-static int pc_setup_build(PcFactor& f, int fill, int level, const double* shift, double turbDiag)
+// One subdomain for the level (adflow_gpu_pc_set_coupled): col[d N + c] = the natural number (PETSc layout: block after block in
+// ascending nn, then k, j, i) of the column of cell c in direction d (0..2: -i, -j, -k; 3..5: +i, +j, +k), -1: none.  Inside a block
+// the neighbour; on a first-layer face halo the owned cell of this process that the registered 2-layer pattern of the level names as
+// its donor (another block, the block itself, any orientation), as adflow_gpu_jacobian_mult reads it; a halo without such a donor
+// (boundary faces, halos fed by messages) stays outside M.  nCross: the entries that came from the pattern.  Refused, because the
+// per-cell relations of kernels_pc_coupled.hip do not hold: the same column behind two faces of a cell, a cell that is its own
+// column, two neighbours of a cell that are neighbours of each other, a neighbour that does not lead back; and a rotational
+// periodicity when the matrix covers the velocities, as the product refuses it.
+static int pc_coupled_columns(int level, const std::vector<JmBlk>& hb, const std::vector<int>& nnOf, long N, std::vector<int>& col,
+                              long& nCross)
+{
+    col.assign((size_t)6 * N, -1);
+    nCross = 0;
+    std::vector<char> iface(N, 0);                // cells with a column behind a face: only they can break the relations
+    for (auto& q : hb) {
+        long nat = q.vecOff;
+        const long sj = q.nx, sk = (long)q.nx * q.ny;
+        for (int k = 0; k < q.nz; ++k)
+            for (int j = 0; j < q.ny; ++j)
+                for (int i = 0; i < q.nx; ++i, ++nat) {
+                    if (i > 0) col[0 * N + nat] = (int)(nat - 1);
+                    if (j > 0) col[1 * N + nat] = (int)(nat - sj);
+                    if (k > 0) col[2 * N + nat] = (int)(nat - sk);
+                    if (i < q.nx - 1) col[3 * N + nat] = (int)(nat + 1);
+                    if (j < q.ny - 1) col[4 * N + nat] = (int)(nat + sj);
+                    if (k < q.nz - 1) col[5 * N + nat] = (int)(nat + sk);
+                }
+    }
+    auto it = g_comm.find(std::make_pair(level, 2));
+    if (it != g_comm.end()) {
+        const CommPattern& cp = it->second;
+        if (g_jac.lStart == 0 && g_jac.nState >= 5)
+            for (auto& pd : cp.periodic) {
+                bool identity = true;
+                for (int q = 0; q < 9; ++q)
+                    if (pd.rotMatrix[q] != ((q % 4 == 0) ? 1.0 : 0.0)) identity = false;
+                if (!identity && !pd.h_block.empty())
+                    return fail("pc_setup: rotational periodicity is not supported by the factor over the level (a registered periodic "
+                                "transformation of level %d rotates the velocities of its halos); no factor is kept", level);
+            }
+        std::map<int, int> slotOf;
+        for (size_t s = 0; s < nnOf.size(); ++s) slotOf[nnOf[s]] = (int)s;
+        const int nc = (int)cp.h_haloBlock.size();
+        for (int t = 0; t < nc; ++t) {
+            auto hs = slotOf.find(cp.h_haloBlock[t]), ds = slotOf.find(cp.h_donorBlock[t]);
+            if (hs == slotOf.end() || ds == slotOf.end()) continue;
+            const JmBlk &q = hb[hs->second], &dq = hb[ds->second];
+            const int h[3] = {cp.h_haloIdx[t], cp.h_haloIdx[nc + t], cp.h_haloIdx[2 * nc + t]};
+            const int g[3] = {cp.h_donorIdx[t] - 2, cp.h_donorIdx[nc + t] - 2, cp.h_donorIdx[2 * nc + t] - 2};
+            const int n[3] = {q.nx, q.ny, q.nz};
+            // a first-layer FACE halo: one index at 1 or n + 2, the other two owned; it is the column of one owned cell in one direction
+            int dir = -1, nOut = 0, c[3];
+            for (int a = 0; a < 3; ++a) {
+                c[a] = h[a] - 2;
+                if (h[a] == 1) { dir = a; c[a] = 0; ++nOut; }
+                else if (h[a] == n[a] + 2) { dir = 3 + a; c[a] = n[a] - 1; ++nOut; }
+                else if (h[a] < 2 || h[a] > n[a] + 1) nOut += 2;
+            }
+            if (nOut != 1) continue;
+            if (g[0] < 0 || g[0] >= dq.nx || g[1] < 0 || g[1] >= dq.ny || g[2] < 0 || g[2] >= dq.nz) continue;     // no owned cell
+            const long nat = q.vecOff + ((long)c[2] * q.ny + c[1]) * q.nx + c[0];
+            if (col[(size_t)dir * N + nat] < 0) ++nCross;
+            iface[nat] = 1;
+            col[(size_t)dir * N + nat] = (int)(dq.vecOff + ((long)g[2] * dq.ny + g[1]) * dq.nx + g[0]);
+        }
+    }
+    // where cell `nat` lies, for the messages: block number and (i, j, k) as the reference counts them
+    auto where = [&](long nat, int* ijk) {
+        size_t s = 0;
+        while (s + 1 < hb.size() && hb[s + 1].vecOff <= nat) ++s;
+        const long loc = nat - hb[s].vecOff;
+        ijk[0] = (int)(loc % hb[s].nx) + 2; ijk[1] = (int)(loc / hb[s].nx % hb[s].ny) + 2; ijk[2] = (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2;
+        return nnOf[s];
+    };
+    for (long c = 0; c < N; ++c)
+        for (int d = 0; d < 6 && iface[c]; ++d) {
+            const long n = col[(size_t)d * N + c];
+            if (n < 0) continue;
+            int p[3], o[3];
+            if (n == c) {
+                const int nn = where(c, p);
+                return fail("pc_setup: cell (%d,%d,%d) of block %d has itself as a column behind a face (a block periodic onto itself "
+                            "over one cell); the factor over the level does not take it, no factor is kept", p[0], p[1], p[2], nn);
+            }
+            bool back = false;
+            for (int e = 0; e < 6; ++e) {
+                const long m = col[(size_t)e * N + n];
+                if (m == c) back = true;
+                if (m < 0 || m == c) continue;
+                for (int d2 = 0; d2 < 6; ++d2)
+                    if (d2 != d && col[(size_t)d2 * N + c] == m) {
+                        const int nn = where(c, p), nn2 = where(n, o);
+                        return fail("pc_setup: two neighbours of cell (%d,%d,%d) of block %d are neighbours of each other (cell (%d,%d,%d) "
+                                    "of block %d is one of them: an edge with three blocks around it, or a period of three cells); the "
+                                    "factor over the level does not take it, no factor is kept", p[0], p[1], p[2], nn, o[0], o[1], o[2], nn2);
+                    }
+            }
+            for (int d2 = 0; d2 < d; ++d2)
+                if (col[(size_t)d2 * N + c] == n) {
+                    const int nn = where(c, p);
+                    return fail("pc_setup: cell (%d,%d,%d) of block %d has the same column behind two faces (a block periodic onto "
+                                "itself over fewer than three cells); the factor over the level does not take it, no factor is kept",
+                                p[0], p[1], p[2], nn);
+                }
+            if (!back) {
+                const int nn = where(c, p), nn2 = where(n, o);
+                return fail("pc_setup: cell (%d,%d,%d) of block %d has cell (%d,%d,%d) of block %d as a column, which does not have it as "
+                            "one (the 2-layer pattern of level %d is not 1-to-1 there); no factor is kept", p[0], p[1], p[2], nn, o[0],
+                            o[1], o[2], nn2, level);
+            }
+        }
+    return 0;
+}
+
+// the factor f of the assembled 7-point matrix of `level` with `fill` levels of fill; coupled: one subdomain for the level (fill 0)
+static int pc_setup_build(PcFactor& f, int fill, int coupled, int level, const double* shift, double turbDiag)
 {
     int sten[7];
     std::vector<JmBlk> hb;
@@ -4498,7 +4650,13 @@ static int pc_setup_build(PcFactor& f, int fill, int level, const double* shift,
     long N = 0;
     std::vector<std::array<int, 3>> slots;
     if (pc_level_blocks(level, sten, hb, nnOf, N) || pc_tab_init(f, fill, N, sten, slots)) return 1;
-    return pc_build(f, level, fill, slots, hb, nnOf, shift, turbDiag);
+    if (!coupled) return pc_build(f, level, fill, slots, hb, nnOf, shift, turbDiag);
+    std::vector<int> col;
+    long nCross = 0;
+    if (pc_coupled_columns(level, hb, nnOf, N, col, nCross) || pc_build(f, level, fill, slots, hb, nnOf, shift, turbDiag, 0, &col))
+        return 1;
+    f.nCross = nCross;
+    return 0;
 }
 
 // ---- the multigrid hierarchy (adflow_gpu_pc_set_mg; kernels_pc_mg.hip) -------------------------------------------------------------
@@ -4627,8 +4785,16 @@ static int pc_setup_selected(int level, const double* shift = nullptr, double tu
     HIPCHK(hipStreamSynchronize(g_stream));
     (void)pc_release(f);
     const PcMgSetting& mg = g_pc_mg[g_pc_slot];
+    const int coupled = g_pc_coupled[g_pc_slot];
+    if (coupled && g_pc_fill[g_pc_slot] > 0)
+        return fail("pc_setup: slot %d is set to one subdomain for the level (adflow_gpu_pc_set_coupled) and to fill %d; across a block "
+                    "interface the pattern of fill 1 and 2 is no fixed stencil, the factor over the level takes fill 0; no factor is kept",
+                    g_pc_slot, g_pc_fill[g_pc_slot]);
+    if (coupled && mg.levels > 1)
+        return fail("pc_setup: slot %d is set to one subdomain for the level (adflow_gpu_pc_set_coupled) and to a multigrid hierarchy of "
+                    "%d levels, which is built block by block; no factor is kept", g_pc_slot, mg.levels);
     if (mg.levels > 1 ? pc_mg_setup_build(f, g_pc_fill[g_pc_slot], mg, level, shift, turbDiag)
-                      : pc_setup_build(f, g_pc_fill[g_pc_slot], level, shift, turbDiag)) {
+                      : pc_setup_build(f, g_pc_fill[g_pc_slot], coupled, level, shift, turbDiag)) {
         if (g_stream) (void)hipStreamSynchronize(g_stream);
         (void)pc_release(f);
         return 1;
@@ -4666,6 +4832,23 @@ int adflow_gpu_pc_set_fill(int fill)
         return fail("pc_set_fill: fill %d; the block ILU takes 0, 1 or 2 levels of fill (from 3 on the pattern of a block in the natural "
                     "ordering is no fixed stencil)", fill);
     g_pc_fill[g_pc_slot] = fill;
+    return 0;
+}
+
+int adflow_gpu_pc_set_coupled(int coupled)
+{
+    if (coupled != 0 && coupled != 1)
+        return fail("pc_set_coupled: %d; 0 = one subdomain per block, 1 = one subdomain for the level", coupled);
+    g_pc_coupled[g_pc_slot] = coupled;
+    return 0;
+}
+
+int adflow_gpu_pc_coupled_info(int32_t* coupled, int32_t* nLevelSets, int64_t* nCrossEntries)
+{
+    if (!pc_sel().valid) return fail("pc_coupled_info: no factor (call adflow_gpu_pc_setup first)");
+    if (coupled) *coupled = pc_sel().coupled;
+    if (nLevelSets) *nLevelSets = pc_sel().nPlanes;
+    if (nCrossEntries) *nCrossEntries = pc_sel().nCross;
     return 0;
 }
 
@@ -4734,6 +4917,7 @@ int adflow_gpu_pc_release(int64_t* bytes)
 // z = M^-1 r or M^-T r with the selected factor, whatever its fill, for nv = 1 .. PC_MAXW columns ldr / ldz apart in the same launches
 static int pc_factor_apply(const PcFactor& f, int transpose, const double* r, double* z, hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0)
 {
+    if (f.coupled) return launch_pcc_apply(f.tab, f.nState, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
     if (f.fill > 0) return launch_pcf_apply(f.tab, f.nState, f.nEnt, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
     return launch_pc_apply(f.tab, f.nState, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
 }

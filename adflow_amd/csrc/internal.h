@@ -437,6 +437,9 @@ struct PcTab {
     signed char tgt[121]; // tgt[e nLow + u]: slot of this row that L_{c,n} U_{n,m} lands in (n: lower entry e, m: upper entry u
                           // of row n), -1: outside the pattern
     double* wsx;          // the work space of vectors 1 .. of a multi-vector application, laid out like ws; NULL until the first one
+    // the factor over the whole level only (kernels_pc_coupled.hip); NULL otherwise
+    const unsigned* cw;   // per cell: bits 0..5 "the neighbour of slot d is lower", bits 6+3d..8+3d the slot in which that neighbour
+                          // keeps its entry back to this cell; nbr[] then names neighbours in any block of the level
 };
 int launch_pc_factor(const PcTab& T, int nState, const std::vector<int>& planeStart, hipStream_t s);
 // nv = 1 .. PC_MAXW vectors through the same launches: column v of r and z starts v ldr / v ldz doubles behind column 0 and uses the
@@ -444,6 +447,11 @@ int launch_pc_factor(const PcTab& T, int nState, const std::vector<int>& planeSt
 enum { PC_MAXW = 4 };
 int launch_pc_apply(const PcTab& T, int nState, int transpose, const std::vector<int>& planeStart, const double* r, double* z,
                     hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0);
+// ILU(0) over the whole level (kernels_pc_coupled.hip; adflow_gpu_pc_set_coupled): the same storage with slot d = 0..5 holding L or U
+// as the mask of cw says, setStart = first position of every dependency level set of the level, and the end
+int launch_pcc_factor(const PcTab& T, int nState, const std::vector<int>& setStart, hipStream_t s);
+int launch_pcc_apply(const PcTab& T, int nState, int transpose, const std::vector<int>& setStart, const double* r, double* z,
+                     hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0);
 // block ILU(1) / ILU(2) of the same matrix (kernels_pc_fill.hip): nEnt = 13 or 23 entries per row, levelStart = first position of
 // every dependency level set in the order of the factor, and the end
 int launch_pcf_factor(const PcTab& T, int nState, int nEnt, const std::vector<int>& levelStart, hipStream_t s);

@@ -4,11 +4,12 @@
 // Reference semantics: the PCApply of setupStandardKSP (adjointUtils.F90:1374-1562) in the configuration PCBJACOBI (= PCASM with
 // overlap 0), one subdomain per structured block, sub-preconditioner ILU with 0 levels in the natural ordering (k, j, i with i
 // fastest) on BAIJ blocks of size nState.  A column on a halo cell, with or without a donor, is not part of a subdomain.
+// (One subdomain for the level -- what the reference gives a process that owns several blocks, the couplings across its block
+// interfaces inside M -- is adflow_gpu_pc_set_coupled(1): kernels_pc_coupled.hip, fill 0, the same storage.)
 // Fill: natural ordering, fill <= 2.  This file is fill 0; ILU(1) and ILU(2) (adflow_gpu_pc_set_fill; the reference defaults to 2)
 // are in kernels_pc_fill.hip and leave a factor that everything above the two launch_pc_* calls takes unchanged.
-// Out of scope: fill > 2 and the RCM ordering (the reference's default ordering), ASM overlap and couplings across blocks, GMRES
-// across ranks.  (The pseudo-time diagonal term of ANK and the matrix-free operator: adflow_gpu_ank_pc_setup / _ank_solve,
-// kernels_ank.hip.)
+// Out of scope: fill > 2 and the RCM ordering (the reference's default ordering), ASM overlap between ranks, GMRES across ranks.
+// (The pseudo-time diagonal term of ANK and the matrix-free operator: adflow_gpu_ank_pc_setup / _ank_solve, kernels_ank.hip.)
 //
 // Arithmetic: eliminating row c of a 7-point stencil in natural order with the rows c - e_i, c - e_j, c - e_k creates no entry
 // inside the pattern but on the diagonal, so

@@ -201,6 +201,18 @@ class Engine:
         self._chk(self.lib.adflow_gpu_pc_info2(ctypes.byref(f), ctypes.byref(ne), ctypes.byref(nl)))
         return int(f.value), int(ne.value), int(nl.value)
 
+    def pcSetCoupled(self, coupled: int):
+        """0: one ILU subdomain per block (PCBJACOBI); 1: one subdomain for the level, the couplings across the block interfaces of
+        this process inside M (the ASM subdomain of setupStandardKSP; fill 0, no hierarchy) -- for the next pcSetup / ankPcSetup of the
+        selected slot; a factor that exists keeps its own"""
+        self._chk(self.lib.adflow_gpu_pc_set_coupled(int(coupled)))
+
+    def pcCoupledInfo(self):
+        """(coupled, number of level sets, entries of M whose column lies behind a block interface) of the factor"""
+        c, nl, nx = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        self._chk(self.lib.adflow_gpu_pc_coupled_info(ctypes.byref(c), ctypes.byref(nl), ctypes.byref(nx)))
+        return int(c.value), int(nl.value), int(nx.value)
+
     def pcSetMg(self, levels: int, nSmooth: int = 1, fillCoarse: int = 0):
         """the multigrid preconditioner of amg.F90 (precondType = 'mg') for the next pcSetup / ankPcSetup of the selected slot: `levels`
         levels of 2 x 2 x 2 aggregates per block (1: the plain factor), nSmooth Richardson iterations of the ILU smoother per level,

@@ -353,6 +353,17 @@ module adflowGpuShim
             import :: c_int, c_int32_t
             integer(c_int32_t), intent(out) :: fill, nEntries, nLevelSets
         end function
+        ! the subdomain of the next setup of the selected slot: 0 = one per block, 1 = one for the level (the ASM subdomain of a process:
+        ! couplings across its block interfaces inside the ILU(0); fill 0, no hierarchy), and what the selected factor was built with
+        integer(c_int) function adflow_gpu_pc_set_coupled(coupled) bind(C, name="adflow_gpu_pc_set_coupled")
+            import :: c_int
+            integer(c_int), value :: coupled
+        end function
+        integer(c_int) function adflow_gpu_pc_coupled_info(coupled, nLevelSets, nCrossEntries) bind(C, name="adflow_gpu_pc_coupled_info")
+            import :: c_int, c_int32_t, c_int64_t
+            integer(c_int32_t), intent(out) :: coupled, nLevelSets
+            integer(c_int64_t), intent(out) :: nCrossEntries
+        end function
         ! the multigrid preconditioner of amg.F90 (precondType = 'mg') for the next setup of the selected slot: AMGLevels, AMGNSmooth and
         ! the fill of the coarse levels; what the selected slot holds; the blocks of one block on one level (nx_l, ny_l, nz_l, nState, nState, 7)
         integer(c_int) function adflow_gpu_pc_set_mg(levels, nSmooth, fillCoarse) bind(C, name="adflow_gpu_pc_set_mg")
@@ -1020,6 +1031,16 @@ contains
         integer(kind=intType), intent(in) :: fill
         call gpuCheck(adflow_gpu_pc_set_fill(int(fill, c_int)), "gpuPCSetFill")
     end subroutine gpuPCSetFill
+
+    ! the ILU subdomain of the next gpuPCSetup / gpuANKPCSetup of the selected slot: .false. one per block, .true. one for the level
+    ! (what setupStandardKSP gives a process that owns several blocks; fill 0 only)
+    subroutine gpuPCSetCoupled(coupled)
+        logical, intent(in) :: coupled
+        integer(c_int) :: c
+        c = 0_c_int
+        if (coupled) c = 1_c_int
+        call gpuCheck(adflow_gpu_pc_set_coupled(c), "gpuPCSetCoupled")
+    end subroutine gpuPCSetCoupled
 
     ! precondType = 'mg' (setupAMG / setupShellPC / applyShellPC of amg.F90): the next gpuPCSetup / gpuANKPCSetup of the selected slot
     ! builds `levels` levels (ANKAMGLevels, NKAMGLevels, adjointAMGLevels) smoothed nSmooth times (...AMGNSmooth) with an ILU of

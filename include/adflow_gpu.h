@@ -525,6 +525,27 @@ int adflow_gpu_pc_setup(int level);
 int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes);
 int adflow_gpu_pc_set_fill(int fill);
 int adflow_gpu_pc_info2(int32_t* fill, int32_t* nEntries, int32_t* nLevelSets);
+/* The subdomain of the ILU(0).  adflow_gpu_pc_set_coupled(coupled) sets what the next adflow_gpu_pc_setup / _ank_pc_setup of the SELECTED
+ * slot builds; it is kept per slot across setups and releases, default 0; a factor that exists keeps what it was built with.
+ *   0  one subdomain per structured block (PCBJACOBI): every column behind a block face is dropped from M.
+ *   1  one subdomain for the level, the ASM subdomain setupStandardKSP gives a process (adjointUtils.F90:1374-1562): the 7-point matrix
+ *      of the whole level is factored.  A column on a first-layer face halo whose donor in the registered 2-layer pattern of the level
+ *      is an owned cell of this process is the column of that donor cell, as adflow_gpu_jacobian_mult reads it -- interfaces to another
+ *      block, to the block itself (translational periodicity), rotated interfaces.  A halo without such a donor (boundary faces, halos
+ *      fed by messages from other ranks) stays outside M.  Ordering: the PETSc layout, block after block in ascending nn, then k, j, i.
+ *      Fill 0.  Everything that takes a factor takes this one (pc_apply[_dev], the _multi entries with up to four columns per chain of
+ *      launches, gmres_solve, ank_solve, both slots, the enqueue-only mode); adflow_gpu_pc_info counts its one extra table (a word
+ *      per cell, nPlanes = the level sets of the whole level), adflow_gpu_pc_release frees it.
+ * Errors of the setup with coupled = 1, each with a message; the selected slot then keeps no factor, the other slot is untouched:
+ * a fill > 0 set for the slot; adflow_gpu_pc_set_mg levels > 1 set for the slot; a cell that has the same column behind two faces
+ * (a block periodic onto itself over fewer than three cells); a cell that has itself as a column; two neighbours of one cell that
+ * are neighbours of each other (an edge with three blocks around it); a column that does not have the cell as a column in return;
+ * a rotational periodicity on the pattern when the matrix covers the velocities (as adflow_gpu_jacobian_mult).
+ * adflow_gpu_pc_set_coupled refuses any value but 0 and 1.
+ * adflow_gpu_pc_coupled_info: of the selected factor, whether it spans the level, its level sets and the number of entries of M whose
+ * column lies behind a block face (0 for a block-local factor); each may be NULL; an error without a factor. */
+int adflow_gpu_pc_set_coupled(int coupled);
+int adflow_gpu_pc_coupled_info(int32_t* coupled, int32_t* nLevelSets, int64_t* nCrossEntries);
 int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, long n);
 int adflow_gpu_pc_apply_dev(int level, int transpose, const double* d_r, double* d_z, long n);
 int adflow_gpu_pc_release(int64_t* bytes);

@@ -11,8 +11,12 @@ for N right-hand sides through adflow_gpu_gmres_solve_multi_dev against N calls 
 N Richardson iterations of the ILU smoother per level, fill F below the first level): the same lines, with the cells of every level,
 the bytes the hierarchy holds and the launches of one cycle; floor_bytes is then one pass over the matrix and the factor of every
 level per smoothing iteration.  Without --mg nothing changes.
-usage: pc_apply.py [--fill 0|1|2] [--mg L [--nsmooth N] [--fill-coarse F]] [--rtol 1e-8] [--nvec N] [n] [nx ny nz]
-       (n timed applications of each kind, default 10)"""
+--brick Bi Bj Bk builds the matrix on Bi x Bj x Bk blocks of nx x ny x nz with wall / symmetry / farfield on the outside of the brick and
+1-to-1 interfaces inside (the benchmark's layout); --coupled (fill 0, no --mg) then runs every line twice in the same process, with
+one ILU subdomain per block (adflow_gpu_pc_set_coupled(0)) and with one for the level (1): setup, both applications with launches,
+level sets, microseconds per launch and GB/s on the factor bytes, and GMRES.
+usage: pc_apply.py [--fill 0|1|2] [--mg L [--nsmooth N] [--fill-coarse F]] [--rtol 1e-8] [--nvec N] [--brick Bi Bj Bk] [--coupled]
+       [n] [nx ny nz]      (n timed applications of each kind, default 10)"""
 import json
 import os
 import sys
@@ -22,7 +26,7 @@ sys.path.insert(0, ROOT)
 from adflow_amd.engine import Engine  # noqa: E402
 from adflow_amd.params import FlowParams, RANSEquations, upwind, vanAlbeda  # noqa: E402
 from adflow_amd.synth import make_block, make_bocos  # noqa: E402
-from adflow_amd.topology import CommPattern  # noqa: E402
+from adflow_amd.topology import BrickTopology, CommPattern, apply_local_copies_fast  # noqa: E402
 
 WALL = {1: -6, 2: -6, 3: -1, 4: -1, 5: -3, 6: -6}
 
@@ -31,6 +35,13 @@ def main():
     import torch
     argv, fill, rtol, nvec = list(sys.argv[1:]), 0, 1e-8, 0
     mg, nsmooth, fillc = 1, 1, 0
+    brick, both = None, "--coupled" in argv
+    if both:
+        argv.remove("--coupled")
+    if "--brick" in argv:
+        at = argv.index("--brick")
+        brick = tuple(int(a) for a in argv[at + 1:at + 4])
+        del argv[at:at + 4]
     for opt in ("--fill", "--rtol", "--nvec", "--mg", "--nsmooth", "--fill-coarse"):
         if opt in argv:
             at = argv.index(opt)
@@ -51,25 +62,70 @@ def main():
     dims = tuple(int(a) for a in argv[1:4]) if len(argv) > 3 else (160, 128, 64)
     eng = Engine(0)
     prm = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda).replace(currentLevel=1, groundLevel=1)
-    blk = make_block(*dims, prm, seed=7, stretch_k=2.0)
-    faces, nvisc = make_bocos(blk, prm, WALL, seed=8)
     eng.release_all()
     eng.set_options(prm)
-    eng.register(blk)
-    eng.bc_register(faces, nvisc)
-    for L in (1, 2):
-        eng.comm_register(1, L, CommPattern())
+    if brick:
+        cells = register_brick(eng, BrickTopology(*brick, *dims, periodic=(False,) * 3), prm)
+    else:
+        blk = make_block(*dims, prm, seed=7, stretch_k=2.0)
+        faces, nvisc = make_bocos(blk, prm, WALL, seed=8)
+        eng.register(blk)
+        eng.bc_register(faces, nvisc)
+        for L in (1, 2):
+            eng.comm_register(1, L, CommPattern())
+        cells = blk.nx * blk.ny * blk.nz
     eng.applyAllBC(1, True)
     eng.setupStateResidualMatrix(1, True, useAD=True)
     eng.releaseWorkspace()
     ns, st = eng.jacobianInfo()
-    cells = blk.nx * blk.ny * blk.nz
     n = ns * cells
-    if fill:                                              # (a library without the entry point still serves fill 0)
-        eng.pcSetFill(fill)
+    if both:
+        if fill or mg > 1:
+            sys.exit("--coupled: the factor over the level takes fill 0 and no hierarchy")
+        for coupled in (0, 1):
+            eng.pcSetCoupled(coupled)
+            one_factor(eng, torch, dims, brick, ns, cells, n, n_it, 0, 1, rtol, 0, coupled)
+        eng.pcSetCoupled(0)
+    else:
+        if fill:                                          # (a library without the entry point still serves fill 0)
+            eng.pcSetFill(fill)
+        if mg > 1:
+            eng.pcSetMg(mg, nsmooth, fillc)
+        one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec, None)
+    eng.releaseWorkspace()
+    eng.close()
+
+
+def register_brick(eng, topo, prm):
+    """the blocks of a wall-bounded brick with their boundary subfaces and both patterns on the engine; returns the owned cells"""
+    from adflow_amd.synth import set_porosities
+    lid = topo.local_ids()
+    blocks = {lid[g]: make_block(topo.nx, topo.ny, topo.nz, prm, seed=7 + 17 * g, wall_kmin=False, stretch_k=2.0)
+              for g in range(topo.nblocks)}
+    bocos = {}
+    for g in range(topo.nblocks):
+        spec = topo.boundary_spec(g, WALL)
+        if spec:
+            bocos[lid[g]] = make_bocos(blocks[lid[g]], prm, spec, seed=8 + 31 * g)
+        set_porosities(blocks[lid[g]], bocos[lid[g]][0] if lid[g] in bocos else [])
+    pats = {L: topo.patterns(L)[0] for L in (1, 2)}
+    apply_local_copies_fast(blocks, pats[2])
+    for nn, b in blocks.items():
+        eng.register(b, nn=nn, level=1)
+        if nn in bocos:
+            eng.bc_register(*bocos[nn], nn=nn, level=1)
+    for L in (1, 2):
+        eng.comm_register(1, L, pats[L])
+    return sum(b.nx * b.ny * b.nz for b in blocks.values())
+
+
+def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec, coupled):
+    """setup, applications and GMRES with the settings of the selected slot as they stand; coupled: None, or the subdomain setting
+    the lines name (then with the level sets, the microseconds per launch and the GB/s on the factor bytes)"""
+    tag = {} if coupled is None else {"coupled": coupled}
+    if brick:
+        tag["brick"] = list(brick)
     floor = {0: 7, 1: 13, 2: 23}[fill] * ns * ns * 8 * cells
-    if mg > 1:
-        eng.pcSetMg(mg, nsmooth, fillc)
     eng.pcSetup(1)                                        # warm-up (allocations, tables)
     eng.sync()
     eng.event_record(1)
@@ -78,7 +134,7 @@ def main():
     eng.sync()
     _, planes, nbytes = eng.pcInfo()
     print(json.dumps({"what": "pc_setup (tables, allocation, factorisation)", "dims": list(dims), "nState": ns, "ms": round(eng.event_elapsed_ms(1, 2), 3),
-                      "fill": fill, "hyperplanes_or_level_sets": planes, "factor_bytes": nbytes}), flush=True)
+                      "fill": fill, "hyperplanes_or_level_sets": planes, "factor_bytes": nbytes, **tag}), flush=True)
     if mg > 1:
         planes, floor = cycle_cost(eng, dims, ns, fill, planes)
     gen = torch.Generator(device="cuda").manual_seed(5)
@@ -100,9 +156,13 @@ def main():
             eng.sync()
             ms = eng.event_elapsed_ms(1, 2) / n_it
             ms_of[what] = ms
+            more = dict(tag)
+            if coupled is not None and what != "J x":
+                more.update(level_sets=planes, us_per_launch=round(1e3 * ms / launches, 2),
+                            GB_per_s_on_the_factor=round(floor / (ms * 1e-3) / 1e9, 1))
             print(json.dumps({"what": what, "ms": round(ms, 4), "floor_bytes": floor, "TB_per_s": round(floor / (ms * 1e-3) / 1e12, 3),
                               "launches": int(launches), "ratio_to_J_x": round(ms / ms_of["J x"], 2),
-                              "checksum": float(y.abs().sum().item())}), flush=True)
+                              "checksum": float(y.abs().sum().item()), **more}), flush=True)
     finally:
         eng.set_async(False)
     b = torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 0.5
@@ -114,12 +174,10 @@ def main():
             eng.event_record(2)
             eng.sync()
         print(json.dumps({"what": f"gmres on the PC matrix, rtol {rtol:g}", "fill": fill, "transpose": tr, "iterations": its, "ms": round(eng.event_elapsed_ms(1, 2), 3),
-                          "rnorm0": r0, "true_rnorm": rn}), flush=True)
+                          "rnorm0": r0, "true_rnorm": rn, **tag}), flush=True)
     if nvec > 1:
         multi_columns(eng, torch, gen, n, nvec, n_it, fill, planes, floor, rtol)
     eng.pcRelease()
-    eng.releaseWorkspace()
-    eng.close()
 
 
 def cycle_cost(eng, dims, ns, fill, planes1):
