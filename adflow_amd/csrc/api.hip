@@ -491,6 +491,8 @@ int adflow_gpu_set_options(const adflow_opts* o)
                     (o->unsupported & 4) ? " wall functions;" : "", (o->unsupported & 8) ? " overset blocks;" : "");
     if (o->equations == ADFLOW_RANS && o->turbModel != 2)   // spalartAllmaras (constants.F90)
         return fail("turbModel=%d not supported (Spalart-Allmaras only)", o->turbModel);
+    if (o->equations == ADFLOW_RANS && o->turbProd != ADFLOW_TURBPROD_STRAIN && o->turbProd != ADFLOW_TURBPROD_VORTICITY)   // sa.F90:136-139 stops
+        return fail("turbProd=%d not supported with Spalart-Allmaras (strain or vorticity; the reference stops for katoLaunder)", o->turbProd);
     if (memcmp(&g_opts, o, sizeof g_opts) != 0) ++g_state_gen;
     g_opts = *o;
     g_have_opts = true;

@@ -104,6 +104,7 @@ class FlowParams:
     #     initializeFlow.F90:10-182: pRef=pInfDim, rhoRef=rhoInfDim, TRef=TInfDim)
     Mach: float = 0.8
     alphaDeg: float = 1.8
+    betaDeg: float = 0.0        # sideslip angle: the free stream turned out of the x-y plane
     pInfDim: float = 26500.0
     rhoInfDim: float = 0.4135
     TInfDim: float = 223.25
@@ -187,7 +188,10 @@ class FlowParams:
     @property
     def velDirFreestream(self):
         a = math.radians(self.alphaDeg)
-        return (math.cos(a), math.sin(a), 0.0)
+        if self.betaDeg == 0.0:
+            return (math.cos(a), math.sin(a), 0.0)
+        b = math.radians(self.betaDeg)
+        return (math.cos(a) * math.cos(b), math.sin(a), math.cos(a) * math.sin(b))
 
     def wInf(self):
         d = self.velDirFreestream

@@ -190,6 +190,40 @@ def draw_jac_case(rng):
     return (nx, ny, nz), kw, mk, entry
 
 
+# the reference's Runge-Kutta stage sets next to the default five-stage one (inputParamRoutines.F90:3576-3635): {nRKStages: (etaRK, cdisRK)}
+STAGE_SETS = {1: ([1.0], [1.0]), 2: ([0.2222, 1.0], [1.0, 1.0]), 3: ([0.2846, 0.6067, 1.0], [1.0, 1.0, 1.0]),
+              4: ([0.33333333, 0.26666667, 0.55555555, 1.0], [1.0, 0.5, 0.0, 0.0]),
+              6: ([0.0722, 0.1421, 0.2268, 0.3425, 0.5349, 1.0], [1.0, 1.0, 1.0, 1.0, 1.0, 1.0])}
+
+
+def draw_options(orng, kw, mk, entry):
+    """options that every earlier draw left at their defaults: the gas model, the free stream, the stage set, the explicit turbulence
+    relaxation.  A stream of its own (the cases of a seed keep their sizes, schemes and entries), and each option only where the entry
+    reads it and the reference stays finite: no free-stream change under the multigrid cycles and the lattice (their draws are
+    tuned to states that survive a cycle), the supersonic free stream only where no smoother sweep follows."""
+    out = {}
+    eq = kw["equations"]
+    if entry in ("mg", "lattice"):
+        return out
+    if orng.random() < 0.4:
+        out["gammaConstant"] = float(orng.choice([1.3, 1.5]))
+        if mk.get("floor_p"):
+            out.pop("gammaConstant")          # (check_blockette_res_with_bc floors with the factor 0.4 = gamma - 1 of the default gas)
+    if eq != EulerEquations and orng.random() < 0.4:
+        out["prandtl"] = float(orng.choice([0.9, 0.6]))
+        out["prandtlTurb"] = float(orng.choice([0.6, 0.8]))
+    if orng.random() < 0.4:
+        quiet = entry in ("rk", "dadi", "sa_solve")
+        out["Mach"] = float(orng.choice([0.3, 0.6] if quiet else [0.3, 1.3, 2.0]))
+        out["alphaDeg"] = float(orng.choice([-7.0, 0.0, 12.0]))
+    if entry == "rk" and orng.random() < 0.6:
+        n = int(orng.choice(sorted(STAGE_SETS)))
+        out.update(nRKStages=n, etaRK=list(STAGE_SETS[n][0]), cdisRK=list(STAGE_SETS[n][1]))
+    if entry in ("sa_solve", "dadi") and eq == RANSEquations and orng.random() < 0.5:
+        out.update(turbRelax=1, alfaTurb=float(orng.choice([0.6, 0.9])))
+    return out
+
+
 def run_case(engine, dims, kw, mk, entry):
     prm = FlowParams(**kw)
     mk = dict(mk)
@@ -288,6 +322,8 @@ def sweep(engine, cases, seed, only=-1, quiet=False, big=False, jac=False):
             for _ in range(int(trng.integers(1, 3))):
                 k_, vals = KERNEL_KEYS[int(trng.integers(0, len(KERNEL_KEYS)))]
                 tune[k_] = int(trng.choice(vals))
+        # the options no earlier draw moved (draw_options), again from a stream of their own
+        kw = {**kw, **draw_options(np.random.default_rng([seed, n, 7]), kw, mk, entry)}
         if only >= 0 and n != only:
             continue
         try:
