@@ -14,6 +14,8 @@
 // Arithmetic: eliminating row c of a 7-point stencil in natural order with the rows c - e_i, c - e_j, c - e_k creates no entry
 // inside the pattern but on the diagonal, so
 //   D_c = A_cc - sum_lower A_{c,n} D_n^-1 A_{n,c},    L_{c,n} = A_{c,n} D_n^-1,    U_{c,n} = A_{c,n},    M = L (D + U)
+// (L_{c,n} is formed by the thread of row n, by a solve with D_n before D_n is inverted -- pc_right_solve, pc_block.h -- and read by
+// row c; only the sweeps multiply by the stored D^-1)
 // and D_c needs the cells of the hyperplane i + j + k - 1 only: setup, forward and backward sweep run hyperplane by hyperplane,
 // one plain launch per hyperplane that covers every block of the level, in stream order.  M^T = (D + U)^T L^T has the diagonal
 // blocks D_c^T: the same factor serves M^-1 r and M^-T r.
@@ -82,25 +84,10 @@ __global__ __launch_bounds__(PC_T) void k_pc_factor(PcTab T, int q0, int cnt)
             continue;
         }
         const unsigned n8 = (unsigned)n * 8u;
-        GPTR(const double) A = (GPTR(const double))(b.jac + (long)T.sten[s] * (NS * NS) * b.nbox);
         double X[NS * NS], L[NS * NS];
-        {
-            GPTR(const double) Fd = F + (long)6 * (NS * NS) * N;
+        // L_{c,n} = A_{c,n} D_n^-1: the lower neighbour wrote it into this slot when it held D_n (below), by a solve
 #pragma unroll
-            for (int e = 0; e < NS * NS; ++e) X[e] = ldg(Fd + e * N, n8);           // D_n^-1
-        }
-#pragma unroll
-        for (int e = 0; e < NS * NS; ++e) L[e] = 0.0;
-#pragma unroll
-        for (int m = 0; m < NS; ++m)
-#pragma unroll
-            for (int r = 0; r < NS; ++r) {
-                const double arm = ldg(A, c8 + (unsigned)(m * NS + r) * nb8);        // A_{c,n}(r, m)
-#pragma unroll
-                for (int l = 0; l < NS; ++l) PCE(L, r, l) += arm * PCE(X, m, l);
-            }
-#pragma unroll
-        for (int e = 0; e < NS * NS; ++e) stg(Fs + e * N, q8, L[e]);
+        for (int e = 0; e < NS * NS; ++e) L[e] = ldg((GPTR(const double))Fs + e * N, q8);
         {
             GPTR(const double) Fu = F + (long)(3 + s) * (NS * NS) * N;
 #pragma unroll
@@ -119,6 +106,21 @@ __global__ __launch_bounds__(PC_T) void k_pc_factor(PcTab T, int q0, int cnt)
         GPTR(double) Fs = F + (long)s * (NS * NS) * N;
 #pragma unroll
         for (int e = 0; e < NS * NS; ++e) stg(Fs + e * N, q8, in ? ldg(A, c8 + e * nb8) : 0.0);
+    }
+    // the L blocks of the three upper neighbours c = q + e_s towards this cell, L_{c,q} = A_{c,q} D_q^-1, while D_q itself is at hand:
+    // a solve with D_q (pc_right_solve), written into slot s of c, which c's row reads on a later hyperplane
+    for (int s = 0; s < 3; ++s) {
+        const int c = T.nbr[(long)(3 + s) * N + q];
+        if (c < 0) continue;
+        GPTR(const double) A = (GPTR(const double))(b.jac + (long)T.sten[s] * (NS * NS) * b.nbox);
+        const unsigned cc8 = (unsigned)T.cbox[c] * 8u;
+        double X[NS * NS];
+#pragma unroll
+        for (int e = 0; e < NS * NS; ++e) X[e] = ldg(A, cc8 + e * nb8);              // A_{c,q}
+        pc_right_solve<NS>(D, X);
+        GPTR(double) Fs = F + (long)s * (NS * NS) * N;
+#pragma unroll
+        for (int e = 0; e < NS * NS; ++e) stg(Fs + e * N, (unsigned)c * 8u, X[e]);
     }
     if (!pc_invert<NS>(D)) T.flag[0] = (int)q + 1;      // any of the failing cells: the host names one of them
     GPTR(double) Fd = F + (long)6 * (NS * NS) * N;

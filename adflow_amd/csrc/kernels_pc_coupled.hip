@@ -79,25 +79,10 @@ __global__ __launch_bounds__(PCC_T) void k_pcc_factor(PcTab T, int q0, int cnt)
             for (int e = 0; e < NS * NS; ++e) stg(Fs + e * N, q8, ldg(A, c8 + e * nb8));
             continue;
         }
-        const unsigned n8 = (unsigned)n * 8u;
         double X[NS * NS], L[NS * NS];
-        {
-            GPTR(const double) Fd = F + (long)6 * (NS * NS) * N;
+        // L_{c,n} = A_{c,n} D_n^-1: the lower neighbour wrote it into this slot when it held D_n (below), by a solve, as k_pc_factor
 #pragma unroll
-            for (int e = 0; e < NS * NS; ++e) X[e] = ldg(Fd + e * N, n8);           // D_n^-1
-        }
-#pragma unroll
-        for (int e = 0; e < NS * NS; ++e) L[e] = 0.0;
-#pragma unroll
-        for (int m = 0; m < NS; ++m)
-#pragma unroll
-            for (int r = 0; r < NS; ++r) {
-                const double arm = ldg(A, c8 + (unsigned)(m * NS + r) * nb8);        // A_{c,n}(r, m)
-#pragma unroll
-                for (int l = 0; l < NS; ++l) PCE(L, r, l) += arm * PCE(X, m, l);
-            }
-#pragma unroll
-        for (int e = 0; e < NS * NS; ++e) stg(Fs + e * N, q8, L[e]);
+        for (int e = 0; e < NS * NS; ++e) L[e] = ldg((GPTR(const double))Fs + e * N, q8);
         {
             // U_{n,c}: the neighbour holds it in the slot of ITS direction towards c, which differs from lane to lane
             const long back = (w >> (6 + 3 * d)) & 7u;
@@ -111,6 +96,23 @@ __global__ __launch_bounds__(PCC_T) void k_pcc_factor(PcTab T, int q0, int cnt)
             for (int l = 0; l < NS; ++l)
 #pragma unroll
                 for (int r = 0; r < NS; ++r) PCE(D, r, l) -= PCE(L, r, m) * PCE(X, m, l);
+    }
+    // the L blocks of the upper neighbours towards this cell, L_{c,q} = A_{c,q} D_q^-1, by a solve with D_q while it is at hand
+    // (pc_right_solve), written into the slot in which c keeps its entry back to this cell; c's row reads it in a later set
+    for (int d = 0; d < 6; ++d) {
+        const int c = T.nbr[(long)d * N + q];
+        if (c < 0 || ((w >> d) & 1u)) continue;
+        const long back = (w >> (6 + 3 * d)) & 7u;
+        const JmBlk bc = T.blk[T.cblk[c]];
+        GPTR(const double) A = (GPTR(const double))(bc.jac + (long)T.sten[back] * (NS * NS) * bc.nbox);
+        const unsigned cc8 = (unsigned)T.cbox[c] * 8u, nbc8 = (unsigned)bc.nbox * 8u;
+        double X[NS * NS];
+#pragma unroll
+        for (int e = 0; e < NS * NS; ++e) X[e] = ldg(A, cc8 + e * nbc8);             // A_{c,q}
+        pc_right_solve<NS>(D, X);
+        GPTR(double) Fs = F + back * (NS * NS) * N;
+#pragma unroll
+        for (int e = 0; e < NS * NS; ++e) stg(Fs + e * N, (unsigned)c * 8u, X[e]);
     }
     if (!pc_invert<NS>(D)) T.flag[0] = (int)q + 1;      // any of the failing cells: the host names one of them
     GPTR(double) Fd = F + (long)6 * (NS * NS) * N;

@@ -3,14 +3,11 @@
 
 #define PCE(a, r, c) a[(c) * NS + (r)]
 
-// a <- a^-1 by LU with partial pivoting on [a | 1] and back substitution, in registers (every index is a compile-time constant;
-// a row exchange is a conditional swap).  Returns false when a pivot is zero or not finite.
+// b <- a^-1 b by LU with partial pivoting on [a | b] and back substitution, in registers (every index is a compile-time constant;
+// a row exchange is a conditional swap); a is destroyed.  Returns false when a pivot is zero or not finite.
 template <int NS>
-__device__ __forceinline__ bool pc_invert(double (&a)[NS * NS])
+__device__ __forceinline__ bool pc_solve(double (&a)[NS * NS], double (&b)[NS * NS])
 {
-    double b[NS * NS];
-#pragma unroll
-    for (int e = 0; e < NS * NS; ++e) b[e] = (e % (NS + 1) == 0) ? 1.0 : 0.0;
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
@@ -52,7 +49,39 @@ __device__ __forceinline__ bool pc_invert(double (&a)[NS * NS])
             PCE(b, k, c) = t / piv;
         }
     }
+    return ok;
+}
+
+// a <- a^-1: pc_solve on [a | 1]
+template <int NS>
+__device__ __forceinline__ bool pc_invert(double (&a)[NS * NS])
+{
+    double b[NS * NS];
+#pragma unroll
+    for (int e = 0; e < NS * NS; ++e) b[e] = (e % (NS + 1) == 0) ? 1.0 : 0.0;
+    const bool ok = pc_solve<NS>(a, b);
 #pragma unroll
     for (int e = 0; e < NS * NS; ++e) a[e] = b[e];
     return ok;
+}
+
+// x <- x d^-1 by a SOLVE with d (d^T y = x^T, pc_solve), not by a product with the explicit inverse: for a pivot block whose inverse
+// spans many orders of magnitude (a wall-clustered RANS cell: condition numbers of 1e11) the product x d^-1 loses a digit that the
+// solve keeps, and the loss enters every later pivot through the Schur update.  d is left as it is.
+template <int NS>
+__device__ __forceinline__ void pc_right_solve(const double (&d)[NS * NS], double (&x)[NS * NS])
+{
+    double at[NS * NS], bt[NS * NS];
+#pragma unroll
+    for (int r = 0; r < NS; ++r)
+#pragma unroll
+        for (int c = 0; c < NS; ++c) {
+            PCE(at, r, c) = PCE(d, c, r);
+            PCE(bt, r, c) = PCE(x, c, r);
+        }
+    pc_solve<NS>(at, bt);          // (a singular d is reported by the pc_invert that follows in the same thread)
+#pragma unroll
+    for (int r = 0; r < NS; ++r)
+#pragma unroll
+        for (int c = 0; c < NS; ++c) PCE(x, c, r) = PCE(bt, r, c);
 }

@@ -38,6 +38,7 @@ class Block:
     coarsened: tuple = ("regular", "regular", "regular")   # blockType%iCoarsened / jCoarsened / kCoarsened (block.F90:230-233)
     frame: Optional[dict] = None         # LatticeTopology.frame: the block's place in the one analytic map of a multi-block mesh
     nodeMap: Optional[tuple] = None      # coarse block: per direction the FINE node of every coarse node 1..il (imap of createCoarseBlocks)
+    shape: Optional[object] = None       # make_nodes' shape: the physical map of the block instead of the wavy unit cube
 
     # index helpers (reference naming)
     @property
@@ -73,7 +74,7 @@ class Block:
 
     def copy(self) -> "Block":
         return Block(self.nx, self.ny, self.nz, self.nw, {k: v.copy(order="F") for k, v in self.a.items()}, self.rotRate, self.rightHanded,
-                     self.nodeParams, self.coarsened, self.frame, self.nodeMap)
+                     self.nodeParams, self.coarsened, self.frame, self.nodeMap, self.shape)
 
 
 def add_grid_velocities(blk: "Block", prm, rotRate=(0.05, -0.03, 0.12), rotCenter=(0.3, -0.2, 0.1)):
@@ -117,13 +118,18 @@ def node_params(nx, ny, nz, stretch_k=1.0):
     return xi, et, ze
 
 
-def make_nodes(nx, ny, nz, lengths=(1.0, 1.0, 1.0), amp=0.02, stretch_k=1.0, origin=(0.0, 0.0, 0.0), params=None, frame=None):
+def make_nodes(nx, ny, nz, lengths=(1.0, 1.0, 1.0), amp=0.02, stretch_k=1.0, origin=(0.0, 0.0, 0.0), params=None, frame=None,
+               shape=None):
     """Nodes x(0:ie,0:je,0:ke,3): smooth non-orthogonal right-handed map of the
     unit cube (node 1 -> 0, node il -> 1; halo nodes 0 and ie continue the map).
     params: the nodes' (xi, eta, zeta) instead of the uniform division (irregularly coarsened multigrid levels).
     frame (LatticeTopology.frame): the block is one of several that share ONE map; `params` are then the nodes' offsets from
     node 1 along the block's own index directions in lattice units, the lattice position of a node is o + T offsets and its
-    (xi, eta, zeta) that position times `scale` -- blocks of any orientation and size get identical coordinates on shared nodes."""
+    (xi, eta, zeta) that position times `scale` -- blocks of any orientation and size get identical coordinates on shared nodes.
+    shape: a callable (X, E, Z) -> (..., 3) that replaces the wavy unit cube: it gets the parameter arrays after the frame transform
+    and after the stretch_k / stretch_z clustering and returns the points of its own map, which `lengths` scale and `origin` moves
+    as they do the cube.  Blocks that share a frame evaluate it on bit-identical parameters of their shared nodes.  With a wall
+    on k = kMin it also carries wall_distance(points, lengths, origin) (make_block).  None: the cube, bit for bit."""
     ie, je, ke = nx + 2, ny + 2, nz + 2
     xi, et, ze = params if params is not None else node_params(nx, ny, nz, stretch_k)
     assert len(xi) == ie + 1 and len(et) == je + 1 and len(ze) == ke + 1
@@ -138,6 +144,12 @@ def make_nodes(nx, ny, nz, lengths=(1.0, 1.0, 1.0), amp=0.02, stretch_k=1.0, ori
             Z = np.sign(Z) * (np.expm1(sz * np.abs(Z)) / math.expm1(sz))
     tp = 2.0 * math.pi
     x = F((ie + 1, je + 1, ke + 1, 3))
+    if shape is not None:
+        pts = np.asarray(shape(X, E, Z), dtype=np.float64)
+        assert pts.shape == x.shape
+        for a in range(3):
+            x[..., a] = origin[a] + lengths[a] * pts[..., a]
+        return x
     x[..., 0] = origin[0] + lengths[0] * (X + amp * np.sin(tp * E) * np.sin(tp * Z))
     x[..., 1] = origin[1] + lengths[1] * (E + amp * np.sin(tp * X) * np.sin(tp * Z + 0.3))
     x[..., 2] = origin[2] + lengths[2] * (Z + amp * np.sin(tp * X + 0.7) * np.sin(tp * E))
@@ -223,17 +235,19 @@ def sa_eddy_viscosity(prm: FlowParams, rho, nut, rlv):
 
 def make_block(nx, ny, nz, prm: FlowParams, seed=20260925, lengths=(1.0, 1.0, 1.0), amp=0.02,
                stretch_k=1.0, wall_kmin=None, noise=0.02, wave=0.05, origin=(0.0, 0.0, 0.0), holes=0.0,
-               noflux_jmax=False, moving=False, left_handed=False, params=None, frame=None) -> Block:
+               noflux_jmax=False, moving=False, left_handed=False, params=None, frame=None, shape=None) -> Block:
     """Analytic curvilinear block + perturbed free-stream state.
     moving: a block of a steadily rotating frame (add_grid_velocities).
-    params: (xi, eta, zeta) of the nodes (make_nodes) instead of the uniform division; frame: see make_nodes."""
+    params: (xi, eta, zeta) of the nodes (make_nodes) instead of the uniform division; frame, shape: see make_nodes.
+    With a shape d2Wall is shape.wall_distance(cell centres, lengths, origin): the distance to the wall that the map puts on k = kMin."""
     rng = np.random.default_rng(seed)
     nw = prm.nw
     b = Block(nx, ny, nz, nw)
     ib, jb, kb = b.ib, b.jb, b.kb
     b.nodeParams = params if params is not None else node_params(nx, ny, nz, stretch_k)
     b.frame = frame
-    x = make_nodes(nx, ny, nz, lengths, amp, stretch_k, origin, b.nodeParams, frame)
+    b.shape = shape
+    x = make_nodes(nx, ny, nz, lengths, amp, stretch_k, origin, b.nodeParams, frame, shape)
     sI, sJ, sK = face_metrics(x)
     if frame is not None and np.linalg.det(frame["T"]) < 0:
         assert not left_handed
@@ -303,7 +317,11 @@ def make_block(nx, ny, nz, prm: FlowParams, seed=20260925, lengths=(1.0, 1.0, 1.
     # wall distance: distance from the cell centre to the k=kmin plane (>= 1e-6)
     xc = 0.125 * (x[1:, 1:, 1:] + x[:-1, 1:, 1:] + x[1:, :-1, 1:] + x[:-1, :-1, 1:]
                   + x[1:, 1:, :-1] + x[:-1, 1:, :-1] + x[1:, :-1, :-1] + x[:-1, :-1, :-1])
-    d = xc[1:nx + 1, 1:ny + 1, 1:nz + 1, 2] - origin[2]
+    if shape is not None:
+        d = np.asarray(shape.wall_distance(xc[1:nx + 1, 1:ny + 1, 1:nz + 1], lengths, origin), dtype=np.float64)
+        assert d.shape == (nx, ny, nz)
+    else:
+        d = xc[1:nx + 1, 1:ny + 1, 1:nz + 1, 2] - origin[2]
     b["d2Wall"] = np.asfortranarray(np.maximum(d, 1e-6))
     if moving:
         add_grid_velocities(b, prm)
@@ -508,6 +526,8 @@ def make_coarse_block(fine: Block, prm: FlowParams, keep=((), (), ()), **mk) -> 
     regular = all((m[1] == 1.0).all() for m in maps)
     if fine.frame is not None:
         mk["frame"] = fine.frame
+    if fine.shape is not None:
+        mk["shape"] = fine.shape
     if fine.frame is None and regular and (2 * ncs[0], 2 * ncs[1], 2 * ncs[2]) == (fine.nx, fine.ny, fine.nz):
         mk.pop("params", None)
         c = make_block(ncs[0], ncs[1], ncs[2], prm, **mk)

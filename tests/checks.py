@@ -548,13 +548,31 @@ def check_apply_bc(engine, dims, prm, spec, secondHalo=True, seed=51, level=1, s
     return blk, r
 
 
-def _warp_owned_nodes(blocks, seed):
-    """move the nodes 1..il x 1..jl x 1..kl of every block (the halo nodes are what xhalo / exchangeCoor rebuild)"""
+def local_warp(x, rel, rng):
+    """a displacement of every node of x by at most `rel` times the shortest edge that ends in it, per coordinate: a warp that keeps
+    the character of a clustered, scaled or collapsed mesh (coincident nodes have an edge of length zero and stay where they are)"""
+    big = np.full(x.shape[:3], np.inf)
+    for ax in range(3):
+        e = np.sqrt((np.diff(x, axis=ax) ** 2).sum(axis=-1))
+        lo = [slice(None)] * 3
+        hi = [slice(None)] * 3
+        lo[ax], hi[ax] = slice(0, -1), slice(1, None)
+        big[tuple(lo)] = np.minimum(big[tuple(lo)], e)
+        big[tuple(hi)] = np.minimum(big[tuple(hi)], e)
+    return rel * big[..., None] * rng.uniform(-1, 1, x.shape)
+
+
+def _warp_owned_nodes(blocks, seed, warp=None):
+    """move the nodes 1..il x 1..jl x 1..kl of every block (the halo nodes are what xhalo / exchangeCoor rebuild).
+    warp: relative to the local edge length (local_warp) instead of 5 % of the unit cube's mean spacing"""
     rng = np.random.default_rng(seed)
     for nn in sorted(blocks):
         b = blocks[nn]
         h = 1.0 / max(b.nx, b.ny, b.nz)
-        d = 0.05 * h * rng.uniform(-1, 1, b["x"][1:-1, 1:-1, 1:-1].shape)
+        if warp is not None:
+            d = local_warp(b["x"], warp, rng)[1:-1, 1:-1, 1:-1]
+        else:
+            d = 0.05 * h * rng.uniform(-1, 1, b["x"][1:-1, 1:-1, 1:-1].shape)
         b["x"][1:-1, 1:-1, 1:-1] += d
         # poison the halo nodes so that a missing update cannot pass
         for sl in ((0,), (-1,)):
@@ -579,11 +597,12 @@ def check_coordinate_halos_brick(engine, topo, prm, seed=83, **mk):
     brick of blocks after the owned nodes moved: the front part of the `useSpatial` branch of blocketteRes."""
     from oracle import ref
     translate, quantise = mk.get("translate"), mk.get("quantise")
+    warp = mk.pop("warp", None)
     shifted = translate is not None or quantise is not None
     blocks, rblocks = setup_brick(engine, topo, prm, seed, **mk)
     npat = topo.patterns(0)[0]
     engine.comm_register(1, 0, npat)
-    _warp_owned_nodes(blocks, seed)
+    _warp_owned_nodes(blocks, seed, warp)
 
     def reference(rb):
         ref.set_internal_comm(1, 0, npat)
@@ -688,6 +707,7 @@ def check_coarse_level_geometry(engine, topo, prm, seed=87, **mk):
     nodes by injection (coarseOwnedCoordinates, coarseUtils.F90:780-858, restated with numpy: a pure copy of every
     second node), then xhalo + exchangeCoor + volume / metric of the coarse level against the reference's routines."""
     from oracle import ref
+    warp = mk.pop("warp", None)
     levels, rlevels = setup_multilevel_brick(engine, topo, prm, nlevels=2, seed=seed, **mk)
     c1 = next(iter(levels[1].values()))
     t2 = topo.coarse() if hasattr(topo, "coarse") else type(topo)(topo.Bi, topo.Bj, topo.Bk, c1.nx, c1.ny, c1.nz)
@@ -695,7 +715,7 @@ def check_coarse_level_geometry(engine, topo, prm, seed=87, **mk):
         npat = t.patterns(0)[0]
         ref.set_internal_comm(lv, 0, npat)
         engine.comm_register(lv, 0, npat)
-    _warp_owned_nodes(levels[0], seed)
+    _warp_owned_nodes(levels[0], seed, warp)
     for nn, b in levels[0].items():
         engine.upload_coordinates(nn, 1)
         # numpy statement of coarseOwnedCoordinates: coarse node ii = the fine node that survived the coarsening
@@ -737,6 +757,7 @@ def check_xhalo_symmetry(engine, dims, prm, spec, split=(), seed=85, **mk):
     from oracle import ref
     from adflow_amd.synth import make_bocos
     new_level(engine)
+    warp = mk.pop("warp", None)
     prm = prm.replace(currentLevel=1, groundLevel=1)
     blk = make_block(*dims, prm, seed=seed, **mk)
     faces, nvisc = make_bocos(blk, prm, spec, seed=seed + 1, split=split)
@@ -746,7 +767,7 @@ def check_xhalo_symmetry(engine, dims, prm, spec, split=(), seed=85, **mk):
     engine.set_options(prm)
     engine.register(blk, nn=1, level=1)
     engine.bc_register(faces, nvisc, nn=1, level=1)
-    _warp_owned_nodes({1: blk}, seed)
+    _warp_owned_nodes({1: blk}, seed, warp)
     r = blk.copy()
     ref.bind_block(r, prm)
     ref.set_bocos(faces, nvisc)
@@ -838,7 +859,7 @@ def check_wall_stress(engine, dims, prm, spec, split=(), seed=57, dadi=False, **
     assert_dw(blk, dw, r["dw"], 5, what="dw with wall stress storage")
 
 
-def check_update_geometry(engine, dims, prm, spec, seed=81, translate=None, quantise=None, **mk):
+def check_update_geometry(engine, dims, prm, spec, seed=81, translate=None, quantise=None, warp=None, **mk):
     """volume_block + metric_block + boundaryNormals (adjointExtra.F90:5-364) after the nodes moved: vol, sI/sJ/sK
     and - through a boundary-condition pass that reads them - the unit normals of the boundary subfaces."""
     from oracle import ref
@@ -853,7 +874,7 @@ def check_update_geometry(engine, dims, prm, spec, seed=81, translate=None, quan
     # warp the mesh (same on both sides), then derive the metrics
     rng = np.random.default_rng(seed)
     h = 1.0 / max(dims)
-    blk["x"] += 0.05 * h * rng.uniform(-1, 1, blk["x"].shape)
+    blk["x"] += 0.05 * h * rng.uniform(-1, 1, blk["x"].shape) if warp is None else local_warp(blk["x"], warp, rng)
     geo0 = None
     if translate is not None or quantise is not None:
         # the warped nodes quantised (volume_block adds eight coordinates: q = 36) and shifted; the reference on the unshifted nodes first
@@ -890,7 +911,7 @@ def check_update_geometry(engine, dims, prm, spec, seed=81, translate=None, quan
     assert_state(engine, {1: blk}, {1: r}, prm, "BCs with the recomputed boundary normals")
 
 
-def check_wall_distance(engine, dims, prm, seed=83, at_wall=False, translate=None, quantise=None, **mk):
+def check_wall_distance(engine, dims, prm, seed=83, at_wall=False, translate=None, quantise=None, warp=None, **mk):
     """wallDistance::updateWallDistancesQuickly (wallDistance.F90:36-120) after a mesh warp: d2Wall of the owned cells from the
     wall association (four surface nodes + (u, v) per cell, cells without a wall in reach = large) and the moved surface nodes.
     at_wall: the surface is the block's own kMin node plane and every cell is associated with the quad under it, (u, v) from
@@ -942,14 +963,14 @@ def check_wall_distance(engine, dims, prm, seed=83, at_wall=False, translate=Non
         assert (np.abs(np.where(far, 1.0, out) - near) / near).max() <= TOL
         assert 0.0 < r["d2Wall"].min() < 0.05 * np.where(far, 0.0, r["d2Wall"]).max()
         return
-    blk, ind, uv, xSurf, r = wall_distance_case(blk, prm, rng, dims)
+    blk, ind, uv, xSurf, r = wall_distance_case(blk, prm, rng, dims, warp)
     engine.registerWallAssociation(ind, uv)
     engine.upload_coordinates(1, 1)
     engine.updateWallDistancesQuickly(xSurf, 1)
     assert_wall_distance(engine, r, ind)
 
 
-def wall_distance_case(blk, prm, rng, dims):
+def wall_distance_case(blk, prm, rng, dims, warp=None):
     """the general case of check_wall_distance up to the reference's result, for the block `blk`: a random
     association with 57 surface nodes, the mesh and the surface warped, the reference's d2Wall in r.  Nothing of it is handed to the
     engine yet.  Returns (blk, surfNodeIndices, uv, xSurf, r)."""
@@ -961,8 +982,11 @@ def wall_distance_case(blk, prm, rng, dims):
     uv[:, 0, 0, 0] = (0.0, 1.0)
     # warp the mesh and the surface, then update
     h = 1.0 / max(dims)
-    blk["x"] += 0.05 * h * rng.uniform(-1, 1, blk["x"].shape)
+    blk["x"] += 0.05 * h * rng.uniform(-1, 1, blk["x"].shape) if warp is None else local_warp(blk["x"], warp, rng)
     xSurf = rng.uniform(-0.2, 1.2, size=3 * nsurf)
+    if warp is not None:        # the surface where the mesh is, whatever its place and unit of length
+        lo, hi = blk["x"].reshape(-1, 3).min(axis=0), blk["x"].reshape(-1, 3).max(axis=0)
+        xSurf = (lo + (hi - lo) * xSurf.reshape(nsurf, 3)).reshape(-1)
     r = blk.copy()
     ref.alloc_doms(1, 1)
     ref.bind_block(r, prm)

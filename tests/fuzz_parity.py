@@ -305,8 +305,37 @@ KERNEL_DEFAULTS = {"roe_march": 1, "inviscid_march": 2, "viscous_tiled": 2, "sa_
                    "ra_pcr": 1, "rvec_joint": 1, "metric_from_x": 5}
 
 
-def sweep(engine, cases, seed, only=-1, quiet=False, big=False, jac=False):
-    """Run `cases` random cases; returns (number run, description of the first failure or None)."""
+ALL_DEFAULTS = {"split_eval": 1, "pc_fused": 1, "jac_snap": 1, **KERNEL_DEFAULTS}
+
+# entries whose mesh a family may replace: the ones that build single blocks or periodic bricks with make_block's keywords (the
+# lattice has its own map; the multigrid cycles and the smoother sweeps are tuned to states that survive on the cube)
+FAMILY_ENTRIES = ("block_res", "blockette", "blockette_intermed", "approx", "bc", "nk", "full_bc", "ad")
+
+
+def draw_family(frng, mk, entry):
+    """the mesh family (tests/mesh_families.py) and the unit of length of a case, from a stream of its own: {} or the keywords shape /
+    lengths of make_block.  `pole` only under the residual entries: the entries with boundary subfaces build them with make_bocos,
+    whose unit normals of a collapsed face (0 / 0) need the definition that mesh_checks._finite_bocos gives them."""
+    import mesh_families as mf
+    out = {}
+    if entry not in FAMILY_ENTRIES or mk.get("left_handed"):
+        return out
+    names = ["annulus", "sheared", "clustered"] + (["pole"] if entry in ("block_res", "blockette", "blockette_intermed") else [])
+    name = str(frng.choice(names + ["cube"]))
+    if name != "cube":
+        out["shape"] = mf.family(name)
+        # the far-origin draw's clustering (exp(11 z), halo nodes at z = 2 on a one-cell block) is made for the cube: under a map with a
+        # growth law of its own it overflows; the family keeps the mild clustering only
+        if mk.get("stretch_k", 1.0) > 3.0 or name in ("annulus", "clustered"):
+            out["stretch_k"] = 2.0 if name in ("sheared", "pole") else 1.0
+    k = int(frng.integers(0, len(mf.UNIT_LENGTHS) + 2))
+    if k < len(mf.UNIT_LENGTHS):
+        out["lengths"] = mf.UNIT_LENGTHS[k]
+    return out
+
+
+def cases_of(cases, seed, big=False, jac=False, families=False):
+    """the cases of a sweep, in order: (n, dims, options, make_block keywords, entry, tuning keys)"""
     rng = np.random.default_rng(seed)
     for n in range(cases):
         dims, kw, mk, entry = draw_jac_case(rng) if jac else draw_case(rng, big)
@@ -324,6 +353,22 @@ def sweep(engine, cases, seed, only=-1, quiet=False, big=False, jac=False):
                 tune[k_] = int(trng.choice(vals))
         # the options no earlier draw moved (draw_options), again from a stream of their own
         kw = {**kw, **draw_options(np.random.default_rng([seed, n, 7]), kw, mk, entry)}
+        if families:
+            # the mesh family and the unit of length: a stream seeded by the case's own seed, as the far-origin draw's is
+            mk = {**mk, **draw_family(np.random.default_rng([int(mk["seed"]), 8]), mk, entry)}
+        yield n, dims, kw, mk, entry, tune
+
+
+def describe(dims, kw, mk, entry, tune):
+    """a case as one line of text (tests/golden/fuzz_sweep_cases.json holds the lines of the 300 cases of test_random_parity_sweep)"""
+    return repr((tuple(int(d) for d in dims), entry, sorted(kw.items()), sorted((k, str(v)) for k, v in mk.items()),
+                 sorted({**ALL_DEFAULTS, **tune}.items())))
+
+
+def sweep(engine, cases, seed, only=-1, quiet=False, big=False, jac=False, families=False):
+    """Run `cases` random cases; returns (number run, description of the first failure or None).
+    families: the mesh family and the lengths drawn too (draw_family); without it the cases are what they always were."""
+    for n, dims, kw, mk, entry, tune in cases_of(cases, seed, big, jac, families):
         if only >= 0 and n != only:
             continue
         try:
@@ -335,7 +380,7 @@ def sweep(engine, cases, seed, only=-1, quiet=False, big=False, jac=False):
         except AssertionError as ex:
             return n + 1, f"case {n} (seed {seed}): {dims} {entry} {kw} {mk} {tune}: {ex}"
         finally:
-            for k_, v_ in {"split_eval": 1, "pc_fused": 1, "jac_snap": 1, **KERNEL_DEFAULTS}.items():
+            for k_, v_ in ALL_DEFAULTS.items():
                 engine.set_tuning(k_, v_)
     return cases, None
 
@@ -348,6 +393,7 @@ def main():
     ap.add_argument("--only", type=int, default=-1, help="run this case index only")
     ap.add_argument("--big", action="store_true", help="blocks of 100-200 x 5-40 x 40-100 cells (residual entry points only; for --gpu)")
     ap.add_argument("--jac", action="store_true", help="the Jacobian assemblies only (draw_jac_case)")
+    ap.add_argument("--families", action="store_true", help="draw the mesh family and the unit of length too (tests/mesh_families.py)")
     a = ap.parse_args()
     from adflow_amd.engine import Engine
     if a.gpu:
@@ -356,11 +402,12 @@ def main():
         from hostsim.build import build
         eng = Engine(0, _lib_path=build())
     t0 = time.time()
-    n, failure = sweep(eng, a.cases, a.seed, a.only, big=a.big, jac=a.jac)
+    n, failure = sweep(eng, a.cases, a.seed, a.only, big=a.big, jac=a.jac, families=a.families)
     if failure:
         print("FAIL", failure)
         print(f"reproduce: python tests/fuzz_parity.py --seed {a.seed} --cases {a.cases} --only {n - 1}" + (" --gpu" if a.gpu else "")
-              + (" --big" if a.big else "") + (" --jac" if a.jac else ""))
+              + (" --big" if a.big else "") + (" --jac" if a.jac else "")
+              + (" --families" if a.families else ""))
     print(f"{n} cases, {1 if failure else 0} failures, {time.time() - t0:.0f} s")
     nfail = 1 if failure else 0
     eng.close()

@@ -169,7 +169,7 @@ def assert_identity(engine, op, first, seed):
 
 def single_block(engine, dims, prm, spec, seed=107, **jac):
     """the preconditioner matrix by forward mode on one block with six boundary faces; returns (blk, operator)"""
-    mk = {k: jac.pop(k) for k in ("stretch_k",) if k in jac}
+    mk = {k: jac.pop(k) for k in ("stretch_k", "shape", "lengths") if k in jac}
     blk, rblk, prm = checks.setup_block_with_bc(engine, dims, prm, spec, seed, **mk)
     _REF_BLOCKS[:] = [rblk]          # the reference's flowDoms point into these arrays: alive as long as ref may be called
     engine.setupStateResidualMatrix(1, True, useAD=True, **jac)
