@@ -160,6 +160,7 @@ EXPORTS = [
     "adflow_gpu_pc_setup", "adflow_gpu_pc_info", "adflow_gpu_pc_apply", "adflow_gpu_pc_apply_dev", "adflow_gpu_pc_release", "adflow_gpu_pc_select",
     "adflow_gpu_pc_set_fill", "adflow_gpu_pc_info2", "adflow_gpu_pc_set_coupled", "adflow_gpu_pc_coupled_info", "adflow_gpu_pc_set_mg", "adflow_gpu_pc_mg_info", "adflow_gpu_pc_mg_download",
     "adflow_gpu_gmres_solve", "adflow_gpu_gmres_solve_dev",
+    "adflow_gpu_jacfree_mult", "adflow_gpu_jacfree_mult_dev", "adflow_gpu_jacfree_solve", "adflow_gpu_jacfree_solve_dev",
     "adflow_gpu_jacobian_mult_multi", "adflow_gpu_jacobian_mult_multi_dev", "adflow_gpu_pc_apply_multi", "adflow_gpu_pc_apply_multi_dev",
     "adflow_gpu_gmres_solve_multi", "adflow_gpu_gmres_solve_multi_dev",
     "adflow_gpu_ank_set_w", "adflow_gpu_ank_set_w_dev", "adflow_gpu_ank_get_r", "adflow_gpu_ank_get_r_dev", "adflow_gpu_ank_time_step",
@@ -230,6 +231,11 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     lib.adflow_gpu_pc_release.argtypes = [POINTER(ctypes.c_int64)]
     for f in (lib.adflow_gpu_gmres_solve, lib.adflow_gpu_gmres_solve_dev):
         f.argtypes = [c_int, c_int, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_double, c_double, c_int,
+                      POINTER(c_int), POINTER(c_double), POINTER(c_double)]
+    lib.adflow_gpu_jacfree_mult.argtypes = [c_int, c_uint, c_void_p, c_void_p, ctypes.c_long]
+    lib.adflow_gpu_jacfree_mult_dev.argtypes = [c_int, c_uint, c_void_p, c_void_p, ctypes.c_long]
+    for f in (lib.adflow_gpu_jacfree_solve, lib.adflow_gpu_jacfree_solve_dev):
+        f.argtypes = [c_int, c_uint, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_double, c_double, c_int,
                       POINTER(c_int), POINTER(c_double), POINTER(c_double)]
     for f in (lib.adflow_gpu_jacobian_mult_multi, lib.adflow_gpu_jacobian_mult_multi_dev, lib.adflow_gpu_pc_apply_multi,
               lib.adflow_gpu_pc_apply_multi_dev):

@@ -1727,7 +1727,8 @@ static int ad_layout(int level, bool viscous)
     });
 }
 
-static int ad_prepare(int level)
+// sync = false (the matrix-free products in the enqueue-only mode): the host waits only where the slab had to be laid out
+static int ad_prepare(int level, bool sync = true)
 {
     if (ensure_table(level)) return 1;
     const int maxnn = g_tab_size[level];
@@ -1766,6 +1767,7 @@ static int ad_prepare(int level)
         HIPCHK(hipMalloc((void**)&g_ad_tab, sizeof(BlkView) * h.size()));
         HIPCHK(hipMemcpyAsync(g_ad_tab, h.data(), sizeof(BlkView) * h.size(), hipMemcpyHostToDevice, g_stream));
         g_ad_sig = sig;
+        sync = true;                   // (h is read by the copy above)
     }
     // values of this call: the passive arrays and the frozen closures from the library's arrays, zero elsewhere
     for (auto& kv : g_ad)
@@ -1773,7 +1775,7 @@ static int ad_prepare(int level)
             if (q.src) ad_launch_from_real(q.src, q.dst, (long)q.n, g_stream);
             else HIPCHK(hipMemsetAsync(q.dst, 0, q.zeroBytes, g_stream));
         }
-    HIPCHK(hipStreamSynchronize(g_stream));
+    if (sync) HIPCHK(hipStreamSynchronize(g_stream));
     return 0;
 }
 
@@ -1815,23 +1817,24 @@ struct PcSwitchGuard {
 };
 }  // namespace
 
-static int jac_check_args(int level, unsigned flags, double delta)
+// who: the entry that reports; ad: what it appends where forward mode is the reason ("(useAD)", or nothing for the matrix-free entries)
+static int jac_check_args(int level, unsigned flags, double delta, const char* who = "fd_jacobian", const char* ad = "(useAD)")
 {
     if (flags & ~(ADFLOW_JAC_PC | ADFLOW_JAC_FROZEN_TURB | ADFLOW_JAC_TURB_ONLY | ADFLOW_JAC_VISC_PC | ADFLOW_JAC_USE_AD | ADFLOW_JAC_APPROX_SA))
-        return fail("fd_jacobian: unknown flags 0x%x", flags);
+        return fail("%s: unknown flags 0x%x", who, flags);
     const bool useAD = (flags & ADFLOW_JAC_USE_AD) != 0;
-    if (!useAD && !(delta > 0.0)) return fail("fd_jacobian: delta must be positive");     // forward mode has no step size
+    if (!useAD && !(delta > 0.0)) return fail("%s: delta must be positive", who);     // forward mode has no step size
     if (useAD) {
         // forward-mode seeds instead of perturbations (adjointUtils.F90:227-409): kernels on dual numbers, blocks at rest
-        if (!level_at_rest(level)) return fail("fd_jacobian(useAD): moving blocks are not linearised (grid velocities)");
-        if (!g_act.empty()) return fail("fd_jacobian(useAD): actuator regions are not linearised");
-        if (g_bc_callback) return fail("fd_jacobian(useAD): a host boundary-condition hook cannot be linearised");
+        if (!level_at_rest(level)) return fail("%s%s: moving blocks are not linearised (grid velocities)", who, ad);
+        if (!g_act.empty()) return fail("%s%s: actuator regions are not linearised", who, ad);
+        if (g_bc_callback) return fail("%s%s: a host boundary-condition hook cannot be linearised", who, ad);
         if (g_turb_bc_callback && g_opts.equations == ADFLOW_RANS && !(flags & ADFLOW_JAC_FROZEN_TURB))
-            return fail("fd_jacobian(useAD): a host turbulence boundary-condition hook cannot be linearised");
+            return fail("%s%s: a host turbulence boundary-condition hook cannot be linearised", who, ad);
     }
-    if (level != g_opts.groundLevel) return fail("fd_jacobian: level %d is not the ground level %d (setupStateResidualMatrix sets both)", level, g_opts.groundLevel);
-    if ((flags & ADFLOW_JAC_TURB_ONLY) && g_opts.equations != ADFLOW_RANS) return fail("fd_jacobian: ADFLOW_JAC_TURB_ONLY needs the RANS equations");
-    if ((flags & ADFLOW_JAC_TURB_ONLY) && (flags & ADFLOW_JAC_FROZEN_TURB)) return fail("fd_jacobian: TURB_ONLY and FROZEN_TURB exclude each other");
+    if (level != g_opts.groundLevel) return fail("%s: level %d is not the ground level %d (setupStateResidualMatrix sets both)", who, level, g_opts.groundLevel);
+    if ((flags & ADFLOW_JAC_TURB_ONLY) && g_opts.equations != ADFLOW_RANS) return fail("%s: ADFLOW_JAC_TURB_ONLY needs the RANS equations", who);
+    if ((flags & ADFLOW_JAC_TURB_ONLY) && (flags & ADFLOW_JAC_FROZEN_TURB)) return fail("%s: TURB_ONLY and FROZEN_TURB exclude each other", who);
     return 0;
 }
 
@@ -3799,48 +3802,52 @@ struct JmWork {
     BlkView *tabX = nullptr, *tabY = nullptr;    // the level's block table with w -> xs / ys: the halo kernels on a foreign array
     size_t slots() const { return h.size(); }
 };
-JmWork g_jm;
+JmWork g_jm;                           // the products with the assembled matrix
+JmWork g_jf;                           // the matrix-free products (adflow_gpu_jacfree_mult): xs and its tables only, no matrix
 }  // namespace
 
-static int64_t jm_release()
+static int64_t jm_release_work(JmWork& W)
 {
-    const int64_t n = (int64_t)g_jm.bytes;
-    for (void* p : g_jm.raw) (void)hipFree(p);
-    if (g_jm.tab) (void)hipFree(g_jm.tab);
-    if (g_jm.tabX) (void)hipFree(g_jm.tabX);
-    if (g_jm.tabY) (void)hipFree(g_jm.tabY);
-    g_jm = JmWork();
+    const int64_t n = (int64_t)W.bytes;
+    for (void* p : W.raw) (void)hipFree(p);
+    if (W.tab) (void)hipFree(W.tab);
+    if (W.tabX) (void)hipFree(W.tabX);
+    if (W.tabY) (void)hipFree(W.tabY);
+    W = JmWork();
     return n;
 }
+static int64_t jm_release() { return jm_release_work(g_jm) + jm_release_work(g_jf); }
 
 // scratch arrays and tables of the product on `level` for nv vectors at once (kept between calls at the widest nv asked for; laid out
-// again when blocks or matrix changed)
-static int jm_prepare(int level, int nv = 1)
+// again when blocks or matrix changed).  matrix: W serves the assembled matrix g_jac (its blocks in the table, xs and ys); otherwise
+// the matrix-free product of nS variables per cell: the same halo'd xs and tables, no blocks and no ys
+static int jm_layout(JmWork& W, int level, int nS, int nv, bool matrix, const char* who)
 {
-    const int nS = g_jac.nState;
     std::vector<long> sig = {level, nS};
     int maxnn = 0;
     int rc = for_level(level, [&](Block* b) {
-        if (!b->jac || b->jac_ncomp != g_jac.nStencil * nS * nS)
-            return fail("jacobian_mult: a block of level %d has no assembled blocks (registered after the assembly?)", level);
-        if ((double)b->v.nbox * nS * nS * 8.0 >= 4294967296.0)
-            return fail("jacobian_mult: block of %ld box cells: nState^2 planes exceed the 4 GiB the kernels address from one base", b->v.nbox);
+        if (matrix && (!b->jac || b->jac_ncomp != g_jac.nStencil * nS * nS))
+            return fail("%s: a block of level %d has no assembled blocks (registered after the assembly?)", who, level);
+        if (matrix && (double)b->v.nbox * nS * nS * 8.0 >= 4294967296.0)
+            return fail("%s: block of %ld box cells: nState^2 planes exceed the 4 GiB the kernels address from one base", who, b->v.nbox);
         return 0;
     });
     if (rc) return rc;
     for (auto& kv : g_blocks)
         if (std::get<0>(kv.first) == level) {
-            sig.push_back(std::get<2>(kv.first)); sig.push_back((long)(intptr_t)kv.second); sig.push_back((long)(intptr_t)kv.second->jac);
+            sig.push_back(std::get<2>(kv.first)); sig.push_back((long)(intptr_t)kv.second);
+            sig.push_back(matrix ? (long)(intptr_t)kv.second->jac : 0);
             sig.push_back(kv.second->v.nbox);
             maxnn = std::max(maxnn, std::get<2>(kv.first));
         }
-    if (g_jm.tab && sig == g_jm.sig && nv <= g_jm.nv) return 0;
-    if (g_jm.tab && sig == g_jm.sig) nv = std::max(nv, g_jm.nv);
+    if (W.tab && sig == W.sig && nv <= W.nv) return 0;
+    if (W.tab && sig == W.sig) nv = std::max(nv, W.nv);
     HIPCHK(hipStreamSynchronize(g_stream));
-    (void)jm_release();
-    g_jm.level = level; g_jm.nState = nS; g_jm.nslots = maxnn; g_jm.nv = nv;
-    g_jm.h.assign(maxnn + 1, JmBlk());
-    memset(g_jm.h.data(), 0, sizeof(JmBlk) * g_jm.h.size());
+    (void)jm_release_work(W);
+    const int halves = matrix ? 2 : 1;                                    // xs and ys, or xs alone
+    W.level = level; W.nState = nS; W.nslots = maxnn; W.nv = nv;
+    W.h.assign(maxnn + 1, JmBlk());
+    memset(W.h.data(), 0, sizeof(JmBlk) * W.h.size());
     const size_t nt = (size_t)maxnn + 1;
     std::vector<BlkView> hx(nt * nv), hy(nt * nv);
     memset(hx.data(), 0, sizeof(BlkView) * hx.size());
@@ -3849,53 +3856,55 @@ static int jm_prepare(int level, int nv = 1)
         if (std::get<0>(kv.first) != level) continue;
         Block* b = kv.second;
         const BlkView& v = b->v;
-        const size_t bytes = (size_t)v.nbox * 2 * nS * nv * sizeof(double) + 256;
+        const size_t bytes = (size_t)v.nbox * halves * nS * nv * sizeof(double) + 256;
         void* raw = nullptr;
         if (hipMalloc(&raw, bytes) != hipSuccess) {
             (void)hipGetLastError();
-            (void)jm_release();
-            return fail("jacobian_mult: cannot allocate %zu bytes of scratch for %d vectors on a block of %ld box cells", bytes, nv, v.nbox);
+            (void)jm_release_work(W);
+            return fail("%s: cannot allocate %zu bytes of scratch for %d vectors on a block of %ld box cells", who, bytes, nv, v.nbox);
         }
-        g_jm.raw.push_back(raw);
-        g_jm.bytes += bytes;
+        W.raw.push_back(raw);
+        W.bytes += bytes;
         HIPCHK(hipMemsetAsync(raw, 0, bytes, g_stream));
-        JmBlk& q = g_jm.h[std::get<2>(kv.first)];
+        JmBlk& q = W.h[std::get<2>(kv.first)];
         q.nx = v.nx; q.ny = v.ny; q.nz = v.nz; q.il = v.il; q.jl = v.jl; q.kl = v.kl; q.ib = v.ib; q.jb = v.jb; q.kb = v.kb;
         q.ldi = v.ldi; q.ldk = v.ldk; q.nbox = v.nbox;
-        q.jac = b->jac;
+        q.jac = matrix ? b->jac : nullptr;
         q.xs = (double*)raw + ADF_PAD0;
-        q.ys = q.xs + (size_t)v.nbox * nS * nv;
+        q.ys = matrix ? q.xs + (size_t)v.nbox * nS * nv : nullptr;
         for (int c = 0; c < nv; ++c) {
             BlkView &x = hx[c * nt + std::get<2>(kv.first)], &y = hy[c * nt + std::get<2>(kv.first)];
             x = v; x.w = q.xs + (size_t)v.nbox * nS * c;
-            y = v; y.w = q.ys + (size_t)v.nbox * nS * c;
+            y = v; y.w = matrix ? q.ys + (size_t)v.nbox * nS * c : nullptr;
         }
-        g_jm.nx = std::max(g_jm.nx, v.nx); g_jm.ny = std::max(g_jm.ny, v.ny); g_jm.nz = std::max(g_jm.nz, v.nz);
+        W.nx = std::max(W.nx, v.nx); W.ny = std::max(W.ny, v.ny); W.nz = std::max(W.nz, v.nz);
     }
     long off = 0;                     // PETSc vector order: block nn ascending (NKSolvers.F90:1240-1253), nState entries per cell
-    for (auto& q : g_jm.h) { q.vecOff = off; off += (long)q.nx * q.ny * q.nz * nS; }
-    g_jm.ndof = off;
+    for (auto& q : W.h) { q.vecOff = off; off += (long)q.nx * q.ny * q.nz * nS; }
+    W.ndof = off;
     std::vector<JmBlk> ht(nt * nv);
     for (int c = 0; c < nv; ++c)
         for (size_t q = 0; q < nt; ++q) {
             JmBlk& t = ht[c * nt + q];
-            t = g_jm.h[q];
-            if (t.xs) { t.xs += (size_t)t.nbox * nS * c; t.ys += (size_t)t.nbox * nS * c; }
+            t = W.h[q];
+            if (t.xs) t.xs += (size_t)t.nbox * nS * c;
+            if (t.ys) t.ys += (size_t)t.nbox * nS * c;
         }
-    if (hipMalloc((void**)&g_jm.tab, sizeof(JmBlk) * ht.size()) != hipSuccess ||
-        hipMalloc((void**)&g_jm.tabX, sizeof(BlkView) * hx.size()) != hipSuccess ||
-        hipMalloc((void**)&g_jm.tabY, sizeof(BlkView) * hy.size()) != hipSuccess) {
+    if (hipMalloc((void**)&W.tab, sizeof(JmBlk) * ht.size()) != hipSuccess ||
+        hipMalloc((void**)&W.tabX, sizeof(BlkView) * hx.size()) != hipSuccess ||
+        hipMalloc((void**)&W.tabY, sizeof(BlkView) * hy.size()) != hipSuccess) {
         (void)hipGetLastError();
-        (void)jm_release();           // the scratch arrays as well: a later call lays everything out again
-        return fail("jacobian_mult: cannot allocate the block tables of %d vectors (%zu blocks); no scratch is held", nv, nt);
+        (void)jm_release_work(W);           // the scratch arrays as well: a later call lays everything out again
+        return fail("%s: cannot allocate the block tables of %d vectors (%zu blocks); no scratch is held", who, nv, nt);
     }
-    HIPCHK(hipMemcpy(g_jm.tab, ht.data(), sizeof(JmBlk) * ht.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(g_jm.tabX, hx.data(), sizeof(BlkView) * hx.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(g_jm.tabY, hy.data(), sizeof(BlkView) * hy.size(), hipMemcpyHostToDevice));
-    g_jm.sig = sig;
-    g_jm.zeroGen = g_state_gen;
+    HIPCHK(hipMemcpy(W.tab, ht.data(), sizeof(JmBlk) * ht.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(W.tabX, hx.data(), sizeof(BlkView) * hx.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(W.tabY, hy.data(), sizeof(BlkView) * hy.size(), hipMemcpyHostToDevice));
+    W.sig = sig;
+    W.zeroGen = g_state_gen;
     return 0;
 }
+static int jm_prepare(int level, int nv = 1) { return jm_layout(g_jm, level, g_jac.nState, nv, true, "jacobian_mult"); }
 
 // one reverse exchange as a donor-sorted list: targets (tb, to) with sources (sb, so), or with the position in the message
 static int jm_acc_build(JmAccList& a, const int* d_tBlk, const long* d_tOff, const int* d_sBlk, const long* d_sOff, int n)
@@ -3957,20 +3966,52 @@ static int jm_acc_lists(CommPattern* cp)
 
 // the registered 2-layer cell pattern of the level, or NULL when there is none (then no halo has a donor).  A rotational
 // periodicity would have to turn the velocity entries of the halos (forward: rotMatrix, reverse: its transpose): refused
-static int jm_pattern(int level, CommPattern** out)
+static int jm_pattern_of(int level, int lStart, int nState, const char* who, CommPattern** out)
 {
     *out = nullptr;
     if (!g_comm.count(std::make_pair(level, 2))) return 0;
     if (build_comm(level, 2, out)) return 1;
-    if (g_jac.lStart == 0 && g_jac.nState >= 5)
+    if (lStart == 0 && nState >= 5)
         for (auto& pd : (*out)->periodic) {
             bool identity = true;
             for (int q = 0; q < 9; ++q)
                 if (pd.rotMatrix[q] != ((q % 4 == 0) ? 1.0 : 0.0)) identity = false;
             if (!identity && !pd.h_block.empty())
-                return fail("jacobian_mult: rotational periodicity is not supported by the product (a registered periodic transformation of "
-                            "level %d rotates the velocities of its halos)", level);
+                return fail("%s: rotational periodicity is not supported by the product (a registered periodic transformation of "
+                            "level %d rotates the velocities of its halos)", who, level);
         }
+    return 0;
+}
+static int jm_pattern(int level, CommPattern** out) { return jm_pattern_of(level, g_jac.lStart, g_jac.nState, "jacobian_mult", out); }
+
+// the owned entries of the nv vectors into the halo'd arrays xs of W (halos without a donor read as zero) ...
+static int jm_scatter_x(JmWork& W, const double* d_x, int nv, long ldx)
+{
+    const int nS = W.nState;
+    const size_t nt = W.slots();
+    if (W.zeroGen != g_state_gen) {
+        // patterns may have changed: a halo that lost its donor must read as zero again
+        for (auto& q : W.h)
+            if (q.xs) HIPCHK(hipMemsetAsync(q.xs - ADF_PAD0, 0, ((size_t)q.nbox * nS * W.nv + ADF_PAD0) * sizeof(double), g_stream));
+        W.zeroGen = g_state_gen;
+    }
+    for (int v = 0; v < nv; ++v) launch_jm_scatter(W.tab + v * nt, W.nslots, W.nx, W.ny, W.nz, nS, d_x + v * ldx, g_stream);
+    return 0;
+}
+// ... and the 2-layer exchange on them: every halo with a donor takes its donor's entries
+static int jm_exchange_x(JmWork& W, CommPattern* cp, int nv)
+{
+    const int nS = W.nState;
+    const unsigned mask = (1u << nS) - 1u;
+    const size_t nt = W.slots();
+    for (int v = 0; cp && v < nv; ++v) {
+        bool remote = false;
+        if (comm_exchange_begin(cp, W.tabX + v * nt, mask, nS, &remote)) return 1;
+#ifndef ADFLOW_NO_RCCL
+        if (remote && g_overlap) HIPCHK(hipStreamWaitEvent(g_stream, g_evComm, 0));
+#endif
+        for (auto& l : cp->recvs) launch_halo_unpack(W.tabX + v * nt, l.blkA, l.offA, l.n, mask, l.buf, g_stream);
+    }
     return 0;
 }
 
@@ -3992,23 +4033,9 @@ static int jm_mult_enqueue(int level, int transpose, const double* d_x, double* 
             S.d[s][d] = g_jac.st[s][d];
             if (S.d[s][d] < -2 || S.d[s][d] > 2) return fail("jacobian_mult: stencil offset beyond the two halo layers");
         }
-    if (g_jm.zeroGen != g_state_gen) {
-        // patterns may have changed: a halo that lost its donor must read as zero again
-        for (auto& q : g_jm.h)
-            if (q.xs) HIPCHK(hipMemsetAsync(q.xs - ADF_PAD0, 0, ((size_t)q.nbox * nS * g_jm.nv + ADF_PAD0) * sizeof(double), g_stream));
-        g_jm.zeroGen = g_state_gen;
-    }
-    for (int v = 0; v < nv; ++v)
-        launch_jm_scatter(g_jm.tab + v * nt, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, d_x + v * ldx, g_stream);
+    if (jm_scatter_x(g_jm, d_x, nv, ldx)) return 1;
     if (!transpose) {
-        for (int v = 0; cp && v < nv; ++v) {
-            bool remote = false;
-            if (comm_exchange_begin(cp, g_jm.tabX + v * nt, mask, nS, &remote)) return 1;
-#ifndef ADFLOW_NO_RCCL
-            if (remote && g_overlap) HIPCHK(hipStreamWaitEvent(g_stream, g_evComm, 0));
-#endif
-            for (auto& l : cp->recvs) launch_halo_unpack(g_jm.tabX + v * nt, l.blkA, l.offA, l.n, mask, l.buf, g_stream);
-        }
+        if (jm_exchange_x(g_jm, cp, nv)) return 1;
         launch_jac_mult(g_jm.tab, g_jm.nslots, g_jm.nx, g_jm.ny, g_jm.nz, nS, S, d_y, g_stream, nv, ldy);
         return 0;
     }
@@ -5241,6 +5268,161 @@ int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x,
     const GmOperator op = [=](const double* v, double* y) { return jm_mult_enqueue(level, transpose, v, y); };
     return gm_solve("gmres_solve", op, transpose, s[0], s[1], n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm) ||
            s.out(x, 1) || s.done();
+}
+
+// ---- matrix-free exact products by forward mode: y = (dR/dw) x without an assembled matrix ------------------------------------------
+// The shell matrix the reference solves the direct equations on (useMatrixFreedRdw, pyADflow.py:5918; createPETScVars makes dRdwT a
+// shell, adjointAPI.F90:1199-1214): its forward product dRdwMatMult (:1050-1128) is ONE master_d with the vector as seed.  Here: the
+// vector goes through the halo'd scratch array and the 2-layer exchange of jacobian_mult (the column rule is the same), the seed
+// kernel writes the dual state from it, block_res_state_d runs once, and the read-out kernel takes the derivative part of the scaled
+// residual into y.  The evaluation is the one a coloured pass of adflow_gpu_fd_jacobian(flags | USE_AD) runs, so y is the product
+// with the matrix that call would assemble.
+namespace {
+struct JfSetup {
+    JacSpec J;
+    unsigned resFlags = 0;
+    bool pc = false, viscPC = false, turbBC = false, rans = false;
+};
+}  // namespace
+
+// the refusals of a product; on success S says what the flags select
+static int jf_check(const char* who, int level, unsigned flags, const double* x, const double* y, long n, JfSetup* S)
+{
+    if (need_ready()) return 1;
+    if (jac_check_args(level, flags | ADFLOW_JAC_USE_AD, 0.0, who, "")) return 1;
+    if (!x || !y) return fail("%s: %s is NULL", who, !x ? "x" : "y");
+    if (x == y) return fail("%s: x and y are the same vector (the product is not done in place)", who);
+    S->rans = g_opts.equations == ADFLOW_RANS;
+    jac_spec(flags & ~(ADFLOW_JAC_USE_AD | ADFLOW_JAC_APPROX_SA), S->rans || g_opts.equations == ADFLOW_NS, S->rans, &S->J);
+    long cells = 0;
+    int rc = for_level(level, [&](Block* b) {
+        cells += (long)b->v.nx * b->v.ny * b->v.nz;
+        return 0;
+    });
+    if (rc) return rc;
+    if (n != cells * S->J.nState)
+        return fail("%s: n=%ld but the operator of level %d has %ld rows (nState = %d x %ld owned cells)", who, n, level,
+                    cells * S->J.nState, S->J.nState, cells);
+    CommPattern* cp;
+    if (jm_pattern_of(level, S->J.lStart, S->J.nState, who, &cp)) return 1;
+    // the switches of adflow_gpu_fd_jacobian
+    S->pc = (flags & ADFLOW_JAC_PC) != 0;
+    S->viscPC = (flags & ADFLOW_JAC_VISC_PC) != 0;
+    S->turbBC = S->rans && !(flags & ADFLOW_JAC_FROZEN_TURB);
+    S->resFlags = 0;
+    if (!(flags & ADFLOW_JAC_TURB_ONLY)) S->resFlags |= ADFLOW_RES_FLOW;
+    if (S->turbBC) S->resFlags |= ADFLOW_RES_TURB;
+    if (S->turbBC && (flags & ADFLOW_JAC_APPROX_SA)) S->resFlags |= ADFLOW_RES_APPROX_SA;
+    if (S->pc) S->resFlags |= ADFLOW_RES_DISS_APPROX | ADFLOW_RES_VISC_APPROX;
+    return 0;
+}
+
+// what one linearisation point needs (PcSwitchGuard in force): whalo2 of the state, the frozen shock sensor of the preconditioner
+// matrix, the passive dual arrays, the scratch of the vector.  The host waits only where the slab or the scratch is laid out, or sync
+static int jf_prepare(const char* who, int level, const JfSetup& S, bool sync)
+{
+    if (g_comm.count(std::make_pair(level, 2)))
+        if (halo_exchange_enqueue(level, 1, S.rans ? 6 : 5, 1, 1, 2)) return 1;
+    if (S.pc && reference_shock_sensor_enqueue(level)) return 1;
+    if (ad_prepare(level, sync)) return 1;
+    return jm_layout(g_jf, level, S.J.nState, 1, false, who);
+}
+
+// seed, evaluate, read out (PcSwitchGuard in force, jf_prepare done)
+static int jf_product_enqueue(const char* who, int level, const JfSetup& S, const double* d_x, double* d_y)
+{
+    CommPattern* cp;
+    if (jm_pattern_of(level, S.J.lStart, S.J.nState, who, &cp)) return 1;
+    if (jm_scatter_x(g_jf, d_x, 1, 0) || jm_exchange_x(g_jf, cp, 1)) return 1;
+    const KParams kp = res_kparams(level, S.resFlags);
+    for (auto& kv : g_blocks)
+        if (std::get<0>(kv.first) == level)
+            ad_launch_seed_vector(kv.second->v, g_ad[kv.second].v, g_jf.h[std::get<2>(kv.first)].xs, S.J.lStart, S.J.nState, kp, g_stream);
+    if (block_res_state_enqueue(DUAL, level, S.resFlags, S.turbBC, S.viscPC, true)) return 1;
+    for (auto& kv : g_blocks)
+        if (std::get<0>(kv.first) == level)
+            ad_launch_jf_readout(g_ad[kv.second].v, d_y, g_jf.h[std::get<2>(kv.first)].vecOff, S.J.lStart, S.J.nState, g_opts.turbResScale,
+                                 g_stream);
+    return 0;
+}
+
+// after the last product of a call: a failed call, or tuning "ad_cache" = 0, gives the slab back (the queue is drained first)
+static int jf_finish(int rc)
+{
+    if (rc || !g_ad_cache) {
+        (void)hipStreamSynchronize(g_stream);
+        ad_drop();
+    }
+    return rc;
+}
+
+static int jf_mult_enqueue(const char* who, int level, const JfSetup& S, const double* d_x, double* d_y, bool sync)
+{
+    PcSwitchGuard switches(S.pc);
+    int rc = jf_prepare(who, level, S, sync);
+    if (!rc) rc = jf_product_enqueue(who, level, S, d_x, d_y);
+    return jf_finish(rc);
+}
+
+int adflow_gpu_jacfree_mult_dev(int level, unsigned flags, const double* d_x, double* d_y, long n)
+{
+    JfSetup S;
+    if (jf_check("jacfree_mult", level, flags, d_x, d_y, n, &S)) return 1;
+    if (jf_mult_enqueue("jacfree_mult", level, S, d_x, d_y, !g_async)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_jacfree_mult(int level, unsigned flags, const double* x, double* y, long n)
+{
+    JfSetup S;
+    Stage s;
+    return jf_check("jacfree_mult", level, flags, x, y, n, &S) || stage_open(&s, n, 2) || s.in(0, x) ||
+           jf_mult_enqueue("jacfree_mult", level, S, s[0], s[1], false) || s.out(y, 1) || s.done();
+}
+
+// GMRES on the shell matrix: the KSP of solveDirectForRHS (adjointAPI.F90) with dRdwMatMult as operator and the factor of the selected
+// slot as right preconditioner, never transposed.  One preparation, then every product only seeds, evaluates and reads out
+static int jf_solve_check(int level, unsigned flags, const double* b, const double* x, long n, int restart, int maxIts, double rtol,
+                          double atol, JfSetup* S)
+{
+    if (gm_check_ranks("jacfree_solve", "adflow_gpu_jacfree_mult_dev")) return 1;
+    if (pc_check("jacfree_solve", level, b, x, n, false)) return 1;
+    if (jf_check("jacfree_solve", level, flags, b, x, n, S)) return 1;
+    if (S->J.nState != pc_sel().nState)
+        return fail("jacfree_solve: the factor was set up for nState = %d, the flags select nState = %d", pc_sel().nState, S->J.nState);
+    if (n != pc_sel().ncell * pc_sel().nState) return fail("jacfree_solve: n=%ld but the factor has %ld rows", n, pc_sel().ncell * pc_sel().nState);
+    return gm_check_caps("jacfree_solve", restart, maxIts, rtol, atol);
+}
+
+static int jf_solve_run(int level, const JfSetup& S, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol,
+                        double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
+{
+    PcSwitchGuard switches(S.pc);
+    int rc = jf_prepare("jacfree_solve", level, S, true);
+    const GmOperator op = [&](const double* v, double* y) { return jf_product_enqueue("jacfree_solve", level, S, v, y); };
+    if (!rc) rc = gm_solve("jacfree_solve", op, 0, d_b, d_x, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm);
+    return jf_finish(rc);
+}
+
+int adflow_gpu_jacfree_solve_dev(int level, unsigned flags, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol,
+                                 double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
+{
+    JfSetup S;
+    if (jf_solve_check(level, flags, d_b, d_x, n, restart, maxIts, rtol, atol, &S)) return 1;
+    if (jf_solve_run(level, S, d_b, d_x, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm)) return 1;
+    return sync_and_check();
+}
+
+int adflow_gpu_jacfree_solve(int level, unsigned flags, const double* b, double* x, long n, int restart, int maxIts, double rtol,
+                             double atol, int useGuess, int* its, double* rnorm0, double* rnorm)
+{
+    JfSetup S;
+    if (jf_solve_check(level, flags, b, x, n, restart, maxIts, rtol, atol, &S)) return 1;
+    DevBuf buf;                        // b and x of this call, not g_vec_dev
+    HIPCHK(hipMalloc(&buf.p, sizeof(double) * 2 * n));
+    const Stage s{n, (double*)buf.p};
+    if (s.in(0, b) || (useGuess && s.in(1, x))) return 1;
+    return jf_solve_run(level, S, s[0], s[1], n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm) || s.out(x, 1) || s.done();
 }
 
 // nvec right-hand sides on the assembled matrix with the selected factor, in lock-step: every iteration is ONE application of M^-1

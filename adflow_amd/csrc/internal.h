@@ -652,6 +652,9 @@ void ad_launch_viscous(const BlkView& adv, const KParams& kp, hipStream_t s);
 void ad_launch_viscous_approx(const BlkView& adv, const KParams& kp, hipStream_t s);
 void ad_launch_seed_closures(const BlkView& real, const BlkView& adv, int l, int col, const JacSpec& J, const KParams& kp, hipStream_t s,
                              bool onlyL);
+// matrix-free products (adflow_gpu_jacfree_mult): the seed from the halo'd scratch array xs of the product, the result into the vector y
+void ad_launch_seed_vector(const BlkView& real, const BlkView& adv, const double* xs, int lStart, int nState, const KParams& kp, hipStream_t s);
+void ad_launch_jf_readout(const BlkView& adv, double* y, long vecOff, int lStart, int nState, double turbResScale, hipStream_t s);
 void ad_launch_pc_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, int kch, hipStream_t s);
 void ad_launch_sa_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
 void ad_launch_visc_gf(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);

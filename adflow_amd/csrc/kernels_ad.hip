@@ -205,6 +205,49 @@ __global__ __launch_bounds__(256) void k_seed_closures(BlkView b, const adf_real
     }
     closures_halo_cell(b, kp, i, j, k, c, wv);
 }
+// the seed of a matrix-free product (dRdwMatMult, adjointAPI.F90:1050-1128: the vector is the wd of ONE master_d): k_seed_closures with
+// a vector in place of a colour.  xs is the halo'd component-major array k_jm_scatter and the 2-layer exchange filled (nState
+// components, zero on every halo without a donor): component lStart + q of the cell takes xs(q) as derivative, every other component
+// a zero one.  All nw components are written in the one pass, the closures come from the values in registers
+__global__ __launch_bounds__(256) void k_seed_vector(BlkView b, const adf_real8* __restrict__ wsrc, const adf_real8* __restrict__ xs,
+                                                     int lStart, int nState, KParams kp)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x - 14;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int k = blockIdx.z;
+    if (i < 0 || i > b.ib || j > b.jb) return;
+    const long c = b.idx(i, j, k), nb = b.nbox;
+    double wv[6];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) {
+        if (m < b.nw) {
+            const int q = m - lStart;
+            const adf_real8 seed = (q >= 0 && q < nState) ? xs[c + q * nb] : 0.0;
+            wv[m] = Dual(wsrc[c + m * nb], seed);
+            b.w[c + m * nb] = wv[m];
+        } else
+            wv[m] = 0.0;
+    }
+    closures_halo_cell(b, kp, i, j, k, c, wv);
+}
+// the result of a matrix-free product: k_ad_snap and k_jm_gather in one pass.  The derivative part of the dual residual of the owned
+// cells, scaled as k_ad_snap scales it (1 / volRef, turbResScale on the turbulence row), goes into the PETSc-layout vector y (block,
+// k, j, i, nState variables fastest; vecOff: first entry of the block)
+__global__ __launch_bounds__(256) void k_jf_readout(BlkView b, adf_real8* __restrict__ y, long vecOff, int lStart, int nState,
+                                                    adf_real8 turbResScale)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x + 2;
+    const int j = blockIdx.y * 4 + threadIdx.y + 2;
+    const int k = blockIdx.z + 2;
+    if (i > b.il || j > b.jl) return;
+    const long c = b.idx(i, j, k);
+    const adf_real8 ovol = 1.0 / b.volRef[c];
+    const long m = vecOff + (((long)(k - 2) * b.ny + (j - 2)) * b.nx + (i - 2)) * nState;
+    for (int q = 0; q < nState; ++q) {
+        const int ll = lStart + q;
+        y[m + q] = b.dw[c + ll * b.nbox].d * ovol * (ll >= 5 ? turbResScale : 1.0);
+    }
+}
 
 #include "kernels_inviscid.hip"
 #include "kernels_timestep.hip"
@@ -240,6 +283,16 @@ void ad_launch_seed_closures(const BlkView& real, const BlkView& adv, int l, int
 {
     hipLaunchKernelGGL(adj::k_seed_closures, dim3((adv.ib + 15 + 63) / 64, (adv.jb + 4) / 4, adv.kb + 1), dim3(64, 4, 1), 0, s, *ADV(&adv),
                        real.w, l, col, J, kp, onlyL ? 1 : 0);
+}
+void ad_launch_seed_vector(const BlkView& real, const BlkView& adv, const double* xs, int lStart, int nState, const KParams& kp, hipStream_t s)
+{
+    hipLaunchKernelGGL(adj::k_seed_vector, dim3((adv.ib + 15 + 63) / 64, (adv.jb + 4) / 4, adv.kb + 1), dim3(64, 4, 1), 0, s, *ADV(&adv),
+                       real.w, xs, lStart, nState, kp);
+}
+void ad_launch_jf_readout(const BlkView& adv, double* y, long vecOff, int lStart, int nState, double turbResScale, hipStream_t s)
+{
+    hipLaunchKernelGGL(adj::k_jf_readout, dim3((adv.nx + 63) / 64, (adv.ny + 3) / 4, adv.nz), dim3(64, 4, 1), 0, s, *ADV(&adv), y, vecOff,
+                       lStart, nState, turbResScale);
 }
 void ad_launch_closures_halo(const BlkView& adv, const KParams& kp, hipStream_t s)
 {

@@ -276,6 +276,50 @@ class Engine:
                                                       ctypes.byref(its), ctypes.byref(r0), ctypes.byref(rn)))
         return int(its.value), float(r0.value), float(rn.value)
 
+    # ---- matrix-free exact products by forward mode (dRdwMatMult, adjointAPI.F90:1050-1128): no assembled matrix
+    @staticmethod
+    def _jacFreeFlags(usePC, frozenTurb, useTurbOnly, viscPC, approxSA):
+        return (capi.JAC_PC if usePC else 0) | (capi.JAC_FROZEN_TURB if frozenTurb else 0) | (capi.JAC_TURB_ONLY if useTurbOnly else 0) \
+            | (capi.JAC_VISC_PC if viscPC else 0) | (capi.JAC_APPROX_SA if approxSA else 0)
+
+    def jacFreeMult(self, x, level=1, usePC=False, frozenTurb=False, useTurbOnly=False, viscPC=False, approxSA=False):
+        """y = (dR/dw) x by ONE forward-mode evaluation seeded with x, about the state on the device: what jacobianMult returns after
+        setupStateResidualMatrix(level, usePC, ..., useAD=True), without the matrix.  Vectors as for jacobianMult"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.zeros_like(x)
+        flags = self._jacFreeFlags(usePC, frozenTurb, useTurbOnly, viscPC, approxSA)
+        self._chk(self.lib.adflow_gpu_jacfree_mult(level, flags, x.ctypes.data, y.ctypes.data, x.size))
+        return y
+
+    def jacFreeMultDev(self, d_x: int, d_y: int, n: int, level=1, usePC=False, frozenTurb=False, useTurbOnly=False, viscPC=False,
+                       approxSA=False):
+        """the same on device pointers (e.g. torch.Tensor.data_ptr())"""
+        flags = self._jacFreeFlags(usePC, frozenTurb, useTurbOnly, viscPC, approxSA)
+        self._chk(self.lib.adflow_gpu_jacfree_mult_dev(level, flags, ctypes.c_void_p(d_x), ctypes.c_void_p(d_y), int(n)))
+
+    def jacFreeSolve(self, b, level=1, restart=50, maxIts=200, rtol=1e-8, atol=0.0, x0=None, usePC=False, frozenTurb=False,
+                     useTurbOnly=False, viscPC=False, approxSA=False):
+        """right-preconditioned GMRES(restart) on the matrix-free product with the factor of pcSetup, never transposed (the KSP of
+        solveDirectForRHS on the shell dRdwT); returns (x, iterations, initial residual norm, true residual norm of x)"""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        x = np.zeros_like(b) if x0 is None else np.array(x0, dtype=np.float64, order="C", copy=True)
+        its, r0, rn = ctypes.c_int(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        flags = self._jacFreeFlags(usePC, frozenTurb, useTurbOnly, viscPC, approxSA)
+        self._chk(self.lib.adflow_gpu_jacfree_solve(level, flags, b.ctypes.data, x.ctypes.data, b.size, int(restart), int(maxIts),
+                                                    float(rtol), float(atol), int(x0 is not None), ctypes.byref(its), ctypes.byref(r0),
+                                                    ctypes.byref(rn)))
+        return x, int(its.value), float(r0.value), float(rn.value)
+
+    def jacFreeSolveDev(self, d_b: int, d_x: int, n: int, level=1, restart=50, maxIts=200, rtol=1e-8, atol=0.0, useGuess=False,
+                        usePC=False, frozenTurb=False, useTurbOnly=False, viscPC=False, approxSA=False):
+        """the same on device pointers; returns (iterations, initial residual norm, true residual norm)"""
+        its, r0, rn = ctypes.c_int(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        flags = self._jacFreeFlags(usePC, frozenTurb, useTurbOnly, viscPC, approxSA)
+        self._chk(self.lib.adflow_gpu_jacfree_solve_dev(level, flags, ctypes.c_void_p(d_b), ctypes.c_void_p(d_x), int(n), int(restart),
+                                                        int(maxIts), float(rtol), float(atol), int(bool(useGuess)), ctypes.byref(its),
+                                                        ctypes.byref(r0), ctypes.byref(rn)))
+        return int(its.value), float(r0.value), float(rn.value)
+
     # ---- several right-hand sides at once: columns as the rows of a C-contiguous (nvec, n) array, so ld = n
     @staticmethod
     def _columns(A):

@@ -420,6 +420,42 @@ module adflowGpuShim
             integer(c_int), intent(out) :: its
             real(c_double), intent(out) :: rnorm0, rnorm
         end function
+        ! matrix-free exact products by forward mode (dRdwMatMult, adjointAPI.F90:1050-1128: one master_d with the vector as seed) and
+        ! the GMRES of solveDirectForRHS on them; flags: ADFLOW_JAC_PC / _FROZEN_TURB / _TURB_ONLY / _VISC_PC / _APPROX_SA
+        integer(c_int) function adflow_gpu_jacfree_mult(level, flags, x, y, n) bind(C, name="adflow_gpu_jacfree_mult")
+            import :: c_int, c_long, c_double
+            integer(c_int), value :: level, flags
+            real(c_double), intent(in) :: x(*)
+            real(c_double), intent(out) :: y(*)
+            integer(c_long), value :: n
+        end function
+        integer(c_int) function adflow_gpu_jacfree_mult_dev(level, flags, x, y, n) bind(C, name="adflow_gpu_jacfree_mult_dev")
+            import :: c_int, c_ptr, c_long
+            integer(c_int), value :: level, flags
+            type(c_ptr), value :: x, y
+            integer(c_long), value :: n
+        end function
+        integer(c_int) function adflow_gpu_jacfree_solve(level, flags, b, x, n, restart, maxIts, rtol, atol, useGuess, its, &
+                                                         rnorm0, rnorm) bind(C, name="adflow_gpu_jacfree_solve")
+            import :: c_int, c_long, c_double
+            integer(c_int), value :: level, flags, restart, maxIts, useGuess
+            real(c_double), intent(in) :: b(*)
+            real(c_double), intent(inout) :: x(*)
+            integer(c_long), value :: n
+            real(c_double), value :: rtol, atol
+            integer(c_int), intent(out) :: its
+            real(c_double), intent(out) :: rnorm0, rnorm
+        end function
+        integer(c_int) function adflow_gpu_jacfree_solve_dev(level, flags, b, x, n, restart, maxIts, rtol, atol, useGuess, its, &
+                                                             rnorm0, rnorm) bind(C, name="adflow_gpu_jacfree_solve_dev")
+            import :: c_int, c_ptr, c_long, c_double
+            integer(c_int), value :: level, flags, restart, maxIts, useGuess
+            type(c_ptr), value :: b, x
+            integer(c_long), value :: n
+            real(c_double), value :: rtol, atol
+            integer(c_int), intent(out) :: its
+            real(c_double), intent(out) :: rnorm0, rnorm
+        end function
         ! several right-hand sides at once (the adjoints of several functions, the seeds of solveAdjointForRHS / solveDirectForRHS):
         ! column c is the n doubles at X + c ld, ld >= n, every column as the single entry takes its vector; its, rnorm0, rnorm: nvec
         ! entries each
@@ -1018,6 +1054,37 @@ contains
         if (transposed) tr = 1_c_int
         call gpuCheck(adflow_gpu_jacobian_mult_dev(int(level, c_int), tr, xDev, yDev, int(n, c_long)), "gpuJacobianMult")
     end subroutine gpuJacobianMult
+
+    ! the body of dRdwMatMult (adjointAPI.F90:1050-1128), the MATOP_MULT of the shell dRdwT that useMatrixFreedRdw selects: one
+    ! forward-mode evaluation seeded with the vector, no assembled matrix.  flags: the ADFLOW_JAC_* bits of the operator (0: the exact
+    ! dRdw; frozenTurbulence adds ADFLOW_JAC_FROZEN_TURB); xDev, yDev, n as for gpuJacobianMult
+    subroutine gpuJacFreeMult(level, flags, xDev, yDev, n)
+        integer(kind=intType), intent(in) :: level, flags
+        type(c_ptr), intent(in) :: xDev, yDev
+        integer(kind=intType), intent(in) :: n
+        call gpuCheck(adflow_gpu_jacfree_mult_dev(int(level, c_int), int(flags, c_int), xDev, yDev, int(n, c_long)), "gpuJacFreeMult")
+    end subroutine gpuJacFreeMult
+
+    ! KSPSolve of solveDirectForRHS (adjointAPI.F90) on that shell with the factor of the selected slot as right preconditioner, on ONE
+    ! rank: bDev, xDev the device arrays of the right-hand side and the solution
+    subroutine gpuJacFreeSolve(level, flags, bDev, xDev, n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm)
+        integer(kind=intType), intent(in) :: level, flags, n, restart, maxIts
+        logical, intent(in) :: useGuess
+        type(c_ptr), intent(in) :: bDev, xDev
+        real(kind=realType), intent(in) :: rtol, atol
+        integer(kind=intType), intent(out) :: its
+        real(kind=realType), intent(out) :: rnorm0, rnorm
+        integer(c_int) :: ug, itsC
+        real(c_double) :: r0C, rC
+        ug = 0_c_int
+        if (useGuess) ug = 1_c_int
+        call gpuCheck(adflow_gpu_jacfree_solve_dev(int(level, c_int), int(flags, c_int), bDev, xDev, int(n, c_long), int(restart, c_int), &
+                                                   int(maxIts, c_int), real(rtol, c_double), real(atol, c_double), ug, itsC, r0C, rC), &
+                      "gpuJacFreeSolve")
+        its = int(itsC, intType)
+        rnorm0 = real(r0C, realType)
+        rnorm = real(rC, realType)
+    end subroutine gpuJacFreeSolve
 
     ! after the preconditioner matrix is assembled (setupStateResidualMatrix with usePC = .true.): factor it on the device, in
     ! place of PCSetUp on the assembled usePC matrix (adjointUtils.F90:1374-1562)

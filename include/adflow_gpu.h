@@ -451,7 +451,7 @@ enum { ADFLOW_JAC_PC = 1u, ADFLOW_JAC_FROZEN_TURB = 2u, ADFLOW_JAC_TURB_ONLY = 4
        ADFLOW_JAC_APPROX_SA = 32u };
 int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta);
 /* Hands back the work space an assembly keeps between calls -- the slab of dual arrays of ADFLOW_JAC_USE_AD (about 640 B per box cell:
- * 8.4 GB on the 8 x 160x128x64 mesh) -- and the scratch arrays of adflow_gpu_jacobian_mult to the device allocator: what the host calls when the matrix is assembled and the memory is
+ * 8.4 GB on the 8 x 160x128x64 mesh) -- and the scratch arrays of adflow_gpu_jacobian_mult and adflow_gpu_jacfree_mult to the device allocator: what the host calls when the matrix is assembled and the memory is
  * wanted elsewhere (PETSc objects, further multigrid levels).  *bytes (may be NULL): what was released.  The next forward-mode
  * assembly lays the slab out again.  Mirrors nothing in the reference, whose Tapenade derivative arrays live in flowDomsd for the
  * whole run (adjointUtils.F90:87-99 allocDerivativeValues). */
@@ -610,6 +610,39 @@ int adflow_gpu_gmres_solve(int level, int transpose, const double* b, double* x,
                            double atol, int useGuess, int* its, double* rnorm0, double* rnorm);
 int adflow_gpu_gmres_solve_dev(int level, int transpose, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol,
                                double atol, int useGuess, int* its, double* rnorm0, double* rnorm);
+/* Matrix-free exact products by forward mode: y = (dR/dw) x without an assembled matrix.  The reference does not assemble the exact
+ * matrix by default either: useMatrixFreedRdw defaults to True (pyADflow.py:5918), createPETScVars makes dRdwT a shell matrix
+ * (adjointAPI.F90:1199-1214) and its forward product is dRdwMatMult (:1050-1128), ONE call of master_d with the vector as seed --
+ * what solveDirectForRHS iterates on and computeJacobianVectorProductFwd(wDot = ...) returns.
+ * flags: ADFLOW_JAC_PC, _FROZEN_TURB, _TURB_ONLY, _VISC_PC, _APPROX_SA with their meaning for adflow_gpu_fd_jacobian; ADFLOW_JAC_USE_AD
+ * is implied and ignored.  y is the product adflow_gpu_jacobian_mult(level, 0, x, y, n) returns after adflow_gpu_fd_jacobian(level,
+ * flags | ADFLOW_JAC_USE_AD, .), to rounding, linearised about the state that is on the device at the call; no assembled matrix is
+ * read or written.  Vectors as for adflow_gpu_jacobian_mult, with the nState and first variable the flags select (6, 5 or 1).  Columns
+ * as there: an owned cell is its own column, a halo with a donor in the 2-layer pattern of adflow_gpu_comm_register(level, 2, ...)
+ * carries its donor's entry of x (same process or another rank), every other halo carries a zero seed.
+ * The evaluation is the one a coloured pass of the forward-mode assembly runs: whalo2 of the state once, the frozen shock sensor
+ * first under ADFLOW_JAC_PC, the switches of the preconditioner matrix for the evaluation only, block_res_state_d on the seeded dual
+ * state, the result scaled by 1 / volRef and turbResScale on the turbulence row.  It works in the slab of dual arrays of
+ * ADFLOW_JAC_USE_AD (shared with the assembly) and a scratch array of nState doubles per box cell, both kept between calls and
+ * released -- and counted -- by adflow_gpu_release_workspace and with the blocks.  State, residual, assembled matrix and factors are
+ * left as they were.  adflow_gpu_jacfree_mult prepares on every call (exchange, sensor, passive dual arrays), so it is always about
+ * the current state.  The _dev form honours adflow_gpu_set_async: the host then waits only when the slab or the scratch has to be
+ * laid out.
+ * adflow_gpu_jacfree_solve: the restarted GMRES of adflow_gpu_gmres_solve with this product as operator and the factor of the SELECTED
+ * slot as right preconditioner, never transposed -- the KSP of solveDirectForRHS on the shell dRdwT.  It prepares once; its products
+ * only seed, evaluate and read out.  Arguments and results as for adflow_gpu_gmres_solve.
+ * Errors, each with a message before anything is launched: what adflow_gpu_fd_jacobian refuses for ADFLOW_JAC_USE_AD (moving blocks,
+ * actuator regions, host boundary hooks, a level that is not the ground level, TURB_ONLY without RANS or with FROZEN_TURB), unknown
+ * flags, x == y, a wrong n, a registered ROTATIONAL periodicity when the mean-flow variables are covered; for the solve also no factor
+ * in the selected slot, a factor of another nState, more than one rank, bad caps.
+ * Out of scope: the transposed product (it needs reverse mode; the adjoint keeps the assembled J^T and adflow_gpu_jacobian_mult),
+ * several vectors per pass, and the spatial and extra seeds of master_d (xDot, forces, functions). */
+int adflow_gpu_jacfree_mult(int level, unsigned flags, const double* x, double* y, long n);
+int adflow_gpu_jacfree_mult_dev(int level, unsigned flags, const double* d_x, double* d_y, long n);
+int adflow_gpu_jacfree_solve(int level, unsigned flags, const double* b, double* x, long n, int restart, int maxIts, double rtol,
+                             double atol, int useGuess, int* its, double* rnorm0, double* rnorm);
+int adflow_gpu_jacfree_solve_dev(int level, unsigned flags, const double* d_b, double* d_x, long n, int restart, int maxIts, double rtol,
+                                 double atol, int useGuess, int* its, double* rnorm0, double* rnorm);
 
 /* ---- several right-hand sides at once: the product, the ILU application and GMRES on nvec columns -------------------------------
  * The adjoints of several functions (the loop in front of solveAdjoint, pyADflow.py:1723-1743) and the seeds of solveAdjointForRHS /

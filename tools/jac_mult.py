@@ -6,7 +6,13 @@ cell: one pass over the matrix), TB/s and the fraction of the measured copy ceil
 --nvec N adds, on the 160 x 128 x 64 block and in the same process: Y = J X and J^T X for N columns through
 adflow_gpu_jacobian_mult_multi_dev (one call) against N calls of adflow_gpu_jacobian_mult_dev, with the GB/s on the matrix of the multi
 call, and the wall time of GMRES (block ILU(0)) for N right-hand sides through adflow_gpu_gmres_solve_multi_dev against N single solves.
-usage: jac_mult.py [--nvec N] [n]   (n timed products of each kind, default 20)"""
+--free times, in one process on one 160 x 128 x 64 RANS Roe block (or --dims NX NY NZ), one product of each of the three operators a
+Krylov solver for the exact dR/dw can run on: adflow_gpu_jacfree_mult_dev with the exact flags (one forward-mode evaluation, no
+matrix), adflow_gpu_ank_mult_dev (a finite difference of two residuals) and adflow_gpu_jacobian_mult_dev on the assembled exact
+33-point matrix, with the bytes each one keeps on the device.  --free --no-matrix leaves the assembled matrix out (a mesh on which
+it does not fit).
+--blocks N puts N such blocks on the level (8: the size of the benchmark mesh).
+usage: jac_mult.py [--nvec N] [--free [--no-matrix] [--blocks N] [--dims NX NY NZ]] [n]   (n timed products of each kind, default 20)"""
 import json
 import os
 import sys
@@ -104,9 +110,101 @@ def multi_columns(eng, torch, gen, n, nvec, n_it, floor):
     eng.pcRelease()
 
 
+def free_case(eng, torch, dims, n_it, with_matrix=True, nblocks=1):
+    """the matrix-free exact product against the finite-difference operator of ANK and the assembled exact matrix; nblocks: that many
+    wall-bounded blocks of `dims` side by side on the level (the size of the benchmark mesh with 8)"""
+    prm = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda).replace(currentLevel=1, groundLevel=1)
+    blk = make_block(*dims, prm, seed=7, stretch_k=2.0)
+    blocks = [blk] + [blk.copy() for _ in range(nblocks - 1)]
+    bocos = [make_bocos(b, prm, WALL, seed=8) for b in blocks]
+    eng.release_all()
+    eng.set_options(prm)
+    for nn, (b, (faces, nvisc)) in enumerate(zip(blocks, bocos), start=1):
+        eng.register(b, nn=nn)
+        eng.bc_register(faces, nvisc, nn=nn)
+    for L in (1, 2):
+        eng.comm_register(1, L, CommPattern())
+    eng.applyAllBC(1, True)
+    cells = nblocks * blk.nx * blk.ny * blk.nz
+    n = blk.nw * cells
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 0.5
+    y = torch.empty_like(x)
+    torch.cuda.synchronize()
+
+    def timed(fn):
+        eng.set_async(True)
+        try:
+            for _ in range(3):
+                fn()
+            eng.event_record(1)
+            for _ in range(n_it):
+                fn()
+            eng.event_record(2)
+            eng.sync()
+        finally:
+            eng.set_async(False)
+        return eng.event_elapsed_ms(1, 2) / n_it
+
+    def report(what, ms, kept, **more):
+        print(json.dumps(dict({"operator": what, "dims": list(dims), "blocks": nblocks, "cells": cells, "ms": round(ms, 4), "bytes_kept": int(kept),
+                               "checksum": float(y.abs().sum().item())}, **more)), flush=True)
+
+    eng.releaseWorkspace()
+    ms = timed(lambda: eng.jacFreeMultDev(x.data_ptr(), y.data_ptr(), n, 1))
+    y_free = y.clone()
+    report("adflow_gpu_jacfree_mult_dev, exact flags (slab of dual arrays + scratch of the vector)", ms, eng.releaseWorkspace())
+    # the finite-difference operator of the coupled ANK step: (R(w + h v) - r0) / h + T v
+    eng.timeStep(1)
+    eng.ankTimeStep(5.0, 2.5, coupled=True)
+    eng.download_state(1, 1)
+    w6 = np.tile(np.ascontiguousarray(np.transpose(blk.owned("w"), (2, 1, 0, 3))).reshape(-1), nblocks)
+    eng.ankSetBase(w6, coupled=True)
+    ms = timed(lambda: eng.ankMultDev(x.data_ptr(), y.data_ptr(), n))
+    report("adflow_gpu_ank_mult_dev, coupled (base state, base residual, T)", ms, eng.ankRelease())
+    for nn in range(1, nblocks + 1):                      # (the ANK product leaves the perturbed state on the device)
+        eng.upload_state(nn, 1)
+    eng.applyAllBC(1, True)
+    if with_matrix:
+        eng.event_record(1)
+        eng.setupStateResidualMatrix(1, False, useAD=True)
+        eng.event_record(2)
+        eng.sync()
+        ms_asm = eng.event_elapsed_ms(1, 2)
+        ns, st = eng.jacobianInfo()
+        nbox = nblocks * (blk.nx + 4) * (blk.ny + 4) * (blk.nz + 4)
+        eng.releaseWorkspace()
+        ms = timed(lambda: eng.jacobianMultDev(x.data_ptr(), y.data_ptr(), n, 1, False))
+        floor = st.shape[0] * ns * ns * 8 * cells
+        rel = float(((y - y_free).abs().max() / y.abs().max()).item())
+        report("adflow_gpu_jacobian_mult_dev, assembled exact 33-point matrix (blocks over the box + scratch of two vectors)", ms,
+               st.shape[0] * ns * ns * 8 * nbox + eng.releaseWorkspace(), matrix_bytes_owned_rows=floor,
+               TB_per_s_on_the_matrix=round(floor / (ms * 1e-3) / 1e12, 3), assembly_ms=round(ms_asm, 1),
+               max_difference_to_the_matrix_free_product_rel=rel)
+    eng.releaseWorkspace()
+
+
 def main():
     import torch
     argv, nvec = list(sys.argv[1:]), 0
+    if "--free" in argv:
+        argv.remove("--free")
+        dims, with_matrix, nblocks = (160, 128, 64), True, 1
+        if "--blocks" in argv:
+            at = argv.index("--blocks")
+            nblocks = int(argv[at + 1])
+            del argv[at:at + 2]
+        if "--no-matrix" in argv:
+            argv.remove("--no-matrix")
+            with_matrix = False
+        if "--dims" in argv:
+            at = argv.index("--dims")
+            dims = tuple(int(a) for a in argv[at + 1:at + 4])
+            del argv[at:at + 4]
+        eng = Engine(0)
+        free_case(eng, torch, dims, int(argv[0]) if argv else 20, with_matrix, nblocks)
+        eng.close()
+        return
     if "--nvec" in argv:
         at = argv.index("--nvec")
         nvec = int(argv[at + 1])
