@@ -93,12 +93,7 @@ __global__ __launch_bounds__(PC_T) void k_pc_factor(PcTab T, int q0, int cnt)
 #pragma unroll
             for (int e = 0; e < NS * NS; ++e) X[e] = ldg(Fu + e * N, n8);           // U_{n,c} = A_{n, n + e_s}
         }
-#pragma unroll
-        for (int m = 0; m < NS; ++m)
-#pragma unroll
-            for (int l = 0; l < NS; ++l)
-#pragma unroll
-                for (int r = 0; r < NS; ++r) PCE(D, r, l) -= PCE(L, r, m) * PCE(X, m, l);
+        pc_schur_sub<NS>(D, L, X);
     }
     for (int s = 3; s < 6; ++s) {
         const bool in = T.nbr[(long)s * N + q] >= 0;

@@ -90,12 +90,7 @@ __global__ __launch_bounds__(PCC_T) void k_pcc_factor(PcTab T, int q0, int cnt)
 #pragma unroll
             for (int e = 0; e < NS * NS; ++e) X[e] = Fu[(long)e * N];
         }
-#pragma unroll
-        for (int m = 0; m < NS; ++m)
-#pragma unroll
-            for (int l = 0; l < NS; ++l)
-#pragma unroll
-                for (int r = 0; r < NS; ++r) PCE(D, r, l) -= PCE(L, r, m) * PCE(X, m, l);
+        pc_schur_sub<NS>(D, L, X);
     }
     // the L blocks of the upper neighbours towards this cell, L_{c,q} = A_{c,q} D_q^-1, by a solve with D_q while it is at hand
     // (pc_right_solve), written into the slot in which c keeps its entry back to this cell; c's row reads it in a later set

@@ -120,17 +120,21 @@ __global__ __launch_bounds__(PCF_T) void k_pcf_factor(PcTab T, int q0, int cnt)
             GPTR(double) Ft = F + (long)tg * NB * N;
 #pragma unroll
             for (int l = 0; l < NS; ++l) {                                           // column l of the target
-                double uc[NS], tc[NS];
+                // the product L_{c,n} U_{n,m} is summed on its own and subtracted from the target ONCE: subtracting its nState terms
+                // from the target one by one costs a digit on wall-clustered curved meshes (`annulus` x `ilu-fill`)
+                double uc[NS], tc[NS], pr[NS];
 #pragma unroll
                 for (int m = 0; m < NS; ++m) uc[m] = ldg(Fu + (l * NS + m) * N, n8);
 #pragma unroll
                 for (int r = 0; r < NS; ++r) tc[r] = ldg(Ft + (l * NS + r) * N, q8);
 #pragma unroll
+                for (int r = 0; r < NS; ++r) pr[r] = 0.0;
+#pragma unroll
                 for (int m = 0; m < NS; ++m)
 #pragma unroll
-                    for (int r = 0; r < NS; ++r) tc[r] -= PCE(L, r, m) * uc[m];
+                    for (int r = 0; r < NS; ++r) pr[r] += PCE(L, r, m) * uc[m];
 #pragma unroll
-                for (int r = 0; r < NS; ++r) stg(Ft + (l * NS + r) * N, q8, tc[r]);
+                for (int r = 0; r < NS; ++r) stg(Ft + (l * NS + r) * N, q8, tc[r] - pr[r]);
             }
         }
     }

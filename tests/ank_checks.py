@@ -137,9 +137,9 @@ def shifted(op, Tn):
     return out
 
 
-def assert_shifted_factor(engine, blocks, op, prm, coupled, seed, what):
+def assert_shifted_factor(engine, blocks, op, prm, coupled, seed, what, matches=None):
     """pcApply after ankPcSetup against NumpyILU0 of J + T (pc_checks' rule); then pcSetup on the same matrix is bit-identical to
-    the application taken before any ANK entry was called"""
+    the application taken before any ANK entry was called.  matches: the comparison (default pc_checks.assert_apply_matches, one draw)"""
     rng = np.random.default_rng(seed)
     r = rng.uniform(-1.0, 1.0, op.n)
     engine.pcSetup(1)
@@ -149,7 +149,7 @@ def assert_shifted_factor(engine, blocks, op, prm, coupled, seed, what):
     engine.ankPcSetup(1)
     ns, npl, nb = engine.pcInfo()
     assert ns == op.ns and npl == max(sum(d) - 2 for d in op.dims.values())
-    first, ilus = pc.assert_apply_matches(engine, ops, seed + 1, f"shifted factor, {what}")
+    first, ilus = (matches or pc.assert_apply_matches)(engine, ops, seed + 1, f"shifted factor, {what}")
     assert not np.array_equal(engine.pcApply(r, 1), plain[False]), "T does not reach the factor"
     engine.pcSetup(1)
     for tr in (False, True):
@@ -163,6 +163,17 @@ def check_shifted_single(engine, dims, seed=311):
     assert_shifted_factor(engine, {1: blk}, op, RANS_UPWIND, False, seed, f"RANS decoupled {dims}")
     engine.pcRelease()
     engine.ankRelease()
+
+
+def check_shifted_block(engine, dims, prm, spec, coupled, seed=311, matches=None, **mk):
+    """one block with six boundary faces: decoupled (frozen turbulence, nState 5) or coupled (nState 6, T with the turbulence entry)"""
+    blk, op = pc.single_block(engine, dims, prm, spec, seed, frozenTurb=not coupled, **mk)
+    assert op.ns == (6 if coupled else 5)
+    try:
+        assert_shifted_factor(engine, {1: blk}, op, prm, coupled, seed, f"{dims} coupled={coupled}", matches=matches)
+    finally:
+        engine.pcRelease()
+        engine.ankRelease()
 
 
 def check_shifted_ell(engine, topo, seed=313):

@@ -119,8 +119,9 @@ def check_against_reference(engine, dims, prm, spec, seed=211, **jac):
     return opg
 
 
-def brick_operator(engine, topo, prm, seed=223, useAD=False):
-    blocks, _ = checks.setup_brick(engine, topo, prm, seed)
+def brick_operator(engine, topo, prm, seed=223, useAD=False, **mk):
+    """mk: the mesh keywords of checks.setup_brick (make_block / topo.make_block)"""
+    blocks, _ = checks.setup_brick(engine, topo, prm, seed, **mk)
     engine.setupStateResidualMatrix(1, True, delta=1e-6, useAD=useAD)
     return blocks, operator_of(engine, blocks, topo.patterns(2)[0])
 

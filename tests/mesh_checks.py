@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE.  The entries of the library on the mesh families of tests/mesh_families.py, through the checkers that
-exist (checks.py, ank_checks.py, pc_checks.py): no comparison of its own.  Every checker call goes through `on`: first the
+exist (checks.py, ank_checks.py, pc_checks.py and the checkers of everything built on the assembled matrix: pc_fill_checks.py,
+pc_coupled_checks.py, pc_mg_checks.py, multi_checks.py, jacmult_checks.py, jacfree_checks.py): no comparison of its own.  Every checker call goes through `on`: first the
 family's recount on a block -- or on every block of the brick, through frame -- built with the very keywords and topology the checker
 gets, then the checker under a spy that asserts that each block it builds itself carries the case's shape and lengths, so that
 neither a later edit nor a keyword filter inside a checker can quietly turn the mesh back into a cube.
@@ -17,8 +18,14 @@ import numpy as np
 
 import ank_checks
 import checks
+import jacfree_checks
+import jacmult_checks
 import mesh_families as mf
+import multi_checks
 import pc_checks
+import pc_coupled_checks
+import pc_fill_checks
+import pc_mg_checks
 from adflow_amd import synth
 from adflow_amd.params import (FlowParams, NSEquations, RANSEquations, dissScalar, dissMatrix, upwind, vanAlbeda, minmod, DADI,
                                noResAveraging, alternateResAveraging)
@@ -301,9 +308,57 @@ def _ilu(engine, case, big):
     L_{c,n} = A_{c,n} D_n^-1 formed as a PRODUCT with the explicit inverse loses a digit there (emulator: 9.4e-11 / 1.34e-10 for
     M^-1 r / M^-T r against 1.58e-11 / 7.2e-12 of the numpy run, ratios 6.0 / 18.6), and k_pc_factor / k_pcc_factor now form it by a
     solve with D_n (pc_right_solve, csrc/pc_block.h): 4.4e-11 / 4.4e-11 on the emulator, 3.3e-11 / 2.8e-11 on the MI355X (numpy there:
-    4.3e-11 / 6.9e-11).  DESIGN §5 has the experiment that located the loss in the factorisation and not in the sweeps."""
+    4.3e-11 / 6.9e-11).  DESIGN §5 has the experiment that located the loss in the factorisation and not in the sweeps.
+    After the one draw the same factor goes under pc_checks.assert_apply_median (16 vectors per transpose, the median ratio at MARGIN)."""
     assert case.family in ("annulus", "clustered")
-    on(case, pc_checks.check_single, engine, JAC, RANS_UP, WALL, **case.mk(True))
+    on(case, pc_checks.check_single, engine, JAC, RANS_UP, WALL, median=True, **case.mk(True))
+
+
+# ---- everything built on the assembled matrix --------------------------------------------------------------------------------------
+# The factor entries are held to pc_checks.assert_apply_median: the median over 16 vectors per transpose of e_lib / e_np at MARGIN.  The
+# one draw of assert_apply_matches is noise at these condition numbers (DESIGN §5: e_np varies by 4 to 21 from vector to vector).
+MEDIAN = pc_checks.assert_apply_median
+FACTOR_MESHES = ("annulus", "clustered", "units-annulus-2^-20", "units-clustered-2^10", "sheared")
+MG_CONFIGS = [(3, 2, 2, 1), (2, 1, 0, 0)]          # (levels, nSmooth, fill, fillCoarse)
+
+
+def _ilu_fill(engine, case, big):
+    """ILU(1) and ILU(2) at nState 6, 5 and 1: pattern and level sets against the symbolic yardstick, applications, identity"""
+    for jac in (dict(), dict(frozenTurb=True), dict(useTurbOnly=True)):
+        on(case, pc_fill_checks.check_single, engine, JAC, RANS_UP, WALL, matches=MEDIAN, **jac, **case.mk(True))
+
+
+def _ilu_coupled(engine, case, big):
+    """the factor over the level on two blocks joined in i inside one map, against the level-wide yardstick, and far from block-local"""
+    on(case, pc_coupled_checks.check_wall_topo, engine, case.brick((6, 8, 6), True), RANS_UP, WALL, matches=MEDIAN, **case.brick_mk())
+
+
+def _pc_mg(engine, case, big):
+    """the hierarchy: the coarse sums at their TERMS bar on volumes that span 1e5, the cycle against the numpy cycle"""
+    on(case, pc_mg_checks.check_single, engine, JAC, RANS_UP, WALL, MG_CONFIGS, matches=MEDIAN, **case.mk(True))
+
+
+def _ilu_multi(engine, case, big):
+    on(case, multi_checks.check_sweeps_median, engine, JAC, RANS_UP, WALL, **case.mk(True))
+
+
+def _ank_shifted(engine, case, big):
+    """the ILU(0) of J + T, decoupled (nState 5) and coupled (nState 6: turbResScale and turbCFLScale both /= 1, as ank_checks.RANS_COUPLED)"""
+    for coupled in (False, True):
+        prm = RANS_UP.replace(turbResScale=1.0e3) if coupled else RANS_UP
+        on(case, ank_checks.check_shifted_block, engine, JAC, prm, WALL, coupled, matches=MEDIAN, **case.mk(True))
+
+
+def _jacmult(engine, case, big):
+    """jacobianMult, both transposes, against numpy applying the REFERENCE's forward-mode blocks; then its own blocks to rounding"""
+    for dims, usePC in ((JAC, True), (JAC_EXACT, False)):
+        on(case, jacmult_checks.check_against_reference, engine, dims, RANS_UP, WALL, usePC=usePC, **case.mk(True))
+
+
+def _jacfree(engine, case, big):
+    """jacFreeMult against the reference's blocks, under the default dispatch and with the marches off"""
+    for dims, jac in ((JAC, dict(usePC=True)), (JAC_EXACT, dict(usePC=False)), (JAC_EXACT, dict(usePC=False, frozenTurb=True))):
+        on(case, jacfree_checks.check_against_reference, engine, dims, RANS_UP, WALL, **jac, **case.mk(True))
 
 
 ENTRIES = {
@@ -316,19 +371,27 @@ ENTRIES = {
     "smoothers": _smoothers, "multigrid": _multigrid,
     "jac-fd-pc": _jac(False, True), "jac-fd-exact": _jac(False, False), "jac-ad-pc": _jac(True, True), "jac-ad-exact": _jac(True, False),
     "nk": _nk, "ank-T": _ank_T, "ank-operator": _ank_operator, "ilu": _ilu,
+    "ilu-fill": _ilu_fill, "ilu-coupled": _ilu_coupled, "pc-mg": _pc_mg, "ilu-multi": _ilu_multi, "ank-shifted": _ank_shifted,
+    "jacmult": _jacmult, "jacfree": _jacfree,
 }
 # the entries the reference cannot run on `pole`: none -- reference_floor finds its outputs finite in every entry
 POLE_OUT = ()
 # entries whose yardstick is not the oracle but an extended-precision restatement built on the library's own matrix or time step, with a
 # bar relative to the float64 run of the same restatement (ank_checks.py, pc_checks.py): there is no reference output to move.  What
 # the oracle contributes to them -- the state, the boundary halos and, for `ilu`, the very matrix (forward mode, preconditioner, RANS
-# upwind, WALL, (7, 6, 5)) -- has its floor asserted under `jac-ad-pc` and `bc` of the same mesh.
-NO_FLOOR = ("ank-T", "ank-operator", "ilu")
+# upwind, WALL, (7, 6, 5)) -- has its floor asserted under `jac-ad-pc` and `bc` of the same mesh.  The same holds for every factor entry
+# (`ilu-fill`, `ilu-coupled`, `pc-mg`, `ilu-multi`, `ank-shifted`): the matrix they factor is that assembly (on the brick: the same
+# routine block by block), covered by `jac-ad-pc` of the same mesh.  `jacmult` and `jacfree` compare with the reference's matrix, which
+# reference_floor records from their first call of check_ad_jacobian: they have a floor test of their own, at the assembly's bar.
+NO_FLOOR = ("ank-T", "ank-operator", "ilu", "ilu-fill", "ilu-coupled", "pc-mg", "ilu-multi", "ank-shifted")
 # the bars of the entries whose checker has one of its own: (global, local or None where the checker applies no local measure) --
 # check_fd_jacobian: 1e-9 of the largest entry at delta = 1e-5 (a difference quotient amplifies rounding by 1 / delta), check_ad_jacobian: 1e-10
-BARS = {"jac-fd-pc": (1e-9, None), "jac-fd-exact": (1e-9, None), "jac-ad-pc": (1e-10, None), "jac-ad-exact": (1e-10, None)}
+BARS = {"jac-fd-pc": (1e-9, None), "jac-fd-exact": (1e-9, None), "jac-ad-pc": (1e-10, None), "jac-ad-exact": (1e-10, None),
+        "jacmult": (1e-10, None), "jacfree": (1e-10, None)}
 ONLY = {"pole-polar-symmetry": ("pole",), "pole-symmetry": ("pole",), "pole-euler-wall": ("pole",),
-        "ilu": ("annulus", "clustered", "units-annulus-2^-20", "units-clustered-2^10")}
+        "ilu": ("annulus", "clustered", "units-annulus-2^-20", "units-clustered-2^10"),
+        "ilu-fill": FACTOR_MESHES, "ilu-coupled": FACTOR_MESHES, "pc-mg": FACTOR_MESHES, "ank-shifted": FACTOR_MESHES,
+        "ilu-multi": ("annulus", "clustered")}
 
 
 def pairs():

@@ -172,6 +172,34 @@ def check_sweeps_all_fills(engine, op, seed, what, nvecs=NVEC_SWEEP, fills=(0, 1
             engine.pcRelease()
 
 
+def check_sweeps_median(engine, dims, prm, spec, seed=107, nvec=3, fills=(0, 1), **jac):
+    """pcApplyMulti with nvec columns on one block with six boundary faces, every column position held to pc.assert_apply_median: its 16
+    vectors go through in 16 calls of nvec columns, call g carrying the vectors g, g + 1, .. (cyclically), so that every vector passes
+    every column position once and the yardstick is run once per vector.  Column 0 of an nvec = 1 call is pcApply to the bit"""
+    _, op = single_block(engine, dims, prm, spec, seed, **jac)
+
+    def apply(R, transpose):
+        K = len(R)
+        Z = np.empty((nvec,) + R.shape)
+        for g in range(K):
+            idx = [(g + c) % K for c in range(nvec)]
+            Zg = engine.pcApplyMulti(R[idx], 1, transpose=transpose)
+            for c in range(nvec):
+                Z[c, idx[c]] = Zg[c]
+        return Z
+
+    for fill in fills:
+        with pcf.fill_of(engine, fill):
+            engine.pcSetup(1)
+            assert engine.pcInfo2()[0] == fill
+            first, _ = pc.assert_apply_median(engine, op, seed + 1 + fill, f"{dims} {nvec} columns fill {fill}", ilus=ilus_of(op, fill),
+                                              apply=apply)
+            for tr in (False, True):
+                r = first[tr][0]
+                assert np.array_equal(engine.pcApplyMulti(r[None], 1, transpose=tr)[0], engine.pcApply(r, 1, transpose=tr)), (fill, tr)
+            engine.pcRelease()
+
+
 def check_blocks_stay_subdomains(engine, op, fill, seed):
     """column a is non-zero on block a only: it comes back zero on every other block, and non-zero on its own"""
     rng = np.random.default_rng(seed)

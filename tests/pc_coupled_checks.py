@@ -174,10 +174,17 @@ def check_rotated(engine):
 WALL_TOPO = dict(Bi=2, Bj=2, Bk=2, nx=6, ny=5, nz=4, periodic=(False,) * 3)
 
 
-def wall_brick(engine, seed=107, **jac):
-    """2 x 2 x 2 wall-bounded blocks, RANS Roe preconditioner matrix by forward mode; returns (blocks, prm, operator)"""
-    topo = BrickTopology(**WALL_TOPO)
-    blocks, rblocks, bocos, prm = checks.setup_brick_with_bc(engine, topo, pc.RANS, jm.WALL, seed, stretch_k=2.0)
+MK_KEYS = ("stretch_k", "shape", "lengths")
+
+
+def wall_brick(engine, seed=107, topo=None, prm=pc.RANS, spec=jm.WALL, **jac):
+    """2 x 2 x 2 wall-bounded blocks, RANS Roe preconditioner matrix by forward mode; returns (blocks, prm, operator).
+    topo, prm, spec and the mesh keywords among jac (MK_KEYS, handed to checks.setup_brick_with_bc): another wall-bounded brick"""
+    mk = {k: jac.pop(k) for k in MK_KEYS if k in jac}
+    if topo is None:
+        topo = BrickTopology(**WALL_TOPO)
+        mk.setdefault("stretch_k", 2.0)
+    blocks, rblocks, bocos, prm = checks.setup_brick_with_bc(engine, topo, prm, spec, seed, **mk)
     _KEEP[:] = [rblocks, bocos]
     engine.applyAllBC(1, True)
     engine.setupStateResidualMatrix(1, True, useAD=True, **jac)
@@ -189,6 +196,19 @@ def check_wall_brick_apply(engine, **jac):
         blocks, prm, op = wall_brick(engine, **jac)
         ilus = setup_coupled(engine, op)
         assert_coupled_apply(engine, op, 109, f"wall-bounded brick {jac}", ilus)
+
+
+def check_wall_topo(engine, topo, prm, spec, seed=107, matches=None, **mk):
+    """the factor over the level on a wall-bounded brick given by the caller (topology, boundary kinds, mesh keywords): the
+    applications under `matches` (default pc_checks.assert_apply_matches), the identity, and far from the block-local factor"""
+    with coupled_slots(engine):
+        blocks, prm, op = wall_brick(engine, seed, topo, prm, spec, **mk)
+        ilus = setup_coupled(engine, op)
+        assert ilus[0].ncross > 0
+        what = f"{len(blocks)} wall-bounded blocks"
+        first, _ = (matches or pc.assert_apply_matches)(engine, op, seed + 2, what, ilus=ilus)
+        pc.assert_identity(engine, op, first, seed + 3)
+        assert_far_from_block_local(engine, op, first, what)
 
 
 CAP_WALL = 46            # 2 x the 23 iterations scipy's gmres takes with the numpy factor over the level on this matrix (22 transposed)

@@ -104,8 +104,9 @@ def yardsticks(op, fill):
     return NumpyILUk(op, np.float64, fill), NumpyILUk(op, np.longdouble, fill)
 
 
-def assert_factor(engine, op, fill, seed, what, ilus=None, expect=None):
-    """the factor that stands in the selected slot against the yardstick: info, pattern facts, both applications, the identity"""
+def assert_factor(engine, op, fill, seed, what, ilus=None, expect=None, matches=None):
+    """the factor that stands in the selected slot against the yardstick: info, pattern facts, both applications, the identity.
+    matches: the comparison of the applications (default pc_checks.assert_apply_matches, one draw; pc_checks.assert_apply_median: 16)"""
     f64, fld = ilus or yardsticks(op, fill)
     info = engine.pcInfo2()
     ns, npl, nb = engine.pcInfo()
@@ -116,19 +117,19 @@ def assert_factor(engine, op, fill, seed, what, ilus=None, expect=None):
         assert info == expect, (info, expect)
     assert len(f64.offsets) <= ENTRIES[fill]            # a thin block cuts offsets everywhere; none may lie outside the stencil
     assert ns == op.ns and npl == info[2] and nb >= ENTRIES[fill] * ns * ns * 8 * op.ncell, (ns, npl, nb)
-    first, _ = pc.assert_apply_matches(engine, op, seed + 1, f"{what} fill {fill}", ilus=(f64, fld))
+    first, _ = (matches or pc.assert_apply_matches)(engine, op, seed + 1, f"{what} fill {fill}", ilus=(f64, fld))
     pc.assert_identity(engine, op, first, seed + 2)
     return first, (f64, fld)
 
 
-def check_single(engine, dims, prm, spec, seed=107, expect=None, all_offsets=False, **jac):
-    """one block, fill 1 and 2 on the same assembly; expect = {fill: pcInfo2()}"""
+def check_single(engine, dims, prm, spec, seed=107, expect=None, all_offsets=False, matches=None, **jac):
+    """one block, fill 1 and 2 on the same assembly; expect = {fill: pcInfo2()}; matches: see assert_factor"""
     blk, op = pc.single_block(engine, dims, prm, spec, seed, **jac)
     out = {}
     for fill in (1, 2):
         with fill_of(engine, fill):
             engine.pcSetup(1)
-            out[fill] = assert_factor(engine, op, fill, seed, f"{dims} nState={op.ns}", expect=expect and expect[fill])
+            out[fill] = assert_factor(engine, op, fill, seed, f"{dims} nState={op.ns}", expect=expect and expect[fill], matches=matches)
             if all_offsets:
                 assert len(out[fill][1][0].offsets) == ENTRIES[fill]
             engine.pcRelease()

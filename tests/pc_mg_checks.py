@@ -191,8 +191,9 @@ def assert_matrices(engine, op, levels, what, T=None):
             fine = coarse
 
 
-def assert_hierarchy(engine, op, levels, nsmooth, fill, fill_coarse, seed, what, T=None, cells=None):
-    """info, matrices and both applications of the hierarchy that stands in the selected slot.  Returns pc_checks' (first, yardsticks)"""
+def assert_hierarchy(engine, op, levels, nsmooth, fill, fill_coarse, seed, what, T=None, cells=None, matches=None):
+    """info, matrices and both applications of the hierarchy that stands in the selected slot.  Returns pc_checks' (first, yardsticks).
+    matches: the comparison of the applications (default pc_checks.assert_apply_matches, one draw; pc_checks.assert_apply_median: 16)"""
     ys = yardsticks(op, levels, nsmooth, fill, fill_coarse)
     info = engine.pcMgInfo()
     print(f"{what}: pcMgInfo = {info}, pcInfo = {engine.pcInfo()}")
@@ -201,16 +202,19 @@ def assert_hierarchy(engine, op, levels, nsmooth, fill, fill_coarse, seed, what,
         assert info[3] == tuple(cells), (info, cells)
     assert engine.pcInfo2()[0] == fill and engine.pcInfo()[0] == op.ns
     assert_matrices(engine, op, levels, what, T)
-    return pc.assert_apply_matches(engine, op, seed + 1, f"{what} levels={levels} nSmooth={nsmooth} fills=({fill},{fill_coarse})", ilus=ys)
+    return (matches or pc.assert_apply_matches)(engine, op, seed + 1, f"{what} levels={levels} nSmooth={nsmooth} fills=({fill},{fill_coarse})",
+                                                ilus=ys)
 
 
-def check_single(engine, dims, prm, spec, configs, seed=107, cells=None, **jac):
-    """one block; configs: (levels, nSmooth, fill, fillCoarse) on the same assembly; cells = {levels: cells of every level}"""
+def check_single(engine, dims, prm, spec, configs, seed=107, cells=None, matches=None, **jac):
+    """one block; configs: (levels, nSmooth, fill, fillCoarse) on the same assembly; cells = {levels: cells of every level}; matches: see
+    assert_hierarchy"""
     blk, op = pc.single_block(engine, dims, prm, spec, seed, **jac)
     for levels, nsmooth, fill, fc in configs:
         with mg_of(engine, levels, nsmooth, fc, fill):
             engine.pcSetup(1)
-            assert_hierarchy(engine, op, levels, nsmooth, fill, fc, seed, f"{dims} nState={op.ns}", cells=cells and cells[levels])
+            assert_hierarchy(engine, op, levels, nsmooth, fill, fc, seed, f"{dims} nState={op.ns}", cells=cells and cells[levels],
+                             matches=matches)
             engine.pcRelease()
     return blk, op
 
