@@ -135,6 +135,8 @@ std::map<std::pair<int, int>, CommPattern> g_comm;   // (level, nLayers)
 double* g_rvec_target = nullptr;     // residual vector the kernels of the evaluation in flight write (nk_residual_dev)
 int g_rvec_done = 0;                  // bit 0: flow entries written, bit 1: turbulence entry written
 int g_snap_done = 0;                  // the same for the snapshot entries of a coloured Jacobian evaluation (KParams::snapTab)
+long g_pc_topo_gen = 0;      // bumped when a block or a comm pattern is registered or released: the pattern tables of a factor over the level
+                             // (adflow_gpu_pc_set_level_fill) are kept across setups while it stands
 long g_state_gen = 0;        // bumped by every call that changes what a multigrid cycle enqueues (options, tuning, blocks, patterns, subfaces)
 int g_split_eval = 1;       // tuning "split_eval": whalo2 + blocketteRes with the halo-free tiles inside the exchange: 1 = when the pattern has messages, 2 = always, 0 = never
 int g_mg_graph = 1;         // tuning "mg_graph": a repeated adflow_gpu_mg_cycle is captured once into a hipGraph and replayed
@@ -603,6 +605,7 @@ int adflow_gpu_block_register(int nn, int level, int sps, const adflow_block_des
     }
     HIPCHK(hipStreamSynchronize(g_stream));
     g_blocks[Key(level, sps, nn)] = b;
+    ++g_pc_topo_gen;
     invalidate_comm_level(level);
     return 0;
 }
@@ -632,6 +635,7 @@ int adflow_gpu_block_release(int nn, int level, int sps)
     for (void* p : it->second->bc_allocs) (void)hipFree(p);
     delete it->second;
     g_blocks.erase(it);
+    ++g_pc_topo_gen;
     invalidate_comm_level(level);
     return 0;
 }
@@ -652,6 +656,7 @@ int adflow_gpu_release_all(void)
         delete kv.second;
     }
     g_blocks.clear();
+    ++g_pc_topo_gen;
     g_jac_valid = false;          // the stencil blocks went with the blocks
     {
         std::vector<int> levels;
@@ -2952,6 +2957,7 @@ int adflow_gpu_comm_info(int* rank, int* nranks, int* commCount, int* commUserRa
 int adflow_gpu_comm_register(int level, int nLayers, const adflow_comm_pattern* p)
 {
     ++g_state_gen;
+    ++g_pc_topo_gen;
     if (g_device < 0) return fail("adflow_gpu_init has not been called");
     if (!p) return fail("null comm pattern");
     if (nLayers < 0 || nLayers > 2) return fail("nLayers must be 1 or 2 (cell halos) or 0 (the node pattern of exchangeCoor)");
@@ -2990,6 +2996,7 @@ int adflow_gpu_comm_register(int level, int nLayers, const adflow_comm_pattern* 
 int adflow_gpu_comm_register_periodic(int level, int nLayers, int nPeriodic, const adflow_periodic_data* pd)
 {
     ++g_state_gen;
+    ++g_pc_topo_gen;
     auto it = g_comm.find(std::make_pair(level, nLayers));
     if (it == g_comm.end()) return fail("comm_register_periodic: no pattern registered for level %d, nLayers %d", level, nLayers);
     if (nPeriodic < 0 || (nPeriodic > 0 && !pd)) return fail("comm_register_periodic: nPeriodic=%d", nPeriodic);
@@ -4188,6 +4195,17 @@ struct PcFactor {
     std::vector<int> planeStart;      // first position of every hyperplane in the order of the factor, and the end
     PcTab tab;
     struct PcMg* mg = nullptr;        // adflow_gpu_pc_set_mg with levels > 1: the hierarchy this factor is level 1 of (owned)
+    struct PcLevel* lvl = nullptr;    // adflow_gpu_pc_set_level_fill >= 0: the tables of the general pattern (owned); tab is not used then
+};
+// The ILU(k) over the whole level on a general block pattern (kernels_pc_level.hip): its tables hang on the pattern, not on the numbers,
+// and outlive a new setup of the same level and fill on the same blocks and comm pattern (ANKStep sets up at every Jacobian refresh).
+struct PcLevel {
+    PclTab tab;
+    long gen = -1;                    // g_pc_topo_gen the tables were built at
+    int maxRow = 0, reused = 0;       // the longest row; 1: the last setup kept the tables and redid the numbers only
+    long nEntries = 0;                // blocks of the pattern over all rows, diagonal included
+    std::vector<int> vec, cblk;       // host copies for the message of a failing pivot
+    JmBlk* dblk = nullptr;            // the block table on the device (the assembly may have moved: written at every setup)
 };
 // The multigrid hierarchy of a slot (kernels_pc_mg.hip).  Level 1 is lv[0]: its matrix is the slot's own copy of the in-block 7-point
 // blocks (T included) and its factor is the PcFactor that owns this hierarchy; the levels below carry their own factor.
@@ -4213,6 +4231,7 @@ PcFactor g_pc_slots[2];              // adflow_gpu_pc_select: e.g. the flow fact
 int g_pc_slot = 0;
 int g_pc_fill[2] = {0, 0};           // adflow_gpu_pc_set_fill: the fill the next setup of each slot uses (outlives the factors)
 int g_pc_coupled[2] = {0, 0};        // adflow_gpu_pc_set_coupled: 1 = the next setup of the slot factors the whole level as one subdomain
+int g_pc_level_fill[2] = {-1, -1};   // adflow_gpu_pc_set_level_fill: >= 0 = the next setup of the slot builds the ILU(fill) of the whole level
 static PcFactor& pc_sel() { return g_pc_slots[g_pc_slot]; }
 struct DevBuf {                       // a device allocation that lives as long as one call
     void* p = nullptr;
@@ -4241,6 +4260,7 @@ static int64_t pc_release(PcFactor& f)
         delete f.mg;
     }
     for (void* p : f.raw) (void)hipFree(p);
+    delete f.lvl;
     f = PcFactor();
     return n;
 }
@@ -4564,8 +4584,9 @@ static int pc_tab_init(PcFactor& f, int fill, long N, const int* sten, std::vect
 // per-cell relations of kernels_pc_coupled.hip do not hold: the same column behind two faces of a cell, a cell that is its own
 // column, two neighbours of a cell that are neighbours of each other, a neighbour that does not lead back; and a rotational
 // periodicity when the matrix covers the velocities, as the product refuses it.
+// general: the caller eliminates on a general pattern (pc_level_build), which takes two neighbours that are neighbours of each other
 static int pc_coupled_columns(int level, const std::vector<JmBlk>& hb, const std::vector<int>& nnOf, long N, std::vector<int>& col,
-                              long& nCross)
+                              long& nCross, bool general = false)
 {
     col.assign((size_t)6 * N, -1);
     nCross = 0;
@@ -4645,7 +4666,7 @@ static int pc_coupled_columns(int level, const std::vector<JmBlk>& hb, const std
                 const long m = col[(size_t)e * N + n];
                 if (m == c) back = true;
                 if (m < 0 || m == c) continue;
-                for (int d2 = 0; d2 < 6; ++d2)
+                for (int d2 = 0; d2 < 6 && !general; ++d2)
                     if (d2 != d && col[(size_t)d2 * N + c] == m) {
                         const int nn = where(c, p), nn2 = where(n, o);
                         return fail("pc_setup: two neighbours of cell (%d,%d,%d) of block %d are neighbours of each other (cell (%d,%d,%d) "
@@ -4686,6 +4707,214 @@ static int pc_setup_build(PcFactor& f, int fill, int coupled, int level, const d
         return 1;
     f.nCross = nCross;
     return 0;
+}
+
+// ---- ILU(k) over the whole level on a general block pattern (adflow_gpu_pc_set_level_fill; kernels_pc_level.hip) ------------------
+// The tables of the factor f of `level` at `fill` for the N cells of the blocks hb: the symbolic ILU(fill) of the cell graph of the level
+// (columns: pc_coupled_columns), the level sets, the order and the slices of the storage; everything that does not depend on the
+// numbers.  The host decides every refusal before the first allocation.
+static int pc_level_tables(PcFactor& f, int level, int fill, const std::vector<JmBlk>& hb, const std::vector<int>& nnOf, long N)
+{
+    const int nS = g_jac.nState;
+    std::vector<int> col;
+    long nCross = 0;
+    if (pc_coupled_columns(level, hb, nnOf, N, col, nCross, true)) return 1;
+    // symbolic ILU(fill): level(i, j) = min over the pivots k < min(i, j) of level(i, k) + level(k, j) + 1, kept while <= fill.  One level per
+    // entry suffices, the blocks are dense.  Rows in CSR, every row in ascending column order; dg[i]: where the diagonal stands in row i
+    std::vector<size_t> rp(N + 1, 0);
+    std::vector<int> cj, dg(N);
+    std::vector<unsigned char> lv;
+    cj.reserve((size_t)N * (fill == 0 ? 7 : fill == 1 ? 14 : fill == 2 ? 26 : 48));
+    lv.reserve(cj.capacity());
+    std::vector<int> wc;
+    std::vector<unsigned char> wl;
+    for (long i = 0; i < N; ++i) {
+        int a[7], na = 0;
+        for (int d = 0; d < 6; ++d)
+            if (col[(size_t)d * N + i] >= 0) a[na++] = col[(size_t)d * N + i];
+        a[na++] = (int)i;
+        std::sort(a, a + na);
+        wc.assign(a, a + na);
+        wl.assign(na, 0);
+        for (size_t p = 0; p < wc.size() && wc[p] < i; ++p) {        // the pivots in ascending order, those the loop adds included
+            const int k = wc[p], lk = wl[p];
+            if (lk >= fill) continue;                                 // lk + level(k, j) + 1 > fill whatever row k holds
+            size_t w = p + 1;
+            for (size_t e = rp[k] + dg[k] + 1; e < rp[k + 1]; ++e) { // the upper entries of row k: a merge, both rows ascend
+                const int j = cj[e], nw = lk + lv[e] + 1;
+                if (nw > fill) continue;
+                while (w < wc.size() && wc[w] < j) ++w;
+                if (w < wc.size() && wc[w] == j) {
+                    if (nw < wl[w]) wl[w] = (unsigned char)nw;
+                } else {
+                    wc.insert(wc.begin() + w, j);
+                    wl.insert(wl.begin() + w, (unsigned char)nw);
+                }
+            }
+        }
+        dg[i] = (int)(std::lower_bound(wc.begin(), wc.end(), (int)i) - wc.begin());
+        if (wc.size() > 65535)
+            return fail("pc_setup: row %ld of the ILU(%d) over level %d has %zu entries; the tables keep the entry number in 16 bits (at most "
+                        "65535); no factor is kept", i, fill, level, wc.size());
+        cj.insert(cj.end(), wc.begin(), wc.end());
+        lv.insert(lv.end(), wl.begin(), wl.end());
+        rp[i + 1] = cj.size();
+    }
+    // level sets: the longest path over the lower entries; the order (set, natural number)
+    std::vector<int> lvl(N);
+    int nSets = 0, maxRow = 0;
+    for (long i = 0; i < N; ++i) {
+        int l = 0;
+        for (size_t e = rp[i]; e < rp[i] + dg[i]; ++e) l = std::max(l, lvl[cj[e]] + 1);
+        lvl[i] = l;
+        nSets = std::max(nSets, l + 1);
+        maxRow = std::max(maxRow, (int)(rp[i + 1] - rp[i]));
+    }
+    std::vector<int> start(nSets + 1, 0);
+    for (long c = 0; c < N; ++c) start[lvl[c] + 1]++;
+    for (int p = 0; p < nSets; ++p) start[p + 1] += start[p];
+    std::vector<int> cur(start.begin(), start.end() - 1), pos(N), vec(N), cblk(N), cbox(N);
+    for (size_t s = 0; s < hb.size(); ++s) {
+        const JmBlk& q = hb[s];
+        long nat = q.vecOff;
+        for (int k = 0; k < q.nz; ++k)
+            for (int j = 0; j < q.ny; ++j)
+                for (int i = 0; i < q.nx; ++i, ++nat) {
+                    const int at = cur[lvl[nat]]++;
+                    pos[nat] = at;
+                    vec[at] = (int)nat;
+                    cblk[at] = (int)s;
+                    cbox[at] = (i + 2) + (j + 2) * q.ldi + (k + 2) * q.ldk;
+                }
+    }
+    // the slices: the rows of one workgroup (64 positions of a set, fewer at its end) share the width of their longest row
+    std::vector<long> ebase(N);
+    std::vector<int> rinfo(N), rcnt(N);
+    long E = 0;
+    for (int p = 0; p < nSets; ++p)
+        for (int s0 = start[p]; s0 < start[p + 1]; s0 += 64) {
+            const int st = std::min(64, start[p + 1] - s0);
+            int w = 0;
+            for (int t = 0; t < st; ++t) w = std::max(w, (int)(rp[vec[s0 + t] + 1] - rp[vec[s0 + t]]));
+            for (int t = 0; t < st; ++t) {
+                const int nat = vec[s0 + t];
+                ebase[s0 + t] = E;
+                rinfo[s0 + t] = t | (st << 8);
+                rcnt[s0 + t] = dg[nat] | ((int)(rp[nat + 1] - rp[nat]) << 16);
+            }
+            E += (long)w * st;
+        }
+    std::vector<int> epos((size_t)E, 0), enat((size_t)E, 0), einfo((size_t)E, 0);
+    for (long at = 0; at < N; ++at) {
+        const int nat = vec[at], st = rinfo[at] >> 8, t = rinfo[at] & 0xff;
+        for (size_t e = rp[nat]; e < rp[nat + 1]; ++e) {
+            const int c = cj[e];
+            const size_t slot = (size_t)ebase[at] + (e - rp[nat]) * st + t;
+            epos[slot] = pos[c];
+            enat[slot] = c;
+            int from = 0;                                              // 1 + direction of the assembled entry, 0: a fill entry
+            if (c == nat) from = 7;
+            else if (lv[e] == 0)
+                for (int d = 0; d < 6; ++d)
+                    if (col[(size_t)d * N + nat] == c) from = d + 1;
+            const int* rb = cj.data() + rp[c];
+            const int* re = cj.data() + rp[c + 1];
+            const int* mi = std::lower_bound(rb, re, nat);
+            if (mi == re || *mi != nat)
+                return fail("pc_setup: the pattern of the ILU(%d) over level %d has the entry (%d, %d) but not its mirror entry: a column that "
+                            "does not lead back; no factor is kept", fill, level, nat, c);
+            einfo[slot] = (int)(mi - rb) | (from << 16);
+        }
+    }
+    // ---- device: the factor, its work space, the tables
+    PcLevel* L = new PcLevel;
+    f.lvl = L;                                    // from here on pc_release(f) frees whatever is held
+    memset(&f.tab, 0, sizeof f.tab);
+    memset(&L->tab, 0, sizeof L->tab);
+    f.tab.ncell = N;
+    PclTab& T = L->tab;
+    T.ncell = N;
+    void *de, *dr, *dc, *dp, *dn, *di, *dv, *db, *dx, *df;
+    auto alloc = [&](void** p, size_t bytes) { return pc_alloc(f, fill, p, bytes); };
+    if (alloc((void**)&T.fac, (size_t)E * nS * nS * sizeof(double)) || alloc((void**)&f.tab.ws, (size_t)N * nS * sizeof(double)) ||
+        alloc((void**)&T.rpiv, sizeof(int) * N))
+        return 1;
+    if (alloc(&de, sizeof(long) * N) || alloc(&dr, sizeof(int) * N) || alloc(&dc, sizeof(int) * N) || alloc(&dp, sizeof(int) * (size_t)E) ||
+        alloc(&dn, sizeof(int) * (size_t)E) || alloc(&di, sizeof(int) * (size_t)E) || alloc(&dv, sizeof(int) * N) ||
+        alloc(&db, sizeof(int) * N) || alloc(&dx, sizeof(int) * N) || alloc((void**)&L->dblk, sizeof(JmBlk) * hb.size()) ||
+        alloc(&df, sizeof(int)))
+        return 1;
+    // (padding slots of the factor are never read; cleared so that a download of the storage shows no stale numbers)
+    HIPCHK(hipMemsetAsync(T.fac, 0, (size_t)E * nS * nS * sizeof(double), g_stream));
+    HIPCHK(hipMemcpy(de, ebase.data(), sizeof(long) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dr, rinfo.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dc, rcnt.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dp, epos.data(), sizeof(int) * (size_t)E, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dn, enat.data(), sizeof(int) * (size_t)E, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(di, einfo.data(), sizeof(int) * (size_t)E, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dv, vec.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db, cblk.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dx, cbox.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    T.ws = f.tab.ws;
+    T.ebase = (const long*)de; T.rinfo = (const int*)dr; T.rcnt = (const int*)dc;
+    T.epos = (const int*)dp; T.enat = (const int*)dn; T.einfo = (const int*)di;
+    T.vec = (const int*)dv; T.cblk = (const int*)db; T.cbox = (const int*)dx;
+    T.blk = L->dblk; T.flag = (int*)df;
+    L->gen = g_pc_topo_gen;
+    L->maxRow = maxRow;
+    L->nEntries = (long)cj.size();
+    L->vec = vec;
+    L->cblk = cblk;
+    f.level = level; f.nState = nS; f.nPlanes = nSets; f.ncell = N;
+    f.fill = fill; f.nEnt = maxRow;
+    f.coupled = 1;
+    f.nCross = nCross;
+    f.planeStart = start;
+    return 0;
+}
+
+// the numbers of the factor over the level f, whose tables stand: the assembled rows into its storage, the elimination, the pivots
+static int pc_level_numeric(PcFactor& f, const int* sten, const std::vector<JmBlk>& hb, const std::vector<int>& nnOf, const double* shift,
+                            double turbDiag)
+{
+    PcLevel& L = *f.lvl;
+    PclTab T = L.tab;
+    for (int q = 0; q < 7; ++q) T.sten[q] = sten[q];
+    T.tsm = shift; T.turbDiag = turbDiag;
+    HIPCHK(hipMemcpyAsync(L.dblk, hb.data(), sizeof(JmBlk) * hb.size(), hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemsetAsync(T.flag, 0, sizeof(int), g_stream));
+    if (launch_pcl_factor(T, f.nState, f.planeStart, g_stream)) return 1;
+    int flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, T.flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));       // hb, which the copy above reads, lives until the caller returns
+    HIPCHK(hipGetLastError());
+    if (flag) {
+        const int at = flag - 1, s = L.cblk[at];
+        const long loc = L.vec[at] - hb[s].vecOff;
+        return fail("pc_setup: the pivot block of cell (%d,%d,%d) of block %d is singular or not finite (ILU(%d) over the level in natural "
+                    "order, level %d); no factor is kept", (int)(loc % hb[s].nx) + 2, (int)(loc / hb[s].nx % hb[s].ny) + 2,
+                    (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2, nnOf[s], f.fill, f.level);
+    }
+    f.valid = true;
+    return 0;
+}
+
+// The ILU(fill) over the whole level in f.  A level factor of the same level, fill and nState that stands in f, built on the blocks and
+// comm patterns registered now, keeps its tables (reused = 1); anything else in f is released first.
+static int pc_level_setup(PcFactor& f, int fill, int level, const double* shift, double turbDiag)
+{
+    int sten[7];
+    std::vector<JmBlk> hb;
+    std::vector<int> nnOf;
+    long N = 0;
+    const bool keep = f.valid && f.lvl && f.level == level && f.fill == fill && f.nState == g_jac.nState && f.lvl->gen == g_pc_topo_gen;
+    if (!keep) (void)pc_release(f);
+    if (pc_level_blocks(level, sten, hb, nnOf, N)) return 1;
+    if (keep && N != f.ncell) return fail("pc_setup: internal: the level has %ld cells, the tables of its factor %ld", N, f.ncell);
+    if (!keep && pc_level_tables(f, level, fill, hb, nnOf, N)) return 1;
+    f.valid = false;                              // until the numbers stand
+    f.lvl->reused = keep ? 1 : 0;
+    return pc_level_numeric(f, sten, hb, nnOf, shift, turbDiag);
 }
 
 // ---- the multigrid hierarchy (adflow_gpu_pc_set_mg; kernels_pc_mg.hip) -------------------------------------------------------------
@@ -4812,9 +5041,30 @@ static int pc_setup_selected(int level, const double* shift = nullptr, double tu
 {
     PcFactor& f = pc_sel();
     HIPCHK(hipStreamSynchronize(g_stream));
-    (void)pc_release(f);
     const PcMgSetting& mg = g_pc_mg[g_pc_slot];
     const int coupled = g_pc_coupled[g_pc_slot];
+    if (g_pc_level_fill[g_pc_slot] >= 0) {
+        // the ILU(k) over the level is a factor of its own kind: it takes none of the other settings of the slot
+        const int lf = g_pc_level_fill[g_pc_slot];
+        const char* with = nullptr;
+        char what[96];
+        if (coupled) { with = "adflow_gpu_pc_set_coupled"; snprintf(what, sizeof what, "coupled = 1"); }
+        else if (g_pc_fill[g_pc_slot] > 0) { with = "adflow_gpu_pc_set_fill"; snprintf(what, sizeof what, "fill %d", g_pc_fill[g_pc_slot]); }
+        else if (mg.levels > 1) { with = "adflow_gpu_pc_set_mg"; snprintf(what, sizeof what, "a multigrid hierarchy of %d levels", mg.levels); }
+        if (with) {
+            (void)pc_release(f);
+            return fail("pc_setup: slot %d is set to the ILU(%d) over the level (adflow_gpu_pc_set_level_fill) and to %s (%s); the factor "
+                        "over the level takes neither the subdomain setting, nor the block-local fill, nor a hierarchy: set that one back "
+                        "or level_fill to -1; no factor is kept", g_pc_slot, lf, what, with);
+        }
+        if (pc_level_setup(f, lf, level, shift, turbDiag)) {
+            if (g_stream) (void)hipStreamSynchronize(g_stream);
+            (void)pc_release(f);
+            return 1;
+        }
+        return 0;
+    }
+    (void)pc_release(f);
     if (coupled && g_pc_fill[g_pc_slot] > 0)
         return fail("pc_setup: slot %d is set to one subdomain for the level (adflow_gpu_pc_set_coupled) and to fill %d; across a block "
                     "interface the pattern of fill 1 and 2 is no fixed stencil, the factor over the level takes fill 0; no factor is kept",
@@ -4878,6 +5128,29 @@ int adflow_gpu_pc_coupled_info(int32_t* coupled, int32_t* nLevelSets, int64_t* n
     if (coupled) *coupled = pc_sel().coupled;
     if (nLevelSets) *nLevelSets = pc_sel().nPlanes;
     if (nCrossEntries) *nCrossEntries = pc_sel().nCross;
+    return 0;
+}
+
+int adflow_gpu_pc_set_level_fill(int fill)
+{
+    if (fill < -1 || fill > 3)
+        return fail("pc_set_level_fill: %d; -1 = off, 0, 1, 2 or 3 levels of fill of the ILU over the whole level", fill);
+    g_pc_level_fill[g_pc_slot] = fill;
+    return 0;
+}
+
+int adflow_gpu_pc_level_info(int32_t* fill, int32_t* maxRow, int64_t* nEntries, int32_t* nLevelSets, int64_t* nCrossEntries, int32_t* reused)
+{
+    const PcFactor& f = pc_sel();
+    if (!f.valid) return fail("pc_level_info: no factor (call adflow_gpu_pc_setup first)");
+    if (!f.lvl)
+        return fail("pc_level_info: the factor of slot %d is no ILU over the level (adflow_gpu_pc_set_level_fill before the setup)", g_pc_slot);
+    if (fill) *fill = f.fill;
+    if (maxRow) *maxRow = f.lvl->maxRow;
+    if (nEntries) *nEntries = f.lvl->nEntries;
+    if (nLevelSets) *nLevelSets = f.nPlanes;
+    if (nCrossEntries) *nCrossEntries = f.nCross;
+    if (reused) *reused = f.lvl->reused;
     return 0;
 }
 
@@ -4946,6 +5219,10 @@ int adflow_gpu_pc_release(int64_t* bytes)
 // z = M^-1 r or M^-T r with the selected factor, whatever its fill, for nv = 1 .. PC_MAXW columns ldr / ldz apart in the same launches
 static int pc_factor_apply(const PcFactor& f, int transpose, const double* r, double* z, hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0)
 {
+    if (f.lvl) {
+        if (nv != 1) return fail("pc_apply: internal: the sweeps of the ILU over the level take one vector");
+        return launch_pcl_apply(f.lvl->tab, f.nState, transpose, f.planeStart, r, z, s);
+    }
     if (f.coupled) return launch_pcc_apply(f.tab, f.nState, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
     if (f.fill > 0) return launch_pcf_apply(f.tab, f.nState, f.nEnt, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
     return launch_pc_apply(f.tab, f.nState, transpose, f.planeStart, r, z, s, nv, ldr, ldz);
@@ -5032,7 +5309,8 @@ static int pc_apply_multi_enqueue(const char* who, int transpose, int nvec, cons
     // fill 2: one column per chain of launches, the kernels of the single entry -- its sweeps of several vectors are not shipped
     // (kernels_pc_fill.hip), so there the multi entry costs what the single calls cost
     // a hierarchy: one column per cycle as well (a cycle of several vectors is not built)
-    const int width = (pc_sel().fill == 2 || pc_sel().mg) ? 1 : (int)PC_MAXW;
+    // the ILU over the level: one column per chain as well, as at fill 2
+    const int width = (pc_sel().fill == 2 || pc_sel().mg || pc_sel().lvl) ? 1 : (int)PC_MAXW;
     if (pc_ws_reserve(who, std::min(width, nvec))) return 1;
     for (int c = 0; c < nvec; c += width)
         if (pc_apply_enqueue(transpose, r + c * ldr, z + c * ldz, s, std::min(width, nvec - c), ldr, ldz)) return 1;

@@ -457,6 +457,35 @@ int launch_pcc_apply(const PcTab& T, int nState, int transpose, const std::vecto
 int launch_pcf_factor(const PcTab& T, int nState, int nEnt, const std::vector<int>& levelStart, hipStream_t s);
 int launch_pcf_apply(const PcTab& T, int nState, int nEnt, int transpose, const std::vector<int>& levelStart, const double* r,
                      double* z, hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0);
+// ILU(k) over the whole level on a general block pattern (kernels_pc_level.hip; adflow_gpu_pc_set_level_fill): the factor as its
+// kernels see it.  Position q of the order (set, natural number) is lane q % 64 of slice q / 64 of its set (counted from the first
+// position of the set): the rows of one workgroup.  A slice of st rows whose longest row has w entries owns the w st entry slots from
+// ebase on; entry j of lane t is slot ebase + j st + t of epos / enat / einfo, and its block is fac[ebase nState^2 + (j nState^2 + e) st + t].
+// The entries of a row ascend in the natural number of their column: nLow lower entries, the pivot block (as its LU factors, kernels_pc_level.hip), the upper ones.
+struct PclTab {
+    long ncell;           // owned cells of the level
+    double* fac;
+    double* ws;           // nState components in the order of the factor: the vector between and during the two sweeps
+    int* rpiv;            // per row: the row exchanges of the LU of its pivot block, three bits each (written by the factorisation)
+    const long* ebase;   // per row: first entry slot of its slice (64-bit: the factor of the benchmark mesh has > 2^31 doubles)
+    const int* rinfo;     // per row: lane (bits 0..7) and rows of its slice (bits 8..)
+    const int* rcnt;      // per row: nLow (bits 0..15) and entries (bits 16..)
+    const int* epos;      // per entry: position of the row of its column
+    const int* enat;      // per entry: natural number of its column, the key of the merge in k_pcl_factor
+    const int* einfo;     // per entry: bits 0..15 the number of the mirror entry (n, c) in row n; bits 16..: 1 + the direction
+                          // (0..5, 6: the diagonal) of the assembled entry it starts from, 0: a fill entry (starts from zero)
+    const int* vec;       // the cell's number in the PETSc layout (block, k, j, i)
+    const int* cblk;      // setup only: slot of the cell's block in blk[] and its box index
+    const int* cbox;
+    const JmBlk* blk;
+    int* flag;            // != 0: 1 + position of a cell whose pivot block is singular or not finite
+    int sten[7];          // stencil entries of the assembly, as PcTab::sten
+    const double* tsm;    // setup only, as PcTab::tsm
+    double turbDiag;
+};
+int launch_pcl_factor(const PclTab& T, int nState, const std::vector<int>& setStart, hipStream_t s);
+int launch_pcl_apply(const PclTab& T, int nState, int transpose, const std::vector<int>& setStart, const double* r, double* z,
+                     hipStream_t s);
 // the multigrid preconditioner (kernels_pc_mg.hip): every level keeps its 7-point matrix in the box layout of JmBlk (jac = the blocks
 // of the level, vecOff = the first CELL of the block in the vectors of the level) with the stencil entries of the assembly;
 // PcMgSten: those entries in the order of PcTab::sten.  Tables hold one JmBlk per block, the same slot on every level; maxn*: the

@@ -213,6 +213,21 @@ class Engine:
         self._chk(self.lib.adflow_gpu_pc_coupled_info(ctypes.byref(c), ctypes.byref(nl), ctypes.byref(nx)))
         return int(c.value), int(nl.value), int(nx.value)
 
+    def pcSetLevelFill(self, fill: int):
+        """-1: off; 0 .. 3: the next pcSetup / ankPcSetup of the selected slot builds the ILU(fill) of the 7-point matrix of the WHOLE level
+        on its general block pattern (one ASM subdomain with PCFactorSetLevels(fill), what setupStandardKSP gives one process); excludes
+        pcSetCoupled(1), pcSetFill > 0 and pcSetMg > 1 in the same slot; a factor that exists keeps its own"""
+        self._chk(self.lib.adflow_gpu_pc_set_level_fill(int(fill)))
+
+    def pcLevelInfo(self):
+        """(fill, longest row, blocks of the pattern over all rows, level sets, entries of the assembled matrix behind a block face,
+        reused: 1 when the last setup kept the tables) of the factor over the level in the selected slot"""
+        f, mr, nl, rs = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        ne, nx = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self.lib.adflow_gpu_pc_level_info(ctypes.byref(f), ctypes.byref(mr), ctypes.byref(ne), ctypes.byref(nl), ctypes.byref(nx),
+                                                    ctypes.byref(rs)))
+        return int(f.value), int(mr.value), int(ne.value), int(nl.value), int(nx.value), int(rs.value)
+
     def pcSetMg(self, levels: int, nSmooth: int = 1, fillCoarse: int = 0):
         """the multigrid preconditioner of amg.F90 (precondType = 'mg') for the next pcSetup / ankPcSetup of the selected slot: `levels`
         levels of 2 x 2 x 2 aggregates per block (1: the plain factor), nSmooth Richardson iterations of the ILU smoother per level,

@@ -364,6 +364,18 @@ module adflowGpuShim
             integer(c_int32_t), intent(out) :: coupled, nLevelSets
             integer(c_int64_t), intent(out) :: nCrossEntries
         end function
+        ! the ILU(fill) over the whole level for the next setup of the selected slot (ILUFill / ANKPCILUFill / NKPCILUFill on one process):
+        ! -1 = off, 0 .. 3; and what the selected factor over the level holds
+        integer(c_int) function adflow_gpu_pc_set_level_fill(fill) bind(C, name="adflow_gpu_pc_set_level_fill")
+            import :: c_int
+            integer(c_int), value :: fill
+        end function
+        integer(c_int) function adflow_gpu_pc_level_info(fill, maxRow, nEntries, nLevelSets, nCrossEntries, reused) &
+            bind(C, name="adflow_gpu_pc_level_info")
+            import :: c_int, c_int32_t, c_int64_t
+            integer(c_int32_t), intent(out) :: fill, maxRow, nLevelSets, reused
+            integer(c_int64_t), intent(out) :: nEntries, nCrossEntries
+        end function
         ! the multigrid preconditioner of amg.F90 (precondType = 'mg') for the next setup of the selected slot: AMGLevels, AMGNSmooth and
         ! the fill of the coarse levels; what the selected slot holds; the blocks of one block on one level (nx_l, ny_l, nz_l, nState, nState, 7)
         integer(c_int) function adflow_gpu_pc_set_mg(levels, nSmooth, fillCoarse) bind(C, name="adflow_gpu_pc_set_mg")

@@ -546,6 +546,29 @@ int adflow_gpu_pc_info2(int32_t* fill, int32_t* nEntries, int32_t* nLevelSets);
  * column lies behind a block face (0 for a block-local factor); each may be NULL; an error without a factor. */
 int adflow_gpu_pc_set_coupled(int coupled);
 int adflow_gpu_pc_coupled_info(int32_t* coupled, int32_t* nLevelSets, int64_t* nCrossEntries);
+/* ILU(k) over the whole level.  adflow_gpu_pc_set_level_fill(fill), fill = -1 (default: off), 0, 1, 2 or 3: with fill >= 0 the next
+ * adflow_gpu_pc_setup / _ank_pc_setup of the SELECTED slot builds the ILU(fill) of the 7-point matrix of the WHOLE level -- what
+ * setupStandardKSP gives one process: one ASM subdomain, PCFactorSetLevels(ILUFill / ANKPCILUFill / NKPCILUFill, default 2).  Columns
+ * and ordering are those of coupled = 1 above.  The host runs the symbolic ILU(k) of the cell graph of the level once; the device
+ * factors by IKJ restricted to that pattern (csrc/kernels_pc_level.hip) and sweeps over whatever rows come out (7 to 37 entries at
+ * fill 2 across interfaces), so an edge with three blocks around it and a period of three cells, which coupled = 1 refuses, are
+ * factored.  The storage is proportional to the entries of the pattern.  adflow_gpu_ank_pc_setup adds T as for every other factor.
+ * Kept per slot across setups and releases; a factor that exists keeps what it was built with; any other value is an error that
+ * names it and changes nothing.  With -1 in both slots every other path is what it was, bit for bit.
+ * Everything that takes a factor takes this one: pc_apply[_dev] with and without transpose from the one factor, gmres_solve,
+ * ank_solve, jacfree_solve, both slots, the enqueue-only mode, the _multi entries column by column (as at fill 2).
+ * Errors of the setup, each with a message, decided before anything is allocated; the slot then keeps no factor, the other slot is
+ * untouched: coupled = 1, a fill > 0 or a hierarchy set for the same slot; a matrix that is not 7-point; the same column behind two
+ * faces of a cell; a cell that is its own column; a pattern entry without its mirror entry (a column that does not lead back); a
+ * rotational periodicity when the matrix covers the velocities; a row of more than 65535 entries.
+ * Tables once: a setup into a slot that holds such a factor of the same level, fill and nState, with no block or comm pattern
+ * registered or released since, keeps the tables and redoes the numbers only (reused = 1).
+ * On such a factor adflow_gpu_pc_info gives nState, the level sets and the bytes held, adflow_gpu_pc_info2 the fill, the longest row
+ * and the level sets, adflow_gpu_pc_coupled_info 1, the level sets and nCrossEntries.
+ * adflow_gpu_pc_level_info: the fill, the longest row, the blocks of the pattern over all rows (diagonal included), the level sets, the
+ * entries of the assembled matrix whose column lies behind a block face, and reused; each may be NULL; an error without such a factor. */
+int adflow_gpu_pc_set_level_fill(int fill);
+int adflow_gpu_pc_level_info(int32_t* fill, int32_t* maxRow, int64_t* nEntries, int32_t* nLevelSets, int64_t* nCrossEntries, int32_t* reused);
 int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, long n);
 int adflow_gpu_pc_apply_dev(int level, int transpose, const double* d_r, double* d_z, long n);
 int adflow_gpu_pc_release(int64_t* bytes);

@@ -15,7 +15,11 @@ level per smoothing iteration.  Without --mg nothing changes.
 1-to-1 interfaces inside (the benchmark's layout); --coupled (fill 0, no --mg) then runs every line twice in the same process, with
 one ILU subdomain per block (adflow_gpu_pc_set_coupled(0)) and with one for the level (1): setup, both applications with launches,
 level sets, microseconds per launch and GB/s on the factor bytes, and GMRES.
+--level-fill F (0 .. 3, also with --brick) runs the same lines three times in the same process: the block-local factor of fill F
+(F <= 2), the coupled fill-0 factor, and the ILU(F) over the whole level (adflow_gpu_pc_set_level_fill: longest row, entries of the
+pattern, level sets, whether the timed setup kept the tables; GB/s on the bytes of the pattern's blocks).
 usage: pc_apply.py [--fill 0|1|2] [--mg L [--nsmooth N] [--fill-coarse F]] [--rtol 1e-8] [--nvec N] [--brick Bi Bj Bk] [--coupled]
+       [--level-fill F]
        [n] [nx ny nz]      (n timed applications of each kind, default 10)"""
 import json
 import os
@@ -34,7 +38,7 @@ WALL = {1: -6, 2: -6, 3: -1, 4: -1, 5: -3, 6: -6}
 def main():
     import torch
     argv, fill, rtol, nvec = list(sys.argv[1:]), 0, 1e-8, 0
-    mg, nsmooth, fillc = 1, 1, 0
+    mg, nsmooth, fillc, level_fill = 1, 1, 0, None
     brick, both = None, "--coupled" in argv
     if both:
         argv.remove("--coupled")
@@ -42,7 +46,7 @@ def main():
         at = argv.index("--brick")
         brick = tuple(int(a) for a in argv[at + 1:at + 4])
         del argv[at:at + 4]
-    for opt in ("--fill", "--rtol", "--nvec", "--mg", "--nsmooth", "--fill-coarse"):
+    for opt in ("--fill", "--rtol", "--nvec", "--mg", "--nsmooth", "--fill-coarse", "--level-fill"):
         if opt in argv:
             at = argv.index(opt)
             if opt == "--fill":
@@ -55,6 +59,8 @@ def main():
                 nsmooth = int(argv[at + 1])
             elif opt == "--fill-coarse":
                 fillc = int(argv[at + 1])
+            elif opt == "--level-fill":
+                level_fill = int(argv[at + 1])
             else:
                 rtol = float(argv[at + 1])
             del argv[at:at + 2]
@@ -79,7 +85,20 @@ def main():
     eng.releaseWorkspace()
     ns, st = eng.jacobianInfo()
     n = ns * cells
-    if both:
+    if level_fill is not None:
+        if fill or mg > 1 or both:
+            sys.exit("--level-fill: runs the block-local factor of that fill and the coupled fill-0 factor itself; no --fill, --mg, --coupled")
+        if level_fill <= 2:
+            eng.pcSetFill(level_fill)
+            one_factor(eng, torch, dims, brick, ns, cells, n, n_it, level_fill, 1, rtol, 0, 0)
+            eng.pcSetFill(0)
+        eng.pcSetCoupled(1)
+        one_factor(eng, torch, dims, brick, ns, cells, n, n_it, 0, 1, rtol, 0, 1)
+        eng.pcSetCoupled(0)
+        eng.pcSetLevelFill(level_fill)
+        one_factor(eng, torch, dims, brick, ns, cells, n, n_it, level_fill, 1, rtol, 0, None, level_fill)
+        eng.pcSetLevelFill(-1)
+    elif both:
         if fill or mg > 1:
             sys.exit("--coupled: the factor over the level takes fill 0 and no hierarchy")
         for coupled in (0, 1):
@@ -119,13 +138,16 @@ def register_brick(eng, topo, prm):
     return sum(b.nx * b.ny * b.nz for b in blocks.values())
 
 
-def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec, coupled):
+def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec, coupled, level_fill=None):
     """setup, applications and GMRES with the settings of the selected slot as they stand; coupled: None, or the subdomain setting
-    the lines name (then with the level sets, the microseconds per launch and the GB/s on the factor bytes)"""
+    the lines name (then with the level sets, the microseconds per launch and the GB/s on the factor bytes); level_fill: None, or the
+    fill of the ILU over the level the slot is set to (the same extra figures, the floor from the entries of its pattern)"""
     tag = {} if coupled is None else {"coupled": coupled}
+    if level_fill is not None:
+        tag["level_fill"] = level_fill
     if brick:
         tag["brick"] = list(brick)
-    floor = {0: 7, 1: 13, 2: 23}[fill] * ns * ns * 8 * cells
+    floor = {0: 7, 1: 13, 2: 23}.get(fill, 7) * ns * ns * 8 * cells
     eng.pcSetup(1)                                        # warm-up (allocations, tables)
     eng.sync()
     eng.event_record(1)
@@ -133,6 +155,11 @@ def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec
     eng.event_record(2)
     eng.sync()
     _, planes, nbytes = eng.pcInfo()
+    if level_fill is not None:
+        _, max_row, n_entries, _, n_cross, reused = eng.pcLevelInfo()
+        floor = n_entries * ns * ns * 8
+        tag.update(longest_row=max_row, pattern_entries=n_entries, entries_per_cell=round(n_entries / cells, 2), cross_entries=n_cross,
+                   timed_setup_reused_tables=reused)
     print(json.dumps({"what": "pc_setup (tables, allocation, factorisation)", "dims": list(dims), "nState": ns, "ms": round(eng.event_elapsed_ms(1, 2), 3),
                       "fill": fill, "hyperplanes_or_level_sets": planes, "factor_bytes": nbytes, **tag}), flush=True)
     if mg > 1:
@@ -157,7 +184,7 @@ def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec
             ms = eng.event_elapsed_ms(1, 2) / n_it
             ms_of[what] = ms
             more = dict(tag)
-            if coupled is not None and what != "J x":
+            if (coupled is not None or level_fill is not None) and what != "J x":
                 more.update(level_sets=planes, us_per_launch=round(1e3 * ms / launches, 2),
                             GB_per_s_on_the_factor=round(floor / (ms * 1e-3) / 1e9, 1))
             print(json.dumps({"what": what, "ms": round(ms, 4), "floor_bytes": floor, "TB_per_s": round(floor / (ms * 1e-3) / 1e12, 3),
