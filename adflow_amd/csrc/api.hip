@@ -4182,8 +4182,24 @@ int adflow_gpu_jacobian_mult_multi(int level, int transpose, int nvec, const dou
 // The PCApply and the KSPSolve of setupStandardKSP (adjointUtils.F90:1374-1562) in the configuration PCBJACOBI / ILU(0) / natural
 // ordering, one subdomain per block; see the header for what is out of scope.
 namespace {
+// adflow_gpu_pc_set_its: the Richardson iterations around the factor (globalPreConIts, localPreConIts and amgLocalPreConIts below level 1)
+struct PcIts {
+    int outer = 1, inner = 1, innerCoarse = 1;
+    bool operator==(const PcIts& o) const { return outer == o.outer && inner == o.inner && innerCoarse == o.innerCoarse; }
+};
+// What the iterations of a factor need beyond the factor (kernels_pc_rich.hip): the copy of the 7-point matrix of the whole level as
+// it stood at the setup, its tables and the work vectors of the recurrences.  Everything is allocated through pc_alloc of the factor
+// that owns it, so pc_info counts it and pc_release frees it.
+struct PcRich {
+    PcRichTab tab;
+    size_t matBytes = 0;              // the copy and its tables
+    int nWork = 0, width = 1;         // work vectors per column (0, 2 or 4) and the columns they serve at once (pc_ws_reserve)
+    double* work = nullptr;           // nWork x width vectors; vector q of column v at work + (q width + v) n
+};
 struct PcFactor {
     bool valid = false;
+    PcIts its;                        // what the factor was built with
+    PcRich* rich = nullptr;           // its.outer > 1, or its.inner > 1 on a plain factor (owned)
     int level = 0, nState = 0, nPlanes = 0;      // nPlanes: hyperplanes at fill 0, dependency level sets at fill 1 and 2
     int fill = 0, nEnt = 7;                        // levels of fill the factor was built with and its entries per row
     int coupled = 0;                  // adflow_gpu_pc_set_coupled: 1 = one subdomain for the level (kernels_pc_coupled.hip)
@@ -4215,6 +4231,7 @@ struct PcMgLevel {
     long ncell = 0;
     int maxnx = 0, maxny = 0, maxnz = 0;
     double* v[4] = {nullptr, nullptr, nullptr, nullptr};      // rhs, sol, res, x of the cycle
+    double* w[2] = {nullptr, nullptr};                        // inner iterations > 1 on this level: their residual, their result
     PcFactor fac;                     // levels >= 2
 };
 struct PcMg {
@@ -4232,6 +4249,7 @@ int g_pc_slot = 0;
 int g_pc_fill[2] = {0, 0};           // adflow_gpu_pc_set_fill: the fill the next setup of each slot uses (outlives the factors)
 int g_pc_coupled[2] = {0, 0};        // adflow_gpu_pc_set_coupled: 1 = the next setup of the slot factors the whole level as one subdomain
 int g_pc_level_fill[2] = {-1, -1};   // adflow_gpu_pc_set_level_fill: >= 0 = the next setup of the slot builds the ILU(fill) of the whole level
+PcIts g_pc_its[2];                   // adflow_gpu_pc_set_its: the iterations the next setup of each slot builds (outlives the factors)
 static PcFactor& pc_sel() { return g_pc_slots[g_pc_slot]; }
 struct DevBuf {                       // a device allocation that lives as long as one call
     void* p = nullptr;
@@ -4261,6 +4279,7 @@ static int64_t pc_release(PcFactor& f)
     }
     for (void* p : f.raw) (void)hipFree(p);
     delete f.lvl;
+    delete f.rich;
     f = PcFactor();
     return n;
 }
@@ -4691,6 +4710,98 @@ static int pc_coupled_columns(int level, const std::vector<JmBlk>& hb, const std
     return 0;
 }
 
+// ---- the preconditioner Richardson iterations (adflow_gpu_pc_set_its; kernels_pc_rich.hip) ----------------------------------------
+// What the host decides before anything is allocated: the blocks of the assembly, the column table of the whole level
+// (pc_coupled_columns in its general mode, with its refusals) and the word of every row -- which columns lie behind a block face, and
+// in which direction every column keeps its entry back to the row (the mirror entry of the transposed product).
+namespace {
+struct PcRichHost {
+    int sten[7];
+    std::vector<JmBlk> hb;
+    long N = 0;
+    std::vector<int> col;
+    std::vector<unsigned> cw;
+};
+}  // namespace
+
+static int pc_rich_tables(int level, PcRichHost& H)
+{
+    std::vector<int> nnOf;
+    long nCross = 0;
+    if (pc_level_blocks(level, H.sten, H.hb, nnOf, H.N) || pc_coupled_columns(level, H.hb, nnOf, H.N, H.col, nCross, true)) return 1;
+    const long N = H.N;
+    H.cw.assign(N, 0u);
+    for (auto& q : H.hb) {
+        long nat = q.vecOff;
+        for (int k = 0; k < q.nz; ++k)
+            for (int j = 0; j < q.ny; ++j)
+                for (int i = 0; i < q.nx; ++i, ++nat) {
+                    const bool inside[6] = {i > 0, j > 0, k > 0, i < q.nx - 1, j < q.ny - 1, k < q.nz - 1};
+                    unsigned w = 0;
+                    for (int d = 0; d < 6; ++d) {
+                        const long n = H.col[(size_t)d * N + nat];
+                        if (n < 0) continue;
+                        if (!inside[d]) w |= 1u << d;
+                        // the way back: the opposite direction inside a block, any across an interface (exactly one: pc_coupled_columns)
+                        int b = (d + 3) % 6, tries = 0;
+                        while (H.col[(size_t)b * N + n] != nat && ++tries < 6) b = (b + 1) % 6;
+                        if (tries == 6) return fail("pc_setup: internal: a column of the level does not lead back to its row");
+                        w |= (unsigned)b << (6 + 3 * d);
+                    }
+                    H.cw[nat] = w;
+                }
+    }
+    return 0;
+}
+
+// the numbers of the copy of f from the blocks hb of the assembly as it stands now (T of ANK on the diagonal blocks)
+static int pc_rich_copy(PcFactor& f, const std::vector<JmBlk>& hb, const int* sten, const double* shift, double turbDiag)
+{
+    const int nb = (int)hb.size();
+    DevBuf src;
+    if (hipMalloc(&src.p, sizeof(JmBlk) * nb) != hipSuccess) {
+        (void)hipGetLastError();
+        src.p = nullptr;
+        return fail("pc_setup: cannot allocate %zu bytes for the block table of the assembly; no factor is kept", sizeof(JmBlk) * nb);
+    }
+    HIPCHK(hipMemcpy(src.p, hb.data(), sizeof(JmBlk) * nb, hipMemcpyHostToDevice));
+    PcMgSten S;
+    int maxnx = 0, maxny = 0, maxnz = 0;
+    for (int q = 0; q < 7; ++q) S.s[q] = sten[q];
+    for (auto& q : hb) { maxnx = std::max(maxnx, q.nx); maxny = std::max(maxny, q.ny); maxnz = std::max(maxnz, q.nz); }
+    const PcRichTab& T = f.rich->tab;
+    launch_rich_copy((const JmBlk*)src.p, nb, maxnx, maxny, maxnz, g_jac.nState, S, shift, turbDiag, T.ncell, T.col, const_cast<double*>(T.mat),
+                     g_stream);
+    HIPCHK(hipStreamSynchronize(g_stream));       // the table of the assembly is freed on return
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The copy, its tables and the work vectors of the factor f, which stands and was built with `its`: outer > 1, or inner > 1 on a
+// plain factor.  Work vectors per column: two for the outer loop (its residual, the result of the inner application), two for the
+// inner loop of a plain factor (its residual, the correction: no sweep runs in place here).
+static int pc_rich_attach(PcFactor& f, const PcIts& its, const PcRichHost& H, const double* shift, double turbDiag)
+{
+    const int nS = g_jac.nState;
+    const long N = H.N;
+    PcRich* R = new PcRich;
+    f.rich = R;                                   // from here on pc_release(f) frees whatever is held
+    memset(&R->tab, 0, sizeof R->tab);
+    R->tab.ncell = N;
+    R->nWork = (its.outer > 1 ? 2 : 0) + (its.inner > 1 && !f.mg ? 2 : 0);
+    const size_t before = f.bytes;
+    void *dm, *dc, *dw;
+    if (pc_alloc(f, f.fill, &dm, (size_t)7 * nS * nS * N * sizeof(double)) || pc_alloc(f, f.fill, &dc, sizeof(int) * 6 * (size_t)N) ||
+        pc_alloc(f, f.fill, &dw, sizeof(unsigned) * (size_t)N))
+        return 1;
+    R->matBytes = f.bytes - before;
+    if (pc_alloc(f, f.fill, (void**)&R->work, (size_t)R->nWork * N * nS * sizeof(double))) return 1;
+    HIPCHK(hipMemcpy(dc, H.col.data(), sizeof(int) * 6 * (size_t)N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dw, H.cw.data(), sizeof(unsigned) * (size_t)N, hipMemcpyHostToDevice));
+    R->tab.mat = (const double*)dm; R->tab.col = (const int*)dc; R->tab.cw = (const unsigned*)dw;
+    return pc_rich_copy(f, H.hb, H.sten, shift, turbDiag);
+}
+
 // the factor f of the assembled 7-point matrix of `level` with `fill` levels of fill; coupled: one subdomain for the level (fill 0)
 static int pc_setup_build(PcFactor& f, int fill, int coupled, int level, const double* shift, double turbDiag)
 {
@@ -4935,7 +5046,7 @@ static int pc_mg_alloc(PcMg& M, void** p, size_t bytes, const char* what, int mg
     return 0;
 }
 
-static int pc_mg_setup_build(PcFactor& f, int fill, const PcMgSetting& set, int level, const double* shift, double turbDiag)
+static int pc_mg_setup_build(PcFactor& f, int fill, const PcMgSetting& set, const PcIts& its, int level, const double* shift, double turbDiag)
 {
     const int nS = g_jac.nState;
     int sten[7];
@@ -5000,6 +5111,9 @@ static int pc_mg_setup_build(PcFactor& f, int fill, const PcMgSetting& set, int 
         HIPCHK(hipMemcpy(L.dtab, L.hb.data(), sizeof(JmBlk) * nb, hipMemcpyHostToDevice));
         for (int v = 0; v < 4; ++v)
             if (pc_mg_alloc(M, (void**)&L.v[v], (size_t)L.ncell * nS * sizeof(double), "vectors", l + 1)) return 1;
+        // inner iterations on this level (adflow_gpu_pc_set_its): the level owns its matrix, two vectors more is all they need
+        for (int v = 0; v < 2 && (l == 0 ? its.inner : its.innerCoarse) > 1; ++v)
+            if (pc_mg_alloc(M, (void**)&L.w[v], (size_t)L.ncell * nS * sizeof(double), "vectors of the inner iterations", l + 1)) return 1;
     }
     // level 1: the copy of the in-block blocks with T on the diagonal, then its factor -- of the copy, so without a shift
     {
@@ -5043,6 +5157,8 @@ static int pc_setup_selected(int level, const double* shift = nullptr, double tu
     HIPCHK(hipStreamSynchronize(g_stream));
     const PcMgSetting& mg = g_pc_mg[g_pc_slot];
     const int coupled = g_pc_coupled[g_pc_slot];
+    const PcIts its = g_pc_its[g_pc_slot];
+    PcRichHost H;
     if (g_pc_level_fill[g_pc_slot] >= 0) {
         // the ILU(k) over the level is a factor of its own kind: it takes none of the other settings of the slot
         const int lf = g_pc_level_fill[g_pc_slot];
@@ -5057,11 +5173,21 @@ static int pc_setup_selected(int level, const double* shift = nullptr, double tu
                         "over the level takes neither the subdomain setting, nor the block-local fill, nor a hierarchy: set that one back "
                         "or level_fill to -1; no factor is kept", g_pc_slot, lf, what, with);
         }
-        if (pc_level_setup(f, lf, level, shift, turbDiag)) {
+        // tables that stand are kept only with the iterations they were built for; then the copy is redone, the numbers changed
+        if (!(f.its == its)) (void)pc_release(f);
+        int rc = pc_level_setup(f, lf, level, shift, turbDiag);
+        if (!rc && f.rich) {
+            std::vector<int> nnOf;
+            rc = pc_level_blocks(level, H.sten, H.hb, nnOf, H.N) || pc_rich_copy(f, H.hb, H.sten, shift, turbDiag);
+        } else if (!rc && (its.outer > 1 || its.inner > 1)) {
+            rc = pc_rich_tables(level, H) || pc_rich_attach(f, its, H, shift, turbDiag);
+        }
+        if (rc) {
             if (g_stream) (void)hipStreamSynchronize(g_stream);
             (void)pc_release(f);
             return 1;
         }
+        f.its = its;
         return 0;
     }
     (void)pc_release(f);
@@ -5072,12 +5198,17 @@ static int pc_setup_selected(int level, const double* shift = nullptr, double tu
     if (coupled && mg.levels > 1)
         return fail("pc_setup: slot %d is set to one subdomain for the level (adflow_gpu_pc_set_coupled) and to a multigrid hierarchy of "
                     "%d levels, which is built block by block; no factor is kept", g_pc_slot, mg.levels);
-    if (mg.levels > 1 ? pc_mg_setup_build(f, g_pc_fill[g_pc_slot], mg, level, shift, turbDiag)
-                      : pc_setup_build(f, g_pc_fill[g_pc_slot], coupled, level, shift, turbDiag)) {
+    // the iterations need the matrix of the whole level: every refusal about its columns before anything is allocated
+    const bool copy = its.outer > 1 || (its.inner > 1 && mg.levels <= 1);
+    if (copy && pc_rich_tables(level, H)) return 1;
+    if ((mg.levels > 1 ? pc_mg_setup_build(f, g_pc_fill[g_pc_slot], mg, its, level, shift, turbDiag)
+                       : pc_setup_build(f, g_pc_fill[g_pc_slot], coupled, level, shift, turbDiag)) ||
+        (copy && pc_rich_attach(f, its, H, shift, turbDiag))) {
         if (g_stream) (void)hipStreamSynchronize(g_stream);
         (void)pc_release(f);
         return 1;
     }
+    f.its = its;
     return 0;
 }
 
@@ -5167,6 +5298,29 @@ int adflow_gpu_pc_set_mg(int levels, int nSmooth, int fillCoarse)
     return 0;
 }
 
+int adflow_gpu_pc_set_its(int outer, int inner, int innerCoarse)
+{
+    if (outer < 1) return fail("pc_set_its: outer = %d; every count is at least 1 (1 = no iteration beyond the application)", outer);
+    if (inner < 1) return fail("pc_set_its: inner = %d; every count is at least 1 (1 = no iteration beyond the application)", inner);
+    if (innerCoarse < 1)
+        return fail("pc_set_its: innerCoarse = %d; every count is at least 1 (1 = no iteration beyond the application)", innerCoarse);
+    g_pc_its[g_pc_slot].outer = outer;
+    g_pc_its[g_pc_slot].inner = inner;
+    g_pc_its[g_pc_slot].innerCoarse = innerCoarse;
+    return 0;
+}
+
+int adflow_gpu_pc_its_info(int32_t* outer, int32_t* inner, int32_t* innerCoarse, int64_t* matrixBytes)
+{
+    const PcFactor& f = pc_sel();
+    if (!f.valid) return fail("pc_its_info: no factor (call adflow_gpu_pc_setup first)");
+    if (outer) *outer = f.its.outer;
+    if (inner) *inner = f.its.inner;
+    if (innerCoarse) *innerCoarse = f.its.innerCoarse;
+    if (matrixBytes) *matrixBytes = f.rich ? (int64_t)f.rich->matBytes : 0;
+    return 0;
+}
+
 int adflow_gpu_pc_mg_info(int32_t* levels, int32_t* nSmooth, int32_t* fillCoarse, int64_t* cells)
 {
     const PcFactor& f = pc_sel();
@@ -5231,17 +5385,35 @@ static int pc_factor_apply(const PcFactor& f, int transpose, const double* r, do
 // The smoother of level l (0-based) of the hierarchy of f: Richardson from zero, nSmooth iterations, one ILU application each
 // (setupShellPC):  x = M^-1 b,  then  x += M^-1 (b - A x).  t: a vector of the level that is free; the sweep turns it into the
 // correction in place (the forward sweep has read all of its input before the backward sweep writes the first output).
+// With inner iterations on the level (adflow_gpu_pc_set_its) every "one ILU application" is the Richardson L_l below, on w[] of the level.
 static int pc_mg_smooth(const PcFactor& f, int l, int transpose, const double* b, double* x, double* t, hipStream_t s)
 {
     const PcMg& M = *f.mg;
     const PcMgLevel& L = M.lv[l];
     const PcFactor& fac = l == 0 ? f : L.fac;
     const int nb = (int)L.hb.size();
-    if (pc_factor_apply(fac, transpose, b, x, s)) return 1;
+    const int inner = l == 0 ? f.its.inner : f.its.innerCoarse;
+    // inner > 1 (adflow_gpu_pc_set_its): the one ILU application becomes  y = L_l(c) = S(c; M_l, A_l, inner)  on the level's own matrix
+    // (amgLocalPreConIts, amg.F90:534-615); w[0] carries its residual and, in place, its correction
+    auto local = [&](const double* c, double* y) -> int {
+        if (pc_factor_apply(fac, transpose, c, y, s)) return 1;
+        for (int it = 1; it < inner; ++it) {
+            launch_mg_residual(L.dtab, nullptr, nb, L.maxnx, L.maxny, L.maxnz, f.nState, transpose, M.sten, c, y, nullptr, L.w[0], s);
+            if (pc_factor_apply(fac, transpose, L.w[0], L.w[0], s)) return 1;
+            launch_gm_axpby(y, 1.0, L.w[0], 1.0, L.ncell * f.nState, s);
+        }
+        return 0;
+    };
+    if (local(b, x)) return 1;
     for (int it = 1; it < M.nSmooth; ++it) {
         launch_mg_residual(L.dtab, nullptr, nb, L.maxnx, L.maxny, L.maxnz, f.nState, transpose, M.sten, b, x, nullptr, t, s);
-        if (pc_factor_apply(fac, transpose, t, t, s)) return 1;
-        launch_gm_axpby(x, 1.0, t, 1.0, L.ncell * f.nState, s);
+        if (inner == 1) {
+            if (pc_factor_apply(fac, transpose, t, t, s)) return 1;
+            launch_gm_axpby(x, 1.0, t, 1.0, L.ncell * f.nState, s);
+        } else {
+            if (local(t, L.w[1])) return 1;
+            launch_gm_axpby(x, 1.0, L.w[1], 1.0, L.ncell * f.nState, s);
+        }
     }
     return 0;
 }
@@ -5269,11 +5441,38 @@ static int pc_mg_cycle(const PcFactor& f, int l, int transpose, const double* r,
 static int pc_apply_enqueue(int transpose, const double* r, double* z, hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0)
 {
     const PcFactor& f = pc_sel();
-    if (f.mg) {
-        if (nv != 1) return fail("pc_apply: internal: the multigrid cycle takes one vector");
-        return pc_mg_cycle(f, 0, transpose, r, z, s);
+    if (f.mg && nv != 1) return fail("pc_apply: internal: the multigrid cycle takes one vector");
+    if (!f.rich) return f.mg ? pc_mg_cycle(f, 0, transpose, r, z, s) : pc_factor_apply(f, transpose, r, z, s, nv, ldr, ldz);
+    // The Richardson iterations of adflow_gpu_pc_set_its, from a zero guess, scale 1, no norm (transpose: A^T and M^-T throughout):
+    //   local(b) = S(b; M, A_sub, inner):  y = M^-1 b,  then inner - 1 times  y += M^-1 (b - A_sub y)     (a hierarchy: its cycle)
+    //   P(b):                              z = local(b),  then outer - 1 times  z += local(b - A_full z)
+    // A_sub = A_full without the columns behind block faces for a factor with one subdomain per block.  The work vectors are those
+    // of the setup (pc_ws_reserve for more than one column): launches on s only, no allocation, no synchronise.  No sweep runs in place.
+    const PcRich& R = *f.rich;
+    const long n = f.ncell * f.nState;
+    if (nv > R.width) return fail("pc_apply: internal: the work vectors of the iterations serve %d columns, not %d", R.width, nv);
+    auto work = [&](int q) { return R.work + (size_t)q * R.width * n; };
+    auto add = [&](double* y, long ldy, const double* c) {
+        for (int v = 0; v < nv; ++v) launch_gm_axpby(y + v * ldy, 1.0, c + v * n, 1.0, n, s);
+    };
+    const int wi = f.its.outer > 1 ? 2 : 0;       // the first work vector of the inner loop
+    auto local = [&](const double* b, long ldb, double* y, long ldy) -> int {
+        if (f.mg) return pc_mg_cycle(f, 0, transpose, b, y, s);
+        if (pc_factor_apply(f, transpose, b, y, s, nv, ldb, ldy)) return 1;
+        for (int it = 1; it < f.its.inner; ++it) {
+            if (launch_rich_residual(R.tab, f.nState, transpose, !f.coupled, nv, b, ldb, y, ldy, work(wi), n, s)) return 1;
+            if (pc_factor_apply(f, transpose, work(wi), work(wi + 1), s, nv, n, n)) return 1;
+            add(y, ldy, work(wi + 1));
+        }
+        return 0;
+    };
+    if (local(r, ldr, z, ldz)) return 1;
+    for (int it = 1; it < f.its.outer; ++it) {
+        if (launch_rich_residual(R.tab, f.nState, transpose, 0, nv, r, ldr, z, ldz, work(0), n, s)) return 1;
+        if (local(work(0), n, work(1), n)) return 1;
+        add(z, ldz, work(1));
     }
-    return pc_factor_apply(f, transpose, r, z, s, nv, ldr, ldz);
+    return 0;
 }
 
 // The work space of the selected factor for nv vectors at once: the part beyond the first vector is allocated at the first
@@ -5300,6 +5499,21 @@ static int pc_ws_reserve(const char* who, int nv)
     f.bytes += per * (nv - 1);
     f.tab.wsx = (double*)p;
     f.wsWidth = nv;
+    // the work vectors of the Richardson iterations (adflow_gpu_pc_set_its) at the same width
+    if (f.rich && f.rich->nWork > 0) {
+        PcRich& R = *f.rich;
+        void* q = nullptr;
+        if (hipMalloc(&q, per * R.nWork * nv) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("%s: cannot allocate %zu bytes of work space for the iterations of %d vectors at once; the factor stands and "
+                        "applies one vector at a time", who, per * R.nWork * nv, nv);
+        }
+        (void)hipFree(R.work);
+        *std::find(f.raw.begin(), f.raw.end(), (void*)R.work) = q;
+        f.bytes += per * R.nWork * (nv - R.width);
+        R.work = (double*)q;
+        R.width = nv;
+    }
     return 0;
 }
 

@@ -499,6 +499,22 @@ void launch_mg_restrict(const JmBlk* fine, const JmBlk* coarse, int nslots, int 
                         double* rhs, hipStream_t s);
 void launch_mg_residual(const JmBlk* tab, const JmBlk* coarse, int nslots, int maxnx, int maxny, int maxnz, int nState, int transpose,
                         const PcMgSten& S, const double* r, const double* x, double* y, double* res, hipStream_t s);
+// the preconditioner Richardson iterations (kernels_pc_rich.hip; adflow_gpu_pc_set_its): the copy of the 7-point matrix of the whole
+// level a factor owns, as its residual kernel sees it
+struct PcRichTab {
+    long ncell;           // owned cells of the level
+    const double* mat;    // mat[(q nState^2 + e) ncell + c]: component e of the block of direction q (0..5: -i, -j, -k, +i, +j, +k; 6: the
+                          // diagonal) of row c, c = the cell's number in the PETSc layout; zero where the direction has no column
+    const int* col;       // col[q ncell + c]: the number of the column of direction q of row c, -1: none
+    const unsigned* cw;   // per row: bit q = the column of direction q lies behind a block face; bits 6+3q..8+3q = the direction in which
+                          // that column keeps its entry back to this row
+};
+// src: the blocks of the assembly (vecOff = first CELL of the block); S, tsm, turbDiag, N as launch_mg_fine_copy
+void launch_rich_copy(const JmBlk* src, int nslots, int maxnx, int maxny, int maxnz, int nState, const PcMgSten& S, const double* tsm,
+                      double turbDiag, long N, const int* col, double* mat, hipStream_t s);
+// t = b - A x (transpose: A^T) for nv = 1 .. PC_MAXW columns ldb / ldx / ldt apart; sub: without the columns behind block faces
+int launch_rich_residual(const PcRichTab& T, int nState, int transpose, int sub, int nv, const double* b, long ldb, const double* x,
+                         long ldx, double* t, long ldt, hipStream_t s);
 // the vectors of GMRES: one step of modified Gram-Schmidt per launch (partial sums in, partial sums out), see kernels_pc.hip
 enum { GM_PARTS = 256 };  // the most partial sums one reduction leaves (GM_T of kernels_pc.hip): the size of a buffer of them
 int gm_groups(long n);

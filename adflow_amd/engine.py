@@ -242,6 +242,20 @@ class Engine:
         self._chk(self.lib.adflow_gpu_pc_mg_info(None, None, None, cells.ctypes.data))
         return int(lv.value), int(nsm.value), int(fc.value), tuple(int(c) for c in cells)
 
+    def pcSetIts(self, outer: int = 1, inner: int = 1, innerCoarse: int = 1):
+        """the Richardson iterations of setupStandardKSP around the factor for the next pcSetup / ankPcSetup of the selected slot: `outer`
+        (outerPreconIts: on the 7-point matrix of the whole level, columns behind block faces included), `inner` (innerPreconIts: on
+        the matrix the factor was built from; level 1 of a hierarchy), innerCoarse (innerPreconItsCoarse: the levels below); a
+        factor that exists keeps its own"""
+        self._chk(self.lib.adflow_gpu_pc_set_its(int(outer), int(inner), int(innerCoarse)))
+
+    def pcItsInfo(self):
+        """(outer, inner, innerCoarse, bytes of the owned copy of the matrix of the level and its tables: 0 when none is held) of
+        the factor of the selected slot"""
+        o, i, c, nb = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        self._chk(self.lib.adflow_gpu_pc_its_info(ctypes.byref(o), ctypes.byref(i), ctypes.byref(c), ctypes.byref(nb)))
+        return int(o.value), int(i.value), int(c.value), int(nb.value)
+
     def pcMgMatrix(self, mgLevel: int, nn=1, level=1, sps=1):
         """(nx_l, ny_l, nz_l, nState, nState, 7): the blocks of block nn on level mgLevel of the hierarchy, laid out as jacobianBlocks;
         mgLevel = 1 is the owned copy of the in-block blocks (T included)"""

@@ -387,6 +387,17 @@ module adflowGpuShim
             integer(c_int32_t), intent(out) :: levels, nSmooth, fillCoarse
             integer(c_int64_t), intent(out) :: cells(*)
         end function
+        ! the Richardson iterations of setupStandardKSP around the factor (outerPreconIts, innerPreconIts, innerPreconItsCoarse) for the
+        ! next setup of the selected slot; what the factor of the selected slot was built with and the bytes of its copy of the matrix
+        integer(c_int) function adflow_gpu_pc_set_its(outer, inner, innerCoarse) bind(C, name="adflow_gpu_pc_set_its")
+            import :: c_int
+            integer(c_int), value :: outer, inner, innerCoarse
+        end function
+        integer(c_int) function adflow_gpu_pc_its_info(outer, inner, innerCoarse, matrixBytes) bind(C, name="adflow_gpu_pc_its_info")
+            import :: c_int, c_int32_t, c_int64_t
+            integer(c_int32_t), intent(out) :: outer, inner, innerCoarse
+            integer(c_int64_t), intent(out) :: matrixBytes
+        end function
         integer(c_int) function adflow_gpu_pc_mg_download(mgLevel, nn, blocks) bind(C, name="adflow_gpu_pc_mg_download")
             import :: c_int, c_double
             integer(c_int), value :: mgLevel, nn
@@ -1128,6 +1139,15 @@ contains
         integer(kind=intType), intent(in) :: levels, nSmooth, fillCoarse
         call gpuCheck(adflow_gpu_pc_set_mg(int(levels, c_int), int(nSmooth, c_int), int(fillCoarse, c_int)), "gpuPCSetMG")
     end subroutine gpuPCSetMG
+
+    ! globalPreConIts and localPreConIts of setupStandardKSP, and amgLocalPreConIts below level 1 of the mg shell: the next gpuPCSetup /
+    ! gpuANKPCSetup of the selected slot wraps its factor in `outer` Richardson iterations on the matrix of the whole level and `inner`
+    ! (innerCoarse on the coarse levels of a hierarchy) on the matrix the factor was built from.  outerPreconIts / innerPreconIts /
+    ! innerPreconItsCoarse of the adjoint, ANKOuterPreconIts / ANKInnerPreconIts, NKOuterPreconIts / NKInnerPreconIts; 1, 1, 1 is none
+    subroutine gpuPCSetIts(outer, inner, innerCoarse)
+        integer(kind=intType), intent(in) :: outer, inner, innerCoarse
+        call gpuCheck(adflow_gpu_pc_set_its(int(outer, c_int), int(inner, c_int), int(innerCoarse, c_int)), "gpuPCSetIts")
+    end subroutine gpuPCSetIts
 
     ! the body of a PCSHELL's apply (transposed = .false.) / applyTranspose (.true.): rDev, zDev are the device arrays of the two
     ! PETSc vectors (VECHIP), n their local size

@@ -595,7 +595,8 @@ int adflow_gpu_pc_select(int slot);
  *               res = r - A_k y;  y += S_k(res).  The preconditioner is z = MG(r, 1): the coarse level first, smoothing afterwards.
  *   transpose   the same cycle on A^T, with A_l^T and M_l^-T everywhere (the reference assembles the transposed matrices into the same
  *               hierarchy); it is NOT the transpose of the cycle.
- * outerPreConIts and innerPreConIts[Coarse] are 1.  Out of scope: couplings across blocks and ranks, ASM overlap, the RCM ordering.
+ * outerPreConIts and innerPreConIts[Coarse]: adflow_gpu_pc_set_its below.  Out of scope: couplings across blocks inside the hierarchy
+ * (the outer iterations see them), ranks, ASM overlap, the RCM ordering.
  * adflow_gpu_pc_set_mg(levels, nSmooth, fillCoarse) sets what the next adflow_gpu_pc_setup / _ank_pc_setup of the SELECTED slot
  * builds; each slot keeps its own setting, like its fill.  levels = 1 (the default) is the plain factor, with nSmooth and fillCoarse
  * ignored.  Errors: levels outside 1 .. 10, nSmooth < 1, fillCoarse outside 0 .. 2.  With levels > 1 the setup builds the hierarchy
@@ -616,6 +617,44 @@ int adflow_gpu_pc_select(int slot);
 int adflow_gpu_pc_set_mg(int levels, int nSmooth, int fillCoarse);
 int adflow_gpu_pc_mg_info(int32_t* levels, int32_t* nSmooth, int32_t* fillCoarse, int64_t* cells);
 int adflow_gpu_pc_mg_download(int mgLevel, int nn, double* blocks);
+/* Preconditioner Richardson iterations: the two loops setupStandardKSP (adjointUtils.F90:1374-1562) wraps around the ILU, and the mg
+ * shell with them (amg.F90:487-510, :534-615).  With M the factor of the selected slot and
+ *   S(b; M, A, n):  x = M^-1 b, then n - 1 times x += M^-1 (b - A x)      (PETSc's Richardson from a zero guess, scale 1, no norm:
+ *                                                                          n applications, n - 1 products)
+ *   A_full  the 7-point matrix of the whole level as it stood at the setup (adflow_gpu_ank_pc_setup: T on the diagonal blocks): an owned
+ *           cell is its own column, a first-layer face halo the owned cell it has as donor in the registered 2-layer pattern, a halo
+ *           without such a donor is no column -- the matrix adflow_gpu_jacobian_mult applies for that assembly on one rank
+ *   A_sub   the matrix the factor was built from: A_full without the columns behind block faces for a block-local factor (fill 0, 1, 2
+ *           with coupled = 0), A_full for coupled = 1 and for adflow_gpu_pc_set_level_fill >= 0
+ * a plain factor applies   local(b) = S(b; M, A_sub, inner);   P(b): y = local(b), then outer - 1 times y += local(b - A_full y)
+ * (localPreConIts on the subksp of every subdomain, globalPreConIts on master_PC_KSP).  A hierarchy (levels > 1) replaces the one ILU
+ * application of every smoothing iteration on level l by L_l(r) = S(r; M_l, A_l, inner_l), inner_1 = inner and inner_l = innerCoarse
+ * below level 1 (amgLocalPreConIts), leaves the cycle as it is and applies P(b): y = MG(b), then outer - 1 times y += MG(b - A_full y)
+ * -- the reference's fineMat is the whole matrix, so the outer product includes the columns behind block faces although the hierarchy
+ * is block-local.  transpose: the same recurrences with A^T and M^-T throughout; for a plain factor that is exactly P^T, for a
+ * hierarchy it is not, as before.  outer = inner = innerCoarse = 1 (the default) is every path as it was, bit for bit, holding the
+ * bytes it held.
+ * adflow_gpu_pc_set_its(outer, inner, innerCoarse) sets what the next adflow_gpu_pc_setup / _ank_pc_setup of the SELECTED slot builds;
+ * each slot keeps its own setting across setups and releases, and a factor that exists keeps what it was built with.  A value below 1
+ * is an error that names it and changes nothing.  innerCoarse is ignored with levels = 1.
+ * With outer > 1, or inner > 1 on a plain factor, the setup copies the assembled 7-point blocks (T included) into storage the slot
+ * owns -- the adjoint assembles the preconditioner matrix, factors it and overwrites it with the exact matrix -- with the column
+ * table of the level and, for the transposed product, the mirror entries, and allocates the work vectors of the recurrences; nothing
+ * is allocated at application time.  A hierarchy owns its A_l already: inner iterations on it need two vectors per level, no matrix.
+ * Errors of the setup, decided before anything is allocated, with no factor kept and the other slot untouched: the same column
+ * behind two faces of a cell, a cell that is its own column, a column that does not lead back; a rotational periodicity when the
+ * matrix covers the velocities; an allocation that fails names its size.  adflow_gpu_pc_info counts the new bytes,
+ * adflow_gpu_pc_release, _block_release and _release_all free them, adflow_gpu_release_workspace does not touch them; a setup that
+ * keeps the tables of an ILU over the level (reused = 1) redoes the copy.  Every entry that takes a factor takes the iterations:
+ * adflow_gpu_pc_apply[_dev], _gmres_solve[_dev], _ank_solve[_dev], _jacfree_solve[_dev], both slots, enqueue-only under
+ * adflow_gpu_set_async(1); the _multi entries in groups of up to four columns where the sweeps of the factor take them, column by
+ * column where they do not.
+ * adflow_gpu_pc_its_info: the counts of the selected slot's factor and matrixBytes, what the owned copy of A_full and its tables
+ * hold (0 when none is held); each pointer may be NULL; an error without a factor.
+ * Out of scope: the RCM ordering, ASM overlap, more than one rank in the solver, KSP types other than GMRES and left
+ * preconditioning, inner iterations whose subdomains differ from the factor's own. */
+int adflow_gpu_pc_set_its(int outer, int inner, int innerCoarse);
+int adflow_gpu_pc_its_info(int32_t* outer, int32_t* inner, int32_t* innerCoarse, int64_t* matrixBytes);
 /* Restarted GMRES with the factor as RIGHT preconditioner, the KSPSolve of solveAdjoint (adjointAPI.F90:661-863) with the settings
  * of setupStandardKSP (adjointUtils.F90:1374-1562: KSPGMRES, PC_RIGHT, modified Gram-Schmidt):  A M^-1 u = b, x = M^-1 u, with
  * A = adflow_gpu_jacobian_mult on the matrix assembled last (7-, 13-, 27- or 33-point) and M = the factor of adflow_gpu_pc_setup,

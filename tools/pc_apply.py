@@ -18,8 +18,13 @@ level sets, microseconds per launch and GB/s on the factor bytes, and GMRES.
 --level-fill F (0 .. 3, also with --brick) runs the same lines three times in the same process: the block-local factor of fill F
 (F <= 2), the coupled fill-0 factor, and the ILU(F) over the whole level (adflow_gpu_pc_set_level_fill: longest row, entries of the
 pattern, level sets, whether the timed setup kept the tables; GB/s on the bytes of the pattern's blocks).
+--outer-its N --inner-its N [--inner-its-coarse N] (adflow_gpu_pc_set_its: the Richardson iterations of setupStandardKSP around the
+factor; each takes one count or a comma-separated list, and every combination runs on the same assembly in the same process) prints
+the same lines, with the launches of one application counted from the recurrences, plus -- when outer > 1 -- the ms of one residual
+pass t = b - A x over the owned copy of the 7-point matrix (with the update y += z that follows it), taken as the difference to the
+same factor at outer = 1 set up in the same run, beside the y = J x line of the same matrix.
 usage: pc_apply.py [--fill 0|1|2] [--mg L [--nsmooth N] [--fill-coarse F]] [--rtol 1e-8] [--nvec N] [--brick Bi Bj Bk] [--coupled]
-       [--level-fill F]
+       [--level-fill F] [--outer-its N[,N..]] [--inner-its N[,N..]] [--inner-its-coarse N]
        [n] [nx ny nz]      (n timed applications of each kind, default 10)"""
 import json
 import os
@@ -33,12 +38,14 @@ from adflow_amd.synth import make_block, make_bocos  # noqa: E402
 from adflow_amd.topology import BrickTopology, CommPattern, apply_local_copies_fast  # noqa: E402
 
 WALL = {1: -6, 2: -6, 3: -1, 4: -1, 5: -3, 6: -6}
+ITS = [1, 1, 1]           # the iterations the slot is set to (--outer-its, --inner-its, --inner-its-coarse)
 
 
 def main():
     import torch
     argv, fill, rtol, nvec = list(sys.argv[1:]), 0, 1e-8, 0
     mg, nsmooth, fillc, level_fill = 1, 1, 0, None
+    outers, inners, inner_coarse = [1], [1], 1
     brick, both = None, "--coupled" in argv
     if both:
         argv.remove("--coupled")
@@ -46,7 +53,8 @@ def main():
         at = argv.index("--brick")
         brick = tuple(int(a) for a in argv[at + 1:at + 4])
         del argv[at:at + 4]
-    for opt in ("--fill", "--rtol", "--nvec", "--mg", "--nsmooth", "--fill-coarse", "--level-fill"):
+    for opt in ("--fill", "--rtol", "--nvec", "--mg", "--nsmooth", "--fill-coarse", "--level-fill", "--outer-its", "--inner-its",
+                "--inner-its-coarse"):
         if opt in argv:
             at = argv.index(opt)
             if opt == "--fill":
@@ -61,6 +69,12 @@ def main():
                 fillc = int(argv[at + 1])
             elif opt == "--level-fill":
                 level_fill = int(argv[at + 1])
+            elif opt == "--outer-its":
+                outers = [int(a) for a in argv[at + 1].split(",")]
+            elif opt == "--inner-its":
+                inners = [int(a) for a in argv[at + 1].split(",")]
+            elif opt == "--inner-its-coarse":
+                inner_coarse = int(argv[at + 1])
             else:
                 rtol = float(argv[at + 1])
             del argv[at:at + 2]
@@ -85,32 +99,36 @@ def main():
     eng.releaseWorkspace()
     ns, st = eng.jacobianInfo()
     n = ns * cells
-    if level_fill is not None:
-        if fill or mg > 1 or both:
-            sys.exit("--level-fill: runs the block-local factor of that fill and the coupled fill-0 factor itself; no --fill, --mg, --coupled")
-        if level_fill <= 2:
-            eng.pcSetFill(level_fill)
-            one_factor(eng, torch, dims, brick, ns, cells, n, n_it, level_fill, 1, rtol, 0, 0)
-            eng.pcSetFill(0)
-        eng.pcSetCoupled(1)
-        one_factor(eng, torch, dims, brick, ns, cells, n, n_it, 0, 1, rtol, 0, 1)
-        eng.pcSetCoupled(0)
-        eng.pcSetLevelFill(level_fill)
-        one_factor(eng, torch, dims, brick, ns, cells, n, n_it, level_fill, 1, rtol, 0, None, level_fill)
-        eng.pcSetLevelFill(-1)
-    elif both:
-        if fill or mg > 1:
-            sys.exit("--coupled: the factor over the level takes fill 0 and no hierarchy")
-        for coupled in (0, 1):
-            eng.pcSetCoupled(coupled)
-            one_factor(eng, torch, dims, brick, ns, cells, n, n_it, 0, 1, rtol, 0, coupled)
-        eng.pcSetCoupled(0)
-    else:
-        if fill:                                          # (a library without the entry point still serves fill 0)
-            eng.pcSetFill(fill)
-        if mg > 1:
-            eng.pcSetMg(mg, nsmooth, fillc)
-        one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec, None)
+    for its in [(o, i, inner_coarse) for o in outers for i in inners]:
+        if its != (1, 1, 1) or len(outers) * len(inners) > 1:      # (a library without the entry point still serves the defaults)
+            eng.pcSetIts(*its)
+        ITS[:] = its
+        if level_fill is not None:
+            if fill or mg > 1 or both:
+                sys.exit("--level-fill: runs the block-local factor of that fill and the coupled fill-0 factor itself; no --fill, --mg, --coupled")
+            if level_fill <= 2:
+                eng.pcSetFill(level_fill)
+                one_factor(eng, torch, dims, brick, ns, cells, n, n_it, level_fill, 1, rtol, 0, 0)
+                eng.pcSetFill(0)
+            eng.pcSetCoupled(1)
+            one_factor(eng, torch, dims, brick, ns, cells, n, n_it, 0, 1, rtol, 0, 1)
+            eng.pcSetCoupled(0)
+            eng.pcSetLevelFill(level_fill)
+            one_factor(eng, torch, dims, brick, ns, cells, n, n_it, level_fill, 1, rtol, 0, None, level_fill)
+            eng.pcSetLevelFill(-1)
+        elif both:
+            if fill or mg > 1:
+                sys.exit("--coupled: the factor over the level takes fill 0 and no hierarchy")
+            for coupled in (0, 1):
+                eng.pcSetCoupled(coupled)
+                one_factor(eng, torch, dims, brick, ns, cells, n, n_it, 0, 1, rtol, 0, coupled)
+            eng.pcSetCoupled(0)
+        else:
+            if fill:                                          # (a library without the entry point still serves fill 0)
+                eng.pcSetFill(fill)
+            if mg > 1:
+                eng.pcSetMg(mg, nsmooth, fillc)
+            one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec, None)
     eng.releaseWorkspace()
     eng.close()
 
@@ -147,6 +165,16 @@ def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec
         tag["level_fill"] = level_fill
     if brick:
         tag["brick"] = list(brick)
+    outer, inner, inner_coarse = ITS
+    if ITS != [1, 1, 1]:
+        tag["its"] = list(ITS)
+    base = None
+    if outer > 1:
+        # the same factor without the outer loop, in the same run: what the residual pass is the difference to
+        eng.pcSetIts(1, inner, inner_coarse)
+        eng.pcSetup(1)
+        base = {tr: time_apply(eng, torch, n, n_it, tr) for tr in (False, True)}
+        eng.pcSetIts(outer, inner, inner_coarse)
     floor = {0: 7, 1: 13, 2: 23}.get(fill, 7) * ns * ns * 8 * cells
     eng.pcSetup(1)                                        # warm-up (allocations, tables)
     eng.sync()
@@ -172,8 +200,8 @@ def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec
     eng.set_async(True)
     try:
         for what, fn, launches in (("J x", lambda: eng.jacobianMultDev(x.data_ptr(), y.data_ptr(), n, 1, False), 2),
-                                   ("M^-1 r", lambda: eng.pcApplyDev(x.data_ptr(), y.data_ptr(), n, 1, False), 2 * planes),
-                                   ("M^-T r", lambda: eng.pcApplyDev(x.data_ptr(), y.data_ptr(), n, 1, True), 2 * planes)):
+                                   ("M^-1 r", lambda: eng.pcApplyDev(x.data_ptr(), y.data_ptr(), n, 1, False), its_launches(2 * planes, mg)),
+                                   ("M^-T r", lambda: eng.pcApplyDev(x.data_ptr(), y.data_ptr(), n, 1, True), its_launches(2 * planes, mg))):
             for _ in range(3):
                 fn()
             eng.event_record(1)
@@ -192,6 +220,14 @@ def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec
                               "checksum": float(y.abs().sum().item()), **more}), flush=True)
     finally:
         eng.set_async(False)
+    if base:
+        pass7 = 7 * ns * ns * 8 * cells
+        for tr, what in ((False, "M^-1 r"), (True, "M^-T r")):
+            ms = (ms_of[what] - outer * base[tr]) / (outer - 1)
+            print(json.dumps({"what": "residual pass t = b - A^T x" if tr else "residual pass t = b - A x", "how": "with y += z; (ms at outer - "
+                              "outer x ms at outer 1) / (outer - 1), same factor, same run", "ms": round(ms, 4), "ms_at_outer_1": round(base[tr], 4),
+                              "floor_bytes": pass7, "TB_per_s": round(pass7 / (ms * 1e-3) / 1e12, 3) if ms > 0 else None,
+                              "ratio_to_J_x": round(ms / ms_of["J x"], 2), **tag}), flush=True)
     b = torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 0.5
     for tr in (False, True):
         for timed in (False, True):
@@ -205,6 +241,34 @@ def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec
     if nvec > 1:
         multi_columns(eng, torch, gen, n, nvec, n_it, fill, planes, floor, rtol)
     eng.pcRelease()
+
+
+def time_apply(eng, torch, n, n_it, transpose):
+    """ms of one application of the factor that stands, enqueue-only, as one_factor times it"""
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.rand(n, dtype=torch.float64, device="cuda", generator=gen) - 0.5
+    y = torch.empty_like(x)
+    torch.cuda.synchronize()
+    eng.set_async(True)
+    try:
+        for _ in range(3):
+            eng.pcApplyDev(x.data_ptr(), y.data_ptr(), n, 1, transpose)
+        eng.event_record(1)
+        for _ in range(n_it):
+            eng.pcApplyDev(x.data_ptr(), y.data_ptr(), n, 1, transpose)
+        eng.event_record(2)
+        eng.sync()
+    finally:
+        eng.set_async(False)
+    return eng.event_elapsed_ms(1, 2) / n_it
+
+
+def its_launches(one, mg):
+    """launches of one application from those of one sweep pair or cycle: inner x (sweeps) + (inner - 1) x (residual, update) on a plain
+    factor, that outer times, and (outer - 1) x (residual, update); the inner iterations of a hierarchy are not counted here"""
+    outer, inner, _ = ITS
+    local = one if mg > 1 else inner * one + 2 * (inner - 1)
+    return outer * local + 2 * (outer - 1)
 
 
 def cycle_cost(eng, dims, ns, fill, planes1):
