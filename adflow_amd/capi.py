@@ -160,6 +160,7 @@ EXPORTS = [
     "adflow_gpu_pc_setup", "adflow_gpu_pc_info", "adflow_gpu_pc_apply", "adflow_gpu_pc_apply_dev", "adflow_gpu_pc_release", "adflow_gpu_pc_select",
     "adflow_gpu_pc_set_fill", "adflow_gpu_pc_info2", "adflow_gpu_pc_set_coupled", "adflow_gpu_pc_coupled_info", "adflow_gpu_pc_set_level_fill", "adflow_gpu_pc_level_info", "adflow_gpu_pc_set_mg", "adflow_gpu_pc_mg_info", "adflow_gpu_pc_mg_download",
     "adflow_gpu_pc_set_its", "adflow_gpu_pc_its_info",
+    "adflow_gpu_pc_set_ordering", "adflow_gpu_pc_set_ordering_perm", "adflow_gpu_pc_ordering_info", "adflow_gpu_pc_download_ordering",
     "adflow_gpu_gmres_solve", "adflow_gpu_gmres_solve_dev",
     "adflow_gpu_jacfree_mult", "adflow_gpu_jacfree_mult_dev", "adflow_gpu_jacfree_solve", "adflow_gpu_jacfree_solve_dev",
     "adflow_gpu_jacobian_mult_multi", "adflow_gpu_jacobian_mult_multi_dev", "adflow_gpu_pc_apply_multi", "adflow_gpu_pc_apply_multi_dev",
@@ -275,6 +276,10 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     lib.adflow_gpu_pc_mg_download.argtypes = [c_int, c_int, c_void_p]
     lib.adflow_gpu_pc_set_its.argtypes = [c_int, c_int, c_int]
     lib.adflow_gpu_pc_its_info.argtypes = [POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), POINTER(ctypes.c_int64)]
+    lib.adflow_gpu_pc_set_ordering.argtypes = [c_int]
+    lib.adflow_gpu_pc_set_ordering_perm.argtypes = [c_void_p, ctypes.c_long]
+    lib.adflow_gpu_pc_ordering_info.argtypes = [POINTER(ctypes.c_int32), POINTER(ctypes.c_int64), POINTER(ctypes.c_int32), POINTER(ctypes.c_int64)]
+    lib.adflow_gpu_pc_download_ordering.argtypes = [c_void_p, ctypes.c_long]
     lib.adflow_gpu_ank_select_base.argtypes = [c_uint]
     lib.adflow_gpu_set_tuning.argtypes = [c_char_p, c_int]
     lib.adflow_gpu_abi_sizes.argtypes = [POINTER(c_int), POINTER(c_int)]

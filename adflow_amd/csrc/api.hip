@@ -16,6 +16,7 @@
 
 #include "internal.h"
 #include "flow_plan.h"
+#include "pc_order.h"
 
 extern int g_march_kch, g_viscous_tiled, g_inviscid_march, g_roe_march, g_sa_march;
 int g_test_fault = 0;        // tuning "test_fault" (tests only): bit 0 = the hipGraph capture of a multigrid cycle reports failure, bit 1 = the
@@ -4221,6 +4222,10 @@ struct PcLevel {
     int maxRow = 0, reused = 0;       // the longest row; 1: the last setup kept the tables and redid the numbers only
     long nEntries = 0;                // blocks of the pattern over all rows, diagonal included
     std::vector<int> vec, cblk;       // host copies for the message of a failing pivot
+    int order = 0;                    // adflow_gpu_pc_set_ordering the tables were built with
+    long permGen = 0;                 // order 2: g_pc_order_gen of the slot when the tables were built
+    long bandwidth = 0;               // max |ordered(column) - ordered(row)| over the assembled entries
+    std::vector<int> perm;            // order != 0: perm[new] = old the tables were built with
     JmBlk* dblk = nullptr;            // the block table on the device (the assembly may have moved: written at every setup)
 };
 // The multigrid hierarchy of a slot (kernels_pc_mg.hip).  Level 1 is lv[0]: its matrix is the slot's own copy of the in-block 7-point
@@ -4249,6 +4254,9 @@ int g_pc_slot = 0;
 int g_pc_fill[2] = {0, 0};           // adflow_gpu_pc_set_fill: the fill the next setup of each slot uses (outlives the factors)
 int g_pc_coupled[2] = {0, 0};        // adflow_gpu_pc_set_coupled: 1 = the next setup of the slot factors the whole level as one subdomain
 int g_pc_level_fill[2] = {-1, -1};   // adflow_gpu_pc_set_level_fill: >= 0 = the next setup of the slot builds the ILU(fill) of the whole level
+int g_pc_order[2] = {0, 0};          // adflow_gpu_pc_set_ordering: 0 natural, 1 RCM, 2 the permutation below (outlives the factors)
+std::vector<int> g_pc_order_perm[2]; // adflow_gpu_pc_set_ordering_perm: perm[new] = old, empty = none stored
+long g_pc_order_gen[2] = {0, 0};     // counts the calls of adflow_gpu_pc_set_ordering_perm: tables built before the last one are not kept
 PcIts g_pc_its[2];                   // adflow_gpu_pc_set_its: the iterations the next setup of each slot builds (outlives the factors)
 static PcFactor& pc_sel() { return g_pc_slots[g_pc_slot]; }
 struct DevBuf {                       // a device allocation that lives as long as one call
@@ -4824,12 +4832,48 @@ static int pc_setup_build(PcFactor& f, int fill, int coupled, int level, const d
 // The tables of the factor f of `level` at `fill` for the N cells of the blocks hb: the symbolic ILU(fill) of the cell graph of the level
 // (columns: pc_coupled_columns), the level sets, the order and the slices of the storage; everything that does not depend on the
 // numbers.  The host decides every refusal before the first allocation.
-static int pc_level_tables(PcFactor& f, int level, int fill, const std::vector<JmBlk>& hb, const std::vector<int>& nnOf, long N)
+// Ordering (adflow_gpu_pc_set_ordering): everything below the columns runs in the ORDERED numbering a = inv[natural number] -- the
+// symbolic factorisation, the ascending columns of a row, the level sets, the order (set, ordered number) of the storage; only vec,
+// cblk and cbox lead back to the cell.  order 0: perm and inv stay empty and every number is the natural one, as before.
+static int pc_level_tables(PcFactor& f, int level, int fill, const std::vector<JmBlk>& hb, const std::vector<int>& nnOf, long N, int order,
+                           const std::vector<int>& callerPerm)
 {
     const int nS = g_jac.nState;
     std::vector<int> col;
     long nCross = 0;
     if (pc_coupled_columns(level, hb, nnOf, N, col, nCross, true)) return 1;
+    std::vector<int> perm, inv;
+    if (order == 1) {
+        // the symmetric cell graph of the 7-point pattern, interface columns included, without the diagonal, neighbours ascending
+        std::vector<std::vector<int>> nb((size_t)N);
+        for (long i = 0; i < N; ++i)
+            for (int d = 0; d < 6; ++d) {
+                const int c = col[(size_t)d * N + i];
+                if (c >= 0 && c != i) {
+                    nb[(size_t)i].push_back(c);
+                    nb[(size_t)c].push_back((int)i);
+                }
+            }
+        std::vector<size_t> xadj((size_t)N + 1, 0);
+        std::vector<int> adj;
+        for (long i = 0; i < N; ++i) {
+            std::vector<int>& r = nb[(size_t)i];
+            std::sort(r.begin(), r.end());
+            r.erase(std::unique(r.begin(), r.end()), r.end());
+            adj.insert(adj.end(), r.begin(), r.end());
+            xadj[(size_t)i + 1] = adj.size();
+        }
+        pc_order_rcm(N, xadj, adj, perm);
+    } else if (order == 2) {
+        perm = callerPerm;
+    }
+    if (order) {
+        inv.resize((size_t)N);
+        for (long a = 0; a < N; ++a) inv[(size_t)perm[(size_t)a]] = (int)a;
+    }
+    auto natOf = [&](long a) { return order ? perm[(size_t)a] : (int)a; };
+    auto ordOf = [&](int c) { return order ? inv[(size_t)c] : c; };
+    long bandwidth = 0;
     // symbolic ILU(fill): level(i, j) = min over the pivots k < min(i, j) of level(i, k) + level(k, j) + 1, kept while <= fill.  One level per
     // entry suffices, the blocks are dense.  Rows in CSR, every row in ascending column order; dg[i]: where the diagonal stands in row i
     std::vector<size_t> rp(N + 1, 0);
@@ -4841,8 +4885,13 @@ static int pc_level_tables(PcFactor& f, int level, int fill, const std::vector<J
     std::vector<unsigned char> wl;
     for (long i = 0; i < N; ++i) {
         int a[7], na = 0;
+        const long nati = natOf(i);
         for (int d = 0; d < 6; ++d)
-            if (col[(size_t)d * N + i] >= 0) a[na++] = col[(size_t)d * N + i];
+            if (col[(size_t)d * N + nati] >= 0) {
+                a[na] = ordOf(col[(size_t)d * N + nati]);
+                bandwidth = std::max(bandwidth, a[na] > i ? a[na] - i : i - a[na]);
+                ++na;
+            }
         a[na++] = (int)i;
         std::sort(a, a + na);
         wc.assign(a, a + na);
@@ -4884,15 +4933,19 @@ static int pc_level_tables(PcFactor& f, int level, int fill, const std::vector<J
     std::vector<int> start(nSets + 1, 0);
     for (long c = 0; c < N; ++c) start[lvl[c] + 1]++;
     for (int p = 0; p < nSets; ++p) start[p + 1] += start[p];
-    std::vector<int> cur(start.begin(), start.end() - 1), pos(N), vec(N), cblk(N), cbox(N);
+    // pos: ordered number -> position; ord, vec, cblk, cbox: position -> ordered number, natural number, block slot, box index
+    std::vector<int> cur(start.begin(), start.end() - 1), pos(N), ord(N), vec(N), cblk(N), cbox(N);
+    for (long a = 0; a < N; ++a) {
+        pos[a] = cur[lvl[a]]++;
+        ord[pos[a]] = (int)a;
+    }
     for (size_t s = 0; s < hb.size(); ++s) {
         const JmBlk& q = hb[s];
         long nat = q.vecOff;
         for (int k = 0; k < q.nz; ++k)
             for (int j = 0; j < q.ny; ++j)
                 for (int i = 0; i < q.nx; ++i, ++nat) {
-                    const int at = cur[lvl[nat]]++;
-                    pos[nat] = at;
+                    const int at = pos[ordOf((int)nat)];
                     vec[at] = (int)nat;
                     cblk[at] = (int)s;
                     cbox[at] = (i + 2) + (j + 2) * q.ldi + (k + 2) * q.ldk;
@@ -4906,34 +4959,34 @@ static int pc_level_tables(PcFactor& f, int level, int fill, const std::vector<J
         for (int s0 = start[p]; s0 < start[p + 1]; s0 += 64) {
             const int st = std::min(64, start[p + 1] - s0);
             int w = 0;
-            for (int t = 0; t < st; ++t) w = std::max(w, (int)(rp[vec[s0 + t] + 1] - rp[vec[s0 + t]]));
+            for (int t = 0; t < st; ++t) w = std::max(w, (int)(rp[ord[s0 + t] + 1] - rp[ord[s0 + t]]));
             for (int t = 0; t < st; ++t) {
-                const int nat = vec[s0 + t];
+                const int a = ord[s0 + t];
                 ebase[s0 + t] = E;
                 rinfo[s0 + t] = t | (st << 8);
-                rcnt[s0 + t] = dg[nat] | ((int)(rp[nat + 1] - rp[nat]) << 16);
+                rcnt[s0 + t] = dg[a] | ((int)(rp[a + 1] - rp[a]) << 16);
             }
             E += (long)w * st;
         }
     std::vector<int> epos((size_t)E, 0), enat((size_t)E, 0), einfo((size_t)E, 0);
     for (long at = 0; at < N; ++at) {
-        const int nat = vec[at], st = rinfo[at] >> 8, t = rinfo[at] & 0xff;
-        for (size_t e = rp[nat]; e < rp[nat + 1]; ++e) {
-            const int c = cj[e];
-            const size_t slot = (size_t)ebase[at] + (e - rp[nat]) * st + t;
+        const int a = ord[at], nat = vec[at], st = rinfo[at] >> 8, t = rinfo[at] & 0xff;
+        for (size_t e = rp[a]; e < rp[a + 1]; ++e) {
+            const int c = cj[e];                                       // the ordered number of the column
+            const size_t slot = (size_t)ebase[at] + (e - rp[a]) * st + t;
             epos[slot] = pos[c];
             enat[slot] = c;
             int from = 0;                                              // 1 + direction of the assembled entry, 0: a fill entry
-            if (c == nat) from = 7;
+            if (c == a) from = 7;
             else if (lv[e] == 0)
                 for (int d = 0; d < 6; ++d)
-                    if (col[(size_t)d * N + nat] == c) from = d + 1;
+                    if (col[(size_t)d * N + nat] == natOf(c)) from = d + 1;
             const int* rb = cj.data() + rp[c];
             const int* re = cj.data() + rp[c + 1];
-            const int* mi = std::lower_bound(rb, re, nat);
-            if (mi == re || *mi != nat)
+            const int* mi = std::lower_bound(rb, re, a);
+            if (mi == re || *mi != a)
                 return fail("pc_setup: the pattern of the ILU(%d) over level %d has the entry (%d, %d) but not its mirror entry: a column that "
-                            "does not lead back; no factor is kept", fill, level, nat, c);
+                            "does not lead back; no factor is kept", fill, level, nat, natOf(c));
             einfo[slot] = (int)(mi - rb) | (from << 16);
         }
     }
@@ -4976,6 +5029,10 @@ static int pc_level_tables(PcFactor& f, int level, int fill, const std::vector<J
     L->nEntries = (long)cj.size();
     L->vec = vec;
     L->cblk = cblk;
+    L->order = order;
+    L->permGen = g_pc_order_gen[g_pc_slot];
+    L->bandwidth = bandwidth;
+    L->perm.swap(perm);
     f.level = level; f.nState = nS; f.nPlanes = nSets; f.ncell = N;
     f.fill = fill; f.nEnt = maxRow;
     f.coupled = 1;
@@ -5002,9 +5059,10 @@ static int pc_level_numeric(PcFactor& f, const int* sten, const std::vector<JmBl
     if (flag) {
         const int at = flag - 1, s = L.cblk[at];
         const long loc = L.vec[at] - hb[s].vecOff;
-        return fail("pc_setup: the pivot block of cell (%d,%d,%d) of block %d is singular or not finite (ILU(%d) over the level in natural "
+        return fail("pc_setup: the pivot block of cell (%d,%d,%d) of block %d is singular or not finite (ILU(%d) over the level in %s "
                     "order, level %d); no factor is kept", (int)(loc % hb[s].nx) + 2, (int)(loc / hb[s].nx % hb[s].ny) + 2,
-                    (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2, nnOf[s], f.fill, f.level);
+                    (int)(loc / ((long)hb[s].nx * hb[s].ny)) + 2, nnOf[s], f.fill,
+                    L.order == 0 ? "natural" : L.order == 1 ? "RCM" : "the caller's", f.level);
     }
     f.valid = true;
     return 0;
@@ -5018,11 +5076,20 @@ static int pc_level_setup(PcFactor& f, int fill, int level, const double* shift,
     std::vector<JmBlk> hb;
     std::vector<int> nnOf;
     long N = 0;
-    const bool keep = f.valid && f.lvl && f.level == level && f.fill == fill && f.nState == g_jac.nState && f.lvl->gen == g_pc_topo_gen;
+    const int order = g_pc_order[g_pc_slot];
+    const std::vector<int>& perm = g_pc_order_perm[g_pc_slot];
+    const bool keep = f.valid && f.lvl && f.level == level && f.fill == fill && f.nState == g_jac.nState && f.lvl->gen == g_pc_topo_gen &&
+                      f.lvl->order == order && (order != 2 || f.lvl->permGen == g_pc_order_gen[g_pc_slot]);
     if (!keep) (void)pc_release(f);
     if (pc_level_blocks(level, sten, hb, nnOf, N)) return 1;
     if (keep && N != f.ncell) return fail("pc_setup: internal: the level has %ld cells, the tables of its factor %ld", N, f.ncell);
-    if (!keep && pc_level_tables(f, level, fill, hb, nnOf, N)) return 1;
+    if (!keep && order == 2 && perm.empty())
+        return fail("pc_setup: slot %d is set to the caller's ordering (adflow_gpu_pc_set_ordering(2)) and holds no permutation: call "
+                    "adflow_gpu_pc_set_ordering_perm first; no factor is kept", g_pc_slot);
+    if (!keep && order == 2 && (long)perm.size() != N)
+        return fail("pc_setup: the permutation of slot %d (adflow_gpu_pc_set_ordering_perm) has %zu entries, level %d has %ld owned cells; "
+                    "no factor is kept", g_pc_slot, perm.size(), level, N);
+    if (!keep && pc_level_tables(f, level, fill, hb, nnOf, N, order, perm)) return 1;
     f.valid = false;                              // until the numbers stand
     f.lvl->reused = keep ? 1 : 0;
     return pc_level_numeric(f, sten, hb, nnOf, shift, turbDiag);
@@ -5191,6 +5258,10 @@ static int pc_setup_selected(int level, const double* shift = nullptr, double tu
         return 0;
     }
     (void)pc_release(f);
+    if (g_pc_order[g_pc_slot] != 0)
+        return fail("pc_setup: slot %d is set to ordering %d (adflow_gpu_pc_set_ordering) without the ILU over the level "
+                    "(adflow_gpu_pc_set_level_fill is -1): the patterns of the block-local factors, of coupled = 1 and of a hierarchy are "
+                    "fixed stencils of the natural ordering; no factor is kept", g_pc_slot, g_pc_order[g_pc_slot]);
     if (coupled && g_pc_fill[g_pc_slot] > 0)
         return fail("pc_setup: slot %d is set to one subdomain for the level (adflow_gpu_pc_set_coupled) and to fill %d; across a block "
                     "interface the pattern of fill 1 and 2 is no fixed stencil, the factor over the level takes fill 0; no factor is kept",
@@ -5282,6 +5353,56 @@ int adflow_gpu_pc_level_info(int32_t* fill, int32_t* maxRow, int64_t* nEntries, 
     if (nLevelSets) *nLevelSets = f.nPlanes;
     if (nCrossEntries) *nCrossEntries = f.nCross;
     if (reused) *reused = f.lvl->reused;
+    return 0;
+}
+
+int adflow_gpu_pc_set_ordering(int kind)
+{
+    if (kind < 0 || kind > 2)
+        return fail("pc_set_ordering: %d; 0 = natural, 1 = RCM, 2 = the permutation of adflow_gpu_pc_set_ordering_perm", kind);
+    g_pc_order[g_pc_slot] = kind;
+    return 0;
+}
+
+int adflow_gpu_pc_set_ordering_perm(const int32_t* perm, long n)
+{
+    if (perm) {
+        if (n < 1) return fail("pc_set_ordering_perm: n = %ld; a permutation has at least one entry (index 0); the previous one is kept", n);
+        long bad = 0;
+        const int rc = pc_order_check_perm(perm, n, &bad);
+        if (rc == 1)
+            return fail("pc_set_ordering_perm: perm[%ld] = %d lies outside 0 .. %ld; the previous permutation is kept", bad, (int)perm[bad],
+                        n - 1);
+        if (rc == 2)
+            return fail("pc_set_ordering_perm: perm[%ld] = %d occurs twice; the previous permutation is kept", bad, (int)perm[bad]);
+        g_pc_order_perm[g_pc_slot].assign(perm, perm + n);
+    } else {
+        g_pc_order_perm[g_pc_slot].clear();
+        g_pc_order_perm[g_pc_slot].shrink_to_fit();
+    }
+    g_pc_order_gen[g_pc_slot]++;
+    return 0;
+}
+
+int adflow_gpu_pc_ordering_info(int32_t* kind, int64_t* bandwidth, int32_t* nLevelSets, int64_t* nEntries)
+{
+    const PcFactor& f = pc_sel();
+    if (!f.valid) return fail("pc_ordering_info: no factor (call adflow_gpu_pc_setup first)");
+    if (kind) *kind = f.lvl ? f.lvl->order : 0;
+    if (bandwidth) *bandwidth = f.lvl ? f.lvl->bandwidth : -1;
+    if (nLevelSets) *nLevelSets = f.nPlanes;
+    if (nEntries) *nEntries = f.lvl ? f.lvl->nEntries : (int64_t)f.nEnt * f.ncell;
+    return 0;
+}
+
+int adflow_gpu_pc_download_ordering(int32_t* perm, long n)
+{
+    const PcFactor& f = pc_sel();
+    if (!f.valid) return fail("pc_download_ordering: no factor (call adflow_gpu_pc_setup first)");
+    if (!perm) return fail("pc_download_ordering: perm is NULL");
+    if (n != f.ncell) return fail("pc_download_ordering: n = %ld, the factor has %ld cells", n, f.ncell);
+    const bool ident = !f.lvl || f.lvl->order == 0;
+    for (long a = 0; a < n; ++a) perm[a] = ident ? (int32_t)a : f.lvl->perm[(size_t)a];
     return 0;
 }
 

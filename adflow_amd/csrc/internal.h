@@ -458,10 +458,11 @@ int launch_pcf_factor(const PcTab& T, int nState, int nEnt, const std::vector<in
 int launch_pcf_apply(const PcTab& T, int nState, int nEnt, int transpose, const std::vector<int>& levelStart, const double* r,
                      double* z, hipStream_t s, int nv = 1, long ldr = 0, long ldz = 0);
 // ILU(k) over the whole level on a general block pattern (kernels_pc_level.hip; adflow_gpu_pc_set_level_fill): the factor as its
-// kernels see it.  Position q of the order (set, natural number) is lane q % 64 of slice q / 64 of its set (counted from the first
+// kernels see it.  "Number" below is the cell's number in the ordering of the factor: the natural one, RCM or the caller's
+// (adflow_gpu_pc_set_ordering; api.hip relabels, the kernels do not know).  Position q of the order (set, number) is lane q % 64 of slice q / 64 of its set (counted from the first
 // position of the set): the rows of one workgroup.  A slice of st rows whose longest row has w entries owns the w st entry slots from
 // ebase on; entry j of lane t is slot ebase + j st + t of epos / enat / einfo, and its block is fac[ebase nState^2 + (j nState^2 + e) st + t].
-// The entries of a row ascend in the natural number of their column: nLow lower entries, the pivot block (as its LU factors, kernels_pc_level.hip), the upper ones.
+// The entries of a row ascend in the number of their column: nLow lower entries, the pivot block (as its LU factors, kernels_pc_level.hip), the upper ones.
 struct PclTab {
     long ncell;           // owned cells of the level
     double* fac;
@@ -471,7 +472,8 @@ struct PclTab {
     const int* rinfo;     // per row: lane (bits 0..7) and rows of its slice (bits 8..)
     const int* rcnt;      // per row: nLow (bits 0..15) and entries (bits 16..)
     const int* epos;      // per entry: position of the row of its column
-    const int* enat;      // per entry: natural number of its column, the key of the merge in k_pcl_factor
+    const int* enat;      // per entry: number of its column in the ordering of the factor (adflow_gpu_pc_set_ordering; the natural
+                          // number by default), the key of the merge in k_pcl_factor
     const int* einfo;     // per entry: bits 0..15 the number of the mirror entry (n, c) in row n; bits 16..: 1 + the direction
                           // (0..5, 6: the diagonal) of the assembled entry it starts from, 0: a fill entry (starts from zero)
     const int* vec;       // the cell's number in the PETSc layout (block, k, j, i)

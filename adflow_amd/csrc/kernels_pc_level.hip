@@ -5,6 +5,8 @@
 // Reference semantics: the PCApply of setupStandardKSP (adjointUtils.F90:1374-1562) on one process: one ASM subdomain over every block
 // the process owns, PCFactorSetLevels(fill), natural ordering = block after block in ascending nn, then k, j, i.  The columns are those
 // of kernels_pc_coupled.hip: an owned cell is its own column, a first-layer face halo the owned cell it has as donor.
+// Another ordering (adflow_gpu_pc_set_ordering: RCM, a caller's permutation) is a relabelling in the tables: wherever this file says
+// "natural number" of a row or column, read its number in the ordering of the factor.  PclTab::vec alone leads back to the vectors.
 //
 // Pattern: across an interface the level-of-fill pattern is no stencil (kernels_pc_fill.hip) and elimination does not stay on the
 // diagonal (kernels_pc_coupled.hip).  The host runs the symbolic ILU(k) on the cell graph once; a row holds its entries in ascending

@@ -228,6 +228,33 @@ class Engine:
                                                     ctypes.byref(rs)))
         return int(f.value), int(mr.value), int(ne.value), int(nl.value), int(nx.value), int(rs.value)
 
+    def pcSetOrdering(self, kind: int, perm=None):
+        """the ordering of the ILU over the level (pcSetLevelFill >= 0) for the next pcSetup / ankPcSetup of the selected slot: 0 natural
+        (the default), 1 the library's reverse Cuthill-McKee, 2 the caller's permutation.  perm (perm[new] = old, 0-based cell numbers
+        of the PETSc layout) is handed over first when given and copied; a factor that exists keeps its own"""
+        if perm is not None:
+            p = np.ascontiguousarray(perm, dtype=np.int32)
+            self._chk(self.lib.adflow_gpu_pc_set_ordering_perm(p.ctypes.data, p.size))
+        self._chk(self.lib.adflow_gpu_pc_set_ordering(int(kind)))
+
+    def pcDropOrderingPerm(self):
+        """forget the permutation stored for the selected slot"""
+        self._chk(self.lib.adflow_gpu_pc_set_ordering_perm(None, 0))
+
+    def pcOrderingInfo(self):
+        """(ordering kind, bandwidth of the assembled entries in that ordering, level sets, blocks of the pattern) of the factor of the
+        selected slot; kind 0 and bandwidth -1 for a factor that is no ILU over the level"""
+        k, nl = ctypes.c_int32(0), ctypes.c_int32(0)
+        bw, ne = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self.lib.adflow_gpu_pc_ordering_info(ctypes.byref(k), ctypes.byref(bw), ctypes.byref(nl), ctypes.byref(ne)))
+        return int(k.value), int(bw.value), int(nl.value), int(ne.value)
+
+    def pcOrdering(self):
+        """perm[new] = old the factor of the selected slot was built with (the identity for the natural ordering)"""
+        perm = np.zeros(self.pcMgInfo()[3][0], dtype=np.int32)
+        self._chk(self.lib.adflow_gpu_pc_download_ordering(perm.ctypes.data, perm.size))
+        return perm
+
     def pcSetMg(self, levels: int, nSmooth: int = 1, fillCoarse: int = 0):
         """the multigrid preconditioner of amg.F90 (precondType = 'mg') for the next pcSetup / ankPcSetup of the selected slot: `levels`
         levels of 2 x 2 x 2 aggregates per block (1: the plain factor), nSmooth Richardson iterations of the ILU smoother per level,

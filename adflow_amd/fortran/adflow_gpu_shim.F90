@@ -376,6 +376,17 @@ module adflowGpuShim
             integer(c_int32_t), intent(out) :: fill, maxRow, nLevelSets, reused
             integer(c_int64_t), intent(out) :: nEntries, nCrossEntries
         end function
+        ! the ordering of the ILU over the level for the next setup of the selected slot (matrixOrdering): 0 natural, 1 RCM, 2 the
+        ! permutation handed over (perm(new) = old, 0-based cell numbers of the PETSc layout; the array is copied)
+        integer(c_int) function adflow_gpu_pc_set_ordering(kind) bind(C, name="adflow_gpu_pc_set_ordering")
+            import :: c_int
+            integer(c_int), value :: kind
+        end function
+        integer(c_int) function adflow_gpu_pc_set_ordering_perm(perm, n) bind(C, name="adflow_gpu_pc_set_ordering_perm")
+            import :: c_int, c_int32_t, c_long
+            integer(c_int32_t), intent(in) :: perm(*)
+            integer(c_long), value :: n
+        end function
         ! the multigrid preconditioner of amg.F90 (precondType = 'mg') for the next setup of the selected slot: AMGLevels, AMGNSmooth and
         ! the fill of the coarse levels; what the selected slot holds; the blocks of one block on one level (nx_l, ny_l, nz_l, nState, nState, 7)
         integer(c_int) function adflow_gpu_pc_set_mg(levels, nSmooth, fillCoarse) bind(C, name="adflow_gpu_pc_set_mg")
@@ -1148,6 +1159,27 @@ contains
         integer(kind=intType), intent(in) :: outer, inner, innerCoarse
         call gpuCheck(adflow_gpu_pc_set_its(int(outer, c_int), int(inner, c_int), int(innerCoarse, c_int)), "gpuPCSetIts")
     end subroutine gpuPCSetIts
+
+    ! PCFactorSetMatOrderingType(subpc, localMatrixOrdering) of setupStandardKSP for the ILU over the level (gpuPCSetLevelFill >= 0):
+    ! 0 = natural, 1 = the library's RCM, 2 = the permutation of gpuPCSetOrderingPerm; for the next gpuPCSetup / gpuANKPCSetup of the
+    ! selected slot
+    subroutine gpuPCSetOrdering(kind)
+        integer(kind=intType), intent(in) :: kind
+        call gpuCheck(adflow_gpu_pc_set_ordering(int(kind, c_int)), "gpuPCSetOrdering")
+    end subroutine gpuPCSetOrdering
+
+    ! the permutation of ordering 2: perm(1:n) holds the 0-based cell numbers of the PETSc layout (a row of the state vector divided by
+    ! nState) in their new order -- the indices ISGetIndices returns for the row IS of MatGetOrdering on the local block matrix, so that
+    ! the factor has PETSc's own ordering whatever it is.  The array is copied
+    subroutine gpuPCSetOrderingPerm(perm, n)
+        integer(kind=intType), intent(in) :: n
+        integer(kind=intType), intent(in) :: perm(n)
+        integer(c_int32_t), allocatable :: p(:)
+        allocate (p(n))
+        p = int(perm, c_int32_t)
+        call gpuCheck(adflow_gpu_pc_set_ordering_perm(p, int(n, c_long)), "gpuPCSetOrderingPerm")
+        deallocate (p)
+    end subroutine gpuPCSetOrderingPerm
 
     ! the body of a PCSHELL's apply (transposed = .false.) / applyTranspose (.true.): rDev, zDev are the device arrays of the two
     ! PETSc vectors (VECHIP), n their local size

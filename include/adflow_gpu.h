@@ -519,7 +519,8 @@ int adflow_gpu_jacobian_mult_dev(int level, int transpose, const double* d_x, do
  * takes one of any fill.  adflow_gpu_pc_info reports the number of level sets as nPlanes and the true bytes;
  * adflow_gpu_pc_info2: the fill of the selected factor, its entries per row (7, 13 or 23) and its number of level sets (each may
  * be NULL); an error without a factor.  An allocation that fails leaves no factor, and the message names the size.
- * Out of scope: fill > 2 and the RCM ordering (the reference's default ordering), ASM overlap and couplings across blocks.  (The
+ * Out of scope for these block-local factors: fill > 2 and the RCM ordering (the reference's default ordering; the ILU over the
+ * whole level takes it: adflow_gpu_pc_set_ordering below), ASM overlap and couplings across blocks.  (The
  * pseudo-time diagonal term of ANK: adflow_gpu_ank_pc_setup below, into the same factor slot.) */
 int adflow_gpu_pc_setup(int level);
 int adflow_gpu_pc_info(int32_t* nState, int32_t* nPlanes, int64_t* bytes);
@@ -569,6 +570,44 @@ int adflow_gpu_pc_coupled_info(int32_t* coupled, int32_t* nLevelSets, int64_t* n
  * entries of the assembled matrix whose column lies behind a block face, and reused; each may be NULL; an error without such a factor. */
 int adflow_gpu_pc_set_level_fill(int fill);
 int adflow_gpu_pc_level_info(int32_t* fill, int32_t* maxRow, int64_t* nEntries, int32_t* nLevelSets, int64_t* nCrossEntries, int32_t* reused);
+/* The ordering of the ILU over the whole level: PCFactorSetMatOrderingType(subpc, localMatrixOrdering) of setupStandardKSP
+ * (adjointUtils.F90:1555; the reference's matrixOrdering defaults to "RCM").  adflow_gpu_pc_set_ordering(kind) sets what the next
+ * adflow_gpu_pc_setup / _ank_pc_setup of the SELECTED slot builds; kept per slot across setups and releases, like the fill; a factor
+ * that exists keeps what it was built with; any other value is an error that names it and changes nothing.
+ *   0  natural (the default): block after block in ascending nn, then k, j, i.  Tables, results and bytes are what they were.
+ *   1  reverse Cuthill-McKee, computed by the library on the host: the symmetric cell graph of the 7-point pattern of the level,
+ *      interface columns included, without the diagonal, the neighbours of a cell in ascending natural number; GENRCM of George and
+ *      Liu: the connected components in the order of their lowest-numbered cell; per component a pseudo-peripheral root (the rooted
+ *      level structure from the start cell; while it has more than one level and fewer levels than cells: the first cell of smallest
+ *      degree in the last level becomes the root, and the search ends when its structure has no more levels than the one
+ *      before), Cuthill-McKee from the root (cells visited in the order numbered, the unnumbered neighbours of each appended in
+ *      adjacency order and that run sorted by degree, ascending and stable), reversed.  PETSc's MATORDERINGRCM calls SPARSEPACK's
+ *      routine of that name; identity with the index set PETSc returns is NOT claimed.  A host that wants PETSc's numbers uses kind 2.
+ *   2  the caller's permutation: adflow_gpu_pc_set_ordering_perm(perm, n), perm[new] = old, 0-based, old = the cell number of the PETSc
+ *      layout of the level (a row of adflow_gpu_set_w_vec divided by nState).  The array is copied: it is consumed on return.  Errors,
+ *      which name the first offending index and keep the previous permutation: n < 1, a value outside 0 .. n-1, a value that occurs
+ *      twice.  perm = NULL drops the stored permutation.  Meant for the indices of the IS of PETSc's own MatGetOrdering on the local
+ *      matrix: the factor then has the reference's ordering whatever PETSc's RCM does; nested dissection, minimum degree or a
+ *      colouring pass the same way.
+ * With P the permutation, (P A P^T)[a, b] = A[perm[a], perm[b]]: the setup builds M = ILU(fill) of P A P^T (P (A + T) P^T for
+ * adflow_gpu_ank_pc_setup) and the application is z = P^T M^-1 P r, z = P^T M^-T P r for the transpose; the caller's vectors stay in
+ * the PETSc layout.  The symbolic ILU(k), the ascending columns of a row, the pivot order, the level sets and the storage order run
+ * in the ordered numbering; the columns and the setup refusals of the factor over the level are unchanged.  Everything that takes a
+ * factor takes an ordered one, adflow_gpu_pc_set_its included (its products on A_full stay in the natural layout).
+ * Errors of the setup, each with a message; the slot then holds no factor, the other slot is untouched: kind != 0 while the level
+ * fill of the slot is -1 (the block-local factors, coupled = 1 and the hierarchy have the fixed stencils of the natural ordering);
+ * kind 2 without a stored permutation; kind 2 with n different from the owned cells of the level.
+ * Tables once: reused = 1 also needs the same kind and, for kind 2, no adflow_gpu_pc_set_ordering_perm since the tables were
+ * built.  The RCM ordering is recomputed only when the tables are.
+ * adflow_gpu_pc_ordering_info, of the selected slot's factor: the kind, bandwidth = max |ordered(column) - ordered(row)| over the
+ * assembled 7-point entries (interface columns included), the level sets and the blocks of the pattern; a factor that is no ILU over
+ * the level reports kind 0, bandwidth -1 and its entries per row x cells; each may be NULL; an error without a factor.
+ * adflow_gpu_pc_download_ordering: perm[new] = old the selected factor was built with, n = its cells (the identity for kind 0); an
+ * error without a factor or with another n. */
+int adflow_gpu_pc_set_ordering(int kind);
+int adflow_gpu_pc_set_ordering_perm(const int32_t* perm, long n);
+int adflow_gpu_pc_ordering_info(int32_t* kind, int64_t* bandwidth, int32_t* nLevelSets, int64_t* nEntries);
+int adflow_gpu_pc_download_ordering(int32_t* perm, long n);
 int adflow_gpu_pc_apply(int level, int transpose, const double* r, double* z, long n);
 int adflow_gpu_pc_apply_dev(int level, int transpose, const double* d_r, double* d_z, long n);
 int adflow_gpu_pc_release(int64_t* bytes);
@@ -651,7 +690,7 @@ int adflow_gpu_pc_mg_download(int mgLevel, int nn, double* blocks);
  * column where they do not.
  * adflow_gpu_pc_its_info: the counts of the selected slot's factor and matrixBytes, what the owned copy of A_full and its tables
  * hold (0 when none is held); each pointer may be NULL; an error without a factor.
- * Out of scope: the RCM ordering, ASM overlap, more than one rank in the solver, KSP types other than GMRES and left
+ * Out of scope: ASM overlap, more than one rank in the solver, KSP types other than GMRES and left
  * preconditioning, inner iterations whose subdomains differ from the factor's own. */
 int adflow_gpu_pc_set_its(int outer, int inner, int innerCoarse);
 int adflow_gpu_pc_its_info(int32_t* outer, int32_t* inner, int32_t* innerCoarse, int64_t* matrixBytes);

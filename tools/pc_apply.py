@@ -23,8 +23,13 @@ factor; each takes one count or a comma-separated list, and every combination ru
 the same lines, with the launches of one application counted from the recurrences, plus -- when outer > 1 -- the ms of one residual
 pass t = b - A x over the owned copy of the 7-point matrix (with the update y += z that follows it), taken as the difference to the
 same factor at outer = 1 set up in the same run, beside the y = J x line of the same matrix.
+--ordering natural|rcm|redblack|FILE (with --level-fill; adflow_gpu_pc_set_ordering) runs the ILU over the level alone, in that
+ordering: redblack (cells sorted by the parity of global i + j + k, stably) and FILE (one 0-based cell number of the PETSc layout per
+line, perm[new] = old) go through the caller's permutation.  The setup line then carries the ordering, level sets, entries, bandwidth
+and bytes, and the wall ms of the FIRST setup (ordering, symbolic factorisation, tables, allocation, numbers) beside the timed one,
+which keeps the tables.
 usage: pc_apply.py [--fill 0|1|2] [--mg L [--nsmooth N] [--fill-coarse F]] [--rtol 1e-8] [--nvec N] [--brick Bi Bj Bk] [--coupled]
-       [--level-fill F] [--outer-its N[,N..]] [--inner-its N[,N..]] [--inner-its-coarse N]
+       [--level-fill F [--ordering natural|rcm|redblack|FILE]] [--outer-its N[,N..]] [--inner-its N[,N..]] [--inner-its-coarse N]
        [n] [nx ny nz]      (n timed applications of each kind, default 10)"""
 import json
 import os
@@ -44,7 +49,7 @@ ITS = [1, 1, 1]           # the iterations the slot is set to (--outer-its, --in
 def main():
     import torch
     argv, fill, rtol, nvec = list(sys.argv[1:]), 0, 1e-8, 0
-    mg, nsmooth, fillc, level_fill = 1, 1, 0, None
+    mg, nsmooth, fillc, level_fill, ordering = 1, 1, 0, None, None
     outers, inners, inner_coarse = [1], [1], 1
     brick, both = None, "--coupled" in argv
     if both:
@@ -54,7 +59,7 @@ def main():
         brick = tuple(int(a) for a in argv[at + 1:at + 4])
         del argv[at:at + 4]
     for opt in ("--fill", "--rtol", "--nvec", "--mg", "--nsmooth", "--fill-coarse", "--level-fill", "--outer-its", "--inner-its",
-                "--inner-its-coarse"):
+                "--inner-its-coarse", "--ordering"):
         if opt in argv:
             at = argv.index(opt)
             if opt == "--fill":
@@ -69,6 +74,8 @@ def main():
                 fillc = int(argv[at + 1])
             elif opt == "--level-fill":
                 level_fill = int(argv[at + 1])
+            elif opt == "--ordering":
+                ordering = argv[at + 1]
             elif opt == "--outer-its":
                 outers = [int(a) for a in argv[at + 1].split(",")]
             elif opt == "--inner-its":
@@ -84,6 +91,8 @@ def main():
     prm = FlowParams(equations=RANSEquations, spaceDiscr=upwind, limiter=vanAlbeda).replace(currentLevel=1, groundLevel=1)
     eng.release_all()
     eng.set_options(prm)
+    if ordering is not None and level_fill is None:
+        sys.exit("--ordering: an ordering of the ILU over the level; give --level-fill")
     if brick:
         cells = register_brick(eng, BrickTopology(*brick, *dims, periodic=(False,) * 3), prm)
     else:
@@ -106,6 +115,14 @@ def main():
         if level_fill is not None:
             if fill or mg > 1 or both:
                 sys.exit("--level-fill: runs the block-local factor of that fill and the coupled fill-0 factor itself; no --fill, --mg, --coupled")
+            if ordering is not None:
+                kind, perm = ordering_of(ordering, brick or (1, 1, 1), dims, cells)
+                eng.pcSetLevelFill(level_fill)
+                eng.pcSetOrdering(kind, perm)
+                one_factor(eng, torch, dims, brick, ns, cells, n, n_it, level_fill, 1, rtol, 0, None, level_fill, ordering)
+                eng.pcSetOrdering(0)
+                eng.pcSetLevelFill(-1)
+                continue
             if level_fill <= 2:
                 eng.pcSetFill(level_fill)
                 one_factor(eng, torch, dims, brick, ns, cells, n, n_it, level_fill, 1, rtol, 0, 0)
@@ -133,6 +150,25 @@ def main():
     eng.close()
 
 
+def ordering_of(name, brick, dims, cells):
+    """(kind, permutation or None) of --ordering for adflow_gpu_pc_set_ordering"""
+    import numpy as np
+    if name in ("natural", "rcm"):
+        return ("natural", "rcm").index(name), None
+    if name == "redblack":
+        # the PETSc layout: block after block (i fastest over the blocks), then k, j, i
+        Bi, Bj, Bk = brick
+        nx, ny, nz = dims
+        k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+        par = np.concatenate([((i + bi * nx) + (j + bj * ny) + (k + bk * nz)).reshape(-1) % 2
+                              for bk in range(Bk) for bj in range(Bj) for bi in range(Bi)])
+        return 2, np.argsort(par, kind="stable").astype(np.int32)
+    perm = np.loadtxt(name, dtype=np.int64, ndmin=1)
+    if perm.size != cells:
+        sys.exit(f"--ordering {name}: {perm.size} entries, the level has {cells} cells")
+    return 2, perm.astype(np.int32)
+
+
 def register_brick(eng, topo, prm):
     """the blocks of a wall-bounded brick with their boundary subfaces and both patterns on the engine; returns the owned cells"""
     from adflow_amd.synth import set_porosities
@@ -156,7 +192,7 @@ def register_brick(eng, topo, prm):
     return sum(b.nx * b.ny * b.nz for b in blocks.values())
 
 
-def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec, coupled, level_fill=None):
+def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec, coupled, level_fill=None, ordering=None):
     """setup, applications and GMRES with the settings of the selected slot as they stand; coupled: None, or the subdomain setting
     the lines name (then with the level sets, the microseconds per launch and the GB/s on the factor bytes); level_fill: None, or the
     fill of the ILU over the level the slot is set to (the same extra figures, the floor from the entries of its pattern)"""
@@ -176,8 +212,16 @@ def one_factor(eng, torch, dims, brick, ns, cells, n, n_it, fill, mg, rtol, nvec
         base = {tr: time_apply(eng, torch, n, n_it, tr) for tr in (False, True)}
         eng.pcSetIts(outer, inner, inner_coarse)
     floor = {0: 7, 1: 13, 2: 23}.get(fill, 7) * ns * ns * 8 * cells
+    if ordering is not None:
+        import time
+        tag["ordering"] = ordering
+        eng.sync()
+        t0 = time.perf_counter()
     eng.pcSetup(1)                                        # warm-up (allocations, tables)
     eng.sync()
+    if ordering is not None:
+        kind, bandwidth, _, _ = eng.pcOrderingInfo()
+        tag.update(ordering_kind=kind, bandwidth=bandwidth, first_setup_wall_ms=round(1e3 * (time.perf_counter() - t0), 1))
     eng.event_record(1)
     eng.pcSetup(1)
     eng.event_record(2)
