@@ -81,6 +81,11 @@ struct Block {
     std::vector<BcFaceDev> bc;      // boundary subfaces (device BCData), first nViscBocos = viscous walls
     std::vector<void*> bc_allocs;   // device copies of the BCData members: replaced at every bc_register
     int nViscBocos = 0;
+    bool tau_stored = false;        // a storing evaluation has written viscSubface%tau / %q since the subfaces were registered
+    // adflow_gpu_bc_set_families: BCData(mm)%famID and the device copy of %iblank (NULL = all ones) of every subface; empty = family 0
+    std::vector<int> famID;
+    std::vector<const signed char*> faceBlank;
+    std::vector<void*> fam_allocs;
     // coloured finite-difference Jacobian (adflow_gpu_fd_jacobian): reference state / residual, stencil blocks
     double *wref = nullptr, *dwref = nullptr, *jac = nullptr, *snap = nullptr;
     void *jac_raw = nullptr, *snap_raw = nullptr;
@@ -617,6 +622,8 @@ static void ad_cache_drop();      // the cached dual arrays of the forward-mode 
 static int64_t jm_release();      // ... and so do the scratch arrays of the matrix products (adflow_gpu_jacobian_mult)
 static int64_t pc_release_all();  // ... and the block ILU(0) factors of both slots (adflow_gpu_pc_setup, adflow_gpu_pc_select)
 static int64_t ank_release();     // ... and the pseudo-time term, base vectors and sums of the ANK operator (adflow_gpu_ank_*)
+static int64_t wi_drop(int level);   // ... and the buffers of the surface integration of a level (adflow_gpu_wall_integrate)
+static int64_t wi_drop_all();
 static bool g_jac_valid = false; // adflow_gpu_fd_jacobian left a matrix on the blocks of level g_jac_level
 static int g_jac_level = 0;
 
@@ -634,6 +641,7 @@ int adflow_gpu_block_release(int nn, int level, int sps)
     if (it->second->jac_raw) (void)hipFree(it->second->jac_raw);
     if (it->second->snap_raw) (void)hipFree(it->second->snap_raw);
     for (void* p : it->second->bc_allocs) (void)hipFree(p);
+    for (void* p : it->second->fam_allocs) (void)hipFree(p);
     delete it->second;
     g_blocks.erase(it);
     ++g_pc_topo_gen;
@@ -654,6 +662,7 @@ int adflow_gpu_release_all(void)
         if (kv.second->jac_raw) (void)hipFree(kv.second->jac_raw);
         if (kv.second->snap_raw) (void)hipFree(kv.second->snap_raw);
         for (void* p : kv.second->bc_allocs) (void)hipFree(p);
+        for (void* p : kv.second->fam_allocs) (void)hipFree(p);
         delete kv.second;
     }
     g_blocks.clear();
@@ -1998,7 +2007,8 @@ int adflow_gpu_release_workspace(int64_t* bytes)
     if (need_ready()) return 1;
     if (g_stream) HIPCHK(hipStreamSynchronize(g_stream));
     const int64_t jm = jm_release();
-    if (bytes) *bytes = (int64_t)g_ad_slab_bytes + jm;
+    const int64_t wi = wi_drop_all();
+    if (bytes) *bytes = (int64_t)g_ad_slab_bytes + jm + wi;
     ad_drop();
     return 0;
 }
@@ -2630,6 +2640,11 @@ int adflow_gpu_bc_register(int nn, int level, int sps, int nBocos, int nViscBoco
     b->bc_allocs = fresh;
     b->bc = out;
     b->nViscBocos = nViscBocos;
+    b->tau_stored = false;
+    for (void* q : b->fam_allocs) (void)hipFree(q);      // the families and the blanking belong to the subfaces they were set for
+    b->fam_allocs.clear();
+    b->famID.clear();
+    b->faceBlank.clear();
     if (v.nw > 5 && !v.bmt[0]) {
         // face arrays of the implicit turbulence boundary treatment (bmt/bvt of blockPointers, one turbulence variable)
         const size_t nf[3] = {(size_t)v.je * v.ke, (size_t)v.ie * v.ke, (size_t)v.ie * v.je};
@@ -2674,6 +2689,7 @@ static void bc_plan_drop(int level)
     if (it->second.d_ent) (void)hipFree(it->second.d_ent);
     if (it->second.d_order) (void)hipFree(it->second.d_order);
     g_bcplan.erase(it);
+    (void)wi_drop(level);           // its table of wall subfaces points into the subfaces of the plan
 }
 
 static void bc_plan_drop_all()
@@ -2866,7 +2882,10 @@ static int wall_stress_enqueue(int level, const KParams& kp, bool formGrad)
     LevelTab t;
     if (level_tab(level, &t)) return 1;
     launch_wall_stress(t.tab, pl->d_ent, pl->d_order, pl->wall, kp, formGrad, g_stream);
-    return 0;
+    return for_level(level, [&](Block* b) {
+        if (b->nViscBocos > 0) b->tau_stored = true;
+        return 0;
+    });
 }
 
 int adflow_gpu_download_wall_stress(int nn, int level, int sps, int mm, double* tau, double* q)
@@ -2883,6 +2902,261 @@ int adflow_gpu_download_wall_stress(int nn, int level, int sps, int mm, double* 
     if (tau) HIPCHK(hipMemcpy(tau, f.tauq, sizeof(double) * 6 * no, hipMemcpyDeviceToHost));
     if (q) HIPCHK(hipMemcpy(q, f.tauq + 6 * no, sizeof(double) * 3 * no, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---- surface integration (kernels_wallint.hip): wallIntegrationFace over the wall subfaces of a level -------------------------------
+static bool is_wall_type(int t) { return t == ADFLOW_BC_EULERWALL || t == ADFLOW_BC_NSWALL_ADIABATIC || t == ADFLOW_BC_NSWALL_ISOTHERMAL; }
+
+// What the first integration of a level allocates: the table of wall subfaces, 7 doubles per owned wall face, the partial results of
+// the face kernel, the membership table of the groups and the output of the host form.  Dropped with the boundary plan of the level
+// and by adflow_gpu_release_workspace.
+struct WiLevel {
+    struct Ref { int nn, mm, fam; long no; double* fpv; };      // block, subface (1-based), family, owned faces, its per-face buffer
+    std::vector<Ref> faces;
+    WiFace* d_faces = nullptr;
+    long maxOwned = 0;
+    double* part = nullptr;
+    unsigned char* d_member = nullptr;
+    std::vector<unsigned char> member;      // host copy of the table on the device: a call with the same groups uploads nothing
+    int memberGroups = 0;
+    double* d_out = nullptr;                // the host form's output, memberGroups x ADFLOW_WALLINT_STRIDE
+    bool integrated = false;
+    std::vector<void*> allocs;
+    int64_t bytes = 0;
+};
+static std::map<int, WiLevel> g_wi;
+
+static int64_t wi_drop(int level)
+{
+    auto it = g_wi.find(level);
+    if (it == g_wi.end()) return 0;
+    if (g_stream) (void)hipStreamSynchronize(g_stream);
+    for (void* p : it->second.allocs) (void)hipFree(p);
+    const int64_t n = it->second.bytes;
+    g_wi.erase(it);
+    return n;
+}
+
+static int64_t wi_drop_all()
+{
+    std::vector<int> levels;
+    for (auto& kv : g_wi) levels.push_back(kv.first);
+    int64_t n = 0;
+    for (int l : levels) n += wi_drop(l);
+    return n;
+}
+
+static int wi_alloc(WiLevel& L, void** p, size_t bytes)
+{
+    HIPCHK(hipMalloc(p, bytes));
+    L.allocs.push_back(*p);
+    L.bytes += (int64_t)bytes;
+    return 0;
+}
+
+// the table of wall subfaces of the level and their buffers (the order of g_blocks: block, then subface)
+static int wi_build(int level, WiLevel& L)
+{
+    std::vector<WiFace> tab;
+    for (auto& kv : g_blocks) {
+        if (std::get<0>(kv.first) != level || std::get<1>(kv.first) != 1) continue;
+        Block* b = kv.second;
+        for (int m = 0; m < (int)b->bc.size(); ++m) {
+            const BcFaceDev& f = b->bc[m];
+            if (!is_wall_type(f.type)) continue;
+            WiFace w;
+            w.slot = std::get<2>(kv.first); w.faceID = f.faceID;
+            bc_owned_range(f.faceID, f.icBeg, f.icEnd, f.jcBeg, f.jcEnd, b->v.il, b->v.jl, b->v.kl, w.r);
+            const long no = (long)std::max(0, w.r[1] - w.r[0] + 1) * std::max(0, w.r[3] - w.r[2] + 1);
+            if (no == 0) continue;
+            w.icBeg = f.icBeg; w.jcBeg = f.jcBeg; w.ldn = f.icEnd - f.icBeg + 1; w.pad = 0;
+            w.nnorm = (long)w.ldn * (f.jcEnd - f.jcBeg + 1);
+            w.norm = f.norm;
+            w.tauq = (m < b->nViscBocos && f.type != ADFLOW_BC_EULERWALL) ? f.tauq : nullptr;
+            w.iblank = m < (int)b->faceBlank.size() ? b->faceBlank[m] : nullptr;
+            void* raw = nullptr;
+            if (wi_alloc(L, &raw, sizeof(double) * 7 * (size_t)no)) return 1;
+            HIPCHK(hipMemsetAsync(raw, 0, sizeof(double) * 7 * (size_t)no, g_stream));
+            w.fpv = (double*)raw;
+            tab.push_back(w);
+            WiLevel::Ref r = {std::get<2>(kv.first), m + 1, m < (int)b->famID.size() ? b->famID[m] : 0, no, w.fpv};
+            L.faces.push_back(r);
+            L.maxOwned = std::max(L.maxOwned, no);
+        }
+    }
+    if (tab.empty()) return 0;
+    if (wi_alloc(L, (void**)&L.d_faces, sizeof(WiFace) * tab.size())) return 1;
+    HIPCHK(hipMemcpy(L.d_faces, tab.data(), sizeof(WiFace) * tab.size(), hipMemcpyHostToDevice));
+    const size_t nwg = (size_t)wallint_groups_per_face(L.maxOwned) * tab.size();
+    return wi_alloc(L, (void**)&L.part, sizeof(double) * WI_NQ * nwg);
+}
+
+static int wall_integrate(const char* who, int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out,
+                          bool outOnDevice)
+{
+    if (need_ready()) return 1;
+    if (!par || !out) return fail("%s: par and out must not be NULL", who);
+    if (nGroups < 0) return fail("%s: nGroups = %d", who, nGroups);
+    if (nGroups > 0) {
+        if (!famLists || ldFam < 1) return fail("%s: nGroups = %d needs famLists with ldFam >= 1 (ldFam = %d)", who, nGroups, ldFam);
+        for (int g = 0; g < nGroups; ++g)
+            if (famLists[g] < 0 || famLists[g] > ldFam - 1)
+                return fail("%s: group %d lists %d families, famLists holds at most ldFam - 1 = %d", who, g + 1, famLists[g], ldFam - 1);
+    }
+    const double MachCoef = par[ADFLOW_WALLINT_MACHCOEF];
+    if (!(MachCoef > 0.0)) return fail("%s: MachCoef = %g must be positive", who, MachCoef);
+    WiPar P;
+    P.pInf = g_opts.pInf; P.pRef = g_opts.pRef; P.gammaInf = g_opts.gammaInf; P.MachCoef = MachCoef;
+    double axisLen = 0.0;
+    for (int d = 0; d < 3; ++d) {
+        P.refPoint[d] = g_opts.LRef * par[ADFLOW_WALLINT_POINTREF + d];
+        P.axisPoint[d] = g_opts.LRef * par[ADFLOW_WALLINT_MOMENTAXIS + d];
+        P.axisDir[d] = g_opts.LRef * par[ADFLOW_WALLINT_MOMENTAXIS + 3 + d] - P.axisPoint[d];
+        axisLen += P.axisDir[d] * P.axisDir[d];
+        P.velDir[d] = par[ADFLOW_WALLINT_VELDIRFREESTREAM + d];
+    }
+    axisLen = sqrt(axisLen);
+    if (!(axisLen > 0.0)) return fail("%s: the moment axis (LRef momentAxis) has zero length", who);
+    for (int d = 0; d < 3; ++d) P.axisDir[d] /= axisLen;
+    P.sepOffset = par[ADFLOW_WALLINT_SEPSENSOROFFSET]; P.sepSharpness = par[ADFLOW_WALLINT_SEPSENSORSHARPNESS];
+    P.computeCavitation = par[ADFLOW_WALLINT_COMPUTECAVITATION] != 0.0;
+    P.cavitationNumber = par[ADFLOW_WALLINT_CAVITATIONNUMBER]; P.cavOffset = par[ADFLOW_WALLINT_CAVSENSOROFFSET];
+    P.cavSharpness = par[ADFLOW_WALLINT_CAVSENSORSHARPNESS];
+    const double ce = par[ADFLOW_WALLINT_CAVEXPONENT];
+    if (P.computeCavitation && !(ce >= 0.0 && ce <= 64.0 && ce == (double)(int)ce))
+        return fail("%s: cavExponent = %g must be a whole number in 0 .. 64", who, ce);
+    P.cavExponent = P.computeCavitation ? (int)ce : 0;
+    P.cpminRho = par[ADFLOW_WALLINT_CPMIN_RHO]; P.cpminFamily = par[ADFLOW_WALLINT_CPMIN_FAMILY];
+    P.rans = g_opts.equations == ADFLOW_RANS; P.pad = 0;
+
+    BcPlan* pl;
+    if (bc_plan(level, &pl)) return 1;
+    if (pl->nent == 0) return fail("%s: level %d has no registered boundary subfaces (adflow_gpu_bc_register)", who, level);
+    for (auto& kv : g_blocks) {
+        if (std::get<0>(kv.first) != level || std::get<1>(kv.first) != 1) continue;
+        const Block* b = kv.second;
+        for (int m = 0; m < (int)b->bc.size(); ++m) {
+            const BcFaceDev& f = b->bc[m];
+            if (!is_wall_type(f.type) || f.type == ADFLOW_BC_EULERWALL || m >= b->nViscBocos || !f.tauq) continue;
+            if (!b->tau_stored)
+                return fail("%s: the wall stress of viscous subface %d of block %d was never stored (no storing residual evaluation "
+                            "since adflow_gpu_bc_register)", who, m + 1, std::get<2>(kv.first));
+            if (P.rans && !f.norm)
+                return fail("%s: viscous subface %d of block %d was registered without BCData%%norm, which y+ reads", who, m + 1,
+                            std::get<2>(kv.first));
+        }
+    }
+    LevelTab t;
+    if (level_tab(level, &t)) return 1;
+    auto it = g_wi.find(level);
+    if (it == g_wi.end()) {
+        WiLevel fresh;
+        if (wi_build(level, fresh)) {
+            for (void* p : fresh.allocs) (void)hipFree(p);
+            return 1;
+        }
+        if (fresh.faces.size() > 65535) {
+            for (void* p : fresh.allocs) (void)hipFree(p);
+            return fail("%s: %zu wall subfaces on level %d, one launch takes 65535", who, fresh.faces.size(), level);
+        }
+        it = g_wi.emplace(level, std::move(fresh)).first;
+    }
+    WiLevel& L = it->second;
+    const int nface = (int)L.faces.size();
+    const int nG = nGroups > 0 ? nGroups : 1;
+    // member[g nface + f]: famInList(BCData(mm)%famID, famLists(g, 2:1 + famLists(g, 1))) of integrateSurfaces
+    std::vector<unsigned char> member((size_t)nG * std::max(nface, 1), 0);
+    for (int g = 0; g < nG; ++g)
+        for (int f = 0; f < nface; ++f) {
+            bool in = nGroups == 0;
+            for (int j = 1; !in && j <= famLists[g]; ++j) in = famLists[g + (size_t)nGroups * j] == L.faces[f].fam;
+            member[(size_t)g * nface + f] = in;
+        }
+    if (member != L.member || !L.d_member) {
+        // (the kernels of an earlier enqueue-only call may still read the table)
+        HIPCHK(hipStreamSynchronize(g_stream));
+        if (nG > L.memberGroups) {
+            void* raw = nullptr;
+            if (wi_alloc(L, &raw, member.size())) return 1;
+            L.d_member = (unsigned char*)raw;
+            if (wi_alloc(L, &raw, sizeof(double) * ADFLOW_WALLINT_STRIDE * (size_t)nG)) return 1;
+            L.d_out = (double*)raw;
+            L.memberGroups = nG;
+            L.member.clear();
+        }
+        HIPCHK(hipMemcpy(L.d_member, member.data(), member.size(), hipMemcpyHostToDevice));
+        L.member = member;
+    }
+    double* d_out = outOnDevice ? out : L.d_out;
+    launch_wallint(t.tab, L.d_faces, nface, L.maxOwned, P, L.part, L.d_member, nG, d_out, g_stream);
+    L.integrated = true;
+    if (outOnDevice) return sync_and_check();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * ADFLOW_WALLINT_STRIDE * (size_t)nG, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+int adflow_gpu_bc_set_families(int nn, int level, int sps, int nBocos, const int32_t* famID, const int8_t* const* iblank)
+{
+    Block* b = find_block(nn, level, sps);
+    if (!b) return fail("block (%d,%d,%d) not registered", nn, level, sps);
+    if (nBocos != (int)b->bc.size()) return fail("bc_set_families: block %d has %d registered subfaces, not %d", nn, (int)b->bc.size(), nBocos);
+    if (nBocos > 0 && !famID) return fail("bc_set_families: famID is NULL");
+    std::vector<void*> fresh;
+    std::vector<const signed char*> blank((size_t)nBocos, nullptr);
+    for (int m = 0; m < nBocos; ++m) {
+        if (!iblank || !iblank[m]) continue;
+        const BcFaceDev& f = b->bc[m];
+        int r[4];
+        bc_owned_range(f.faceID, f.icBeg, f.icEnd, f.jcBeg, f.jcEnd, b->v.il, b->v.jl, b->v.kl, r);
+        const long no = (long)std::max(0, r[1] - r[0] + 1) * std::max(0, r[3] - r[2] + 1);
+        if (no == 0) continue;
+        void* raw = nullptr;
+        if (hipMalloc(&raw, (size_t)no) != hipSuccess || hipMemcpy(raw, iblank[m], (size_t)no, hipMemcpyHostToDevice) != hipSuccess) {
+            if (raw) (void)hipFree(raw);
+            for (void* q : fresh) (void)hipFree(q);
+            return fail("bc_set_families: the blanking of subface %d of block %d could not be copied to the device", m + 1, nn);
+        }
+        fresh.push_back(raw);
+        blank[m] = (const signed char*)raw;
+    }
+    (void)wi_drop(level);            // (waits for the queue) its table holds the old families and blanking arrays
+    for (void* q : b->fam_allocs) (void)hipFree(q);
+    b->fam_allocs = fresh;
+    b->faceBlank = blank;
+    b->famID.assign(famID, famID + nBocos);
+    return 0;
+}
+
+int adflow_gpu_wall_integrate(int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out)
+{
+    return wall_integrate("wall_integrate", level, par, nGroups, famLists, ldFam, out, false);
+}
+
+int adflow_gpu_wall_integrate_dev(int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out)
+{
+    return wall_integrate("wall_integrate_dev", level, par, nGroups, famLists, ldFam, out, true);
+}
+
+int adflow_gpu_download_wall_forces(int nn, int level, int sps, int mm, double* Fp, double* Fv, double* area)
+{
+    Block* b = find_block(nn, level, sps);
+    if (!b) return fail("block (%d,%d,%d) not registered", nn, level, sps);
+    if (mm < 1 || mm > (int)b->bc.size() || !is_wall_type(b->bc[mm - 1].type))
+        return fail("download_wall_forces: subface %d is not a wall subface of block %d", mm, nn);
+    auto it = g_wi.find(level);
+    if (it == g_wi.end() || !it->second.integrated)
+        return fail("download_wall_forces: no integration of level %d to read (adflow_gpu_wall_integrate; adflow_gpu_release_workspace frees it)", level);
+    for (const WiLevel::Ref& r : it->second.faces) {
+        if (r.nn != nn || r.mm != mm) continue;
+        HIPCHK(hipStreamSynchronize(g_stream));
+        if (Fp) HIPCHK(hipMemcpy(Fp, r.fpv, sizeof(double) * 3 * r.no, hipMemcpyDeviceToHost));
+        if (Fv) HIPCHK(hipMemcpy(Fv, r.fpv + 3 * r.no, sizeof(double) * 3 * r.no, hipMemcpyDeviceToHost));
+        if (area) HIPCHK(hipMemcpy(area, r.fpv + 6 * r.no, sizeof(double) * r.no, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    return 0;        // a subface without owned face cells
 }
 
 // setCorrectionsCoarseHalos of every coarse block with subfaces (multiGrid.F90:472)

@@ -572,6 +572,35 @@ long ank_unsteady_groups(int nslots, int maxnx, int maxny, int maxnz);
 void launch_ank_unsteady(const BlkView* tab, int nslots, int maxnx, int maxny, int maxnz, int nS, int turb, const double* dW, const double* tsm,
                          long N, double turbDiag, double turbScale, double omega, double* r, double* part, double* out, hipStream_t s);
 
+// surface integration (kernels_wallint.hip; adflow_gpu_wall_integrate): one wall subface of the level as the face kernel sees it
+struct WiFace {
+    int slot, faceID;         // block slot in the level's table, BCFaceID
+    int r[4];                 // the owned face cells (bc_owned_range)
+    int icBeg, jcBeg, ldn;    // BCData%norm: component c of cell (a, b) at (a - icBeg) + (b - jcBeg) ldn + c nnorm
+    int pad;
+    long nnorm;
+    const double* norm;       // NULL where no term reads it (y+ of a viscous wall under RANS does)
+    const double* tauq;       // viscous walls: the stored stress (BcFaceDev::tauq); NULL on an Euler wall
+    const signed char* iblank;   // per owned face cell, NULL = all ones
+    double* fpv;              // BCData%Fp(3), %Fv(3), %area over the owned face cells, component-major
+};
+// the parameters of wallIntegrationFace, lengths already times LRef
+struct WiPar {
+    double pInf, pRef, gammaInf, MachCoef;
+    double refPoint[3], axisPoint[3], axisDir[3], velDir[3];      // axisDir: the unit vector along the moment axis
+    double sepOffset, sepSharpness, cavitationNumber, cavOffset, cavSharpness, cpminRho, cpminFamily;
+    int computeCavitation, cavExponent, rans, pad;
+};
+// the quantities a workgroup of the face kernel reduces: sums, then the maximum of y+ and the minimum of Cp
+enum { WI_FP = 0, WI_FV = 3, WI_MP = 6, WI_MV = 9, WI_SEP = 12, WI_SEPAVG = 13, WI_CAV = 16, WI_AXIS = 17, WI_CPMIN_KS = 18, WI_COF = 19,
+       WI_YPLUS = 28, WI_CPMIN = 29, WI_NQ = 30 };
+enum { WI_T = 256 };          // threads of a workgroup of both kernels
+inline int wallint_groups_per_face(long maxOwned) { return (int)((maxOwned + WI_T - 1) / WI_T); }
+// part: WI_NQ x (workgroups per subface x nface) doubles; member[g nface + f] != 0: subface f belongs to group g; out: nGroups x
+// ADFLOW_WALLINT_STRIDE doubles on the device
+void launch_wallint(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const WiPar& P, double* part,
+                    const unsigned char* member, int nGroups, double* out, hipStream_t s);
+
 // The level-batched launches fold (block slot, plane) into gridDim.z, which HIP limits to 65535: a launcher whose level has more
 // slots than fit calls itself on consecutive slot ranges (the kernels index the table relative to the pointer they get).
 extern int g_max_grid_z;          // 65535; tuning "max_grid_z" lowers it for the tests

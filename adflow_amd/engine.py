@@ -618,6 +618,81 @@ class Engine:
         self._chk(self.lib.adflow_gpu_download_wall_stress(nn, level, sps, mm, tau.ctypes.data, q.ctypes.data))
         return tau, q
 
+    # ---- surface integration (surfaceIntegrations.F90: wallIntegrationFace, computeCpMinFamily) ----
+    @staticmethod
+    def wallPar(MachCoef, pointRef=(0.0, 0.0, 0.0), momentAxis=((0.0, 0.0, 0.0), (1.0, 0.0, 0.0)), velDirFreeStream=(1.0, 0.0, 0.0),
+                sepSensorOffset=0.0, sepSensorSharpness=10.0, computeCavitation=False, cavitationnumber=1.4, cavSensorOffset=0.0,
+                cavSensorSharpness=10.0, cavExponent=0, cpmin_rho=100.0, cpmin_family=0.0):
+        """the parameter array of wallIntegrate; momentAxis = (first point, second point); the defaults of the sensors are those of
+        inputCostFunctions / inputPhysics"""
+        par = np.zeros(capi.WALLINT_NPAR)
+        par[capi.WALLINT_MACHCOEF] = MachCoef
+        par[capi.WALLINT_POINTREF:capi.WALLINT_POINTREF + 3] = pointRef
+        par[capi.WALLINT_MOMENTAXIS:capi.WALLINT_MOMENTAXIS + 6] = np.asarray(momentAxis, dtype=np.float64).reshape(6)
+        par[capi.WALLINT_VELDIRFREESTREAM:capi.WALLINT_VELDIRFREESTREAM + 3] = velDirFreeStream
+        par[capi.WALLINT_SEPSENSOROFFSET], par[capi.WALLINT_SEPSENSORSHARPNESS] = sepSensorOffset, sepSensorSharpness
+        par[capi.WALLINT_COMPUTECAVITATION], par[capi.WALLINT_CAVITATIONNUMBER] = float(bool(computeCavitation)), cavitationnumber
+        par[capi.WALLINT_CAVSENSOROFFSET], par[capi.WALLINT_CAVSENSORSHARPNESS] = cavSensorOffset, cavSensorSharpness
+        par[capi.WALLINT_CAVEXPONENT], par[capi.WALLINT_CPMIN_RHO], par[capi.WALLINT_CPMIN_FAMILY] = cavExponent, cpmin_rho, cpmin_family
+        return par
+
+    @staticmethod
+    def _famLists(groups):
+        """groups: None (one group of every wall subface) or a list of family lists -> (nGroups, famLists (nGroups, ldFam) F-order, ldFam)"""
+        if groups is None:
+            return 0, None, 0
+        ld = 1 + max([len(g) for g in groups] + [0])
+        fl = np.zeros((max(len(groups), 1), ld), np.int32, order="F")
+        for g, fams in enumerate(groups):
+            fl[g, 0] = len(fams)
+            fl[g, 1:1 + len(fams)] = fams
+        return len(groups), fl, ld
+
+    def bcSetFamilies(self, famID, iblank=None, nn: int = 1, level: int = 1, sps: int = 1):
+        """BCData(mm)%famID of the registered subfaces of a block and, optionally, their face blanking: iblank = None or a list with, per
+        subface, None (all ones) or an int8 array over the owned face cells"""
+        fam = np.ascontiguousarray(famID, np.int32)
+        ptrs = None
+        keep = []
+        if iblank is not None:
+            assert len(iblank) == fam.size
+            ptrs = (ctypes.c_void_p * max(fam.size, 1))()
+            for m, a in enumerate(iblank):
+                if a is not None:
+                    a = np.asfortranarray(a, dtype=np.int8)
+                    keep.append(a)
+                    ptrs[m] = a.ctypes.data
+        self._chk(self.lib.adflow_gpu_bc_set_families(nn, level, sps, int(fam.size), fam.ctypes.data, ptrs))
+
+    def wallIntegrate(self, par, groups=None, level: int = 1):
+        """localValues(1:63) of every family group (entries 0..62) and the group's minimum of Cp (entry 63): an (nGroups, 64) array;
+        groups = None: one group holding every wall subface"""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        assert par.size == capi.WALLINT_NPAR
+        n, fl, ld = self._famLists(groups)
+        out = np.zeros((max(n, 1) if groups is None else n, capi.WALLINT_STRIDE))
+        if groups is not None and n == 0:
+            return out
+        self._chk(self.lib.adflow_gpu_wall_integrate(level, par.ctypes.data, n, None if fl is None else fl.ctypes.data, ld, out.ctypes.data))
+        return out
+
+    def wallIntegrateDev(self, par, d_out: int, groups=None, level: int = 1):
+        """the same into a device array of nGroups x 64 doubles; honours set_async"""
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        assert par.size == capi.WALLINT_NPAR
+        n, fl, ld = self._famLists(groups)
+        self._chk(self.lib.adflow_gpu_wall_integrate_dev(level, par.ctypes.data, n, None if fl is None else fl.ctypes.data, ld,
+                                                         ctypes.c_void_p(d_out)))
+
+    def wallForces(self, shape, mm: int, nn: int = 1, level: int = 1, sps: int = 1):
+        """BCData(mm)%Fp, %Fv, %area of wall subface mm (1-based) as the last wallIntegrate left them, over its owned face cells
+        `shape` = (n1, n2)"""
+        Fp = np.zeros(tuple(shape) + (3,), order="F")
+        Fv = np.zeros(tuple(shape) + (3,), order="F")
+        area = np.zeros(tuple(shape), order="F")
+        self._chk(self.lib.adflow_gpu_download_wall_forces(nn, level, sps, mm, Fp.ctypes.data, Fv.ctypes.data, area.ctypes.data))
+        return Fp, Fv, area
+
     def upload_coordinates(self, nn=1, level=1, sps=1):
         self._chk(self.lib.adflow_gpu_upload_coordinates(nn, level, sps))
 

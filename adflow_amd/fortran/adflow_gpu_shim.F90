@@ -80,6 +80,11 @@ module adflowGpuShim
     type intBuf
         integer(c_int32_t), allocatable :: v(:)
     end type intBuf
+    type byteBuf
+        integer(c_int8_t), allocatable :: v(:)
+    end type byteBuf
+    ! adflow_gpu_wall_integrate: size of its parameter array and of one group of its output (ADFLOW_WALLINT_NPAR, _STRIDE)
+    integer, parameter :: WALLINT_NPAR = 22, WALLINT_STRIDE = 64
 
     ! ---- mirror of adflow_periodic_data ----------------------------------------
     type, bind(C) :: adflow_periodic_data
@@ -146,6 +151,35 @@ module adflowGpuShim
             import :: c_int, c_ptr
             integer(c_int), value :: nn, level, sps, mm
             type(c_ptr), value :: tau, q
+        end function
+        integer(c_int) function adflow_gpu_bc_set_families(nn, level, sps, nBocos, famID, iblank) &
+            bind(C, name="adflow_gpu_bc_set_families")
+            import :: c_int, c_int32_t, c_ptr
+            integer(c_int), value :: nn, level, sps, nBocos
+            integer(c_int32_t), intent(in) :: famID(*)
+            type(c_ptr), intent(in) :: iblank(*)           ! per subface: int8 over the owned face cells, or c_null_ptr
+        end function
+        integer(c_int) function adflow_gpu_wall_integrate(level, par, nGroups, famLists, ldFam, out) &
+            bind(C, name="adflow_gpu_wall_integrate")
+            import :: c_int, c_int32_t, c_double
+            integer(c_int), value :: level, nGroups, ldFam
+            real(c_double), intent(in) :: par(*)
+            integer(c_int32_t), intent(in) :: famLists(*)
+            real(c_double), intent(inout) :: out(*)
+        end function
+        integer(c_int) function adflow_gpu_wall_integrate_dev(level, par, nGroups, famLists, ldFam, out) &
+            bind(C, name="adflow_gpu_wall_integrate_dev")
+            import :: c_int, c_int32_t, c_double, c_ptr
+            integer(c_int), value :: level, nGroups, ldFam
+            real(c_double), intent(in) :: par(*)
+            integer(c_int32_t), intent(in) :: famLists(*)
+            type(c_ptr), value :: out                      ! device memory, nGroups x 64 doubles
+        end function
+        integer(c_int) function adflow_gpu_download_wall_forces(nn, level, sps, mm, Fp, Fv, area) &
+            bind(C, name="adflow_gpu_download_wall_forces")
+            import :: c_int, c_ptr
+            integer(c_int), value :: nn, level, sps, mm
+            type(c_ptr), value :: Fp, Fv, area
         end function
         integer(c_int) function adflow_gpu_comm_register(level, nLayers, p) bind(C, name="adflow_gpu_comm_register")
             import :: c_int, adflow_comm_pattern
@@ -995,6 +1029,84 @@ contains
         call gpuCheck(adflow_gpu_bc_register(int(nn, c_int), int(level, c_int), int(sps, c_int), int(nb, c_int), &
                                              int(flowDoms(nn, level, sps)%nViscBocos, c_int), f), "gpuRegisterBocos")
     end subroutine gpuRegisterBocos
+
+    ! BCData(:)%famID and %iblank of a block -> device (after gpuRegisterBocos, which replaces the subfaces and their families).
+    ! The blanking goes over as int8 on the owned face cells inBeg+1:inEnd x jnBeg+1:jnEnd, the faces wallIntegrationFace visits.
+    subroutine gpuBCSetFamilies(nn, level, sps)
+        use block, only: flowDoms
+        integer(kind=intType), intent(in) :: nn, level, sps
+        type(byteBuf), allocatable, target :: bb(:)
+        integer(c_int32_t), allocatable :: fam(:)
+        type(c_ptr), allocatable :: ptr(:)
+        integer :: mm, nb, i, j, ii
+        nb = flowDoms(nn, level, sps)%nBocos
+        allocate (bb(max(nb, 1)), fam(max(nb, 1)), ptr(max(nb, 1)))
+        do mm = 1, nb
+            associate (d => flowDoms(nn, level, sps)%BCData(mm))
+                fam(mm) = int(d%famID, c_int32_t)
+                ptr(mm) = c_null_ptr
+                if (associated(d%iblank) .and. d%inEnd > d%inBeg .and. d%jnEnd > d%jnBeg) then
+                    allocate (bb(mm)%v((d%inEnd - d%inBeg) * (d%jnEnd - d%jnBeg)))
+                    ii = 0
+                    do j = d%jnBeg + 1, d%jnEnd
+                        do i = d%inBeg + 1, d%inEnd
+                            ii = ii + 1
+                            bb(mm)%v(ii) = int(max(-1, min(1, d%iblank(i, j))), c_int8_t)
+                        end do
+                    end do
+                    ptr(mm) = c_loc(bb(mm)%v)
+                end if
+            end associate
+        end do
+        call gpuCheck(adflow_gpu_bc_set_families(int(nn, c_int), int(level, c_int), int(sps, c_int), int(nb, c_int), fam, ptr), &
+                      "gpuBCSetFamilies")
+    end subroutine gpuBCSetFamilies
+
+    ! The wall part of integrateSurfaces (surfaceIntegrations.F90:1264-1361) for one family list, on the device: adds this process's
+    ! contributions of every wall subface whose family is in famList to localValues (the maximum for iyPlus), as the loop over
+    ! wallIntegrationFace does.  cpMinLocal: the minimum of Cp over those faces, what computeCpMinFamily reduces over the processes
+    ! into cpmin_family(sps) before the call that is to give the KS sum.  The parameters come from inputPhysics / inputCostFunctions.
+    subroutine gpuWallIntegrate(localValues, famList, sps, cpMinLocal)
+        use constants, only: nLocalValues, iyPlus
+        use inputPhysics, only: MachCoef, pointRef, momentAxis, velDirFreeStream, cavitationnumber, cpmin_rho, cpmin_family
+        use inputCostFunctions, only: sepSensorOffset, sepSensorSharpness, computeCavitation, cavSensorOffset, &
+                                      cavSensorSharpness, cavExponent
+        real(kind=realType), dimension(nLocalValues), intent(inout) :: localValues
+        integer(kind=intType), dimension(:), intent(in) :: famList
+        integer(kind=intType), intent(in) :: sps
+        real(kind=realType), intent(out), optional :: cpMinLocal
+        real(c_double) :: par(0:WALLINT_NPAR - 1), out(0:WALLINT_STRIDE - 1)
+        integer(c_int32_t), allocatable :: fl(:)
+        integer :: i, n
+        n = size(famList)
+        allocate (fl(n + 1))
+        fl(1) = int(n, c_int32_t)
+        fl(2:n + 1) = int(famList, c_int32_t)
+        par = 0.0_c_double
+        par(0) = MachCoef
+        par(1:3) = pointRef
+        par(4:6) = momentAxis(:, 1)
+        par(7:9) = momentAxis(:, 2)
+        par(10:12) = velDirFreeStream
+        par(13) = sepSensorOffset
+        par(14) = sepSensorSharpness
+        if (computeCavitation) par(15) = 1.0_c_double
+        par(16) = cavitationnumber
+        par(17) = cavSensorOffset
+        par(18) = cavSensorSharpness
+        par(19) = real(cavExponent, c_double)
+        par(20) = cpmin_rho
+        if (allocated(cpmin_family)) par(21) = cpmin_family(sps)
+        call gpuCheck(adflow_gpu_wall_integrate(1_c_int, par, 1_c_int, fl, int(n + 1, c_int), out), "gpuWallIntegrate")
+        do i = 1, nLocalValues
+            if (i == iyPlus) then
+                localValues(i) = max(localValues(i), out(i - 1))
+            else
+                localValues(i) = localValues(i) + out(i - 1)
+            end if
+        end do
+        if (present(cpMinLocal)) cpMinLocal = out(WALLINT_STRIDE - 1)
+    end subroutine gpuWallIntegrate
 
     ! actuatorRegions(1:nActuatorRegions) -> device (after addActuatorRegion; again when force / heat change)
     subroutine gpuRegisterActuatorRegions()

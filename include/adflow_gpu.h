@@ -370,6 +370,65 @@ int adflow_gpu_apply_all_bc(int level, int secondHalo);
  * The device stores them after every such residual evaluation (adflow_gpu_residual with rkStage 0, the D-ADI smoother,
  * the multigrid cycle's closing residual, adflow_gpu_block_res). */
 int adflow_gpu_download_wall_stress(int nn, int level, int sps, int mm, double* tau, double* q);
+/* Surface integration on the device: surfaceIntegrations::wallIntegrationFace (surfaceIntegrations.F90:406-881) over the wall
+ * subfaces (EulerWall, NSWallAdiabatic, NSWallIsoThermal) of every block of a level, as integrateSurfaces calls it per family
+ * group, and the family minimum of Cp of computeCpMinFamily (:1363-1437).
+ *
+ * adflow_gpu_bc_set_families: BCData(mm)%famID of the nBocos registered subfaces of a block (nBocos as given to
+ * adflow_gpu_bc_register) and, optionally, BCData(mm)%iblank over the OWNED face cells inBeg+1:inEnd x jnBeg+1:jnEnd (the bounds of
+ * adflow_gpu_download_wall_stress), Fortran order, int8; iblank NULL, or NULL for a subface, means all ones (overset is refused by
+ * adflow_gpu_set_options, so 1 is what the reference holds).  A block whose families were never set has family 0 everywhere;
+ * adflow_gpu_bc_register replaces the subfaces and with them their families and blanking.
+ *
+ * adflow_gpu_wall_integrate[_dev]: par = ADFLOW_WALLINT_NPAR doubles at the indices below, named after the reference's variables
+ * (inputPhysics, inputCostFunctions); pInf, pRef, gammaInf, LRef and equations come from adflow_gpu_set_options.  famLists = the
+ * reference's famLists array: nGroups rows of ldFam entries, column-major (entry j of group g at g + nGroups j), first entry the
+ * number of families that follow; nGroups = 0 (famLists unused) = one group holding every wall subface.  out = ADFLOW_WALLINT_STRIDE
+ * doubles per group: entries 0..62 are this process's localValues(1:63) at the reference's indices (constants.F90:454-500) -- iFp,
+ * iFv, iMp, iMv, iSepSensor, iSepAvg, iCavitation, iyPlus, iAxisMoment, iCpMin (the KS sum), iCoForceX/Y/Z; every other slot is
+ * zero -- which the host adds into localVal before its own mpi_allreduce and getCostFunctions; entry 63 is the minimum of Cp over
+ * the faces of the group with iblank = 1 (start value 10000).  A host that wants the cavitation KS sum calls once, reduces entry
+ * 63 over its ranks, sets ADFLOW_WALLINT_CPMIN_FAMILY and calls again.  The entry reads what is on the device -- the halos as the last
+ * boundary-condition pass left them, tau as the last storing evaluation left it (see adflow_gpu_download_wall_stress) -- evaluates
+ * nothing itself and changes neither state nor residual.  Deterministic: two-pass sums in a fixed order, no atomics.  The _dev form
+ * takes a device pointer for out and honours adflow_gpu_set_async; it waits for the queue only when the family lists differ from those of
+ * the previous call on the level (the membership table is then replaced).
+ * Errors (nothing is launched or allocated): a level without registered boundary subfaces; a viscous wall subface whose stress was
+ * never stored; nGroups < 0; a family count above ldFam - 1; MachCoef <= 0; a moment axis of zero length.
+ *
+ * adflow_gpu_download_wall_forces: BCData(mm)%Fp(:,:,3), %Fv(:,:,3), %area of subface mm (1-based, any wall subface of the block)
+ * as the last integration of the level left them, over the owned face cells; unblanked, Fv zero on an Euler wall; any pointer may
+ * be NULL.
+ *
+ * Buffers: 7 doubles per owned wall face, the partial sums and the membership table are allocated at the first integration of a
+ * level (a process that never integrates holds the bytes it held).  adflow_gpu_release_workspace FREES them and counts them in
+ * its bytes (the next integration allocates them again); adflow_gpu_bc_register, adflow_gpu_bc_set_families,
+ * adflow_gpu_block_release and adflow_gpu_release_all free them too.
+ * Not here: flowIntegrationFace (mass flow through in- and outflow faces), zippers, user surfaces, actuator regions;
+ * computeSepSensorKs and CpError2 (they need a family maximum and CpTarget; iSepSensorKs, iSepSensorArea, iSepSensorKsArea and
+ * iCpError2 are zero); getCostFunctions, which stays on the host; the derivative seeds of master_d / master_b. */
+enum {
+    ADFLOW_WALLINT_MACHCOEF = 0,
+    ADFLOW_WALLINT_POINTREF = 1,             /* pointRef(3) */
+    ADFLOW_WALLINT_MOMENTAXIS = 4,           /* momentAxis(3,2), column-major: the first point, then the second */
+    ADFLOW_WALLINT_VELDIRFREESTREAM = 10,    /* velDirFreeStream(3) */
+    ADFLOW_WALLINT_SEPSENSOROFFSET = 13,
+    ADFLOW_WALLINT_SEPSENSORSHARPNESS = 14,
+    ADFLOW_WALLINT_COMPUTECAVITATION = 15,   /* 0 / 1 */
+    ADFLOW_WALLINT_CAVITATIONNUMBER = 16,
+    ADFLOW_WALLINT_CAVSENSOROFFSET = 17,
+    ADFLOW_WALLINT_CAVSENSORSHARPNESS = 18,
+    ADFLOW_WALLINT_CAVEXPONENT = 19,         /* a whole number >= 0 */
+    ADFLOW_WALLINT_CPMIN_RHO = 20,
+    ADFLOW_WALLINT_CPMIN_FAMILY = 21,
+    ADFLOW_WALLINT_NPAR = 22
+};
+#define ADFLOW_WALLINT_STRIDE 64
+#define ADFLOW_WALLINT_CPMIN 63              /* entry of a group's output that holds the minimum of Cp */
+int adflow_gpu_bc_set_families(int nn, int level, int sps, int nBocos, const int32_t* famID, const int8_t* const* iblank);
+int adflow_gpu_wall_integrate(int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out);
+int adflow_gpu_wall_integrate_dev(int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out);
+int adflow_gpu_download_wall_forces(int nn, int level, int sps, int mm, double* Fp, double* Fv, double* area);
 /* Actuator regions (actuatorRegionData.F90): residuals::sourceTerms_block (residuals.F90:348-425) adds the body force and
  * heat source of every listed cell to dw of the FINE level: -vol * force / volume / pRef on the momentum residuals,
  * -(F . v) - vol * heat / volume / (pRef uRef LRef^2) on the energy residual, ramped by ordersConverged between
@@ -454,7 +513,7 @@ int adflow_gpu_fd_jacobian(int level, unsigned flags, double delta);
  * 8.4 GB on the 8 x 160x128x64 mesh) -- and the scratch arrays of adflow_gpu_jacobian_mult and adflow_gpu_jacfree_mult to the device allocator: what the host calls when the matrix is assembled and the memory is
  * wanted elsewhere (PETSc objects, further multigrid levels).  *bytes (may be NULL): what was released.  The next forward-mode
  * assembly lays the slab out again.  Mirrors nothing in the reference, whose Tapenade derivative arrays live in flowDomsd for the
- * whole run (adjointUtils.F90:87-99 allocDerivativeValues). */
+ * whole run (adjointUtils.F90:87-99 allocDerivativeValues).  The buffers of adflow_gpu_wall_integrate are freed and counted too. */
 int adflow_gpu_release_workspace(int64_t* bytes);
 /* Self-test of the arithmetic the kernels substitute for the compiler's division, square root, pow and exp (csrc/internal.h: v_rcp_f64 /
  * v_rsq_f64 seeds + Newton steps, x^(1/6), x^a, exp of a negative argument) and of their dual-number forms (csrc/kernels_ad.hip): for
