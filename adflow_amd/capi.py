@@ -159,6 +159,7 @@ EXPORTS = [
     "adflow_gpu_transfer_to_coarse", "adflow_gpu_transfer_to_fine", "adflow_gpu_mg_cycle",
     "adflow_gpu_comm_register", "adflow_gpu_comm_info", "adflow_gpu_halo_slot_info", "adflow_gpu_halo_pack", "adflow_gpu_halo_unpack",
     "adflow_gpu_bc_set_families", "adflow_gpu_wall_integrate", "adflow_gpu_wall_integrate_dev", "adflow_gpu_download_wall_forces",
+    "adflow_gpu_wall_integrate_fwd", "adflow_gpu_wall_integrate_fwd_dev", "adflow_gpu_wall_integrate_bwd", "adflow_gpu_wall_integrate_bwd_dev",
     "adflow_gpu_halo_local_copy", "adflow_gpu_set_bc_callback", "adflow_gpu_bc_register", "adflow_gpu_apply_all_bc", "adflow_gpu_download_wall_stress", "adflow_gpu_abi_sizes2", "adflow_gpu_xhalo", "adflow_gpu_actuator_register", "adflow_gpu_comm_register_periodic", "adflow_gpu_coarse_coordinates", "adflow_gpu_exchange_coor",
     "adflow_gpu_upload_coordinates", "adflow_gpu_update_geometry", "adflow_gpu_reference_shock_sensor",
     "adflow_gpu_wall_distance_register", "adflow_gpu_update_wall_distances",
@@ -218,6 +219,10 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     lib.adflow_gpu_bc_set_families.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     for f in (lib.adflow_gpu_wall_integrate, lib.adflow_gpu_wall_integrate_dev):
         f.argtypes = [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]
+    for f in (lib.adflow_gpu_wall_integrate_fwd, lib.adflow_gpu_wall_integrate_fwd_dev):
+        f.argtypes = [c_int, c_uint, c_void_p, ctypes.c_long, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]
+    for f in (lib.adflow_gpu_wall_integrate_bwd, lib.adflow_gpu_wall_integrate_bwd_dev):
+        f.argtypes = [c_int, c_uint, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_long, ctypes.c_long]
     lib.adflow_gpu_download_wall_forces.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.adflow_gpu_upload_coordinates.argtypes = [c_int, c_int, c_int]
     lib.adflow_gpu_update_geometry.argtypes = [c_int]

@@ -2921,6 +2921,20 @@ struct WiLevel {
     int memberGroups = 0;
     double* d_out = nullptr;                // the host form's output, memberGroups x ADFLOW_WALLINT_STRIDE
     bool integrated = false;
+    // the derivative entries (adflow_gpu_wall_integrate_fwd / _bwd), allocated by the first call that needs them
+    long nOwned = 0, maxBox = 0;            // owned wall faces of the level; the most cells of a subface's box (k_wallint_credit)
+    void* partD = nullptr;                  // the partial results of the dual face kernel
+    double* d_dot = nullptr;                // the host form's out and outDot, 2 x dotGroups x ADFLOW_WALLINT_STRIDE
+    int dotGroups = 0;
+    int barNS = 0, barNv = 0;               // what the buffers of the transposed product were laid out for
+    std::vector<void*> barAllocs;
+    std::vector<double> wq;                 // host copy of the weights on the device
+    double *d_wq = nullptr, *d_g = nullptr; // weights per (set, subface, quantity); contracted derivatives per (set, owned face)
+    JmBlk* barTab = nullptr;                // per weight set the level's table with ys = the halo'd result
+    std::vector<double*> barYs;             // per block slot its ys of all sets (with the front padding)
+    std::vector<size_t> barYsBytes;
+    int64_t barBytes = 0;                   // of barAllocs, part of bytes
+    int barSlots = 0, barNx = 0, barNy = 0, barNz = 0;
     std::vector<void*> allocs;
     int64_t bytes = 0;
 };
@@ -2932,6 +2946,7 @@ static int64_t wi_drop(int level)
     if (it == g_wi.end()) return 0;
     if (g_stream) (void)hipStreamSynchronize(g_stream);
     for (void* p : it->second.allocs) (void)hipFree(p);
+    for (void* p : it->second.barAllocs) (void)hipFree(p);
     const int64_t n = it->second.bytes;
     g_wi.erase(it);
     return n;
@@ -2978,6 +2993,9 @@ static int wi_build(int level, WiLevel& L)
             if (wi_alloc(L, &raw, sizeof(double) * 7 * (size_t)no)) return 1;
             HIPCHK(hipMemsetAsync(raw, 0, sizeof(double) * 7 * (size_t)no, g_stream));
             w.fpv = (double*)raw;
+            w.goff = L.nOwned;
+            L.nOwned += no;
+            L.maxBox = std::max(L.maxBox, (long)(w.r[1] - w.r[0] + 1 + 2 * WI_REACH) * (w.r[3] - w.r[2] + 1 + 2 * WI_REACH) * WI_DEPTH);
             tab.push_back(w);
             WiLevel::Ref r = {std::get<2>(kv.first), m + 1, m < (int)b->famID.size() ? b->famID[m] : 0, no, w.fpv};
             L.faces.push_back(r);
@@ -2991,11 +3009,15 @@ static int wi_build(int level, WiLevel& L)
     return wi_alloc(L, (void**)&L.part, sizeof(double) * WI_NQ * nwg);
 }
 
-static int wall_integrate(const char* who, int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out,
-                          bool outOnDevice)
+// What every entry of the integration does before it launches: the checks of par and of the groups, the parameters of the face kernel,
+// the level's record with its table of wall subfaces, and the membership table of the groups on the device.  needStress: the entry
+// reads the stored wall stress (the derivative entries form the stress of their own pass).  nG: the groups of the output (1 for
+// nGroups = 0)
+static int wi_setup(const char* who, int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, bool needStress,
+                    WiPar* Pout, WiLevel** Lout, int* nGout)
 {
     if (need_ready()) return 1;
-    if (!par || !out) return fail("%s: par and out must not be NULL", who);
+    if (!par) return fail("%s: par must not be NULL", who);
     if (nGroups < 0) return fail("%s: nGroups = %d", who, nGroups);
     if (nGroups > 0) {
         if (!famLists || ldFam < 1) return fail("%s: nGroups = %d needs famLists with ldFam >= 1 (ldFam = %d)", who, nGroups, ldFam);
@@ -3038,7 +3060,7 @@ static int wall_integrate(const char* who, int level, const double* par, int nGr
         for (int m = 0; m < (int)b->bc.size(); ++m) {
             const BcFaceDev& f = b->bc[m];
             if (!is_wall_type(f.type) || f.type == ADFLOW_BC_EULERWALL || m >= b->nViscBocos || !f.tauq) continue;
-            if (!b->tau_stored)
+            if (needStress && !b->tau_stored)
                 return fail("%s: the wall stress of viscous subface %d of block %d was never stored (no storing residual evaluation "
                             "since adflow_gpu_bc_register)", who, m + 1, std::get<2>(kv.first));
             if (P.rans && !f.norm)
@@ -3046,8 +3068,7 @@ static int wall_integrate(const char* who, int level, const double* par, int nGr
                             std::get<2>(kv.first));
         }
     }
-    LevelTab t;
-    if (level_tab(level, &t)) return 1;
+    if (ensure_table(level)) return 1;
     auto it = g_wi.find(level);
     if (it == g_wi.end()) {
         WiLevel fresh;
@@ -3087,6 +3108,23 @@ static int wall_integrate(const char* who, int level, const double* par, int nGr
         HIPCHK(hipMemcpy(L.d_member, member.data(), member.size(), hipMemcpyHostToDevice));
         L.member = member;
     }
+    *Pout = P; *Lout = &L; *nGout = nG;
+    return 0;
+}
+
+static int wall_integrate(const char* who, int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out,
+                          bool outOnDevice)
+{
+    if (need_ready()) return 1;
+    if (!par || !out) return fail("%s: par and out must not be NULL", who);
+    WiPar P;
+    WiLevel* Lp;
+    int nG;
+    if (wi_setup(who, level, par, nGroups, famLists, ldFam, true, &P, &Lp, &nG)) return 1;
+    WiLevel& L = *Lp;
+    const int nface = (int)L.faces.size();
+    LevelTab t;
+    if (level_tab(level, &t)) return 1;
     double* d_out = outOnDevice ? out : L.d_out;
     launch_wallint(t.tab, L.d_faces, nface, L.maxOwned, P, L.part, L.d_member, nG, d_out, g_stream);
     L.integrated = true;
@@ -6310,6 +6348,278 @@ int adflow_gpu_jacfree_solve(int level, unsigned flags, const double* b, double*
     const Stage s{n, (double*)buf.p};
     if (s.in(0, b) || (useGuess && s.in(1, x))) return 1;
     return jf_solve_run(level, S, s[0], s[1], n, restart, maxIts, rtol, atol, useGuess, its, rnorm0, rnorm) || s.out(x, 1) || s.done();
+}
+
+// ---- derivatives of the surface integration with respect to the state (kernels_wallint.hip in namespace adj) ----------------------
+// wallIntegrationFace_d behind the front of block_res_state_d: what master_d adds to funcsDot for the wall subfaces, and -- as a
+// coloured sweep of the same pass -- what master_b adds to wbar.  The functions depend on the state through the closures, the boundary
+// conditions, the nodal gradients of the wall node planes and the stress of the wall faces: the pass runs those on the dual arrays and
+// nothing else (no time step, no flux kernel).  The flags select the state range as for the matrix-free products.
+static int wd_check_flags(const char* who, unsigned flags)
+{
+    if (flags & (ADFLOW_JAC_PC | ADFLOW_JAC_VISC_PC | ADFLOW_JAC_APPROX_SA))
+        return fail("%s: ADFLOW_JAC_PC, ADFLOW_JAC_VISC_PC and ADFLOW_JAC_APPROX_SA select approximations of the fluxes, which the "
+                    "derivatives of the surface integration do not run (flags 0x%x)", who, flags);
+    return 0;
+}
+
+// turbulence and mean-flow boundary conditions and the nodal gradients of the wall node planes, on the dual arrays the seed launch
+// filled (state and closures).  The dual face kernels take the stress from there
+static int wd_front_enqueue(int level, const JfSetup& S, const KParams& kp)
+{
+    if (DUAL.bcs(level, kp, S.turbBC)) return 1;
+    BcPlan* pl;
+    if (bc_plan(level, &pl)) return 1;
+    if (g_opts.equations != ADFLOW_EULER) ad_launch_wall_node_grad(g_ad_tab, pl->d_ent, pl->d_order, pl->wall, g_stream);
+    return 0;
+}
+
+// the dual arrays and the scratch of the vector.  Unlike jf_prepare no whalo2 of the state: like the integration itself the pass reads
+// the halos of the state as they are on the device (whalo2 would also re-form the energy of the owned cells), and writes none of them
+static int wd_prepare(const char* who, int level, const JfSetup& S, bool sync)
+{
+    if (ad_prepare(level, sync)) return 1;
+    return jm_layout(g_jf, level, S.J.nState, 1, false, who);
+}
+
+static int wd_fwd_enqueue(const char* who, int level, const JfSetup& S, const WiPar& P, WiLevel& L, int nG, const double* d_x, double* d_out,
+                          double* d_outDot, bool sync)
+{
+    const int nface = (int)L.faces.size();
+    if (nface == 0) {                  // no wall subface: the neutral elements and a zero derivative
+        ad_launch_wallint_fwd(nullptr, nullptr, 0, 0, P, KParams(), nullptr, L.d_member, nG, d_out, d_outDot, g_stream);
+        return 0;
+    }
+    if (!L.partD) {
+        const size_t nwg = (size_t)wallint_groups_per_face(L.maxOwned) * nface;
+        if (wi_alloc(L, &L.partD, 2 * sizeof(double) * WI_NQ * nwg)) return 1;
+    }
+    int rc = wd_prepare(who, level, S, sync);
+    const KParams kp = res_kparams(level, S.resFlags);
+    CommPattern* cp = nullptr;
+    if (!rc) rc = jm_pattern_of(level, S.J.lStart, S.J.nState, who, &cp);
+    if (!rc) rc = jm_scatter_x(g_jf, d_x, 1, 0) || jm_exchange_x(g_jf, cp, 1);
+    if (!rc) {
+        for (auto& kv : g_blocks)
+            if (std::get<0>(kv.first) == level)
+                ad_launch_seed_vector(kv.second->v, g_ad[kv.second].v, g_jf.h[std::get<2>(kv.first)].xs, S.J.lStart, S.J.nState, kp, g_stream);
+        rc = wd_front_enqueue(level, S, kp);
+    }
+    if (!rc)
+        ad_launch_wallint_fwd(g_ad_tab, L.d_faces, nface, L.maxOwned, P, kp, L.partD, L.d_member, nG, d_out, d_outDot, g_stream);
+    return jf_finish(rc);
+}
+
+static int wd_fwd(const char* who, int level, unsigned flags, const double* x, long n, const double* par, int nGroups, const int32_t* famLists,
+                  int ldFam, double* out, double* outDot, bool dev)
+{
+    if (need_ready()) return 1;
+    if (!x || !outDot) return fail("%s: %s is NULL", who, !x ? "x" : "outDot");
+    if (wd_check_flags(who, flags)) return 1;
+    JfSetup S;
+    if (jf_check(who, level, flags, x, outDot, n, &S)) return 1;
+    WiPar P;
+    WiLevel* L;
+    int nG;
+    if (wi_setup(who, level, par, nGroups, famLists, ldFam, false, &P, &L, &nG)) return 1;
+    const size_t no = (size_t)ADFLOW_WALLINT_STRIDE * nG;
+    if (dev) {
+        if (wd_fwd_enqueue(who, level, S, P, *L, nG, x, out, outDot, !g_async)) return 1;
+        return sync_and_check();
+    }
+    if (nG > L->dotGroups) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        if (L->d_dot) {                 // the smaller buffer goes: the record holds one
+            L->allocs.erase(std::find(L->allocs.begin(), L->allocs.end(), (void*)L->d_dot));
+            (void)hipFree(L->d_dot);
+            L->bytes -= (int64_t)(2 * sizeof(double) * ADFLOW_WALLINT_STRIDE) * L->dotGroups;
+            L->d_dot = nullptr; L->dotGroups = 0;
+        }
+        void* raw = nullptr;
+        if (wi_alloc(*L, &raw, 2 * sizeof(double) * no)) return 1;
+        L->d_dot = (double*)raw;
+        L->dotGroups = nG;
+    }
+    Stage s;
+    if (stage_open(&s, n, 1) || s.in(0, x)) return 1;
+    if (wd_fwd_enqueue(who, level, S, P, *L, nG, s[0], L->d_dot, L->d_dot + no, false)) return 1;
+    if (out && s.scalars(out, L->d_dot, (long)no)) return 1;
+    return s.scalars(outDot, L->d_dot + no, (long)no) || s.done();
+}
+
+int adflow_gpu_wall_integrate_fwd(int level, unsigned flags, const double* x, long n, const double* par, int nGroups, const int32_t* famLists,
+                                  int ldFam, double* out, double* outDot)
+{
+    return wd_fwd("wall_integrate_fwd", level, flags, x, n, par, nGroups, famLists, ldFam, out, outDot, false);
+}
+
+int adflow_gpu_wall_integrate_fwd_dev(int level, unsigned flags, const double* d_x, long n, const double* par, int nGroups,
+                                      const int32_t* famLists, int ldFam, double* d_out, double* d_outDot)
+{
+    return wd_fwd("wall_integrate_fwd_dev", level, flags, d_x, n, par, nGroups, famLists, ldFam, d_out, d_outDot, true);
+}
+
+// the buffers of the transposed product for nS state variables and nv weight sets: the halo'd result ys of every block (nS x nv
+// components), the level's table per set, the weights and the contracted derivatives of the faces
+static int wd_bar_layout(const char* who, int level, WiLevel& L, int nS, int nv)
+{
+    if (L.barTab && L.barNS == nS && L.barNv == nv) return 0;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    for (void* p : L.barAllocs) (void)hipFree(p);
+    L.bytes -= L.barBytes;
+    L.barBytes = 0;
+    L.barAllocs.clear(); L.barYs.clear(); L.barYsBytes.clear();
+    L.barTab = nullptr; L.d_wq = L.d_g = nullptr; L.wq.clear(); L.barNS = L.barNv = 0;
+    auto alloc = [&](void** p, size_t bytes) {
+        if (hipMalloc(p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("%s: cannot allocate %zu bytes for the transposed product of %d weight sets", who, bytes, nv);
+        }
+        L.barAllocs.push_back(*p);
+        L.barBytes += (int64_t)bytes;
+        L.bytes += (int64_t)bytes;
+        return 0;
+    };
+    int maxnn = 0;
+    for (auto& kv : g_blocks)
+        if (std::get<0>(kv.first) == level) maxnn = std::max(maxnn, std::get<2>(kv.first));
+    const size_t nt = (size_t)maxnn + 1;
+    std::vector<JmBlk> h(nt);
+    memset(h.data(), 0, sizeof(JmBlk) * nt);
+    L.barYs.assign(nt, nullptr);
+    L.barYsBytes.assign(nt, 0);
+    L.barNx = L.barNy = L.barNz = 0;
+    for (auto& kv : g_blocks) {
+        if (std::get<0>(kv.first) != level) continue;
+        const BlkView& v = kv.second->v;
+        void* raw = nullptr;
+        if (alloc(&raw, (size_t)v.nbox * nS * nv * sizeof(double) + 256)) return 1;
+        JmBlk& q = h[std::get<2>(kv.first)];
+        q.nx = v.nx; q.ny = v.ny; q.nz = v.nz; q.il = v.il; q.jl = v.jl; q.kl = v.kl; q.ib = v.ib; q.jb = v.jb; q.kb = v.kb;
+        q.ldi = v.ldi; q.ldk = v.ldk; q.nbox = v.nbox;
+        q.ys = (double*)raw + ADF_PAD0;
+        L.barYs[std::get<2>(kv.first)] = (double*)raw;
+        L.barYsBytes[std::get<2>(kv.first)] = (size_t)v.nbox * nS * nv * sizeof(double) + 256;
+        L.barNx = std::max(L.barNx, v.nx); L.barNy = std::max(L.barNy, v.ny); L.barNz = std::max(L.barNz, v.nz);
+    }
+    long off = 0;
+    for (auto& q : h) { q.vecOff = off; off += (long)q.nx * q.ny * q.nz * nS; }
+    std::vector<JmBlk> ht(nt * nv);
+    for (int c = 0; c < nv; ++c)
+        for (size_t q = 0; q < nt; ++q) {
+            ht[c * nt + q] = h[q];
+            if (h[q].ys) ht[c * nt + q].ys += (size_t)h[q].nbox * nS * c;
+        }
+    void* raw = nullptr;
+    if (alloc(&raw, sizeof(JmBlk) * ht.size())) return 1;
+    L.barTab = (JmBlk*)raw;
+    HIPCHK(hipMemcpy(L.barTab, ht.data(), sizeof(JmBlk) * ht.size(), hipMemcpyHostToDevice));
+    if (alloc(&raw, sizeof(double) * std::max<size_t>(1, (size_t)nv * L.faces.size() * WI_NQ))) return 1;
+    L.d_wq = (double*)raw;
+    if (alloc(&raw, sizeof(double) * std::max<size_t>(1, (size_t)nv * L.nOwned))) return 1;
+    L.d_g = (double*)raw;
+    L.barSlots = maxnn; L.barNS = nS; L.barNv = nv;
+    return 0;
+}
+
+static int wd_bwd_enqueue(const char* who, int level, const JfSetup& S, const WiPar& P, WiLevel& L, const std::vector<double>& wq, int nRhs,
+                          double* d_wbar, long n, long ld, bool sync)
+{
+    const int nface = (int)L.faces.size();
+    if (nface == 0) {
+        for (int r = 0; r < nRhs; ++r) HIPCHK(hipMemsetAsync(d_wbar + r * ld, 0, sizeof(double) * n, g_stream));
+        return 0;
+    }
+    const int nS = S.J.nState;
+    if (wd_bar_layout(who, level, L, nS, nRhs)) return 1;
+    if (wq != L.wq) {
+        HIPCHK(hipStreamSynchronize(g_stream));        // (the kernels of an earlier enqueue-only call may still read the weights)
+        HIPCHK(hipMemcpy(L.d_wq, wq.data(), sizeof(double) * wq.size(), hipMemcpyHostToDevice));
+        L.wq = wq;
+    }
+    CommPattern* cp = nullptr;
+    if (jm_pattern_of(level, S.J.lStart, nS, who, &cp)) return 1;
+    if (cp && (!cp->sends.empty() || !cp->recvs.empty())) return fail("%s: the level exchanges halos with other ranks (one rank only)", who);
+    if (cp && jm_acc_lists(cp)) return 1;
+    for (size_t q = 0; q < L.barYs.size(); ++q)
+        if (L.barYs[q]) HIPCHK(hipMemsetAsync(L.barYs[q], 0, L.barYsBytes[q], g_stream));
+    // (from here on every exit goes through jf_finish, which gives the slab back after an error)
+    int rc = wd_prepare(who, level, S, sync);
+    if (!rc) {
+        const KParams kp = res_kparams(level, S.resFlags);
+        const size_t nt = (size_t)L.barSlots + 1;
+        JacSpec C = S.J;
+        C.ca = 1; C.cb = WI_CM; C.cc = WI_CM * WI_CM; C.cn = WI_NCOL; C.cm = WI_CM;
+        for (int l = S.J.lStart; l < S.J.lStart + nS && !rc; ++l)
+            for (int col = 0; col < WI_NCOL && !rc; ++col) {
+                for_level(level, [&](Block* b) {
+                    ad_launch_seed_closures(b->v, g_ad[b].v, l, col, C, kp, g_stream, false);
+                    return 0;
+                });
+                rc = wd_front_enqueue(level, S, kp);
+                if (rc) break;
+                ad_launch_wallint_bar(g_ad_tab, L.d_faces, nface, L.maxOwned, P, kp, L.d_wq, nRhs, L.nOwned, L.d_g, g_stream);
+                launch_wallint_credit(L.d_faces, nface, L.maxBox, L.barTab, (long)nt, nRhs, l - S.J.lStart, col, L.d_g, L.nOwned, g_stream);
+            }
+        for (int r = 0; r < nRhs && !rc; ++r) {
+            // the reverse exchange of jacobian_mult: every halo with a donor is added to it in the fixed order of the donor's list
+            if (cp) launch_jac_halo_accumulate(L.barTab + r * nt, cp->acc[0], nS, nullptr, 0, g_stream);
+            launch_jm_gather(L.barTab + r * nt, L.barSlots, L.barNx, L.barNy, L.barNz, nS, d_wbar + r * ld, g_stream);
+        }
+    }
+    return jf_finish(rc);
+}
+
+static int wd_bwd(const char* who, int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
+                  const double* outBar, int nRhs, double* wbar, long n, long ld, bool dev)
+{
+    if (need_ready()) return 1;
+    if (!outBar || !wbar) return fail("%s: %s is NULL", who, !outBar ? "outBar" : "wbar");
+    if (nRhs < 1 || nRhs > ADFLOW_GPU_MAX_NVEC) return fail("%s: nRhs = %d; one call takes 1 to %d weight sets", who, nRhs, ADFLOW_GPU_MAX_NVEC);
+    if (wd_check_flags(who, flags)) return 1;
+    JfSetup S;
+    if (jf_check(who, level, flags, outBar, wbar, n, &S)) return 1;
+    if (ld < n) return fail("%s: ld = %ld, but a column holds n = %ld entries (ld >= n)", who, ld, n);
+    WiPar P;
+    WiLevel* L;
+    int nG;
+    if (wi_setup(who, level, par, nGroups, famLists, ldFam, false, &P, &L, &nG)) return 1;
+    // the weight of quantity q of subface f in set r: outBar summed over the groups the subface belongs to
+    static const int entryOf[WI_NQ] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 44, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 17, 63};
+    const int nface = (int)L->faces.size();
+    std::vector<double> wq((size_t)nRhs * nface * WI_NQ, 0.0);
+    for (int r = 0; r < nRhs; ++r)
+        for (int g = 0; g < nG; ++g) {
+            const double* ob = outBar + ((size_t)r * nG + g) * ADFLOW_WALLINT_STRIDE;
+            if (ob[17] != 0.0 || ob[63] != 0.0)
+                return fail("%s: weight set %d, group %d: entry %d (%s) has no derivative, its weight must be zero", who, r + 1, g + 1,
+                            ob[17] != 0.0 ? 17 : 63, ob[17] != 0.0 ? "yplusMax" : "the minimum of Cp");
+            for (int f = 0; f < nface; ++f) {
+                if (!L->member[(size_t)g * nface + f]) continue;
+                for (int q = 0; q < WI_YPLUS; ++q) wq[((size_t)r * nface + f) * WI_NQ + q] += ob[entryOf[q]];
+            }
+        }
+    if (dev) {
+        if (wd_bwd_enqueue(who, level, S, P, *L, wq, nRhs, wbar, n, ld, !g_async)) return 1;
+        return sync_and_check();
+    }
+    DevBuf buf;
+    HIPCHK(hipMalloc(&buf.p, sizeof(double) * std::max<size_t>(1, (size_t)nRhs * n)));
+    const Stage s{n, (double*)buf.p};
+    if (wd_bwd_enqueue(who, level, S, P, *L, wq, nRhs, s[0], n, n, false)) return 1;
+    return stage_out_columns(s, wbar, ld, 0, nRhs) || s.done();
+}
+
+int adflow_gpu_wall_integrate_bwd(int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
+                                  const double* outBar, int nRhs, double* wbar, long n, long ld)
+{
+    return wd_bwd("wall_integrate_bwd", level, flags, par, nGroups, famLists, ldFam, outBar, nRhs, wbar, n, ld, false);
+}
+
+int adflow_gpu_wall_integrate_bwd_dev(int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
+                                      const double* outBar, int nRhs, double* d_wbar, long n, long ld)
+{
+    return wd_bwd("wall_integrate_bwd_dev", level, flags, par, nGroups, famLists, ldFam, outBar, nRhs, d_wbar, n, ld, true);
 }
 
 // nvec right-hand sides on the assembled matrix with the selected factor, in lock-step: every iteration is ONE application of M^-1

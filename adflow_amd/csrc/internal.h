@@ -583,6 +583,7 @@ struct WiFace {
     const double* tauq;       // viscous walls: the stored stress (BcFaceDev::tauq); NULL on an Euler wall
     const signed char* iblank;   // per owned face cell, NULL = all ones
     double* fpv;              // BCData%Fp(3), %Fv(3), %area over the owned face cells, component-major
+    long goff;                // the first owned face of the subface among all owned wall faces of the level (table order)
 };
 // the parameters of wallIntegrationFace, lengths already times LRef
 struct WiPar {
@@ -600,6 +601,17 @@ inline int wallint_groups_per_face(long maxOwned) { return (int)((maxOwned + WI_
 // ADFLOW_WALLINT_STRIDE doubles on the device
 void launch_wallint(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const WiPar& P, double* part,
                     const unsigned char* member, int nGroups, double* out, hipStream_t s);
+// derivatives of the integration (adflow_gpu_wall_integrate_fwd / _bwd).  The transposed product is a coloured forward-mode sweep over
+// the front of the evaluation: the colour of a cell is (i mod WI_CM) + WI_CM (j mod WI_CM) + WI_CM^2 (k mod WI_CM), local to its block,
+// halos included.  A term of a face depends on cells at most WI_REACH from it in the plane of the wall and on the WI_DEPTH layers from
+// the first halo to the third interior cell along the normal: a box of 5 x 5 x 4 cells, in which the cube of WI_CM = 5 gives every
+// cell its own colour whichever way the wall faces.  The treatments implemented today (constant / linear pressure, normal momentum)
+// reach one cell in the plane and the second interior layer; the box also holds what the reference's quadratic extrapolation would
+// read (the third layer; at an edge of two walls a second cell in the plane).  DESIGN 8g has the price of that margin.
+enum { WI_CM = 5, WI_NCOL = WI_CM * WI_CM * WI_CM, WI_REACH = 2, WI_DEPTH = 4 };
+struct JmBlk;
+void launch_wallint_credit(const WiFace* faces, int nface, long maxBox, const JmBlk* tab, long nt, int nRhs, int lq, int col,
+                           const double* g, long ldg, hipStream_t s);
 
 // The level-batched launches fold (block slot, plane) into gridDim.z, which HIP limits to 65535: a launcher whose level has more
 // slots than fit calls itself on consecutive slot ranges (the kernels index the table relative to the pointer they get).
@@ -736,5 +748,12 @@ void ad_launch_sa_march(const BlkView* tab, const int4* tiles, int ntiles, const
 void ad_launch_visc_gf(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
 int ad_launch_roe_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
 int ad_launch_inviscid_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);
+// the dual front of the surface integration (kernels_viscous.hip and kernels_wallint.hip in namespace adj): the nodal gradients of the
+// wall node planes; the forward product (part: WI_NQ x workgroups dual numbers); the face kernel of the transposed product
+void ad_launch_wall_node_grad(const BlkView* tab, const BcEntry* ent, const int* order, const BcPhase& ph, hipStream_t s);
+void ad_launch_wallint_fwd(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const WiPar& P, const KParams& kp, void* part,
+                           const unsigned char* member, int nGroups, double* out, double* outDot, hipStream_t s);
+void ad_launch_wallint_bar(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const WiPar& P, const KParams& kp,
+                           const double* wq, int nRhs, long ldg, double* g, hipStream_t s);
 void ad_launch_selftest_math(int which, const double* x, const double* a, long n, double* y, double* dy, hipStream_t s);
 void ad_launch_visc_march_approx(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);

@@ -254,6 +254,7 @@ __global__ __launch_bounds__(256) void k_jf_readout(BlkView b, adf_real8* __rest
 #include "kernels_bc.hip"
 #include "kernels_sa.hip"
 #include "kernels_viscous.hip"
+#include "kernels_wallint.hip"
 #include "kernels_pc_march.hip"
 #include "kernels_sa_march.hip"
 #include "kernels_roe_march.hip"
@@ -347,5 +348,19 @@ void ad_launch_visc_march_approx(const BlkView* tab, const int4* tiles, int ntil
 int ad_launch_inviscid_march(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s)
 {
     return adj::launch_inviscid_march(ADV(tab), tiles, ntiles, kp, s);
+}
+void ad_launch_wall_node_grad(const BlkView* tab, const BcEntry* ent, const int* order, const BcPhase& ph, hipStream_t s)
+{
+    adj::launch_wall_node_grad(ADV(tab), ent, order, ph, s);
+}
+void ad_launch_wallint_fwd(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const WiPar& P, const KParams& kp, void* part,
+                           const unsigned char* member, int nGroups, double* out, double* outDot, hipStream_t s)
+{
+    adj::launch_wallint_fwd(ADV(tab), faces, nface, maxOwned, P, kp, part, member, nGroups, out, outDot, s);
+}
+void ad_launch_wallint_bar(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const WiPar& P, const KParams& kp,
+                           const double* wq, int nRhs, long ldg, double* g, hipStream_t s)
+{
+    adj::launch_wallint_bar(ADV(tab), faces, nface, maxOwned, P, kp, wq, nRhs, ldg, g, s);
 }
 #undef ADV

@@ -273,7 +273,6 @@ __global__ __launch_bounds__(VS_BX* VS_BY) void k_viscous(BlkView b, KParams kp)
     }
 }
 
-#ifndef ADF_AD_BUILD
 // Nodal gradients of the node plane ON a viscous-wall subface: the only gradients the stored wall stress reads (the four nodes of a
 // wall face, fluxes.F90:2849-2879).  k_visc_gf keeps its gradients in LDS; instead of writing all twelve of every node of the block
 // for the sake of the wall faces (96 B per cell), the few nodes of the wall planes are formed again here, in the reference's own
@@ -301,6 +300,16 @@ __global__ __launch_bounds__(256) void k_wall_node_grad(const BlkView* __restric
     node_gradient(b, c);
 }
 
+#ifdef ADF_AD_BUILD
+// forward mode (adflow_gpu_wall_integrate_fwd / _bwd): the dual gradients of the wall node planes; the dual face kernel of
+// kernels_wallint.hip takes the stress from them through visc_face itself, nothing is stored
+void launch_wall_node_grad(const BlkView* tab, const BcEntry* ent, const int* order, const BcPhase& ph, hipStream_t s)
+{
+    if (ph.count <= 0 || ph.maxCells <= 0) return;
+    hipLaunchKernelGGL(k_wall_node_grad, dim3((unsigned)((ph.maxCells + 255) / 256), ph.count, 1), dim3(256, 1, 1), 0, s, tab, ent,
+                       order + ph.first);
+}
+#else
 // Stress tensor and heat flux vector on the faces of the viscous-wall subfaces: what viscousFlux stores in
 // viscSubface(:)%tau / %q when storeWallTensor is set (rkStage == 0 on the ground level, fluxes.F90:2586-2592,
 // 2861-2892, 3155-3185, 3450-3480).  Same face evaluation as the flux kernels, from the nodal gradients they left in

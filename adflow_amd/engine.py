@@ -684,6 +684,51 @@ class Engine:
         self._chk(self.lib.adflow_gpu_wall_integrate_dev(level, par.ctypes.data, n, None if fl is None else fl.ctypes.data, ld,
                                                          ctypes.c_void_p(d_out)))
 
+    # ---- derivatives of the integration with respect to the state (master_d / master_b for the wall subfaces) ----
+    def _wallDerivArgs(self, par, groups, frozenTurb, useTurbOnly):
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        assert par.size == capi.WALLINT_NPAR
+        n, fl, ld = self._famLists(groups)
+        flags = self._jacFreeFlags(False, frozenTurb, useTurbOnly, False, False)
+        return par, n, fl, None if fl is None else fl.ctypes.data, ld, flags
+
+    def wallIntegrateFwd(self, x, par, groups=None, level: int = 1, frozenTurb=False, useTurbOnly=False, values=True):
+        """(out, outDot), each (nGroups, 64): the integration and its derivative in the direction x (a vector in the layout of
+        jacFreeMult) by one forward-mode pass over the front of the evaluation; values=False: out is not asked for (None)"""
+        par, n, fl, pfl, ld, flags = self._wallDerivArgs(par, groups, frozenTurb, useTurbOnly)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.zeros((max(n, 1), capi.WALLINT_STRIDE)) if values else None
+        dot = np.zeros((max(n, 1), capi.WALLINT_STRIDE))
+        self._chk(self.lib.adflow_gpu_wall_integrate_fwd(level, flags, x.ctypes.data, x.size, par.ctypes.data, n, pfl, ld,
+                                                         None if out is None else out.ctypes.data, dot.ctypes.data))
+        return out, dot
+
+    def wallIntegrateFwdDev(self, d_x: int, n: int, par, d_out: int, d_outDot: int, groups=None, level: int = 1, frozenTurb=False,
+                            useTurbOnly=False):
+        """the same on device pointers (d_out may be 0); honours set_async"""
+        par, ng, fl, pfl, ld, flags = self._wallDerivArgs(par, groups, frozenTurb, useTurbOnly)
+        self._chk(self.lib.adflow_gpu_wall_integrate_fwd_dev(level, flags, ctypes.c_void_p(d_x), int(n), par.ctypes.data, ng, pfl, ld,
+                                                             ctypes.c_void_p(d_out) if d_out else None, ctypes.c_void_p(d_outDot)))
+
+    def wallIntegrateBwd(self, outBar, n: int, par, groups=None, level: int = 1, frozenTurb=False, useTurbOnly=False, ld=None, fill=0.0):
+        """outBar: (nRhs, nGroups, 64) weights (or (nGroups, 64) for one set) -> wbar (nRhs, ld), row r = sum outBar[r] d out / d w in its
+        first n entries: the right-hand sides of the adjoint.  ld > n leaves a padding the call does not touch (it keeps `fill`)"""
+        par, ng, fl, pfl, ldf, flags = self._wallDerivArgs(par, groups, frozenTurb, useTurbOnly)
+        ob = np.ascontiguousarray(outBar, dtype=np.float64).reshape(-1, max(ng, 1), capi.WALLINT_STRIDE)
+        ld = int(n) if ld is None else int(ld)
+        wbar = np.full((ob.shape[0], max(ld, 1)), float(fill))
+        self._chk(self.lib.adflow_gpu_wall_integrate_bwd(level, flags, par.ctypes.data, ng, pfl, ldf, ob.ctypes.data, ob.shape[0],
+                                                         wbar.ctypes.data, int(n), ld))
+        return wbar
+
+    def wallIntegrateBwdDev(self, outBar, d_wbar: int, n: int, ld: int, par, groups=None, level: int = 1, frozenTurb=False,
+                            useTurbOnly=False):
+        """the same into device vectors ld doubles apart (outBar stays a host array); honours set_async"""
+        par, ng, fl, pfl, ldf, flags = self._wallDerivArgs(par, groups, frozenTurb, useTurbOnly)
+        ob = np.ascontiguousarray(outBar, dtype=np.float64).reshape(-1, max(ng, 1), capi.WALLINT_STRIDE)
+        self._chk(self.lib.adflow_gpu_wall_integrate_bwd_dev(level, flags, par.ctypes.data, ng, pfl, ldf, ob.ctypes.data, ob.shape[0],
+                                                             ctypes.c_void_p(d_wbar), int(n), int(ld)))
+
     def wallForces(self, shape, mm: int, nn: int = 1, level: int = 1, sps: int = 1):
         """BCData(mm)%Fp, %Fv, %area of wall subface mm (1-based) as the last wallIntegrate left them, over its owned face cells
         `shape` = (n1, n2)"""

@@ -175,6 +175,24 @@ module adflowGpuShim
             integer(c_int32_t), intent(in) :: famLists(*)
             type(c_ptr), value :: out                      ! device memory, nGroups x 64 doubles
         end function
+        integer(c_int) function adflow_gpu_wall_integrate_fwd_dev(level, flags, x, n, par, nGroups, famLists, ldFam, out, outDot) &
+            bind(C, name="adflow_gpu_wall_integrate_fwd_dev")
+            import :: c_int, c_int32_t, c_double, c_ptr, c_long
+            integer(c_int), value :: level, flags, nGroups, ldFam
+            type(c_ptr), value :: x, out, outDot           ! device memory: the vector; nGroups x 64 doubles each (out may be null)
+            integer(c_long), value :: n
+            real(c_double), intent(in) :: par(*)
+            integer(c_int32_t), intent(in) :: famLists(*)
+        end function
+        integer(c_int) function adflow_gpu_wall_integrate_bwd_dev(level, flags, par, nGroups, famLists, ldFam, outBar, nRhs, wbar, n, ld) &
+            bind(C, name="adflow_gpu_wall_integrate_bwd_dev")
+            import :: c_int, c_int32_t, c_double, c_ptr, c_long
+            integer(c_int), value :: level, flags, nGroups, ldFam, nRhs
+            real(c_double), intent(in) :: par(*), outBar(*)   ! outBar: host memory, nRhs x nGroups x 64
+            integer(c_int32_t), intent(in) :: famLists(*)
+            type(c_ptr), value :: wbar                     ! device memory, nRhs vectors ld doubles apart
+            integer(c_long), value :: n, ld
+        end function
         integer(c_int) function adflow_gpu_download_wall_forces(nn, level, sps, mm, Fp, Fv, area) &
             bind(C, name="adflow_gpu_download_wall_forces")
             import :: c_int, c_ptr
@@ -1062,26 +1080,13 @@ contains
                       "gpuBCSetFamilies")
     end subroutine gpuBCSetFamilies
 
-    ! The wall part of integrateSurfaces (surfaceIntegrations.F90:1264-1361) for one family list, on the device: adds this process's
-    ! contributions of every wall subface whose family is in famList to localValues (the maximum for iyPlus), as the loop over
-    ! wallIntegrationFace does.  cpMinLocal: the minimum of Cp over those faces, what computeCpMinFamily reduces over the processes
-    ! into cpmin_family(sps) before the call that is to give the KS sum.  The parameters come from inputPhysics / inputCostFunctions.
-    subroutine gpuWallIntegrate(localValues, famList, sps, cpMinLocal)
-        use constants, only: nLocalValues, iyPlus
+    ! the parameter array of the integration entries from inputPhysics / inputCostFunctions (ADFLOW_WALLINT_* of the header)
+    subroutine gpuWallPar(par, sps)
         use inputPhysics, only: MachCoef, pointRef, momentAxis, velDirFreeStream, cavitationnumber, cpmin_rho, cpmin_family
         use inputCostFunctions, only: sepSensorOffset, sepSensorSharpness, computeCavitation, cavSensorOffset, &
                                       cavSensorSharpness, cavExponent
-        real(kind=realType), dimension(nLocalValues), intent(inout) :: localValues
-        integer(kind=intType), dimension(:), intent(in) :: famList
+        real(c_double), intent(out) :: par(0:WALLINT_NPAR - 1)
         integer(kind=intType), intent(in) :: sps
-        real(kind=realType), intent(out), optional :: cpMinLocal
-        real(c_double) :: par(0:WALLINT_NPAR - 1), out(0:WALLINT_STRIDE - 1)
-        integer(c_int32_t), allocatable :: fl(:)
-        integer :: i, n
-        n = size(famList)
-        allocate (fl(n + 1))
-        fl(1) = int(n, c_int32_t)
-        fl(2:n + 1) = int(famList, c_int32_t)
         par = 0.0_c_double
         par(0) = MachCoef
         par(1:3) = pointRef
@@ -1097,6 +1102,26 @@ contains
         par(19) = real(cavExponent, c_double)
         par(20) = cpmin_rho
         if (allocated(cpmin_family)) par(21) = cpmin_family(sps)
+    end subroutine gpuWallPar
+
+    ! The wall part of integrateSurfaces (surfaceIntegrations.F90:1264-1361) for one family list, on the device: adds this process's
+    ! contributions of every wall subface whose family is in famList to localValues (the maximum for iyPlus), as the loop over
+    ! wallIntegrationFace does.  cpMinLocal: the minimum of Cp over those faces, what computeCpMinFamily reduces over the processes
+    ! into cpmin_family(sps) before the call that is to give the KS sum.  The parameters come from inputPhysics / inputCostFunctions.
+    subroutine gpuWallIntegrate(localValues, famList, sps, cpMinLocal)
+        use constants, only: nLocalValues, iyPlus
+        real(kind=realType), dimension(nLocalValues), intent(inout) :: localValues
+        integer(kind=intType), dimension(:), intent(in) :: famList
+        integer(kind=intType), intent(in) :: sps
+        real(kind=realType), intent(out), optional :: cpMinLocal
+        real(c_double) :: par(0:WALLINT_NPAR - 1), out(0:WALLINT_STRIDE - 1)
+        integer(c_int32_t), allocatable :: fl(:)
+        integer :: i, n
+        n = size(famList)
+        allocate (fl(n + 1))
+        fl(1) = int(n, c_int32_t)
+        fl(2:n + 1) = int(famList, c_int32_t)
+        call gpuWallPar(par, sps)
         call gpuCheck(adflow_gpu_wall_integrate(1_c_int, par, 1_c_int, fl, int(n + 1, c_int), out), "gpuWallIntegrate")
         do i = 1, nLocalValues
             if (i == iyPlus) then
@@ -1107,6 +1132,50 @@ contains
         end do
         if (present(cpMinLocal)) cpMinLocal = out(WALLINT_STRIDE - 1)
     end subroutine gpuWallIntegrate
+
+    ! The wall part of integrateSurfaces_d for one family list (master_d, computeMatrixFreeProductFwd): localValuesd = the derivative of
+    ! this process's wall contributions to localValues in the direction of the device vector xDev (the wd of the product, n entries in
+    ! the layout of gpuJacFreeMult; flags: the ADFLOW_JAC_* state range).  dotDev: device memory for 64 doubles
+    subroutine gpuWallIntegrateFwd(flags, xDev, n, famList, sps, dotDev)
+        integer(kind=intType), intent(in) :: flags, n, sps
+        type(c_ptr), intent(in) :: xDev, dotDev
+        integer(kind=intType), dimension(:), intent(in) :: famList
+        real(c_double) :: par(0:WALLINT_NPAR - 1)
+        integer(c_int32_t), allocatable :: fl(:)
+        integer :: nf
+        nf = size(famList)
+        allocate (fl(nf + 1))
+        fl(1) = int(nf, c_int32_t)
+        fl(2:nf + 1) = int(famList, c_int32_t)
+        call gpuWallPar(par, sps)
+        call gpuCheck(adflow_gpu_wall_integrate_fwd_dev(1_c_int, int(flags, c_int), xDev, int(n, c_long), par, 1_c_int, fl, &
+                                                        int(nf + 1, c_int), c_null_ptr, dotDev), "gpuWallIntegrateFwd")
+    end subroutine gpuWallIntegrateFwd
+
+    ! The wall part of integrateSurfaces_b for one family list (master_b, computeMatrixFreeProductBwd): column r of the device array
+    ! wbarDev (nRhs vectors ld doubles apart) = sum_e localValuesd(e, r) d localValues(e) / d w -- localValuesd(:, r) is what
+    ! getCostFunctions_b makes of funcsBar for objective r -- the right-hand sides of gpuGmresSolve(transpose)
+    subroutine gpuWallIntegrateBwd(flags, localValuesd, nRhs, famList, sps, wbarDev, n, ld)
+        use constants, only: nLocalValues
+        integer(kind=intType), intent(in) :: flags, nRhs, sps, n, ld
+        real(kind=realType), dimension(nLocalValues, nRhs), intent(in) :: localValuesd
+        integer(kind=intType), dimension(:), intent(in) :: famList
+        type(c_ptr), intent(in) :: wbarDev
+        real(c_double) :: par(0:WALLINT_NPAR - 1)
+        real(c_double), allocatable :: ob(:, :)
+        integer(c_int32_t), allocatable :: fl(:)
+        integer :: nf
+        nf = size(famList)
+        allocate (fl(nf + 1), ob(WALLINT_STRIDE, nRhs))
+        fl(1) = int(nf, c_int32_t)
+        fl(2:nf + 1) = int(famList, c_int32_t)
+        ob = 0.0_c_double
+        ob(1:nLocalValues, :) = localValuesd
+        call gpuWallPar(par, sps)
+        call gpuCheck(adflow_gpu_wall_integrate_bwd_dev(1_c_int, int(flags, c_int), par, 1_c_int, fl, int(nf + 1, c_int), ob, &
+                                                        int(nRhs, c_int), wbarDev, int(n, c_long), int(ld, c_long)), &
+                      "gpuWallIntegrateBwd")
+    end subroutine gpuWallIntegrateBwd
 
     ! actuatorRegions(1:nActuatorRegions) -> device (after addActuatorRegion; again when force / heat change)
     subroutine gpuRegisterActuatorRegions()

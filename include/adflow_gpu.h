@@ -406,7 +406,42 @@ int adflow_gpu_download_wall_stress(int nn, int level, int sps, int mm, double* 
  * adflow_gpu_block_release and adflow_gpu_release_all free them too.
  * Not here: flowIntegrationFace (mass flow through in- and outflow faces), zippers, user surfaces, actuator regions;
  * computeSepSensorKs and CpError2 (they need a family maximum and CpTarget; iSepSensorKs, iSepSensorArea, iSepSensorKsArea and
- * iCpError2 are zero); getCostFunctions, which stays on the host; the derivative seeds of master_d / master_b. */
+ * iCpError2 are zero); getCostFunctions, which stays on the host; the derivative seeds of master_d / master_b other than those
+ * of the state (below).
+ *
+ * ---- derivatives of the integration with respect to the state -----------------------------------------------------------------------
+ * What master_d adds to funcsDot and master_b to wbar for the wall subfaces (wallIntegrationFace_d / _b behind the front of
+ * block_res_state_d), on the ground level.  Vectors are in the PETSc layout of adflow_gpu_jacfree_mult; flags is the ADFLOW_JAC_* set
+ * that selects the state range: 0 (all nw variables), ADFLOW_JAC_FROZEN_TURB (the five flow variables) or ADFLOW_JAC_TURB_ONLY.
+ * par, nGroups, famLists, ldFam: as for adflow_gpu_wall_integrate.  Both entries evaluate the front of the residual on dual numbers
+ * themselves -- closures with halos, turbulence boundary conditions where the flags keep them, flow boundary conditions, the nodal
+ * gradients of the wall node planes, the wall stress, the face terms -- at the state on the device, and run no time step and no flux
+ * kernel; the plain state, its halos, the stored wall stress and the per-face Fp / Fv / area are not written, and the halos of
+ * the state are read as they are on the device, as the integration reads them (no 2-layer exchange of the state).  Entries 17 (yplusMax) and 63 (the minimum of Cp) are not differentiated,
+ * as in the reference: their derivative is zero.
+ *
+ * adflow_gpu_wall_integrate_fwd[_dev]: outDot (nGroups x ADFLOW_WALLINT_STRIDE) = the derivative of the output of
+ * adflow_gpu_wall_integrate in the direction x (n = nState x owned cells of the level), by ONE pass seeded with x through the
+ * 2-layer exchange; out, where not NULL, takes the value parts (the integration itself, from the stress of this pass).
+ *
+ * adflow_gpu_wall_integrate_bwd[_dev]: outBar = nRhs weight sets of nGroups x ADFLOW_WALLINT_STRIDE doubles (what getCostFunctions_b
+ * makes of funcsBar), set r at outBar + r nGroups ADFLOW_WALLINT_STRIDE, ALWAYS in host memory; wbar = nRhs vectors ld doubles apart
+ * (ld >= n; the padding is not touched): column r = sum over groups g and entries e of outBar_r[g, e] d out[g, e] / d w, the right-hand
+ * side of the adjoint for adflow_gpu_gmres_solve(transpose) or adflow_gpu_gmres_solve_multi.  A coloured sweep of the pass above: 125
+ * colours (i mod 5, j mod 5, k mod 5 of the block-local index, halos included) x nState variables, every pass serving all weight sets;
+ * per pass the derivative parts of a face's terms are contracted with the weights of its groups and gathered -- per cell, in a fixed
+ * order, no atomics -- onto the one cell of the colour in the face's stencil; halo cells are then added to their donors by the
+ * reverse exchange of adflow_gpu_jacobian_mult (a halo without a donor is no column).  Bit-identical from call to call.
+ * The _dev forms take device pointers for x, out, outDot and wbar and honour adflow_gpu_set_async; they wait for the queue only
+ * where buffers are laid out or the weights or family lists differ from those of the previous call.
+ * Errors: everything adflow_gpu_wall_integrate (but for a stress never stored) and adflow_gpu_jacfree_mult refuse; ADFLOW_JAC_PC,
+ * ADFLOW_JAC_VISC_PC, ADFLOW_JAC_APPROX_SA (approximations of fluxes this path does not run); n of the wrong length; a NULL vector;
+ * a nonzero weight on entry 17 or 63; nRhs < 1 or > ADFLOW_GPU_MAX_NVEC; ld < n; halos exchanged with other ranks (bwd).  A level
+ * without a wall subface is no error: zeros.
+ * Buffers: the partial results, the halo'd result of the sweep (nState x nRhs doubles per box cell) and the contracted derivatives
+ * belong to the level's integration record: released and counted by adflow_gpu_release_workspace, dropped by
+ * adflow_gpu_bc_register and adflow_gpu_bc_set_families; the dual arrays are those of adflow_gpu_jacfree_mult.
+ * Not here: derivatives with respect to the mesh and the flight condition (xvbar, extraBar), nodal force seeds, several ranks. */
 enum {
     ADFLOW_WALLINT_MACHCOEF = 0,
     ADFLOW_WALLINT_POINTREF = 1,             /* pointRef(3) */
@@ -429,6 +464,14 @@ int adflow_gpu_bc_set_families(int nn, int level, int sps, int nBocos, const int
 int adflow_gpu_wall_integrate(int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out);
 int adflow_gpu_wall_integrate_dev(int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out);
 int adflow_gpu_download_wall_forces(int nn, int level, int sps, int mm, double* Fp, double* Fv, double* area);
+int adflow_gpu_wall_integrate_fwd(int level, unsigned flags, const double* x, long n, const double* par, int nGroups,
+                                  const int32_t* famLists, int ldFam, double* out, double* outDot);
+int adflow_gpu_wall_integrate_fwd_dev(int level, unsigned flags, const double* d_x, long n, const double* par, int nGroups,
+                                      const int32_t* famLists, int ldFam, double* d_out, double* d_outDot);
+int adflow_gpu_wall_integrate_bwd(int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
+                                  const double* outBar, int nRhs, double* wbar, long n, long ld);
+int adflow_gpu_wall_integrate_bwd_dev(int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
+                                      const double* outBar, int nRhs, double* d_wbar, long n, long ld);
 /* Actuator regions (actuatorRegionData.F90): residuals::sourceTerms_block (residuals.F90:348-425) adds the body force and
  * heat source of every listed cell to dw of the FINE level: -vol * force / volume / pRef on the momentum residuals,
  * -(F . v) - vol * heat / volume / (pRef uRef LRef^2) on the energy residual, ramped by ordersConverged between
