@@ -144,6 +144,8 @@ ANK_TURB, RES_APPROX_SA, RES_TURB_FIRST_ORDER, JAC_APPROX_SA = 512, 1024, 2048, 
  WALLINT_COMPUTECAVITATION, WALLINT_CAVITATIONNUMBER, WALLINT_CAVSENSOROFFSET, WALLINT_CAVSENSORSHARPNESS, WALLINT_CAVEXPONENT,
  WALLINT_CPMIN_RHO, WALLINT_CPMIN_FAMILY, WALLINT_NPAR) = (0, 1, 4, 10, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22)
 WALLINT_STRIDE, WALLINT_CPMIN = 64, 63
+# adflow_gpu_flow_integrate: indices of its parameter array
+FLOWINT_POINTREF, FLOWINT_INTERNALFLOW, FLOWINT_RHOREF, FLOWINT_RGASDIM, FLOWINT_NPAR = 0, 3, 4, 5, 6
 
 EXPORTS = [
     "adflow_gpu_init", "adflow_gpu_finalize", "adflow_gpu_last_error", "adflow_gpu_device_name",
@@ -160,6 +162,8 @@ EXPORTS = [
     "adflow_gpu_comm_register", "adflow_gpu_comm_info", "adflow_gpu_halo_slot_info", "adflow_gpu_halo_pack", "adflow_gpu_halo_unpack",
     "adflow_gpu_bc_set_families", "adflow_gpu_wall_integrate", "adflow_gpu_wall_integrate_dev", "adflow_gpu_download_wall_forces",
     "adflow_gpu_wall_integrate_fwd", "adflow_gpu_wall_integrate_fwd_dev", "adflow_gpu_wall_integrate_bwd", "adflow_gpu_wall_integrate_bwd_dev",
+    "adflow_gpu_flow_integrate", "adflow_gpu_flow_integrate_dev",
+    "adflow_gpu_flow_integrate_fwd", "adflow_gpu_flow_integrate_fwd_dev", "adflow_gpu_flow_integrate_bwd", "adflow_gpu_flow_integrate_bwd_dev",
     "adflow_gpu_halo_local_copy", "adflow_gpu_set_bc_callback", "adflow_gpu_bc_register", "adflow_gpu_apply_all_bc", "adflow_gpu_download_wall_stress", "adflow_gpu_abi_sizes2", "adflow_gpu_xhalo", "adflow_gpu_actuator_register", "adflow_gpu_comm_register_periodic", "adflow_gpu_coarse_coordinates", "adflow_gpu_exchange_coor",
     "adflow_gpu_upload_coordinates", "adflow_gpu_update_geometry", "adflow_gpu_reference_shock_sensor",
     "adflow_gpu_wall_distance_register", "adflow_gpu_update_wall_distances",
@@ -217,11 +221,13 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
     lib.adflow_gpu_apply_all_bc.argtypes = [c_int, c_int]
     lib.adflow_gpu_download_wall_stress.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.adflow_gpu_bc_set_families.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p]
-    for f in (lib.adflow_gpu_wall_integrate, lib.adflow_gpu_wall_integrate_dev):
+    for f in (lib.adflow_gpu_wall_integrate, lib.adflow_gpu_wall_integrate_dev, lib.adflow_gpu_flow_integrate, lib.adflow_gpu_flow_integrate_dev):
         f.argtypes = [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]
-    for f in (lib.adflow_gpu_wall_integrate_fwd, lib.adflow_gpu_wall_integrate_fwd_dev):
+    for f in (lib.adflow_gpu_wall_integrate_fwd, lib.adflow_gpu_wall_integrate_fwd_dev, lib.adflow_gpu_flow_integrate_fwd,
+              lib.adflow_gpu_flow_integrate_fwd_dev):
         f.argtypes = [c_int, c_uint, c_void_p, ctypes.c_long, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]
-    for f in (lib.adflow_gpu_wall_integrate_bwd, lib.adflow_gpu_wall_integrate_bwd_dev):
+    for f in (lib.adflow_gpu_wall_integrate_bwd, lib.adflow_gpu_wall_integrate_bwd_dev, lib.adflow_gpu_flow_integrate_bwd,
+              lib.adflow_gpu_flow_integrate_bwd_dev):
         f.argtypes = [c_int, c_uint, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_long, ctypes.c_long]
     lib.adflow_gpu_download_wall_forces.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
     lib.adflow_gpu_upload_coordinates.argtypes = [c_int, c_int, c_int]

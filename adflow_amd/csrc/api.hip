@@ -2935,27 +2935,32 @@ struct WiLevel {
     std::vector<size_t> barYsBytes;
     int64_t barBytes = 0;                   // of barAllocs, part of bytes
     int barSlots = 0, barNx = 0, barNy = 0, barNz = 0;
+    int nq = WI_NQ;                         // quantities per workgroup of the face kernel (FI_NQ in the record of the flow subfaces)
     std::vector<void*> allocs;
     int64_t bytes = 0;
 };
 static std::map<int, WiLevel> g_wi;
+static std::map<int, WiLevel> g_fi;      // the same record for the in- and outflow subfaces (adflow_gpu_flow_integrate): same lifetime
 
-static int64_t wi_drop(int level)
+static int64_t wi_drop_in(std::map<int, WiLevel>& recs, int level)
 {
-    auto it = g_wi.find(level);
-    if (it == g_wi.end()) return 0;
+    auto it = recs.find(level);
+    if (it == recs.end()) return 0;
     if (g_stream) (void)hipStreamSynchronize(g_stream);
     for (void* p : it->second.allocs) (void)hipFree(p);
     for (void* p : it->second.barAllocs) (void)hipFree(p);
     const int64_t n = it->second.bytes;
-    g_wi.erase(it);
+    recs.erase(it);
     return n;
 }
+
+static int64_t wi_drop(int level) { return wi_drop_in(g_wi, level) + wi_drop_in(g_fi, level); }
 
 static int64_t wi_drop_all()
 {
     std::vector<int> levels;
     for (auto& kv : g_wi) levels.push_back(kv.first);
+    for (auto& kv : g_fi) levels.push_back(kv.first);
     int64_t n = 0;
     for (int l : levels) n += wi_drop(l);
     return n;
@@ -2984,7 +2989,7 @@ static int wi_build(int level, WiLevel& L)
             bc_owned_range(f.faceID, f.icBeg, f.icEnd, f.jcBeg, f.jcEnd, b->v.il, b->v.jl, b->v.kl, w.r);
             const long no = (long)std::max(0, w.r[1] - w.r[0] + 1) * std::max(0, w.r[3] - w.r[2] + 1);
             if (no == 0) continue;
-            w.icBeg = f.icBeg; w.jcBeg = f.jcBeg; w.ldn = f.icEnd - f.icBeg + 1; w.pad = 0;
+            w.icBeg = f.icBeg; w.jcBeg = f.jcBeg; w.ldn = f.icEnd - f.icBeg + 1; w.inflow = 0;
             w.nnorm = (long)w.ldn * (f.jcEnd - f.jcBeg + 1);
             w.norm = f.norm;
             w.tauq = (m < b->nViscBocos && f.type != ADFLOW_BC_EULERWALL) ? f.tauq : nullptr;
@@ -3009,6 +3014,50 @@ static int wi_build(int level, WiLevel& L)
     return wi_alloc(L, (void**)&L.part, sizeof(double) * WI_NQ * nwg);
 }
 
+static int wi_check_groups(const char* who, int nGroups, const int32_t* famLists, int ldFam)
+{
+    if (nGroups < 0) return fail("%s: nGroups = %d", who, nGroups);
+    if (nGroups > 0) {
+        if (!famLists || ldFam < 1) return fail("%s: nGroups = %d needs famLists with ldFam >= 1 (ldFam = %d)", who, nGroups, ldFam);
+        for (int g = 0; g < nGroups; ++g)
+            if (famLists[g] < 0 || famLists[g] > ldFam - 1)
+                return fail("%s: group %d lists %d families, famLists holds at most ldFam - 1 = %d", who, g + 1, famLists[g], ldFam - 1);
+    }
+    return 0;
+}
+
+// the membership table of the groups on the device, and the output of the host form; nG: the groups of the output (1 for nGroups = 0)
+static int wi_members(WiLevel& L, int nGroups, const int32_t* famLists, int* nGout)
+{
+    const int nface = (int)L.faces.size();
+    const int nG = nGroups > 0 ? nGroups : 1;
+    // member[g nface + f]: famInList(BCData(mm)%famID, famLists(g, 2:1 + famLists(g, 1))) of integrateSurfaces
+    std::vector<unsigned char> member((size_t)nG * std::max(nface, 1), 0);
+    for (int g = 0; g < nG; ++g)
+        for (int f = 0; f < nface; ++f) {
+            bool in = nGroups == 0;
+            for (int j = 1; !in && j <= famLists[g]; ++j) in = famLists[g + (size_t)nGroups * j] == L.faces[f].fam;
+            member[(size_t)g * nface + f] = in;
+        }
+    if (member != L.member || !L.d_member) {
+        // (the kernels of an earlier enqueue-only call may still read the table)
+        HIPCHK(hipStreamSynchronize(g_stream));
+        if (nG > L.memberGroups) {
+            void* raw = nullptr;
+            if (wi_alloc(L, &raw, member.size())) return 1;
+            L.d_member = (unsigned char*)raw;
+            if (wi_alloc(L, &raw, sizeof(double) * ADFLOW_WALLINT_STRIDE * (size_t)nG)) return 1;
+            L.d_out = (double*)raw;
+            L.memberGroups = nG;
+            L.member.clear();
+        }
+        HIPCHK(hipMemcpy(L.d_member, member.data(), member.size(), hipMemcpyHostToDevice));
+        L.member = member;
+    }
+    *nGout = nG;
+    return 0;
+}
+
 // What every entry of the integration does before it launches: the checks of par and of the groups, the parameters of the face kernel,
 // the level's record with its table of wall subfaces, and the membership table of the groups on the device.  needStress: the entry
 // reads the stored wall stress (the derivative entries form the stress of their own pass).  nG: the groups of the output (1 for
@@ -3018,13 +3067,7 @@ static int wi_setup(const char* who, int level, const double* par, int nGroups, 
 {
     if (need_ready()) return 1;
     if (!par) return fail("%s: par must not be NULL", who);
-    if (nGroups < 0) return fail("%s: nGroups = %d", who, nGroups);
-    if (nGroups > 0) {
-        if (!famLists || ldFam < 1) return fail("%s: nGroups = %d needs famLists with ldFam >= 1 (ldFam = %d)", who, nGroups, ldFam);
-        for (int g = 0; g < nGroups; ++g)
-            if (famLists[g] < 0 || famLists[g] > ldFam - 1)
-                return fail("%s: group %d lists %d families, famLists holds at most ldFam - 1 = %d", who, g + 1, famLists[g], ldFam - 1);
-    }
+    if (wi_check_groups(who, nGroups, famLists, ldFam)) return 1;
     const double MachCoef = par[ADFLOW_WALLINT_MACHCOEF];
     if (!(MachCoef > 0.0)) return fail("%s: MachCoef = %g must be positive", who, MachCoef);
     WiPar P;
@@ -3082,33 +3125,8 @@ static int wi_setup(const char* who, int level, const double* par, int nGroups, 
         }
         it = g_wi.emplace(level, std::move(fresh)).first;
     }
-    WiLevel& L = it->second;
-    const int nface = (int)L.faces.size();
-    const int nG = nGroups > 0 ? nGroups : 1;
-    // member[g nface + f]: famInList(BCData(mm)%famID, famLists(g, 2:1 + famLists(g, 1))) of integrateSurfaces
-    std::vector<unsigned char> member((size_t)nG * std::max(nface, 1), 0);
-    for (int g = 0; g < nG; ++g)
-        for (int f = 0; f < nface; ++f) {
-            bool in = nGroups == 0;
-            for (int j = 1; !in && j <= famLists[g]; ++j) in = famLists[g + (size_t)nGroups * j] == L.faces[f].fam;
-            member[(size_t)g * nface + f] = in;
-        }
-    if (member != L.member || !L.d_member) {
-        // (the kernels of an earlier enqueue-only call may still read the table)
-        HIPCHK(hipStreamSynchronize(g_stream));
-        if (nG > L.memberGroups) {
-            void* raw = nullptr;
-            if (wi_alloc(L, &raw, member.size())) return 1;
-            L.d_member = (unsigned char*)raw;
-            if (wi_alloc(L, &raw, sizeof(double) * ADFLOW_WALLINT_STRIDE * (size_t)nG)) return 1;
-            L.d_out = (double*)raw;
-            L.memberGroups = nG;
-            L.member.clear();
-        }
-        HIPCHK(hipMemcpy(L.d_member, member.data(), member.size(), hipMemcpyHostToDevice));
-        L.member = member;
-    }
-    *Pout = P; *Lout = &L; *nGout = nG;
+    if (wi_members(it->second, nGroups, famLists, nGout)) return 1;
+    *Pout = P; *Lout = &it->second;
     return 0;
 }
 
@@ -3195,6 +3213,112 @@ int adflow_gpu_download_wall_forces(int nn, int level, int sps, int mm, double* 
         return 0;
     }
     return 0;        // a subface without owned face cells
+}
+
+// ---- flow integration (kernels_wallint.hip): flowIntegrationFace over the in- and outflow subfaces of a level -----------------------
+static bool is_flow_type(int t)
+{
+    return t == ADFLOW_BC_SUBSONIC_INFLOW || t == ADFLOW_BC_SUPERSONIC_INFLOW || t == ADFLOW_BC_SUBSONIC_OUTFLOW ||
+           t == ADFLOW_BC_SUPERSONIC_OUTFLOW;
+}
+
+// the table of in- and outflow subfaces of the level (the order of g_blocks: block, then subface) and the partial results
+static int fi_build(int level, WiLevel& L)
+{
+    std::vector<WiFace> tab;
+    L.nq = FI_NQ;
+    for (auto& kv : g_blocks) {
+        if (std::get<0>(kv.first) != level || std::get<1>(kv.first) != 1) continue;
+        Block* b = kv.second;
+        for (int m = 0; m < (int)b->bc.size(); ++m) {
+            const BcFaceDev& f = b->bc[m];
+            if (!is_flow_type(f.type)) continue;
+            WiFace w;
+            memset(&w, 0, sizeof(w));
+            w.slot = std::get<2>(kv.first); w.faceID = f.faceID;
+            bc_owned_range(f.faceID, f.icBeg, f.icEnd, f.jcBeg, f.jcEnd, b->v.il, b->v.jl, b->v.kl, w.r);
+            const long no = (long)std::max(0, w.r[1] - w.r[0] + 1) * std::max(0, w.r[3] - w.r[2] + 1);
+            if (no == 0) continue;
+            w.inflow = (f.type == ADFLOW_BC_SUBSONIC_INFLOW || f.type == ADFLOW_BC_SUPERSONIC_INFLOW) ? 1 : 0;
+            w.iblank = m < (int)b->faceBlank.size() ? b->faceBlank[m] : nullptr;
+            w.goff = L.nOwned;
+            L.nOwned += no;
+            L.maxBox = std::max(L.maxBox, (long)(w.r[1] - w.r[0] + 1 + 2 * WI_REACH) * (w.r[3] - w.r[2] + 1 + 2 * WI_REACH) * WI_DEPTH);
+            tab.push_back(w);
+            WiLevel::Ref r = {std::get<2>(kv.first), m + 1, m < (int)b->famID.size() ? b->famID[m] : 0, no, nullptr};
+            L.faces.push_back(r);
+            L.maxOwned = std::max(L.maxOwned, no);
+        }
+    }
+    if (tab.empty()) return 0;
+    if (tab.size() > 65535) return fail("%zu in- and outflow subfaces on level %d, one launch takes 65535", tab.size(), level);
+    if (wi_alloc(L, (void**)&L.d_faces, sizeof(WiFace) * tab.size())) return 1;
+    HIPCHK(hipMemcpy(L.d_faces, tab.data(), sizeof(WiFace) * tab.size(), hipMemcpyHostToDevice));
+    const size_t nwg = (size_t)wallint_groups_per_face(L.maxOwned) * tab.size();
+    return wi_alloc(L, (void**)&L.part, sizeof(double) * FI_NQ * nwg);
+}
+
+// wi_setup for the flow subfaces: the checks, the parameters, the level's record and the membership table
+static int fi_setup(const char* who, int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, FiPar* Pout,
+                    WiLevel** Lout, int* nGout)
+{
+    if (need_ready()) return 1;
+    if (!par) return fail("%s: par must not be NULL", who);
+    if (wi_check_groups(who, nGroups, famLists, ldFam)) return 1;
+    FiPar P;
+    P.pInf = g_opts.pInf; P.pRef = g_opts.pRef; P.gammaInf = g_opts.gammaInf; P.TRef = g_opts.TRef; P.uRef = g_opts.uRef;
+    P.timeRef = g_opts.timeRef; P.RGas = g_opts.RGas;
+    P.rhoRef = par[ADFLOW_FLOWINT_RHOREF]; P.rGasDim = par[ADFLOW_FLOWINT_RGASDIM];
+    P.internalFlowFact = par[ADFLOW_FLOWINT_INTERNALFLOW] != 0.0 ? -1.0 : 1.0;
+    for (int d = 0; d < 3; ++d) P.refPoint[d] = g_opts.LRef * par[ADFLOW_FLOWINT_POINTREF + d];
+    if (!(P.rhoRef > 0.0) || !(P.rGasDim > 0.0)) return fail("%s: rhoRef = %g and rGasDim = %g must be positive", who, P.rhoRef, P.rGasDim);
+    BcPlan* pl;
+    if (bc_plan(level, &pl)) return 1;
+    if (pl->nent == 0) return fail("%s: level %d has no registered boundary subfaces (adflow_gpu_bc_register)", who, level);
+    if (ensure_table(level)) return 1;
+    auto it = g_fi.find(level);
+    if (it == g_fi.end()) {
+        WiLevel fresh;
+        if (fi_build(level, fresh)) {
+            for (void* p : fresh.allocs) (void)hipFree(p);
+            return 1;
+        }
+        it = g_fi.emplace(level, std::move(fresh)).first;
+    }
+    if (wi_members(it->second, nGroups, famLists, nGout)) return 1;
+    *Pout = P; *Lout = &it->second;
+    return 0;
+}
+
+static int flow_integrate(const char* who, int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out,
+                          bool outOnDevice)
+{
+    if (need_ready()) return 1;
+    if (!par || !out) return fail("%s: par and out must not be NULL", who);
+    FiPar P;
+    WiLevel* Lp;
+    int nG;
+    if (fi_setup(who, level, par, nGroups, famLists, ldFam, &P, &Lp, &nG)) return 1;
+    WiLevel& L = *Lp;
+    LevelTab t;
+    if (level_tab(level, &t)) return 1;
+    double* d_out = outOnDevice ? out : L.d_out;
+    launch_flowint(t.tab, L.d_faces, (int)L.faces.size(), L.maxOwned, P, L.part, L.d_member, nG, d_out, g_stream);
+    if (outOnDevice) return sync_and_check();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * ADFLOW_WALLINT_STRIDE * (size_t)nG, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+int adflow_gpu_flow_integrate(int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out)
+{
+    return flow_integrate("flow_integrate", level, par, nGroups, famLists, ldFam, out, false);
+}
+
+int adflow_gpu_flow_integrate_dev(int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out)
+{
+    return flow_integrate("flow_integrate_dev", level, par, nGroups, famLists, ldFam, out, true);
 }
 
 // setCorrectionsCoarseHalos of every coarse block with subfaces (multiGrid.F90:472)
@@ -6365,8 +6489,11 @@ static int wd_check_flags(const char* who, unsigned flags)
 
 // turbulence and mean-flow boundary conditions and the nodal gradients of the wall node planes, on the dual arrays the seed launch
 // filled (state and closures).  The dual face kernels take the stress from there
-static int wd_front_enqueue(int level, const JfSetup& S, const KParams& kp)
+static int wd_front_enqueue(int level, const JfSetup& S, const KParams& kp, bool flow)
 {
+    // (the terms of a flow subface read rho, the velocities, p and gamma of the halo and of the first cell: the flow boundary
+    //  conditions, and neither the turbulence ones nor a nodal gradient)
+    if (flow) return DUAL.bcs(level, kp, false);
     if (DUAL.bcs(level, kp, S.turbBC)) return 1;
     BcPlan* pl;
     if (bc_plan(level, &pl)) return 1;
@@ -6382,17 +6509,27 @@ static int wd_prepare(const char* who, int level, const JfSetup& S, bool sync)
     return jm_layout(g_jf, level, S.J.nState, 1, false, who);
 }
 
-static int wd_fwd_enqueue(const char* who, int level, const JfSetup& S, const WiPar& P, WiLevel& L, int nG, const double* d_x, double* d_out,
-                          double* d_outDot, bool sync)
+// F: the parameters of the flow subfaces where L is their record, NULL for the walls (then P holds)
+static int wd_fwd_enqueue(const char* who, int level, const JfSetup& S, const WiPar& P, const FiPar* F, WiLevel& L, int nG, const double* d_x,
+                          double* d_out, double* d_outDot, bool sync)
 {
     const int nface = (int)L.faces.size();
-    if (nface == 0) {                  // no wall subface: the neutral elements and a zero derivative
-        ad_launch_wallint_fwd(nullptr, nullptr, 0, 0, P, KParams(), nullptr, L.d_member, nG, d_out, d_outDot, g_stream);
+    if (F && d_out) {
+        // the value parts of the flow entry are the integration itself, by the plain kernels in the same queue: the dual pass forms
+        // the pressure of every cell again from its energy and would differ from adflow_gpu_flow_integrate in the last bits
+        LevelTab t;
+        if (level_tab(level, &t)) return 1;
+        launch_flowint(t.tab, L.d_faces, nface, L.maxOwned, *F, L.part, L.d_member, nG, d_out, g_stream);
+        d_out = nullptr;
+    }
+    if (nface == 0) {                  // no subface: the neutral elements and a zero derivative
+        if (F) ad_launch_flowint_fwd(nullptr, nullptr, 0, 0, *F, nullptr, L.d_member, nG, d_out, d_outDot, g_stream);
+        else ad_launch_wallint_fwd(nullptr, nullptr, 0, 0, P, KParams(), nullptr, L.d_member, nG, d_out, d_outDot, g_stream);
         return 0;
     }
     if (!L.partD) {
         const size_t nwg = (size_t)wallint_groups_per_face(L.maxOwned) * nface;
-        if (wi_alloc(L, &L.partD, 2 * sizeof(double) * WI_NQ * nwg)) return 1;
+        if (wi_alloc(L, &L.partD, 2 * sizeof(double) * L.nq * nwg)) return 1;
     }
     int rc = wd_prepare(who, level, S, sync);
     const KParams kp = res_kparams(level, S.resFlags);
@@ -6403,15 +6540,17 @@ static int wd_fwd_enqueue(const char* who, int level, const JfSetup& S, const Wi
         for (auto& kv : g_blocks)
             if (std::get<0>(kv.first) == level)
                 ad_launch_seed_vector(kv.second->v, g_ad[kv.second].v, g_jf.h[std::get<2>(kv.first)].xs, S.J.lStart, S.J.nState, kp, g_stream);
-        rc = wd_front_enqueue(level, S, kp);
+        rc = wd_front_enqueue(level, S, kp, F != nullptr);
     }
-    if (!rc)
-        ad_launch_wallint_fwd(g_ad_tab, L.d_faces, nface, L.maxOwned, P, kp, L.partD, L.d_member, nG, d_out, d_outDot, g_stream);
+    if (!rc) {
+        if (F) ad_launch_flowint_fwd(g_ad_tab, L.d_faces, nface, L.maxOwned, *F, L.partD, L.d_member, nG, d_out, d_outDot, g_stream);
+        else ad_launch_wallint_fwd(g_ad_tab, L.d_faces, nface, L.maxOwned, P, kp, L.partD, L.d_member, nG, d_out, d_outDot, g_stream);
+    }
     return jf_finish(rc);
 }
 
 static int wd_fwd(const char* who, int level, unsigned flags, const double* x, long n, const double* par, int nGroups, const int32_t* famLists,
-                  int ldFam, double* out, double* outDot, bool dev)
+                  int ldFam, double* out, double* outDot, bool dev, bool flow = false)
 {
     if (need_ready()) return 1;
     if (!x || !outDot) return fail("%s: %s is NULL", who, !x ? "x" : "outDot");
@@ -6419,12 +6558,16 @@ static int wd_fwd(const char* who, int level, unsigned flags, const double* x, l
     JfSetup S;
     if (jf_check(who, level, flags, x, outDot, n, &S)) return 1;
     WiPar P;
+    FiPar FP;
+    const FiPar* F = flow ? &FP : nullptr;
     WiLevel* L;
     int nG;
-    if (wi_setup(who, level, par, nGroups, famLists, ldFam, false, &P, &L, &nG)) return 1;
+    if (flow ? fi_setup(who, level, par, nGroups, famLists, ldFam, &FP, &L, &nG)
+             : wi_setup(who, level, par, nGroups, famLists, ldFam, false, &P, &L, &nG))
+        return 1;
     const size_t no = (size_t)ADFLOW_WALLINT_STRIDE * nG;
     if (dev) {
-        if (wd_fwd_enqueue(who, level, S, P, *L, nG, x, out, outDot, !g_async)) return 1;
+        if (wd_fwd_enqueue(who, level, S, P, F, *L, nG, x, out, outDot, !g_async)) return 1;
         return sync_and_check();
     }
     if (nG > L->dotGroups) {
@@ -6442,7 +6585,8 @@ static int wd_fwd(const char* who, int level, unsigned flags, const double* x, l
     }
     Stage s;
     if (stage_open(&s, n, 1) || s.in(0, x)) return 1;
-    if (wd_fwd_enqueue(who, level, S, P, *L, nG, s[0], L->d_dot, L->d_dot + no, false)) return 1;
+    // (the flow entry forms its value parts with two launches of their own: only where the caller asks for them)
+    if (wd_fwd_enqueue(who, level, S, P, F, *L, nG, s[0], (flow && !out) ? nullptr : L->d_dot, L->d_dot + no, false)) return 1;
     if (out && s.scalars(out, L->d_dot, (long)no)) return 1;
     return s.scalars(outDot, L->d_dot + no, (long)no) || s.done();
 }
@@ -6514,7 +6658,7 @@ static int wd_bar_layout(const char* who, int level, WiLevel& L, int nS, int nv)
     if (alloc(&raw, sizeof(JmBlk) * ht.size())) return 1;
     L.barTab = (JmBlk*)raw;
     HIPCHK(hipMemcpy(L.barTab, ht.data(), sizeof(JmBlk) * ht.size(), hipMemcpyHostToDevice));
-    if (alloc(&raw, sizeof(double) * std::max<size_t>(1, (size_t)nv * L.faces.size() * WI_NQ))) return 1;
+    if (alloc(&raw, sizeof(double) * std::max<size_t>(1, (size_t)nv * L.faces.size() * L.nq))) return 1;
     L.d_wq = (double*)raw;
     if (alloc(&raw, sizeof(double) * std::max<size_t>(1, (size_t)nv * L.nOwned))) return 1;
     L.d_g = (double*)raw;
@@ -6522,8 +6666,8 @@ static int wd_bar_layout(const char* who, int level, WiLevel& L, int nS, int nv)
     return 0;
 }
 
-static int wd_bwd_enqueue(const char* who, int level, const JfSetup& S, const WiPar& P, WiLevel& L, const std::vector<double>& wq, int nRhs,
-                          double* d_wbar, long n, long ld, bool sync)
+static int wd_bwd_enqueue(const char* who, int level, const JfSetup& S, const WiPar& P, const FiPar* F, WiLevel& L,
+                          const std::vector<double>& wq, int nRhs, double* d_wbar, long n, long ld, bool sync)
 {
     const int nface = (int)L.faces.size();
     if (nface == 0) {
@@ -6556,9 +6700,10 @@ static int wd_bwd_enqueue(const char* who, int level, const JfSetup& S, const Wi
                     ad_launch_seed_closures(b->v, g_ad[b].v, l, col, C, kp, g_stream, false);
                     return 0;
                 });
-                rc = wd_front_enqueue(level, S, kp);
+                rc = wd_front_enqueue(level, S, kp, F != nullptr);
                 if (rc) break;
-                ad_launch_wallint_bar(g_ad_tab, L.d_faces, nface, L.maxOwned, P, kp, L.d_wq, nRhs, L.nOwned, L.d_g, g_stream);
+                if (F) ad_launch_flowint_bar(g_ad_tab, L.d_faces, nface, L.maxOwned, *F, L.d_wq, nRhs, L.nOwned, L.d_g, g_stream);
+                else ad_launch_wallint_bar(g_ad_tab, L.d_faces, nface, L.maxOwned, P, kp, L.d_wq, nRhs, L.nOwned, L.d_g, g_stream);
                 launch_wallint_credit(L.d_faces, nface, L.maxBox, L.barTab, (long)nt, nRhs, l - S.J.lStart, col, L.d_g, L.nOwned, g_stream);
             }
         for (int r = 0; r < nRhs && !rc; ++r) {
@@ -6571,7 +6716,7 @@ static int wd_bwd_enqueue(const char* who, int level, const JfSetup& S, const Wi
 }
 
 static int wd_bwd(const char* who, int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
-                  const double* outBar, int nRhs, double* wbar, long n, long ld, bool dev)
+                  const double* outBar, int nRhs, double* wbar, long n, long ld, bool dev, bool flow = false)
 {
     if (need_ready()) return 1;
     if (!outBar || !wbar) return fail("%s: %s is NULL", who, !outBar ? "outBar" : "wbar");
@@ -6580,33 +6725,48 @@ static int wd_bwd(const char* who, int level, unsigned flags, const double* par,
     JfSetup S;
     if (jf_check(who, level, flags, outBar, wbar, n, &S)) return 1;
     if (ld < n) return fail("%s: ld = %ld, but a column holds n = %ld entries (ld >= n)", who, ld, n);
+    if (flow) {
+        // (the flow entry refuses before its record exists, so that the refusal leaves nothing allocated; the wall entry refuses
+        //  where it always did, in wd_bwd_enqueue)
+        CommPattern* cp = nullptr;
+        if (jm_pattern_of(level, S.J.lStart, S.J.nState, who, &cp)) return 1;
+        if (cp && (!cp->sends.empty() || !cp->recvs.empty())) return fail("%s: the level exchanges halos with other ranks (one rank only)", who);
+    }
     WiPar P;
+    FiPar FP;
+    const FiPar* F = flow ? &FP : nullptr;
     WiLevel* L;
     int nG;
-    if (wi_setup(who, level, par, nGroups, famLists, ldFam, false, &P, &L, &nG)) return 1;
+    if (flow ? fi_setup(who, level, par, nGroups, famLists, ldFam, &FP, &L, &nG)
+             : wi_setup(who, level, par, nGroups, famLists, ldFam, false, &P, &L, &nG))
+        return 1;
     // the weight of quantity q of subface f in set r: outBar summed over the groups the subface belongs to
     static const int entryOf[WI_NQ] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 44, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 17, 63};
+    static const int flowEntryOf[FI_NQ] = {18, 19, 20, 21, 31, 35, 36, 38, 39, 40, 41, 42, 43, 59, 37, 47, 48, 0, 1, 2, 22, 23, 24,
+                                           25, 26, 27, 28, 29, 30, 50, 51, 52, 53, 54, 55, 56, 57, 58};
+    const int* eo = flow ? flowEntryOf : entryOf;
+    const int nq = L->nq, nqSum = flow ? FI_NQ : WI_YPLUS;
     const int nface = (int)L->faces.size();
-    std::vector<double> wq((size_t)nRhs * nface * WI_NQ, 0.0);
+    std::vector<double> wq((size_t)nRhs * nface * nq, 0.0);
     for (int r = 0; r < nRhs; ++r)
         for (int g = 0; g < nG; ++g) {
             const double* ob = outBar + ((size_t)r * nG + g) * ADFLOW_WALLINT_STRIDE;
-            if (ob[17] != 0.0 || ob[63] != 0.0)
+            if (!flow && (ob[17] != 0.0 || ob[63] != 0.0))
                 return fail("%s: weight set %d, group %d: entry %d (%s) has no derivative, its weight must be zero", who, r + 1, g + 1,
                             ob[17] != 0.0 ? 17 : 63, ob[17] != 0.0 ? "yplusMax" : "the minimum of Cp");
             for (int f = 0; f < nface; ++f) {
                 if (!L->member[(size_t)g * nface + f]) continue;
-                for (int q = 0; q < WI_YPLUS; ++q) wq[((size_t)r * nface + f) * WI_NQ + q] += ob[entryOf[q]];
+                for (int q = 0; q < nqSum; ++q) wq[((size_t)r * nface + f) * nq + q] += ob[eo[q]];
             }
         }
     if (dev) {
-        if (wd_bwd_enqueue(who, level, S, P, *L, wq, nRhs, wbar, n, ld, !g_async)) return 1;
+        if (wd_bwd_enqueue(who, level, S, P, F, *L, wq, nRhs, wbar, n, ld, !g_async)) return 1;
         return sync_and_check();
     }
     DevBuf buf;
     HIPCHK(hipMalloc(&buf.p, sizeof(double) * std::max<size_t>(1, (size_t)nRhs * n)));
     const Stage s{n, (double*)buf.p};
-    if (wd_bwd_enqueue(who, level, S, P, *L, wq, nRhs, s[0], n, n, false)) return 1;
+    if (wd_bwd_enqueue(who, level, S, P, F, *L, wq, nRhs, s[0], n, n, false)) return 1;
     return stage_out_columns(s, wbar, ld, 0, nRhs) || s.done();
 }
 
@@ -6620,6 +6780,32 @@ int adflow_gpu_wall_integrate_bwd_dev(int level, unsigned flags, const double* p
                                       const double* outBar, int nRhs, double* d_wbar, long n, long ld)
 {
     return wd_bwd("wall_integrate_bwd_dev", level, flags, par, nGroups, famLists, ldFam, outBar, nRhs, d_wbar, n, ld, true);
+}
+
+// the same two entries for the in- and outflow subfaces (flowIntegrationFace_d / _b): the record of the flow subfaces, the dual flow
+// boundary conditions as the only front
+int adflow_gpu_flow_integrate_fwd(int level, unsigned flags, const double* x, long n, const double* par, int nGroups, const int32_t* famLists,
+                                  int ldFam, double* out, double* outDot)
+{
+    return wd_fwd("flow_integrate_fwd", level, flags, x, n, par, nGroups, famLists, ldFam, out, outDot, false, true);
+}
+
+int adflow_gpu_flow_integrate_fwd_dev(int level, unsigned flags, const double* d_x, long n, const double* par, int nGroups,
+                                      const int32_t* famLists, int ldFam, double* d_out, double* d_outDot)
+{
+    return wd_fwd("flow_integrate_fwd_dev", level, flags, d_x, n, par, nGroups, famLists, ldFam, d_out, d_outDot, true, true);
+}
+
+int adflow_gpu_flow_integrate_bwd(int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
+                                  const double* outBar, int nRhs, double* wbar, long n, long ld)
+{
+    return wd_bwd("flow_integrate_bwd", level, flags, par, nGroups, famLists, ldFam, outBar, nRhs, wbar, n, ld, false, true);
+}
+
+int adflow_gpu_flow_integrate_bwd_dev(int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
+                                      const double* outBar, int nRhs, double* d_wbar, long n, long ld)
+{
+    return wd_bwd("flow_integrate_bwd_dev", level, flags, par, nGroups, famLists, ldFam, outBar, nRhs, d_wbar, n, ld, true, true);
 }
 
 // nvec right-hand sides on the assembled matrix with the selected factor, in lock-step: every iteration is ONE application of M^-1

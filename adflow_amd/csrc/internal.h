@@ -577,7 +577,7 @@ struct WiFace {
     int slot, faceID;         // block slot in the level's table, BCFaceID
     int r[4];                 // the owned face cells (bc_owned_range)
     int icBeg, jcBeg, ldn;    // BCData%norm: component c of cell (a, b) at (a - icBeg) + (b - jcBeg) ldn + c nnorm
-    int pad;
+    int inflow;               // flow subfaces: 1 on SubsonicInflow / SupersonicInflow (inFlowFact = -1); walls: 0
     long nnorm;
     const double* norm;       // NULL where no term reads it (y+ of a viscous wall under RANS does)
     const double* tauq;       // viscous walls: the stored stress (BcFaceDev::tauq); NULL on an Euler wall
@@ -612,6 +612,21 @@ enum { WI_CM = 5, WI_NCOL = WI_CM * WI_CM * WI_CM, WI_REACH = 2, WI_DEPTH = 4 };
 struct JmBlk;
 void launch_wallint_credit(const WiFace* faces, int nface, long maxBox, const JmBlk* tab, long nt, int nRhs, int lq, int col,
                            const double* g, long ldg, hipStream_t s);
+
+// flow integration (kernels_wallint.hip; adflow_gpu_flow_integrate): flowIntegrationFace over the in- and outflow subfaces of a level.
+// The subfaces come in a WiFace table of their own (norm, tauq, fpv NULL), the groups in a membership table like that of the walls.
+struct FiPar {
+    double pInf, pRef, gammaInf, rhoRef, TRef, uRef, timeRef, RGas, rGasDim;
+    double internalFlowFact;      // -1 for flowType == internalFlow, else 1
+    double refPoint[3];           // LRef pointRef
+};
+// the quantities a workgroup of the flow face kernel reduces, all sums
+enum { FI_MASSFLOW = 0, FI_MASSPTOT = 1, FI_MASSTTOT = 2, FI_MASSPS = 3, FI_MASSMN = 4, FI_MASSA = 5, FI_MASSRHO = 6, FI_MASSV = 7,
+       FI_MASSN = 10, FI_MASSVI = 13, FI_AREA = 14, FI_AREAPTOT = 15, FI_AREAPS = 16, FI_FP = 17, FI_MP = 20, FI_FM = 23, FI_MM = 26,
+       FI_COF = 29, FI_NQ = 38 };
+// part: FI_NQ x (workgroups per subface x nface) doubles; member and out as for launch_wallint
+void launch_flowint(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const FiPar& P, double* part,
+                    const unsigned char* member, int nGroups, double* out, hipStream_t s);
 
 // The level-batched launches fold (block slot, plane) into gridDim.z, which HIP limits to 65535: a launcher whose level has more
 // slots than fit calls itself on consecutive slot ranges (the kernels index the table relative to the pointer they get).
@@ -755,5 +770,10 @@ void ad_launch_wallint_fwd(const BlkView* tab, const WiFace* faces, int nface, l
                            const unsigned char* member, int nGroups, double* out, double* outDot, hipStream_t s);
 void ad_launch_wallint_bar(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const WiPar& P, const KParams& kp,
                            const double* wq, int nRhs, long ldg, double* g, hipStream_t s);
+// the same for the flow subfaces (part: FI_NQ x workgroups dual numbers; wq: FI_NQ weights per set and subface)
+void ad_launch_flowint_fwd(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const FiPar& P, void* part,
+                           const unsigned char* member, int nGroups, double* out, double* outDot, hipStream_t s);
+void ad_launch_flowint_bar(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const FiPar& P, const double* wq, int nRhs,
+                           long ldg, double* g, hipStream_t s);
 void ad_launch_selftest_math(int which, const double* x, const double* a, long n, double* y, double* dy, hipStream_t s);
 void ad_launch_visc_march_approx(const BlkView* tab, const int4* tiles, int ntiles, const KParams& kp, hipStream_t s);

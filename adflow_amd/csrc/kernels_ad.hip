@@ -363,4 +363,14 @@ void ad_launch_wallint_bar(const BlkView* tab, const WiFace* faces, int nface, l
 {
     adj::launch_wallint_bar(ADV(tab), faces, nface, maxOwned, P, kp, wq, nRhs, ldg, g, s);
 }
+void ad_launch_flowint_fwd(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const FiPar& P, void* part,
+                           const unsigned char* member, int nGroups, double* out, double* outDot, hipStream_t s)
+{
+    adj::launch_flowint_fwd(ADV(tab), faces, nface, maxOwned, P, part, member, nGroups, out, outDot, s);
+}
+void ad_launch_flowint_bar(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const FiPar& P, const double* wq, int nRhs,
+                           long ldg, double* g, hipStream_t s)
+{
+    adj::launch_flowint_bar(ADV(tab), faces, nface, maxOwned, P, wq, nRhs, ldg, g, s);
+}
 #undef ADV

@@ -216,6 +216,157 @@ __device__ __forceinline__ void wi_face_terms(const BlkView& b, const WiFace& f,
 #endif
 }
 
+// ---- flowIntegrationFace (surfaceIntegrations.F90:894-1200) over the in- and outflow subfaces ---------------------------------------
+// where owned face t of subface f lies (the decode of wi_face_terms as a function): (a, bb) its cell in the plane, cL the cell left of the face along the normal (the halo of a min
+// face, the first interior cell of a max face), sd the stride along the normal, s1 / s2 those in the plane, sN the face normals, dir
+// the direction 0 / 1 / 2
+struct WiGeom {
+    int a, bb, dir;
+    bool isMin;
+    long cL, sd, s1, s2;
+    const adf_real8* sN;
+};
+__device__ __forceinline__ WiGeom wi_face_geom(const BlkView& b, const WiFace& f, long t)
+{
+    WiGeom G;
+    const int na = f.r[1] - f.r[0] + 1;
+    const int a = f.r[0] + (int)(t % na), bb = f.r[2] + (int)(t / na);
+    const long si = 1, sj = b.ldi, sk = b.ldk;
+    switch (f.faceID) {
+    case ADFLOW_IMIN: case ADFLOW_IMAX:
+        G.cL = b.idx(f.faceID == ADFLOW_IMIN ? 1 : b.il, a, bb); G.sd = si; G.s1 = sj; G.s2 = sk; G.sN = b.sI; G.dir = 0;
+        break;
+    case ADFLOW_JMIN: case ADFLOW_JMAX:
+        G.cL = b.idx(a, f.faceID == ADFLOW_JMIN ? 1 : b.jl, bb); G.sd = sj; G.s1 = si; G.s2 = sk; G.sN = b.sJ; G.dir = 1;
+        break;
+    default:
+        G.cL = b.idx(a, bb, f.faceID == ADFLOW_KMIN ? 1 : b.kl); G.sd = sk; G.s1 = si; G.s2 = sj; G.sN = b.sK; G.dir = 2;
+    }
+    G.a = a; G.bb = bb;
+    G.isMin = (f.faceID == ADFLOW_IMIN || f.faceID == ADFLOW_JMIN || f.faceID == ADFLOW_KMIN);
+    return G;
+}
+
+// the quantity that entry e of a group's output holds (localValues(e + 1)); -1: an entry the flow integration leaves zero
+__device__ __forceinline__ int fi_quantity_of_entry(int e)
+{
+    if (e <= 2) return FI_FP + e;                       // iFp
+    if (e == 18) return FI_MASSFLOW;                    // iMassFlow
+    if (e == 19) return FI_MASSPTOT;                    // iMassPTot
+    if (e == 20) return FI_MASSTTOT;                    // iMassTtot
+    if (e == 21) return FI_MASSPS;                      // iMassPs
+    if (e >= 22 && e <= 24) return FI_MP + (e - 22);    // iFlowMp
+    if (e >= 25 && e <= 27) return FI_FM + (e - 25);    // iFlowFm
+    if (e >= 28 && e <= 30) return FI_MM + (e - 28);    // iFlowMm
+    if (e == 31) return FI_MASSMN;                      // iMassMN
+    if (e == 35) return FI_MASSA;                       // iMassa
+    if (e == 36) return FI_MASSRHO;                     // iMassRho
+    if (e == 37) return FI_AREA;                        // iArea
+    if (e >= 38 && e <= 40) return FI_MASSV + (e - 38); // iMassVx, iMassVy, iMassVz
+    if (e >= 41 && e <= 43) return FI_MASSN + (e - 41); // iMassnx, iMassny, iMassnz
+    if (e == 47) return FI_AREAPTOT;                    // iAreaPTot
+    if (e == 48) return FI_AREAPS;                      // iAreaPs
+    if (e >= 50 && e <= 58) return FI_COF + (e - 50);   // iCoForceX, iCoForceY, iCoForceZ
+    if (e == 59) return FI_MASSVI;                      // iMassVi
+    return -1;
+}
+
+// The terms v[FI_NQ] of owned face t of flow subface f, in the order of the reference.  The geometry, the blanking and the signs are
+// plain numbers in both builds (adf_real8); what comes from the state is `double`
+__device__ __forceinline__ void fi_face_terms(const BlkView& b, const WiFace& f, const FiPar& P, long t, double v[FI_NQ])
+{
+    const WiGeom G = wi_face_geom(b, f, t);
+    const long nb = b.nbox, cL = G.cL;
+    const adf_real8 fact = G.isMin ? 1.0 : -1.0;        // positive mass flow INTO the domain: the opposite of the wall forces
+    const adf_real8 inFlowFact = f.inflow ? -1.0 : 1.0;
+    const long c1 = G.isMin ? cL : cL + G.sd;           // the halo cell (ww1, pp1, gamma1)
+    const long c2 = G.isMin ? cL + G.sd : cL;           // the first interior cell
+    const adf_real8 ss[3] = {G.sN[cL], G.sN[cL + nb], G.sN[cL + 2 * nb]};
+    const adf_real8 sF = b.sFace ? b.sFace[cL + G.dir * nb] : 0.0;      // addGridVelocities: sFaceI / J / K of the boundary face
+    const int ib = f.iblank ? (int)f.iblank[t] : 1;
+    const adf_real8 blk = ib > 0 ? (adf_real8)ib : 0.0;
+
+    const double vxm = 0.5 * (b.w[c1 + nb] + b.w[c2 + nb]);
+    const double vym = 0.5 * (b.w[c1 + 2 * nb] + b.w[c2 + 2 * nb]);
+    const double vzm = 0.5 * (b.w[c1 + 3 * nb] + b.w[c2 + 3 * nb]);
+    const double rhom = 0.5 * (b.w[c1] + b.w[c2]);
+    double pm = 0.5 * (b.p[c1] + b.p[c2]);
+    const double gammam = 0.5 * (b.gamma[c1] + b.gamma[c2]);
+
+    const double vnm = vxm * ss[0] + vym * ss[1] + vzm * ss[2] - sF;
+    const double vmag = sqrt(vxm * vxm + vym * vym + vzm * vzm) - sF;
+    const double am = sqrt(gammam * pm / rhom);
+    const double MNm = vmag / am;
+    const adf_real8 cellArea = sqrt(ss[0] * ss[0] + ss[1] * ss[1] + ss[2] * ss[2]);
+    const adf_real8 overCellArea = 1.0 / cellArea;
+    v[FI_AREA] = cellArea * blk;
+
+    // computePtot, computeTtot of flowUtils for constant cp
+    const adf_real8 govgm1 = P.gammaInf / (P.gammaInf - 1.0), gm1ovg = 1.0 / govgm1;
+    const double kin = 0.5 * (vxm * vxm + vym * vym + vzm * vzm);
+    const double Ptot = pm * pow(1.0 + rhom * kin / (govgm1 * pm), govgm1);
+    const double Ttot = pm / (rhom * P.RGas) * (1.0 + rhom * kin / (govgm1 * pm));
+
+    const adf_real8 mReDim = sqrt(P.pRef * P.rhoRef);
+    double mfl = rhom * vnm * blk * fact * mReDim;      // massFlowRateLocal
+    v[FI_MASSFLOW] = mfl;
+    pm = pm * P.pRef;
+    v[FI_MASSPTOT] = Ptot * mfl * P.pRef;
+    v[FI_MASSTTOT] = Ttot * mfl * P.TRef;
+    v[FI_MASSRHO] = rhom * mfl * P.rhoRef;
+    v[FI_MASSA] = am * mfl * P.uRef;
+    v[FI_MASSPS] = pm * mfl;
+    v[FI_MASSMN] = MNm * mfl;
+    v[FI_AREAPTOT] = Ptot * P.pRef * cellArea * blk;
+    v[FI_AREAPS] = pm * cellArea * blk;
+    v[FI_MASSV + 0] = (vxm * P.uRef - sF * ss[0] * overCellArea) * mfl;
+    v[FI_MASSV + 1] = (vym * P.uRef - sF * ss[1] * overCellArea) * mfl;
+    v[FI_MASSV + 2] = (vzm * P.uRef - sF * ss[2] * overCellArea) * mfl;
+    {
+        const adf_real8 viConst = 2.0 * govgm1 * P.rGasDim;
+        const double pratio = fmin(1.0, 1.0 / Ptot);
+        const double viLocal = sqrt(viConst * (1.0 - pow(pratio, gm1ovg)) * Ttot * P.TRef);
+        v[FI_MASSVI] = viLocal * mfl;
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) v[FI_MASSN + d] = ss[d] * overCellArea * mfl;
+
+    // centroid of the face: its four nodes in the order the reference adds them
+    adf_real8 xco[3], xc[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const adf_real8* xd = b.x + d * nb;
+        xco[d] = 0.25 * (xd[cL - G.s1 - G.s2] + xd[cL - G.s2] + xd[cL - G.s1] + xd[cL]);
+        xc[d] = xco[d] - P.refPoint[d];
+    }
+    // pressure force, with the sign of the wall forces
+    pm = -(pm - P.pInf * P.pRef) * fact * blk;
+    double fo[3] = {pm * ss[0], pm * ss[1], pm * ss[2]};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) v[FI_FP + d] = fo[d];
+    v[FI_MP + 0] = xc[1] * fo[2] - xc[2] * fo[1];
+    v[FI_MP + 1] = xc[2] * fo[0] - xc[0] * fo[2];
+    v[FI_MP + 2] = xc[0] * fo[1] - xc[1] * fo[0];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) v[FI_COF + 3 * d + e] = xco[e] * fo[d];
+    // momentum force: fact is applied again to undo it, the sign flips between in- and outflow and for internal flow
+    mfl = mfl * fact / P.timeRef * blk / cellArea * P.internalFlowFact * inFlowFact;
+    fo[0] = mfl * ss[0] * vxm;
+    fo[1] = mfl * ss[1] * vym;
+    fo[2] = mfl * ss[2] * vzm;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) v[FI_FM + d] = fo[d];
+    v[FI_MM + 0] = xc[1] * fo[2] - xc[2] * fo[1];
+    v[FI_MM + 1] = xc[2] * fo[0] - xc[0] * fo[2];
+    v[FI_MM + 2] = xc[0] * fo[1] - xc[1] * fo[0];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) v[FI_COF + 3 * d + e] += xco[e] * fo[d];
+}
+
 }  // namespace
 
 // The terms of one face and their sums over the workgroup.  part[q nwg + workgroup], nwg = gridDim.x gridDim.y.
@@ -415,6 +566,112 @@ void launch_wallint(const BlkView* tab, const WiFace* faces, int nface, long max
     if (nface > 0)
         hipLaunchKernelGGL(k_wallint_faces, dim3((unsigned)gx, (unsigned)nface, 1), dim3(WI_T, 1, 1), 0, s, tab, faces, P, part);
     hipLaunchKernelGGL(k_wallint_finish, dim3((unsigned)nGroups, ADFLOW_WALLINT_STRIDE, 1), dim3(WI_T, 1, 1), 0, s, part, member, nface, gx,
+                       out);
+}
+#endif
+
+// ---- the flow subfaces: the face kernel, the finish kernel and their launches, as above; every quantity is a sum -------------------
+__global__ __launch_bounds__(WI_T) void k_flowint_faces(const BlkView* __restrict__ tab, const WiFace* __restrict__ faces, FiPar P,
+                                                        double* __restrict__ part)
+{
+    __shared__ double red[WI_T];
+    const WiFace& f = faces[blockIdx.y];
+    const BlkView& b = tab[f.slot];
+    const int na = f.r[1] - f.r[0] + 1, nbb = f.r[3] - f.r[2] + 1;
+    const long n = (na > 0 && nbb > 0) ? (long)na * nbb : 0;
+    const long t = (long)blockIdx.x * WI_T + threadIdx.x;
+    double v[FI_NQ];
+#pragma unroll
+    for (int q = 0; q < FI_NQ; ++q) v[q] = 0.0;
+    if (t < n) fi_face_terms(b, f, P, t, v);
+    const long nwg = (long)gridDim.x * gridDim.y;
+    const long wg = (long)blockIdx.y * gridDim.x + blockIdx.x;
+#pragma unroll
+    for (int q = 0; q < FI_NQ; ++q) {
+        const double r = wi_reduce<0>(v[q], red);
+        if (threadIdx.x == 0) part[q * nwg + wg] = r;
+    }
+}
+
+#ifdef ADF_AD_BUILD
+__global__ __launch_bounds__(WI_T) void k_flowint_finish(const double* __restrict__ part, const unsigned char* __restrict__ member,
+                                                         int nface, int gx, adf_real8* __restrict__ out, adf_real8* __restrict__ outDot)
+#else
+__global__ __launch_bounds__(WI_T) void k_flowint_finish(const double* __restrict__ part, const unsigned char* __restrict__ member,
+                                                         int nface, int gx, double* __restrict__ out)
+#endif
+{
+    __shared__ double red[WI_T];
+    const int g = blockIdx.x, e = blockIdx.y;
+    const int q = fi_quantity_of_entry(e);
+    const long dst = (long)g * ADFLOW_WALLINT_STRIDE + e;
+    double s = 0.0;
+    if (q >= 0) {                                    // (the same branch in every thread of the workgroup)
+        const long nwg = (long)nface * gx;
+        const double* pq = part + q * nwg;
+        const unsigned char* mem = member + (long)g * nface;
+        for (long w = threadIdx.x; w < nwg; w += WI_T)
+            if (mem[w / gx]) s += pq[w];
+        s = wi_reduce<0>(s, red);
+    }
+    if (threadIdx.x == 0) {
+#ifdef ADF_AD_BUILD
+        if (out) out[dst] = s.v;
+        outDot[dst] = s.d;
+#else
+        out[dst] = s;
+#endif
+    }
+}
+
+#ifdef ADF_AD_BUILD
+// the face kernel of the transposed product, as k_wallint_faces_bar: wq[(r nface + subface) FI_NQ + q]
+__global__ __launch_bounds__(WI_T) void k_flowint_faces_bar(const BlkView* __restrict__ tab, const WiFace* __restrict__ faces, FiPar P,
+                                                            const adf_real8* __restrict__ wq, int nRhs, long ldg, adf_real8* __restrict__ g)
+{
+    const WiFace& f = faces[blockIdx.y];
+    const BlkView& b = tab[f.slot];
+    const int na = f.r[1] - f.r[0] + 1, nbb = f.r[3] - f.r[2] + 1;
+    const long n = (na > 0 && nbb > 0) ? (long)na * nbb : 0;
+    const long t = (long)blockIdx.x * WI_T + threadIdx.x;
+    if (t >= n) return;
+    double v[FI_NQ];
+    fi_face_terms(b, f, P, t, v);
+    const int nface = gridDim.y;
+    for (int r = 0; r < nRhs; ++r) {
+        const adf_real8* w = wq + ((long)r * nface + blockIdx.y) * FI_NQ;
+        adf_real8 s = 0.0;
+#pragma unroll
+        for (int q = 0; q < FI_NQ; ++q) s += w[q] * v[q].d;
+        g[r * ldg + f.goff + t] = s;
+    }
+}
+
+void launch_flowint_fwd(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const FiPar& P, void* part,
+                        const unsigned char* member, int nGroups, adf_real8* out, adf_real8* outDot, hipStream_t s)
+{
+    const int gx = wallint_groups_per_face(maxOwned);
+    if (nface > 0)
+        hipLaunchKernelGGL(k_flowint_faces, dim3((unsigned)gx, (unsigned)nface, 1), dim3(WI_T, 1, 1), 0, s, tab, faces, P, (double*)part);
+    hipLaunchKernelGGL(k_flowint_finish, dim3((unsigned)nGroups, ADFLOW_WALLINT_STRIDE, 1), dim3(WI_T, 1, 1), 0, s, (const double*)part,
+                       member, nface, gx, out, outDot);
+}
+
+void launch_flowint_bar(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const FiPar& P, const adf_real8* wq, int nRhs,
+                        long ldg, adf_real8* g, hipStream_t s)
+{
+    if (nface <= 0) return;
+    hipLaunchKernelGGL(k_flowint_faces_bar, dim3((unsigned)wallint_groups_per_face(maxOwned), (unsigned)nface, 1), dim3(WI_T, 1, 1), 0, s, tab,
+                       faces, P, wq, nRhs, ldg, g);
+}
+#else
+void launch_flowint(const BlkView* tab, const WiFace* faces, int nface, long maxOwned, const FiPar& P, double* part,
+                    const unsigned char* member, int nGroups, double* out, hipStream_t s)
+{
+    const int gx = wallint_groups_per_face(maxOwned);
+    if (nface > 0)
+        hipLaunchKernelGGL(k_flowint_faces, dim3((unsigned)gx, (unsigned)nface, 1), dim3(WI_T, 1, 1), 0, s, tab, faces, P, part);
+    hipLaunchKernelGGL(k_flowint_finish, dim3((unsigned)nGroups, ADFLOW_WALLINT_STRIDE, 1), dim3(WI_T, 1, 1), 0, s, part, member, nface, gx,
                        out);
 }
 #endif

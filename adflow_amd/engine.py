@@ -738,6 +738,72 @@ class Engine:
         self._chk(self.lib.adflow_gpu_download_wall_forces(nn, level, sps, mm, Fp.ctypes.data, Fv.ctypes.data, area.ctypes.data))
         return Fp, Fv, area
 
+    # ---- flow integration (surfaceIntegrations.F90: flowIntegrationFace) and its derivatives with respect to the state ----
+    @staticmethod
+    def flowPar(rhoRef, rGasDim, pointRef=(0.0, 0.0, 0.0), internalFlow=False):
+        """the parameter array of flowIntegrate: what flowIntegrationFace reads and set_options does not carry"""
+        par = np.zeros(capi.FLOWINT_NPAR)
+        par[capi.FLOWINT_POINTREF:capi.FLOWINT_POINTREF + 3] = pointRef
+        par[capi.FLOWINT_INTERNALFLOW], par[capi.FLOWINT_RHOREF], par[capi.FLOWINT_RGASDIM] = float(bool(internalFlow)), rhoRef, rGasDim
+        return par
+
+    def _flowArgs(self, par, groups, frozenTurb=False, useTurbOnly=False):
+        par = np.ascontiguousarray(par, dtype=np.float64)
+        assert par.size == capi.FLOWINT_NPAR
+        n, fl, ld = self._famLists(groups)
+        flags = self._jacFreeFlags(False, frozenTurb, useTurbOnly, False, False)
+        return par, n, fl, None if fl is None else fl.ctypes.data, ld, flags
+
+    def flowIntegrate(self, par, groups=None, level: int = 1):
+        """localValues(1:63) of flowIntegrationFace over the in- and outflow subfaces of every family group: an (nGroups, 64) array to
+        be added to that of wallIntegrate; groups = None: one group holding every in- and outflow subface"""
+        par, n, fl, pfl, ld, _ = self._flowArgs(par, groups)
+        out = np.zeros((max(n, 1) if groups is None else n, capi.WALLINT_STRIDE))
+        if groups is not None and n == 0:
+            return out
+        self._chk(self.lib.adflow_gpu_flow_integrate(level, par.ctypes.data, n, pfl, ld, out.ctypes.data))
+        return out
+
+    def flowIntegrateDev(self, par, d_out: int, groups=None, level: int = 1):
+        """the same into a device array of nGroups x 64 doubles; honours set_async"""
+        par, n, fl, pfl, ld, _ = self._flowArgs(par, groups)
+        self._chk(self.lib.adflow_gpu_flow_integrate_dev(level, par.ctypes.data, n, pfl, ld, ctypes.c_void_p(d_out)))
+
+    def flowIntegrateFwd(self, x, par, groups=None, level: int = 1, frozenTurb=False, useTurbOnly=False, values=True):
+        """(out, outDot) as wallIntegrateFwd, for the in- and outflow subfaces"""
+        par, n, fl, pfl, ld, flags = self._flowArgs(par, groups, frozenTurb, useTurbOnly)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.zeros((max(n, 1), capi.WALLINT_STRIDE)) if values else None
+        dot = np.zeros((max(n, 1), capi.WALLINT_STRIDE))
+        self._chk(self.lib.adflow_gpu_flow_integrate_fwd(level, flags, x.ctypes.data, x.size, par.ctypes.data, n, pfl, ld,
+                                                         None if out is None else out.ctypes.data, dot.ctypes.data))
+        return out, dot
+
+    def flowIntegrateFwdDev(self, d_x: int, n: int, par, d_out: int, d_outDot: int, groups=None, level: int = 1, frozenTurb=False,
+                            useTurbOnly=False):
+        """the same on device pointers (d_out may be 0); honours set_async"""
+        par, ng, fl, pfl, ld, flags = self._flowArgs(par, groups, frozenTurb, useTurbOnly)
+        self._chk(self.lib.adflow_gpu_flow_integrate_fwd_dev(level, flags, ctypes.c_void_p(d_x), int(n), par.ctypes.data, ng, pfl, ld,
+                                                             ctypes.c_void_p(d_out) if d_out else None, ctypes.c_void_p(d_outDot)))
+
+    def flowIntegrateBwd(self, outBar, n: int, par, groups=None, level: int = 1, frozenTurb=False, useTurbOnly=False, ld=None, fill=0.0):
+        """wbar (nRhs, ld) as wallIntegrateBwd, for the in- and outflow subfaces"""
+        par, ng, fl, pfl, ldf, flags = self._flowArgs(par, groups, frozenTurb, useTurbOnly)
+        ob = np.ascontiguousarray(outBar, dtype=np.float64).reshape(-1, max(ng, 1), capi.WALLINT_STRIDE)
+        ld = int(n) if ld is None else int(ld)
+        wbar = np.full((ob.shape[0], max(ld, 1)), float(fill))
+        self._chk(self.lib.adflow_gpu_flow_integrate_bwd(level, flags, par.ctypes.data, ng, pfl, ldf, ob.ctypes.data, ob.shape[0],
+                                                         wbar.ctypes.data, int(n), ld))
+        return wbar
+
+    def flowIntegrateBwdDev(self, outBar, d_wbar: int, n: int, ld: int, par, groups=None, level: int = 1, frozenTurb=False,
+                            useTurbOnly=False):
+        """the same into device vectors ld doubles apart (outBar stays a host array); honours set_async"""
+        par, ng, fl, pfl, ldf, flags = self._flowArgs(par, groups, frozenTurb, useTurbOnly)
+        ob = np.ascontiguousarray(outBar, dtype=np.float64).reshape(-1, max(ng, 1), capi.WALLINT_STRIDE)
+        self._chk(self.lib.adflow_gpu_flow_integrate_bwd_dev(level, flags, par.ctypes.data, ng, pfl, ldf, ob.ctypes.data, ob.shape[0],
+                                                             ctypes.c_void_p(d_wbar), int(n), int(ld)))
+
     def upload_coordinates(self, nn=1, level=1, sps=1):
         self._chk(self.lib.adflow_gpu_upload_coordinates(nn, level, sps))
 

@@ -85,6 +85,8 @@ module adflowGpuShim
     end type byteBuf
     ! adflow_gpu_wall_integrate: size of its parameter array and of one group of its output (ADFLOW_WALLINT_NPAR, _STRIDE)
     integer, parameter :: WALLINT_NPAR = 22, WALLINT_STRIDE = 64
+    ! adflow_gpu_flow_integrate: size of its parameter array (ADFLOW_FLOWINT_NPAR); its output has the stride of the wall entries
+    integer, parameter :: FLOWINT_NPAR = 6
 
     ! ---- mirror of adflow_periodic_data ----------------------------------------
     type, bind(C) :: adflow_periodic_data
@@ -186,6 +188,40 @@ module adflowGpuShim
         end function
         integer(c_int) function adflow_gpu_wall_integrate_bwd_dev(level, flags, par, nGroups, famLists, ldFam, outBar, nRhs, wbar, n, ld) &
             bind(C, name="adflow_gpu_wall_integrate_bwd_dev")
+            import :: c_int, c_int32_t, c_double, c_ptr, c_long
+            integer(c_int), value :: level, flags, nGroups, ldFam, nRhs
+            real(c_double), intent(in) :: par(*), outBar(*)   ! outBar: host memory, nRhs x nGroups x 64
+            integer(c_int32_t), intent(in) :: famLists(*)
+            type(c_ptr), value :: wbar                     ! device memory, nRhs vectors ld doubles apart
+            integer(c_long), value :: n, ld
+        end function
+        integer(c_int) function adflow_gpu_flow_integrate(level, par, nGroups, famLists, ldFam, out) &
+            bind(C, name="adflow_gpu_flow_integrate")
+            import :: c_int, c_int32_t, c_double
+            integer(c_int), value :: level, nGroups, ldFam
+            real(c_double), intent(in) :: par(*)
+            integer(c_int32_t), intent(in) :: famLists(*)
+            real(c_double), intent(inout) :: out(*)
+        end function
+        integer(c_int) function adflow_gpu_flow_integrate_dev(level, par, nGroups, famLists, ldFam, out) &
+            bind(C, name="adflow_gpu_flow_integrate_dev")
+            import :: c_int, c_int32_t, c_double, c_ptr
+            integer(c_int), value :: level, nGroups, ldFam
+            real(c_double), intent(in) :: par(*)
+            integer(c_int32_t), intent(in) :: famLists(*)
+            type(c_ptr), value :: out                      ! device memory, nGroups x 64 doubles
+        end function
+        integer(c_int) function adflow_gpu_flow_integrate_fwd_dev(level, flags, x, n, par, nGroups, famLists, ldFam, out, outDot) &
+            bind(C, name="adflow_gpu_flow_integrate_fwd_dev")
+            import :: c_int, c_int32_t, c_double, c_ptr, c_long
+            integer(c_int), value :: level, flags, nGroups, ldFam
+            type(c_ptr), value :: x, out, outDot           ! device memory: the vector; nGroups x 64 doubles each (out may be null)
+            integer(c_long), value :: n
+            real(c_double), intent(in) :: par(*)
+            integer(c_int32_t), intent(in) :: famLists(*)
+        end function
+        integer(c_int) function adflow_gpu_flow_integrate_bwd_dev(level, flags, par, nGroups, famLists, ldFam, outBar, nRhs, wbar, n, ld) &
+            bind(C, name="adflow_gpu_flow_integrate_bwd_dev")
             import :: c_int, c_int32_t, c_double, c_ptr, c_long
             integer(c_int), value :: level, flags, nGroups, ldFam, nRhs
             real(c_double), intent(in) :: par(*), outBar(*)   ! outBar: host memory, nRhs x nGroups x 64
@@ -1176,6 +1212,84 @@ contains
                                                         int(nRhs, c_int), wbarDev, int(n, c_long), int(ld, c_long)), &
                       "gpuWallIntegrateBwd")
     end subroutine gpuWallIntegrateBwd
+
+    ! the parameter array of the flow integration entries (ADFLOW_FLOWINT_* of the header): pointRef, flowType == internalFlow, rhoRef,
+    ! rGasDim -- what flowIntegrationFace reads and gpuSetOptions does not carry
+    subroutine gpuFlowPar(par)
+        use constants, only: internalFlow
+        use inputPhysics, only: pointRef, flowType, rGasDim
+        use flowVarRefState, only: rhoRef
+        real(c_double), intent(out) :: par(0:FLOWINT_NPAR - 1)
+        par = 0.0_c_double
+        par(0:2) = pointRef
+        if (flowType == internalFlow) par(3) = 1.0_c_double
+        par(4) = rhoRef
+        par(5) = rGasDim
+    end subroutine gpuFlowPar
+
+    ! The in- and outflow part of integrateSurfaces (surfaceIntegrations.F90:1303-1361) for one family list, on the device: adds this
+    ! process's contributions of every SubsonicInflow, SupersonicInflow, SubsonicOutflow and SupersonicOutflow subface whose family is
+    ! in famList to localValues, as the loop over flowIntegrationFace does
+    subroutine gpuFlowIntegrate(localValues, famList, sps)
+        use constants, only: nLocalValues
+        real(kind=realType), dimension(nLocalValues), intent(inout) :: localValues
+        integer(kind=intType), dimension(:), intent(in) :: famList
+        integer(kind=intType), intent(in) :: sps
+        real(c_double) :: par(0:FLOWINT_NPAR - 1), out(0:WALLINT_STRIDE - 1)
+        integer(c_int32_t), allocatable :: fl(:)
+        integer :: i, n
+        n = size(famList)
+        allocate (fl(n + 1))
+        fl(1) = int(n, c_int32_t)
+        fl(2:n + 1) = int(famList, c_int32_t)
+        call gpuFlowPar(par)
+        call gpuCheck(adflow_gpu_flow_integrate(1_c_int, par, 1_c_int, fl, int(n + 1, c_int), out), "gpuFlowIntegrate")
+        do i = 1, nLocalValues
+            localValues(i) = localValues(i) + out(i - 1)
+        end do
+    end subroutine gpuFlowIntegrate
+
+    ! The in- and outflow part of integrateSurfaces_d for one family list, as gpuWallIntegrateFwd.  dotDev: device memory for 64
+    ! doubles, to be added to those of the walls
+    subroutine gpuFlowIntegrateFwd(flags, xDev, n, famList, sps, dotDev)
+        integer(kind=intType), intent(in) :: flags, n, sps
+        type(c_ptr), intent(in) :: xDev, dotDev
+        integer(kind=intType), dimension(:), intent(in) :: famList
+        real(c_double) :: par(0:FLOWINT_NPAR - 1)
+        integer(c_int32_t), allocatable :: fl(:)
+        integer :: nf
+        nf = size(famList)
+        allocate (fl(nf + 1))
+        fl(1) = int(nf, c_int32_t)
+        fl(2:nf + 1) = int(famList, c_int32_t)
+        call gpuFlowPar(par)
+        call gpuCheck(adflow_gpu_flow_integrate_fwd_dev(1_c_int, int(flags, c_int), xDev, int(n, c_long), par, 1_c_int, fl, &
+                                                        int(nf + 1, c_int), c_null_ptr, dotDev), "gpuFlowIntegrateFwd")
+    end subroutine gpuFlowIntegrateFwd
+
+    ! The in- and outflow part of integrateSurfaces_b for one family list, as gpuWallIntegrateBwd: the host adds the columns of the two
+    ! (separate device arrays) before the adjoint solve
+    subroutine gpuFlowIntegrateBwd(flags, localValuesd, nRhs, famList, sps, wbarDev, n, ld)
+        use constants, only: nLocalValues
+        integer(kind=intType), intent(in) :: flags, nRhs, sps, n, ld
+        real(kind=realType), dimension(nLocalValues, nRhs), intent(in) :: localValuesd
+        integer(kind=intType), dimension(:), intent(in) :: famList
+        type(c_ptr), intent(in) :: wbarDev
+        real(c_double) :: par(0:FLOWINT_NPAR - 1)
+        real(c_double), allocatable :: ob(:, :)
+        integer(c_int32_t), allocatable :: fl(:)
+        integer :: nf
+        nf = size(famList)
+        allocate (fl(nf + 1), ob(WALLINT_STRIDE, nRhs))
+        fl(1) = int(nf, c_int32_t)
+        fl(2:nf + 1) = int(famList, c_int32_t)
+        ob = 0.0_c_double
+        ob(1:nLocalValues, :) = localValuesd
+        call gpuFlowPar(par)
+        call gpuCheck(adflow_gpu_flow_integrate_bwd_dev(1_c_int, int(flags, c_int), par, 1_c_int, fl, int(nf + 1, c_int), ob, &
+                                                        int(nRhs, c_int), wbarDev, int(n, c_long), int(ld, c_long)), &
+                      "gpuFlowIntegrateBwd")
+    end subroutine gpuFlowIntegrateBwd
 
     ! actuatorRegions(1:nActuatorRegions) -> device (after addActuatorRegion; again when force / heat change)
     subroutine gpuRegisterActuatorRegions()

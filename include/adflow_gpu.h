@@ -404,7 +404,7 @@ int adflow_gpu_download_wall_stress(int nn, int level, int sps, int mm, double* 
  * level (a process that never integrates holds the bytes it held).  adflow_gpu_release_workspace FREES them and counts them in
  * its bytes (the next integration allocates them again); adflow_gpu_bc_register, adflow_gpu_bc_set_families,
  * adflow_gpu_block_release and adflow_gpu_release_all free them too.
- * Not here: flowIntegrationFace (mass flow through in- and outflow faces), zippers, user surfaces, actuator regions;
+ * Not here (the in- and outflow faces: adflow_gpu_flow_integrate below): zippers, user surfaces, actuator regions;
  * computeSepSensorKs and CpError2 (they need a family maximum and CpTarget; iSepSensorKs, iSepSensorArea, iSepSensorKsArea and
  * iCpError2 are zero); getCostFunctions, which stays on the host; the derivative seeds of master_d / master_b other than those
  * of the state (below).
@@ -471,6 +471,57 @@ int adflow_gpu_wall_integrate_fwd_dev(int level, unsigned flags, const double* d
 int adflow_gpu_wall_integrate_bwd(int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
                                   const double* outBar, int nRhs, double* wbar, long n, long ld);
 int adflow_gpu_wall_integrate_bwd_dev(int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
+                                      const double* outBar, int nRhs, double* d_wbar, long n, long ld);
+/* ---- flow integration: mass flow and flow properties over in- and outflow faces -------------------------------------------------------
+ * adflow_gpu_flow_integrate[_dev]: flowIntegrationFace (surfaceIntegrations.F90:894-1200) over the SubsonicInflow, SupersonicInflow,
+ * SubsonicOutflow and SupersonicOutflow subfaces of a level, the other half of integrateSurfaces (:1303-1361).  par =
+ * ADFLOW_FLOWINT_NPAR doubles at the indices below: what the routine reads and adflow_gpu_set_options does not carry (pInf, pRef,
+ * gammaInf, RGas, TRef, uRef, timeRef and LRef come from there).  nGroups, famLists, ldFam, out: as for adflow_gpu_wall_integrate,
+ * families and blanking from adflow_gpu_bc_set_families; nGroups = 0 = one group holding every in- and outflow subface.  Entries of a
+ * group's output, at the reference's indices: iMassFlow, iMassPtot, iMassTtot, iMassPs, iMassMN, iMassa, iMassRho, iMassVx/Vy/Vz,
+ * iMassnx/ny/nz, iMassVi, iArea, iAreaPTot, iAreaPs, iFp(3), iFlowMp(3), iFlowFm(3), iFlowMm(3), iCoForceX/Y/Z(3); every other slot
+ * (entry 63 included) is zero.  iFp and iCoForce* are shared with the wall integration as in the reference: the host adds the two
+ * vectors before its mpi_allreduce and getCostFunctions.  The terms are the reference's: fact +1 on min faces, inFlowFact -1 on the two
+ * inflow kinds, blk = max(iblank, 0), means of halo and first interior cell, sF from sFace on a block with grid velocities, vmag =
+ * sqrt(v . v) - sF, Ptot / Ttot of computePtot / computeTtot for constant cp, pratio = min(1, 1 / Ptot).  Reads the halos as the last
+ * boundary-condition pass left them, changes neither state nor residual nor anything of the wall integration; two-pass sums in a
+ * fixed order, no atomics: bit-identical from call to call and between the two forms.  The _dev form takes a device pointer for out
+ * and honours adflow_gpu_set_async; it waits for the queue only when the family lists differ from those of the previous call.
+ * Errors (nothing is launched or allocated): a level without registered boundary subfaces; nGroups < 0; a family count above
+ * ldFam - 1; rhoRef or rGasDim not positive.  A level without an in- or outflow subface is no error: zeros.
+ *
+ * adflow_gpu_flow_integrate_fwd[_dev], _bwd[_dev]: the derivatives with respect to the state, arguments and layout as for
+ * adflow_gpu_wall_integrate_fwd / _bwd.  The pass runs the closures and the dual flow boundary conditions and nothing else (no
+ * turbulence boundary condition, no nodal gradient: the terms read rho, the velocities, p and gamma of the halo and the first interior
+ * cell), then the face terms on dual numbers; _bwd is the same coloured sweep (125 colours x nState) with the same per-cell gather.
+ * out of _fwd, where not NULL, is adflow_gpu_flow_integrate itself, to the bit: the plain kernels run in the same queue (the dual pass
+ * forms the pressure again from the energy, its value parts agree with them to rounding only).
+ * Supersonic outflow (and extrapolated) halos are not linearised by the dual boundary conditions, as in BCExtra_d.F90: on those
+ * faces the halo is a constant.  ADFLOW_JAC_TURB_ONLY gives exact zeros.  Weights on entries the integration leaves zero are ignored.
+ * Errors: those above and everything adflow_gpu_wall_integrate_fwd / _bwd refuse (the approximating flags, a wrong n, NULL vectors,
+ * nRhs out of range, ld < n, halos exchanged with other ranks in _bwd; moving blocks, which the dual kernels do not linearise).
+ * Every one of them is found by the checks of the arguments, before the level's record is looked up or built: a refused call of
+ * the derivative entries has launched and allocated nothing either.
+ * Buffers: a record per level beside that of the walls, with the same lifetime: allocated by the first call that needs them, freed
+ * and counted by adflow_gpu_release_workspace, dropped by adflow_gpu_bc_register, adflow_gpu_bc_set_families,
+ * adflow_gpu_block_release and adflow_gpu_release_all.
+ * Not here: xvbar / extraBar, zippers, user surfaces, actuator regions, mass-bleed outflow, getCostFunctions, several ranks in _bwd. */
+enum {
+    ADFLOW_FLOWINT_POINTREF = 0,             /* pointRef(3) */
+    ADFLOW_FLOWINT_INTERNALFLOW = 3,         /* 0 / 1: flowType == internalFlow (the momentum force and moment change sign) */
+    ADFLOW_FLOWINT_RHOREF = 4,               /* flowVarRefState::rhoRef */
+    ADFLOW_FLOWINT_RGASDIM = 5,              /* inputPhysics::rGasDim */
+    ADFLOW_FLOWINT_NPAR = 6
+};
+int adflow_gpu_flow_integrate(int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out);
+int adflow_gpu_flow_integrate_dev(int level, const double* par, int nGroups, const int32_t* famLists, int ldFam, double* out);
+int adflow_gpu_flow_integrate_fwd(int level, unsigned flags, const double* x, long n, const double* par, int nGroups,
+                                  const int32_t* famLists, int ldFam, double* out, double* outDot);
+int adflow_gpu_flow_integrate_fwd_dev(int level, unsigned flags, const double* d_x, long n, const double* par, int nGroups,
+                                      const int32_t* famLists, int ldFam, double* d_out, double* d_outDot);
+int adflow_gpu_flow_integrate_bwd(int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
+                                  const double* outBar, int nRhs, double* wbar, long n, long ld);
+int adflow_gpu_flow_integrate_bwd_dev(int level, unsigned flags, const double* par, int nGroups, const int32_t* famLists, int ldFam,
                                       const double* outBar, int nRhs, double* d_wbar, long n, long ld);
 /* Actuator regions (actuatorRegionData.F90): residuals::sourceTerms_block (residuals.F90:348-425) adds the body force and
  * heat source of every listed cell to dw of the FINE level: -vol * force / volume / pRef on the momentum residuals,
